@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the L2HMC hot path on MI355X: chain-leapfrog-steps per second.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--scaling {weak,strong}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--scaling {weak,strong}] [--dump-outputs DIR]
 
 One "step" is one pass of the hot path over one batch of synthetic chains, everything resident in HBM:
   * lattice configs (3, 4, 5): one `apply_transition` (dynamics/gauge_dynamics.py:195-259) -- momenta, direction
@@ -302,9 +302,10 @@ class Job:
         return float(t.item())
 
 
-def run_workload(job, cfg, scaling, steps, warmup, both=True, layered=False, roofline=True, keep=None):
+def run_workload(job, cfg, scaling, steps, warmup, both=True, layered=False, roofline=True, keep=None, dump=False):
     """Builds config `cfg` at this rank's share, runs prewarm + W warm-up + EXACTLY K timed steps bracketed by
-    barrier + synchronize, MAX over ranks.  Returns (result dict, state for the secondary legs)."""
+    barrier + synchronize, MAX over ranks.  Returns (result dict, state for the secondary legs); with `dump`,
+    state["outputs"] holds the last timed step's output arrays as host NumPy arrays."""
     from l2hmc_amd import _lib
     import l2hmc_amd as la
     c = CONFIGS[cfg]
@@ -332,6 +333,13 @@ def run_workload(job, cfg, scaling, steps, warmup, both=True, layered=False, roo
 
         def step(xc):
             return sampler.step(xc, beta)[0]
+
+        def step_out(xc):
+            return sampler.step(xc, beta)
+
+        def outputs_of(r):                             # (x_next, px, observables of x, |dQ|)
+            return {"x_next": r[0], "px": r[1], **{k: r[2][k] for k in ("action", "avg_plaq", "top_charge")},
+                    "dq": r[3]}
         state.update(dyn=dyn, sampler=sampler, stats=stats)
     else:
         dyn, target = build_toy(cfg)
@@ -342,6 +350,12 @@ def run_workload(job, cfg, scaling, steps, warmup, both=True, layered=False, roo
 
         def step(xc):
             return la.propose(xc, dyn, do_mh_step=True)[3][0]
+
+        def step_out(xc):
+            return la.propose(xc, dyn, do_mh_step=True)
+
+        def outputs_of(r):                             # (Lx, Lv, px, [x_out]); Lv is None without init_v
+            return {"Lx": r[0], "px": r[2], "x_out": r[3][0]}
         state.update(dyn=dyn, target=target)
 
     # untimed pre-warm, in ADDITION to the W warm-up steps: after the idle seconds of start-up the GPU clock takes
@@ -359,10 +373,14 @@ def run_workload(job, cfg, scaling, steps, warmup, both=True, layered=False, roo
     job.barrier()
     history = []                                   # references only: no device work in the timed region
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         x = step(x)
         if keep:
             history.append(x)
+    last = outputs_of(step_out(x))                 # the last timed step: every array its caller receives
+    x = last["x_next" if c["kind"] == "gauge" else "x_out"]
+    if keep:
+        history.append(x)
     if stats is not None:
         stats.join()                               # every step's all-reduce is ordered before the synchronize
     job.barrier()
@@ -370,6 +388,9 @@ def run_workload(job, cfg, scaling, steps, warmup, both=True, layered=False, roo
     if stats is not None:
         stats.wait()                               # host-side bookkeeping of the step scalars: not part of a step
     dt = job.max_over_ranks(dt)
+    if dump:
+        state["outputs"] = {k: v.detach().cpu().numpy() for k, v in last.items()}
+    del last
 
     ndir = 2 if both else 1
     useful = glob * c["N"] * steps
@@ -477,6 +498,33 @@ def ess_of(history, chain_stats):
     return float(chain_stats.ESS(A / A[0]))
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(outputs, out_dir, lo):
+    """Writes the timed path's last-step outputs as out_dir/<name>.npy: floating arrays keep float32 / float64,
+    anything else becomes float64.  Every array has one row per chain; if the whole set exceeds
+    DUMP_LIMIT_BYTES, the same fixed, seeded sample of chains is written from every array.  Returns a summary
+    for the JSON line."""
+    arrays = {k: (np.asarray(a) if a.dtype in (np.float32, np.float64) else np.asarray(a, dtype=np.float64))
+              for k, a in outputs.items()}
+    B = next(iter(arrays.values())).shape[0]
+    assert all(a.shape[0] == B for a in arrays.values()), {k: a.shape for k, a in arrays.items()}
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    keep = min(B, (DUMP_LIMIT_BYTES - 256 * len(arrays)) // row_bytes)       # 256: room for each .npy header
+    rows = None
+    if keep < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {k: [list(a.shape), str(a.dtype)] for k, a in arrays.items()},
+            "chains": f"all {B} chains of this rank [{lo}, {lo + B})" if rows is None else
+                      f"{keep} of the {B} chains of this rank [{lo}, {lo + B}): fixed seeded sample "
+                      f"(numpy default_rng(0).choice, sorted)"}
+
+
 def claim_stdout():
     """The driver parses ONE JSON line from stdout, and RCCL prints a version banner there when a communicator is
     created: keep a private handle on the real stdout for the line and point file descriptor 1 at stderr for everything
@@ -507,6 +555,10 @@ def main():
     ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step timing")
     ap.add_argument("--no-trained-ess", action="store_true",
                     help="skip the 250-step training run + ESS/sec of the trained sampler (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned (rank 0's chains) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed seeded sample of chains "
+                         "beyond that); the inputs are seeded, so runs with the same arguments compare array by array")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="test hook (CPU, gloo): start the ranks, barrier, max-over-ranks reduction, print "
                          "{'rendezvous_only': true, ..., 'chains': [[lo, hi) per rank]} and exit -- no GPU")
@@ -521,6 +573,8 @@ def main():
     scaling = args.scaling or c["scaling"]
     steps = args.steps if args.steps is not None else c["steps"]
     warmup = args.warmup if args.warmup is not None else c["warmup"]
+    if steps < 1 or warmup < 0:
+        raise SystemExit(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {steps}, {warmup})")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -560,8 +614,10 @@ def main():
     failed = []                                   # secondary legs that threw: reported AND a non-zero exit
 
     res, st = run_workload(job, cfg, scaling, steps, warmup, both=both, layered=args.layered,
-                           roofline=not args.no_roofline, keep=(c["kind"] == "gauge" and cfg == 3))
+                           roofline=not args.no_roofline, keep=(c["kind"] == "gauge" and cfg == 3),
+                           dump=args.dump_outputs is not None and rank == 0)
     lo, hi = res["chains_this_rank"]
+    dumped = dump_outputs(st.pop("outputs"), args.dump_outputs, lo) if "outputs" in st else None
     short = {1: f"2-D SCG batch {res['global_batch']}, 5 LF", 2: f"2-D MoG batch {res['global_batch']}, 10 LF",
              3: f"8x8 U(1) batch {res['global_batch']}, 10 LF", 4: f"16x16 U(1) conv3D batch {res['global_batch']}, 15 LF",
              5: f"32x32 U(1) batch {res['global_batch']}, 25 LF"}
@@ -583,6 +639,8 @@ def main():
             out["config"][k] = res[k]
     if "roofline" in res:
         out["roofline"] = res["roofline"]
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     x, step, dyn = st["x"], st["step"], st["dyn"]
 
     if cfg == 3:

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -117,3 +119,51 @@ def test_failing_rank_gives_nonzero_exit():
 def test_rank_count_mismatch_is_reported():
     r = _run(["--gpus", "2", "--rendezvous-only"], extra_env={"WORLD_SIZE": "3", "RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE=3" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_writes_every_array_within_the_size_limit(tmp_path):
+    """--dump-outputs: float32 / float64 .npy per output, one shared seeded sample of chains once the set would
+    exceed 64 MB, the same sample on every call."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    small = {"x_next": rng.random((16, 8), dtype=np.float32), "px": rng.random(16, dtype=np.float32),
+             "flag": np.arange(16, dtype=np.int32)}
+    info = bench.dump_outputs(small, str(tmp_path / "small"), 32)
+    for k, a in small.items():
+        got = np.load(tmp_path / "small" / (k + ".npy"))
+        assert got.dtype == (np.float64 if k == "flag" else np.float32)
+        np.testing.assert_array_equal(got, a)
+    assert info["arrays"]["flag"] == [[16], "float64"] and "all 16 chains" in info["chains"]
+
+    B, D = 20000, 1024                                   # 82 MB of rows: must be cut to a sample
+    big = {"x": np.arange(B * D, dtype=np.float32).reshape(B, D), "p": np.arange(B, dtype=np.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d), 0)
+    sizes = sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in big)
+    assert sizes <= 64_000_000
+    xa, pa = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "p.npy")
+    assert 0 < len(pa) < B and xa.shape == (len(pa), D) and np.all(np.diff(pa) > 0)
+    np.testing.assert_array_equal(xa[:, 0], pa * D)      # the same chains from every array
+    for k in big:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy")))
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_are_identical(tmp_path):
+    """Same arguments, same inputs: two runs of the benchmark dump the same last-step arrays, bit for bit, and
+    --steps sets the number of timed steps."""
+    import numpy as np
+    for cfg, names in (("1", ("Lx", "px", "x_out")), ("3", ("x_next", "px", "action", "avg_plaq", "top_charge", "dq"))):
+        lines = []
+        for run in ("a", "b"):
+            r = _run(["--gpus", "1", "--config", cfg, "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                      "--no-roofline", "--no-train", "--no-configs-table", "--dump-outputs", str(tmp_path / cfg / run)])
+            assert r.returncode == 0, r.stderr[-2000:]
+            lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0]))
+        for out in lines:
+            assert out["steps"] == 3 and out["ms_per_step"] > 0 and sorted(out["dump_outputs"]["arrays"]) == sorted(names)
+        for k in names:
+            a, b = (np.load(tmp_path / cfg / run / (k + ".npy")) for run in ("a", "b"))
+            assert a.dtype == np.float32 and a.shape[0] == lines[0]["config"]["global_batch"]
+            assert np.isfinite(a).all()
+            np.testing.assert_array_equal(a, b)

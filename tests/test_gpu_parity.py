@@ -360,7 +360,7 @@ def test_sub_update_methods_on_materialised_stq(la):
     assert torch.all(bad == 0)
 
 
-def test_constructor_surface_and_errors(la):
+def test_constructor_surface_and_errors(la, tmp_path):
     lat = la.GaugeLattice(8, 8, 2, 'U1', num_samples=4, rand=True)
     fn = lat.get_energy_function()
     d = la.GaugeDynamics(lat, fn, eps=0.3, hmc=False, network_arch='generic', num_steps=3, eps_trainable=True,
@@ -377,8 +377,9 @@ def test_constructor_surface_and_errors(la):
         la.GaugeDynamics(lat, fn, eps=0.3, hmc=False, network_arch='bogus', num_steps=3, eps_trainable=True)
     with pytest.raises(NotImplementedError):
         la.GaugeDynamics(lat, lambda x: x.sum(1), eps=0.3, hmc=True, num_steps=3, eps_trainable=True)
-    d.position_fn.save_weights("/tmp/_xnet_weights")
-    d.position_fn.load_weights("/tmp/_xnet_weights")
+    path = str(tmp_path / "xnet_weights")
+    d.position_fn.save_weights(path)
+    d.position_fn.load_weights(path)
 
 
 # ----------------------------------------------------------------- ConvNet3D (network/conv_net.py)

@@ -7,6 +7,7 @@ trainer must reproduce the group-less run bit for bit.  (Multi-rank values are c
 tests/test_dist_gloo.py, tests/test_gpu_train.py::test_data_parallel_gradients_equal_full_batch,
 tests/test_bench_launcher.py.)"""
 import os
+import socket
 
 import numpy as np
 import pytest
@@ -42,7 +43,9 @@ def test_sampler_and_trainer_through_a_one_rank_rccl_group_match_the_plain_run(m
     assert plain[5] == 0                                               # no group: one local gradient buffer
     monkeypatch.setenv("L2HMC_COLLECTIVES_AT_WORLD1", "1")
     monkeypatch.setenv("MASTER_ADDR", "127.0.0.1")
-    monkeypatch.setenv("MASTER_PORT", "29541")
+    with socket.socket() as s:                                         # a free port: the box may be shared
+        s.bind(("127.0.0.1", 0))
+        monkeypatch.setenv("MASTER_PORT", str(s.getsockname()[1]))
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     dist.init_process_group(backend="nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:

@@ -83,7 +83,12 @@ def _check_fixture_grads(g, prefix, grads):
         if f"{prefix}/{k}" in g.files:
             np.testing.assert_allclose(v, g[f"{prefix}/{k}"], rtol=1e-9, atol=1e-12)
         else:
-            np.testing.assert_allclose([v.sum(), np.abs(v).sum(), (v * v).sum()], g[f"{prefix}/{k}/stats"], rtol=1e-9)
+            want = g[f"{prefix}/{k}/stats"]
+            # a plain sum can cancel to rounding level (vnet/x_layer/W of train_L8_generic: 6e-14 out of an absolute
+            # sum of 1e5), where its value depends on the order the CPU's kernels accumulate in: it is held to 1e-12
+            # of the absolute sum as well as to its own rtol
+            np.testing.assert_allclose(v.sum(), want[0], rtol=1e-9, atol=1e-12 * want[1])
+            np.testing.assert_allclose([np.abs(v).sum(), (v * v).sum()], want[1:], rtol=1e-9)
             np.testing.assert_allclose(v.reshape(v.shape[0], -1)[0], g[f"{prefix}/{k}/row0"], rtol=1e-9, atol=1e-12)
 
 

@@ -358,6 +358,22 @@ int l2hmc_gauge_loss_backward(int32_t T, int32_t X, float beta, const float* x0,
                               const float* vN, const float* p, int64_t B, int32_t metric, float loss_scale,
                               float aux_weight, float std_weight, float charge_weight, float inv_count,
                               float* terms, float* dxN, float* dvN, float* dlogdet, l2hmc_stream_t stream);
+/* Reverse of the end of a transition (gauge_dynamics.py:229-257) for ANY loss: the accept probability
+ * p = exp(min(A, 0)), A = H(x0, v0) - H(xN, vN) + sumlogdet, H = beta S(x) + |v|^2 / 2, and the select
+ * x_out = a xN + (1 - a) x0 with a = [p > u] (strict).  What a caller's autograd needs between its cotangents of
+ * (x_prop, v_prop, p, x_out) and l2hmc_gauge_train_backward.  With g = g_p p where 0 < p < 1 (else 0) and
+ * F = beta dS/dx (the `force` of l2hmc_u1_action_force):
+ *   dxN = g_xprop + a g_xout - g F(xN)      dvN = g_vprop - g vN      dlogdet = g
+ *   dx0 = (1 - a) g_xout + g F(x0)          dv0 = g v0
+ * dx0 / dv0 are only the DIRECT dependence on the start state; l2hmc_gauge_train_backward adds the part through
+ * the trajectory.  x0, v0, xN, vN, dxN, dvN, dx0, dv0: [rows][2*T*X]; p, u, g_p, dlogdet: [rows].  Each g_* may be
+ * NULL (= 0); dx0, dv0 may be NULL (not written; v0 may then be NULL).  Rows with g = 0 never form 0 * F, so a
+ * non-finite proposal (p = 0) leaves the other terms finite.  One wave per row, the chain staged in LDS. */
+int l2hmc_gauge_accept_backward(int32_t T, int32_t X, float beta, int64_t rows, const float* x0, const float* v0,
+                                const float* xN, const float* vN, const float* p, const float* u,
+                                const float* g_xprop, const float* g_vprop, const float* g_p, const float* g_xout,
+                                float* dxN, float* dvN, float* dlogdet, float* dx0, float* dv0,
+                                l2hmc_stream_t stream);
 /* *out (device) = [*out +] sum g[i]^2, elements in [tri_lo, tri_hi) counted three times (the packed
  * first-layer bias stands for three reference variables); fixed summation order. */
 int l2hmc_grad_sumsq(const float* g, int64_t n, int64_t tri_lo, int64_t tri_hi, float* out, int32_t accumulate,

@@ -109,6 +109,7 @@ _PROTOS = {
                                                      BUCKET_FN, _P]),
     "l2hmc_gauge_loss_backward": (C.c_int, [_I32, _I32, _F, _P, _P, _P, _P, _I64, _I32, _F, _F, _F, _F, _F, _P, _P,
                                             _P, _P, _P]),
+    "l2hmc_gauge_accept_backward": (C.c_int, [_I32, _I32, _F, _I64] + [_P] * 15 + [_P]),
     "l2hmc_grad_sumsq": (C.c_int, [_P, _I64, _I64, _I64, _P, _I32, _P]),
     "l2hmc_adam_step": (C.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _I64, _I64, _P]),
     "l2hmc_mog_energy_grad": (C.c_int, [C.POINTER(MogTarget), _P, _I64, _P, _P, _P]),

@@ -751,6 +751,71 @@ __global__ __launch_bounds__(64) void loss_bwd_kernel(LossBwdArgs p) {
 }
 
 // =====================================================================
+// reverse of the end of apply_transition (gauge_dynamics.py:229-257): accept probability and Metropolis-
+// Hastings select, for arbitrary cotangents of (x_prop, v_prop, p, x_out) -- the part of a transition
+// l2hmc_gauge_train_backward does not cover.  p = exp(min(H0 - H1 + ld, 0)), a = [p > u],
+// x_out = a x_N + (1 - a) x_0.  g = g_p p where 0 < p < 1, else 0 (loss_bwd_kernel's convention).
+// =====================================================================
+struct AcceptBwdArgs {
+  int T, X; int64_t rows; float beta;
+  const float* x0; const float* v0; const float* xN; const float* vN; const float* p; const float* u;
+  const float* gxp; const float* gvp; const float* gp; const float* gxo;   // each may be NULL (= 0)
+  float* dxN; float* dvN; float* dld; float* dx0; float* dv0;            // dx0, dv0 may be NULL
+};
+
+// one wave per chain; the chain whose force is needed is staged in LDS
+__global__ __launch_bounds__(64) void accept_bwd_kernel(AcceptBwdArgs p) {
+  extern __shared__ float lds[];
+  const int T = p.T, X = p.X, sites = T * X, D = 2 * sites;
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int64_t o = b * D;
+  float* xs = lds;            // [D] staged chain
+  float* sp = xs + D;         // [sites] sin(plaquette)
+  const float pb = p.p[b];
+  const bool acc = pb > p.u[b];                                    // strict, as gauge_dynamics.py:244-257
+  // wave-uniform: rows with g = 0 never form 0 * F (a non-finite proposal has p = 0 and stays NaN-free)
+  const float g = (p.gp != nullptr && pb > 0.f && pb < 1.f) ? p.gp[b] * pb : 0.f;
+  if (lane == 0) p.dld[b] = g;
+  // stages `src` and leaves sin(plaquette) of it in sp
+  auto stage = [&](const float* src) {
+    __syncthreads();
+    for (int c = lane; c < D; c += 64) xs[c] = src[c];
+    __syncthreads();
+    for (int s = lane; s < sites; s += 64) sp[s] = sinf(plaq_at(xs, s, T, X));
+    __syncthreads();
+  };
+  // F = beta dS/dx at link c = 2 s + mu (the `force` of l2hmc_u1_action_force)
+  auto force = [&](int s, int mu) {
+    const int i = s / X, j = s - i * X;
+    if (mu == 0) return p.beta * (sp[s] - sp[i * X + ((j == 0) ? X - 1 : j - 1)]);
+    return p.beta * (-sp[s] + sp[((i == 0) ? T - 1 : i - 1) * X + j]);
+  };
+  if (g != 0.f) stage(p.xN + o);
+  for (int c = lane; c < D; c += 64) {
+    float dx = p.gxp ? p.gxp[o + c] : 0.f;
+    if (acc && p.gxo) dx += p.gxo[o + c];
+    float dv = p.gvp ? p.gvp[o + c] : 0.f;
+    if (g != 0.f) {
+      dx -= g * force(c >> 1, c & 1);
+      dv -= g * p.vN[o + c];
+    }
+    p.dxN[o + c] = dx;
+    p.dvN[o + c] = dv;
+  }
+  if (p.dx0) {
+    if (g != 0.f) stage(p.x0 + o);
+    for (int c = lane; c < D; c += 64) {
+      float dx = (!acc && p.gxo) ? p.gxo[o + c] : 0.f;
+      if (g != 0.f) dx += g * force(c >> 1, c & 1);
+      p.dx0[o + c] = dx;
+    }
+  }
+  if (p.dv0)
+    for (int c = lane; c < D; c += 64) p.dv0[o + c] = g != 0.f ? g * p.v0[o + c] : 0.f;
+}
+
+// =====================================================================
 // optimiser: tf.train.AdamOptimizer.apply_gradients with optional clip_by_global_norm
 // (gauge_model.py:826-827, :942-969)
 // =====================================================================
@@ -1422,6 +1487,28 @@ extern "C" int l2hmc_gauge_loss_backward(int32_t T, int32_t X, float beta, const
   L2HMC_REQUIRE(lds <= 64 * 1024, "loss_backward: lattice too large for one workgroup's LDS");
   hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, a);
   L2HMC_CHECK_LAUNCH("loss_bwd");
+  return L2HMC_OK;
+}
+
+extern "C" int l2hmc_gauge_accept_backward(int32_t T, int32_t X, float beta, int64_t rows, const float* x0,
+                                           const float* v0, const float* xN, const float* vN, const float* p,
+                                           const float* u, const float* g_xprop, const float* g_vprop,
+                                           const float* g_p, const float* g_xout, float* dxN, float* dvN,
+                                           float* dlogdet, float* dx0, float* dv0, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(T > 0 && X > 0 && rows >= 0, "accept_backward: bad arguments");
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x0 && xN && vN && p && u && dxN && dvN && dlogdet, "accept_backward: NULL pointer");
+  L2HMC_REQUIRE(!dv0 || v0, "accept_backward: dv0 needs v0");
+  L2HMC_REQUIRE(rows <= 0x7fffffff, "accept_backward: rows %lld exceeds the grid", (long long)rows);
+  AcceptBwdArgs a{};
+  a.T = T; a.X = X; a.rows = rows; a.beta = beta;
+  a.x0 = x0; a.v0 = v0; a.xN = xN; a.vN = vN; a.p = p; a.u = u;
+  a.gxp = g_xprop; a.gvp = g_vprop; a.gp = g_p; a.gxo = g_xout;
+  a.dxN = dxN; a.dvN = dvN; a.dld = dlogdet; a.dx0 = dx0; a.dv0 = dv0;
+  const size_t lds = sizeof(float) * (size_t)(2 * T * X + T * X);
+  L2HMC_REQUIRE(lds <= 64 * 1024, "accept_backward: lattice too large for one workgroup's LDS");
+  hipLaunchKernelGGL(accept_bwd_kernel, dim3((unsigned)rows), dim3(64), lds, (hipStream_t)stream, a);
+  L2HMC_CHECK_LAUNCH("accept_bwd");
   return L2HMC_OK;
 }
 

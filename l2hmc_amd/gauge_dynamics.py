@@ -16,6 +16,7 @@ import numpy.random as npr
 import torch
 
 from . import _lib
+from . import autograd as _autograd
 from .network import ConvNet3D, GenericNet
 
 
@@ -132,7 +133,7 @@ class GaugeDynamics:
     # ---- plumbing ----------------------------------------------------------
     def _plan(self):
         p = _lib.GaugePlan(T=self.lattice.time_size, X=self.lattice.space_size, num_steps=self.num_steps,
-                           hmc=int(bool(self.hmc)), eps=float(self.eps),
+                           hmc=int(bool(self.hmc)), eps=float(self.eps.detach()),
                            flags=(0 if self.fused else _lib.PLAN_LAYERED)
                            | (0 if self.both_directions else _lib.PLAN_SELECTED_ONLY)
                            | (_lib.PLAN_RECOMPUTE if self.recompute else 0)
@@ -176,8 +177,11 @@ class GaugeDynamics:
     call = __call__
 
     def apply_transition(self, position, beta, momentum_f=None, momentum_b=None, coin=None, u=None):
-        """:195-259 -> (position_post, momentum_post, accept_prob, position_out)."""
+        """:195-259 -> (position_post, momentum_post, accept_prob, position_out).  Differentiable (torch.autograd,
+        l2hmc_amd/autograd.py) when grad mode is on and the position, eps or a weight requires grad."""
         x = self._x(position)
+        if _autograd.wants_grad(self, x):
+            return _autograd.transition(self, x, beta, momentum_f, momentum_b, coin, u)
         B, D = x.shape
         if momentum_f is None and momentum_b is None and coin is None and u is None:
             # no draw injected: the library draws for itself (one stream pair from this object's counter, the

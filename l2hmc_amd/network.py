@@ -42,6 +42,7 @@ class Dense:
 class _DenseSTQ:
     """Shared machinery: three input layers, one hidden layer, three heads."""
     q_tanh = 0
+    _tracks_versions = False   # pack() follows in-place / reassigned reference-layout weights (GaugeDynamics' nets)
     _layer_names = ()   # (first-input, second-input, time, hidden, S, T, Q)
     _coeff_names = ()
 
@@ -105,13 +106,52 @@ class _DenseSTQ:
         cs, cq = (getattr(self, n) for n in self._coeff_names)
         return dict(
             w1_t=torch.cat([la.kernel, lb.kernel], dim=0).t().contiguous(),         # [H][Ka+Kb]
-            wt=lt.kernel.contiguous(),                                               # [2][H]
+            wt=lt.kernel.clone(memory_format=torch.contiguous_format),              # [2][H]
             b1=(la.bias + lb.bias + lt.bias).contiguous(),
             wh_t=lh.kernel.t().contiguous(),                                          # [H][H] (out, in)
-            bh=lh.bias.contiguous(),
+            bh=lh.bias.clone(memory_format=torch.contiguous_format),
             whd_t=torch.stack([ls.kernel.t(), ltr.kernel.t(), lq.kernel.t()]).contiguous(),  # [3][D][H]
             bhd=torch.stack([ls.bias, ltr.bias, lq.bias]).contiguous(),               # [3][D]
-            coeff_s=cs.reshape(-1).contiguous(), coeff_q=cq.reshape(-1).contiguous())
+            coeff_s=cs.reshape(-1).clone(memory_format=torch.contiguous_format),
+            coeff_q=cq.reshape(-1).clone(memory_format=torch.contiguous_format))
+
+    def unpack_grads(self, g):
+        """Inverse of _pack_tensors for gradients: buffers in the layout of struct l2hmc_dense_grads ->
+        {state_dict name: gradient shaped like that reference-layout tensor}.  The packed first-layer bias stands
+        for three biases, each of which gets its whole gradient."""
+        la, lb, lt, lh, ls, ltr, lq = self._layer_names
+        cs, cq = self._coeff_names
+        Ka = getattr(self, la).kernel.shape[0]
+        out = {la + "/W": g["w1_t"][:, :Ka].t().contiguous(), lb + "/W": g["w1_t"][:, Ka:].t().contiguous(),
+               lt + "/W": g["wt"], la + "/b": g["b1"], lb + "/b": g["b1"].clone(), lt + "/b": g["b1"].clone(),
+               lh + "/W": g["wh_t"].t().contiguous(), lh + "/b": g["bh"],
+               cs: g["coeff_s"].reshape(1, -1), cq: g["coeff_q"].reshape(1, -1)}
+        for i, n in enumerate((ls, ltr, lq)):
+            out[n + "/W"] = g["whd_t"][i].t().contiguous()
+            out[n + "/b"] = g["bhd"][i].clone()
+        return out
+
+    def _ref_tensors(self):
+        """Every reference-layout tensor the packed buffers are built from."""
+        out = []
+        for layer in self._layers():
+            out.extend(layer.variables)
+        out.extend(getattr(self, n) for n in self._coeff_names)
+        return out
+
+    def _check_ref_version(self):
+        """Without a trainer's flat master copy the reference-layout tensors are the weights, and a caller (a
+        torch.optim step, an in-place edit, a reassigned tensor) may move them: drop the packed buffers when any
+        tensor's identity or version counter changed since they were built.  Host-side only, no sync."""
+        if not self._tracks_versions or getattr(self, "_flat", None) is not None:
+            return
+        held = self._ref_tensors()
+        sig = tuple([(id(t), t._version) for t in held])
+        if sig != getattr(self, "_ref_sig", None):
+            self._packed = None
+            if hasattr(self, "_front"):
+                self._front = None
+            self._ref_sig, self._ref_held = sig, held     # held: the ids stay those tensors' while compared
 
     SEGMENTS = ("w1_t", "wt", "b1", "wh_t", "bh", "whd_t", "bhd", "coeff_s", "coeff_q")
 
@@ -170,12 +210,17 @@ class _DenseSTQ:
         setattr(self, cq, v["coeff_q"].reshape(1, -1).clone())
 
     def pack(self):
-        """struct l2hmc_dense_net over device buffers (kept alive here); rebuilt after load_state()."""
+        """struct l2hmc_dense_net over device buffers (kept alive here); rebuilt after load_state() and, while no
+        trainer owns a flat master copy, after any reference-layout tensor changed (_check_ref_version)."""
+        self._check_ref_version()
         if self._packed is None:
             la, lb, lt, lh, ls, ltr, lq = self._layers()
             Ka, Kb, H, D = la.kernel.shape[0], lb.kernel.shape[0], lh.kernel.shape[0], ls.kernel.shape[1]
-            bufs = ({k: self._flat[1][k] for k in self.SEGMENTS} if getattr(self, "_flat", None) is not None
-                    else self._pack_tensors())
+            if getattr(self, "_flat", None) is not None:
+                bufs = {k: self._flat[1][k] for k in self.SEGMENTS}
+            else:
+                with torch.no_grad():        # new buffers: a pending autograd tape keeps the ones it ran with
+                    bufs = self._pack_tensors()
             st = _lib.DenseNet(D=D, H=H, Ka=Ka, Kb=Kb, q_tanh=self.q_tanh, reserved=0, packed=None,
                                **{k: _lib.dev_ptr(v, name=k) for k, v in bufs.items()})
             L = _lib.lib()
@@ -217,6 +262,7 @@ class _DenseSTQ:
 class GenericNet(_DenseSTQ):
     """generic_net.py:20-146.  kwargs: x_dim, num_hidden, factor, name_scope, links_shape."""
     q_tanh = 0
+    _tracks_versions = True
     _layer_names = ("v_layer", "x_layer", "t_layer", "h_layer", "scale_layer", "translation_layer",
                     "transformation_layer")
     _coeff_names = ("coeff_scale", "coeff_transformation")
@@ -266,6 +312,7 @@ class ConvNet3D(_DenseSTQ):
     (gauge_dynamics.py:123-134): _input_shape, links_shape, x_dim, factor, spatial_size, num_hidden,
     num_filters, filter_sizes, name_scope, data_format."""
     q_tanh = 0
+    _tracks_versions = True
     _layer_names = GenericNet._layer_names
     _coeff_names = GenericNet._coeff_names
     _conv_names = ("conv_x1", "conv_v1", "conv_x2", "conv_v2")
@@ -343,11 +390,25 @@ class ConvNet3D(_DenseSTQ):
     def _extra_flat_tensors(self):
         return {k: getattr(getattr(self, layer), attr).contiguous() for k, (layer, attr) in self._FRONT.items()}
 
+    def _ref_tensors(self):
+        return super()._ref_tensors() + [t for n in self._conv_names for t in getattr(self, n).variables]
+
+    def unpack_grads(self, g):
+        out = super().unpack_grads(g)
+        for k, (layer, attr) in self._FRONT.items():
+            out[layer + ("/W" if attr == "kernel" else "/b")] = g[k]
+        return out
+
     def pack_front(self):
         """struct l2hmc_conv3d_front over the Keras-layout kernels (or their slices of the flat training buffer)."""
+        self._check_ref_version()
         if self._front is None:
             flat = getattr(self, "_flat", None)
-            bufs = ({k: flat[1][k] for k in self._FRONT} if flat is not None else self._extra_flat_tensors())
+            if flat is not None:
+                bufs = {k: flat[1][k] for k in self._FRONT}
+            else:
+                with torch.no_grad():
+                    bufs = {k: v.clone(memory_format=torch.contiguous_format) for k, v in self._extra_flat_tensors().items()}
             self._front = _lib.Conv3DFront(F=int(self.num_filters), reserved=0,
                                            **{k: _lib.dev_ptr(v, name=k) for k, v in bufs.items()})
             self._front_bufs = bufs          # keep the tensors alive

@@ -452,6 +452,22 @@ int l2hmc_small_train_step(const l2hmc_small_plan* plan, const float* x0, const 
                            int64_t rows, float scale, float inv_count, float* x_out, float* v_out,
                            float* p_accept, float* terms, float* grads, void* ws, size_t ws_bytes,
                            l2hmc_stream_t stream);
+/* Vector-Jacobian product of l2hmc_small_trajectory for ANY cotangents: what a caller's autograd needs to
+ * differentiate a loss of its own through Dynamics.forward / .backward / propose.  Per row r (direction dir[r],
+ * NULL = all forward) the forward from (x0, v0) is recomputed on-chip, then the reverse pass of
+ * l2hmc_small_train_step runs, seeded with the cotangents g_x, g_v [rows][x_dim] of (x_N, v_N) and g_logdet, g_p
+ * [rows] of (sumlogdet, p_accept); each may be NULL (= 0).  With p = min(1, exp(D)), D = H0 - H1 + sumlogdet
+ * (NaN D: p = 0), dD = g_p p where p < 1 and 0 otherwise; dD reaches x_N and v_N through -H1, sumlogdet, and the
+ * start state through +H0 (dx0 += dD grad E(x0) with the tempered energy, dv0 += dD v0).
+ * Outputs: grads (device, overwritten) = [xnet | vnet | d/d eps] in the layout and the fixed summation order of
+ * l2hmc_small_train_step (d/d alpha = eps d/d eps); dx0, dv0 [rows][x_dim] the gradients with respect to each row's
+ * own start state; x_out, v_out, sumlogdet, p_accept the recomputed forward.  Each of dx0, dv0, x_out, v_out,
+ * sumlogdet, p_accept may be NULL (not written).  Same launch geometry as l2hmc_small_train_step, no atomics:
+ * reproducible.  Workspace: l2hmc_small_train_ws_bytes(plan, rows). */
+int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, const float* v0, const int32_t* dir,
+                    int64_t rows, const float* g_x, const float* g_v, const float* g_logdet, const float* g_p,
+                    float* dx0, float* dv0, float* grads, float* x_out, float* v_out, float* sumlogdet,
+                    float* p_accept, void* ws, size_t ws_bytes, l2hmc_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Counter-based RNG (Philox4x32-10) standing in for tf.random_normal /

@@ -347,6 +347,9 @@ struct SmallTrainArgs {
   float* x_out; float* v_out; float* p_accept; float* terms;
   float* part;        // [workgroups][2 * gsize + 1]: xnet gradient | vnet gradient | d loss / d eps
   unsigned long long* stamps;      // diagnostic builds only
+  // cotangent seed (VJP instance only; each may be NULL = 0): of x_N, v_N [rows][dim], sumlogdet, p [rows]
+  const float* g_x; const float* g_v; const float* g_logdet; const float* g_p;
+  float* dx0; float* dv0; float* sumlogdet;       // outputs of the VJP instance, each may be NULL
 };
 
 #ifdef L2HMC_STAMPS
@@ -364,7 +367,10 @@ struct SmallTrainArgs {
 #define ST_ADD(slot, t0) do {} while (0)
 #endif
 
-template <int HP, int MD, int TH>
+// VJP = false: the reverse pass is seeded by the squared-jump-distance loss (l2hmc_small_train_step);
+// VJP = true: by the caller's cotangents of (x_N, v_N, sumlogdet, p) (l2hmc_small_vjp), and the gradient with
+// respect to the start state is written out.  Everything else is the same code.
+template <int HP, int MD, int TH, bool VJP>
 __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   constexpr int kSlots = TH / kLPC, kSmallThreads = TH, SS = kSlots + 4;
   // diagnostic cycle shares (class 7): 0 prologue, 1 forward, 2 loss, 3 net re-evaluation, 4 sub-update + head deltas,
@@ -499,33 +505,57 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
 
   ST_ADD(1, st_t);
   st_t = ST_NOW();
-  // ------------------------------------------------------------------ loss (mog_model.py:336-355)
-  float dist2 = 0.f;
-#pragma unroll
-  for (int d = 0; d < kMaxDim; ++d)
-    if (d < dim) dist2 += (xs[d] - x[d]) * (xs[d] - x[d]);
-  const float vj = dist2 * p + 1e-4f;
-  const float term = a.scale / vj - vj / a.scale;
-  if (live && lsub == 0) {
+  float dx[kMaxDim], dv[kMaxDim], dD, dl;
+  if constexpr (!VJP) {
+    // ---------------------------------------------------------------- loss (mog_model.py:336-355)
+    float dist2 = 0.f;
 #pragma unroll
     for (int d = 0; d < kMaxDim; ++d)
-      if (d < dim) {
-        a.x_out[r * dim + d] = x[d];
-        a.v_out[r * dim + d] = v[d];
-      }
-    a.p_accept[r] = p;
-    a.terms[r] = term;
-  }
-  const float dvj = live ? a.inv_count * (-a.scale / (vj * vj) - 1.f / a.scale) : 0.f;
-  const float dp = dvj * dist2;
-  const float dD = p < 1.f ? dp * p : 0.f;         // through exp(min(., 0))
-  float dx[kMaxDim], dv[kMaxDim];
+      if (d < dim) dist2 += (xs[d] - x[d]) * (xs[d] - x[d]);
+    const float vj = dist2 * p + 1e-4f;
+    const float term = a.scale / vj - vj / a.scale;
+    if (live && lsub == 0) {
 #pragma unroll
-  for (int d = 0; d < kMaxDim; ++d) {
-    dx[d] = d < dim ? dvj * p * (-2.f) * (xs[d] - x[d]) - dD * g[d] : 0.f;
-    dv[d] = d < dim ? -dD * v[d] : 0.f;
+      for (int d = 0; d < kMaxDim; ++d)
+        if (d < dim) {
+          a.x_out[r * dim + d] = x[d];
+          a.v_out[r * dim + d] = v[d];
+        }
+      a.p_accept[r] = p;
+      a.terms[r] = term;
+    }
+    const float dvj = live ? a.inv_count * (-a.scale / (vj * vj) - 1.f / a.scale) : 0.f;
+    const float dp = dvj * dist2;
+    dD = p < 1.f ? dp * p : 0.f;                   // through exp(min(., 0))
+#pragma unroll
+    for (int d = 0; d < kMaxDim; ++d) {
+      dx[d] = d < dim ? dvj * p * (-2.f) * (xs[d] - x[d]) - dD * g[d] : 0.f;
+      dv[d] = d < dim ? -dD * v[d] : 0.f;
+    }
+    dl = dD;
+  } else {
+    // ---------------------------------------------------------------- caller's cotangents
+    if (live && lsub == 0) {
+#pragma unroll
+      for (int d = 0; d < kMaxDim; ++d)
+        if (d < dim) {
+          if (a.x_out) a.x_out[r * dim + d] = x[d];
+          if (a.v_out) a.v_out[r * dim + d] = v[d];
+        }
+      if (a.p_accept) a.p_accept[r] = p;
+      if (a.sumlogdet) a.sumlogdet[r] = logdet;
+    }
+    const float gp = (live && a.g_p) ? a.g_p[r] : 0.f;
+    dD = p < 1.f ? gp * p : 0.f;                   // d Delta, Delta = H0 - H1 + sumlogdet
+#pragma unroll
+    for (int d = 0; d < kMaxDim; ++d) {
+      const float gx = (d < dim && live && a.g_x) ? a.g_x[r * dim + d] : 0.f;
+      const float gv = (d < dim && live && a.g_v) ? a.g_v[r * dim + d] : 0.f;
+      dx[d] = d < dim ? gx - dD * g[d] : 0.f;
+      dv[d] = d < dim ? gv - dD * v[d] : 0.f;
+    }
+    dl = ((live && a.g_logdet) ? a.g_logdet[r] : 0.f) + dD;
   }
-  const float dl = dD;
   float deps = 0.f;
 
   ST_ADD(2, st_t);
@@ -717,6 +747,21 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       }
     }
   }
+  if constexpr (VJP) {
+    // the start state's gradient: the trajectory's part (dx, dv now hold it) + d Delta through +H0
+    if (live && lsub == 0 && (a.dx0 || a.dv0)) {
+      float x0r[kMaxDim], g0[kMaxDim], e0;
+#pragma unroll
+      for (int d = 0; d < kMaxDim; ++d) x0r[d] = d < dim ? a.x0[r * dim + d] : 0.f;
+      energy_grad<MD>(Lt, dim, K, isg, inv_temp, x0r, &e0, g0);
+#pragma unroll
+      for (int d = 0; d < kMaxDim; ++d)
+        if (d < dim) {
+          if (a.dx0) a.dx0[r * dim + d] = dx[d] + dD * g0[d];
+          if (a.dv0) a.dv0[r * dim + d] = dv[d] + dD * a.v0[r * dim + d];
+        }
+    }
+  }
   // ------------------------------------------------------------------ partial gradients of this workgroup
   const int gsize = small_grad_floats(H, dim);
   float* out = a.part + (size_t)blockIdx.x * (2 * gsize + 1);
@@ -769,55 +814,62 @@ extern "C" size_t l2hmc_small_train_ws_bytes(const l2hmc_small_plan* plan, int64
   return sizeof(float) * (size_t)ceil_div(rows, kSlotsMin) * (2 * g + 1);
 }
 
-extern "C" int l2hmc_small_train_step(const l2hmc_small_plan* plan, const float* x0, const float* v0,
-                                      const int32_t* dir, int64_t rows, float scale, float inv_count, float* x_out,
-                                      float* v_out, float* p_accept, float* terms, float* grads, void* ws,
-                                      size_t ws_bytes, l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(plan != nullptr, "small_train_step: plan is NULL");
-  L2HMC_REQUIRE(!plan->hmc, "small_train_step: hmc plans have no trainable networks");
+// the plan / shape checks both entries make before any launch
+static int small_train_check(const l2hmc_small_plan* plan, int64_t rows, const char* who) {
+  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  L2HMC_REQUIRE(!plan->hmc, "%s: hmc plans have no trainable networks", who);
   const int dim = plan->x_dim, H = plan->num_nodes, N = plan->trajectory_length;
   L2HMC_REQUIRE(plan->target.dim == dim && dim > 0 && dim <= kMaxDim && plan->target.K > 0 && plan->target.K <= kMaxMix,
-                "small_train_step: bad target / x_dim");
+                "%s: bad target / x_dim", who);
   L2HMC_REQUIRE(plan->target.mu && plan->target.prec && (plan->target.is_gaussian || plan->target.log_const) &&
                     plan->target.temperature > 0.f,
-                "small_train_step: bad target parameters");
-  L2HMC_REQUIRE(N > 0 && plan->masks != nullptr && H > 0 && H <= 64, "small_train_step: bad plan (num_nodes 1..64)");
-  L2HMC_REQUIRE(rows >= 0 && scale > 0.f, "small_train_step: bad rows / scale");
-  if (rows == 0) return L2HMC_OK;
-  L2HMC_REQUIRE(x0 && v0 && x_out && v_out && p_accept && terms && grads && ws, "small_train_step: NULL pointer");
+                "%s: bad target parameters", who);
+  L2HMC_REQUIRE(N > 0 && plan->masks != nullptr && H > 0 && H <= 64, "%s: bad plan (num_nodes 1..64)", who);
+  L2HMC_REQUIRE(rows >= 0, "%s: bad rows", who);
+  return L2HMC_OK;
+}
+
+static int small_train_check_nets(const l2hmc_small_plan* plan, const char* who) {
+  const int dim = plan->x_dim, H = plan->num_nodes;
   const l2hmc_dense_net* nets[2] = {&plan->xnet, &plan->vnet};
   for (const l2hmc_dense_net* n : nets) {
-    L2HMC_REQUIRE(n->D == dim && n->Ka == dim && n->Kb == dim && n->H == H, "small_train_step: net shape mismatch");
+    L2HMC_REQUIRE(n->D == dim && n->Ka == dim && n->Kb == dim && n->H == H, "%s: net shape mismatch", who);
     L2HMC_REQUIRE(n->w1_t && n->wt && n->b1 && n->wh_t && n->bh && n->whd_t && n->bhd && n->coeff_s && n->coeff_q,
-                  "small_train_step: net has NULL weight pointer");
+                  "%s: net has NULL weight pointer", who);
   }
+  return L2HMC_OK;
+}
+
+// small_train_kernel (loss or VJP seed) over `rows`, then the ordered reduction of the workgroup partials into grads
+template <bool VJP>
+static int small_train_launch(const l2hmc_small_plan* plan, SmallTrainArgs a, float* grads, size_t ws_bytes,
+                              hipStream_t s, const char* who) {
+  const int dim = plan->x_dim, H = plan->num_nodes, N = plan->trajectory_length;
+  const int64_t rows = a.rows;
   if (ws_bytes < l2hmc_small_train_ws_bytes(plan, rows)) {
-    set_error("small_train_step: workspace %zu < %zu bytes", ws_bytes, l2hmc_small_train_ws_bytes(plan, rows));
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, l2hmc_small_train_ws_bytes(plan, rows));
     return L2HMC_ERR_WORKSPACE;
   }
   const int HP = H <= 16 ? 16 : 64;
   const bool d2 = dim <= 2;          // x_dim 2 instance for the benchmark targets
-  hipStream_t s = (hipStream_t)stream;
   int nwg = 0;
   // (TH = 512 -- 32 chains, two waves per SIMD, one round of workgroups for 8192 chains -- was measured: 1.59 ms per
   //  step against 1.46 for two rounds of 16-chain workgroups: the kernel is bound by LDS throughput, not latency)
   auto run = [&](auto hp, auto md) -> int {
     constexpr int HPc = decltype(hp)::value, MDc = decltype(md)::value;
     const size_t lds = small_train_lds<HPc, MDc, 256>(dim, plan->target.K, N);
-    L2HMC_REQUIRE(lds <= 160 * 1024, "small_train_step: LDS image %zu B too large (trajectory too long?)", lds);
+    L2HMC_REQUIRE(lds <= 160 * 1024, "%s: LDS image %zu B too large (trajectory too long?)", who, lds);
     static DeviceOnce attr_once;
     if (attr_once.pending()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_train_kernel<HPc, MDc, 256>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_train_kernel<HPc, MDc, 256, VJP>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr_once.done();
     }
-    SmallTrainArgs a{*plan, x0, v0, dir, rows, scale, inv_count, x_out, v_out, p_accept, terms, static_cast<float*>(ws),
-                     nullptr};
 #ifdef L2HMC_STAMPS
     a.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
 #endif
     nwg = (int)ceil_div(rows, 256 / kLPC);
-    hipLaunchKernelGGL((small_train_kernel<HPc, MDc, 256>), dim3(nwg), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((small_train_kernel<HPc, MDc, 256, VJP>), dim3(nwg), dim3(256), lds, s, a);
     return L2HMC_OK;
   };
   using I16 = std::integral_constant<int, 16>;
@@ -831,7 +883,36 @@ extern "C" int l2hmc_small_train_step(const l2hmc_small_plan* plan, const float*
   L2HMC_CHECK_LAUNCH("small_train");
   const int64_t count = 2 * (int64_t)small_grad_floats(H, dim) + 1;
   hipLaunchKernelGGL(small_reduce_kernel, dim3((unsigned)ceil_div(count, 64)), dim3(256), 0, s,
-                     static_cast<const float*>(ws), nwg, count, grads);
+                     static_cast<const float*>(a.part), nwg, count, grads);
   L2HMC_CHECK_LAUNCH("small_reduce");
   return L2HMC_OK;
+}
+
+extern "C" int l2hmc_small_train_step(const l2hmc_small_plan* plan, const float* x0, const float* v0,
+                                      const int32_t* dir, int64_t rows, float scale, float inv_count, float* x_out,
+                                      float* v_out, float* p_accept, float* terms, float* grads, void* ws,
+                                      size_t ws_bytes, l2hmc_stream_t stream) {
+  const char* who = "small_train_step";
+  if (int rc = small_train_check(plan, rows, who)) return rc;
+  L2HMC_REQUIRE(scale > 0.f, "small_train_step: bad rows / scale");
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x0 && v0 && x_out && v_out && p_accept && terms && grads && ws, "small_train_step: NULL pointer");
+  if (int rc = small_train_check_nets(plan, who)) return rc;
+  SmallTrainArgs a{*plan, x0, v0, dir, rows, scale, inv_count, x_out, v_out, p_accept, terms, static_cast<float*>(ws),
+                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  return small_train_launch<false>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
+}
+
+extern "C" int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, const float* v0, const int32_t* dir,
+                               int64_t rows, const float* g_x, const float* g_v, const float* g_logdet,
+                               const float* g_p, float* dx0, float* dv0, float* grads, float* x_out, float* v_out,
+                               float* sumlogdet, float* p_accept, void* ws, size_t ws_bytes, l2hmc_stream_t stream) {
+  const char* who = "small_vjp";
+  if (int rc = small_train_check(plan, rows, who)) return rc;
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x0 && v0 && grads && ws, "small_vjp: NULL pointer (x0, v0, grads and ws are required)");
+  if (int rc = small_train_check_nets(plan, who)) return rc;
+  SmallTrainArgs a{*plan, x0, v0, dir, rows, 0.f, 0.f, x_out, v_out, p_accept, nullptr, static_cast<float*>(ws),
+                   nullptr, g_x, g_v, g_logdet, g_p, dx0, dv0, sumlogdet};
+  return small_train_launch<true>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
 }

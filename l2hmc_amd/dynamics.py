@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import autograd_toy as _autograd
 
 
 class Dynamics(object):
@@ -53,6 +54,22 @@ class Dynamics(object):
     @property
     def eps(self):
         return torch.exp(self.alpha)
+
+    @property
+    def variables(self):
+        """alpha (eps = exp(alpha)), then XNet's and VNet's reference-layout tensors (layer order, kernel before bias,
+        then the two scale vectors): what a torch optimiser takes.  Each may take requires_grad_(); the one-launch
+        kernels then record an autograd graph (l2hmc_amd/autograd_toy.py)."""
+        out = [self.alpha]
+        if not self.hmc:
+            out += list(self.XNet.variables) + list(self.VNet.variables)
+        return out
+
+    @property
+    def trainable_variables(self):
+        """`variables`, without alpha unless eps_trainable (:51-60)."""
+        v = self.variables
+        return v if self.eps_trainable else v[1:]
 
     def _init_mask(self):
         """:85-96 (legacy global NumPy stream)."""
@@ -160,7 +177,7 @@ class Dynamics(object):
                 "this Dynamics runs layer by layer (arbitrary energy function, x_dim > 8 or more than 64 hidden units): "
                 "the one-launch kernels (l2hmc_small_*) and the one-launch training step do not hold it")
         p = _lib.SmallPlan(x_dim=self.x_dim, trajectory_length=self.trajectory_length, hmc=int(bool(self.hmc)),
-                           eps=float(self.eps), first_layer_form=int(self.first_layer_form), masks=self.mask.data_ptr(),
+                           eps=float(self.eps.detach()), first_layer_form=int(self.first_layer_form), masks=self.mask.data_ptr(),
                            target=self._target.struct(self._temp()), num_nodes=0)
         if not self.hmc:
             p.xnet, p.vnet = self.XNet.pack(), self.VNet.pack()
@@ -176,6 +193,10 @@ class Dynamics(object):
 
     def _run(self, x, init_v, backward, log_jac):
         x = _lib.as_dev(x, self._device).reshape(-1, self.x_dim)
+        if _autograd.wants_grad(self, x, init_v):
+            _autograd.check_differentiable(self)          # before any draw
+            v = _lib.as_dev(init_v, self._device) if init_v is not None else self._normal(tuple(x.shape))
+            return _autograd.run(self, x, v, backward, log_jac)
         v = _lib.as_dev(init_v, self._device) if init_v is not None else self._normal(tuple(x.shape))
         if self.layered:
             return self._layered_run(x, v, backward, log_jac)
@@ -213,13 +234,14 @@ class Dynamics(object):
         return (X[:B], V[:B], third[:B]), (X[B:], V[B:], third[B:])
 
     def forward(self, x, init_v=None, aux=None, log_path=False, log_jac=False):
-        """:255-281."""
+        """:255-281.  Differentiable (torch.autograd, l2hmc_amd/autograd_toy.py) when grad mode is on and x, init_v,
+        alpha or a network weight requires grad."""
         if aux is not None:
             raise NotImplementedError("aux inputs are only used by the out-of-scope VAE scripts")
         return self._run(x, init_v, False, log_jac)
 
     def backward(self, x, init_v=None, aux=None, log_jac=False):
-        """:283-310."""
+        """:283-310.  Differentiable as `forward`."""
         if aux is not None:
             raise NotImplementedError("aux inputs are only used by the out-of-scope VAE scripts")
         return self._run(x, init_v, True, log_jac)

@@ -444,6 +444,7 @@ class MLPNet(_DenseSTQ):
     """utils/network.py:89-114: what `network(x_dim, scope, factor, num_nodes)` returns.
     Callable on [a, b, t, aux]; aux is ignored (the `lambda _: 0.` slot)."""
     q_tanh = 1
+    _tracks_versions = True   # a torch.optim step on the reference-layout weights reaches the kernels (autograd_toy)
     _layer_names = ("embed_1", "embed_2", "embed_3", "linear_1", "linear_s", "linear_t", "linear_f")
     _coeff_names = ("scale_s", "scale_f")
 

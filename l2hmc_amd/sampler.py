@@ -6,6 +6,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from . import autograd_toy as _autograd
 
 
 def _uniform(dynamics, n):
@@ -32,8 +33,16 @@ def tf_accept(x, Lx, px, u=None, dynamics=None):
 
 def propose(x, dynamics, init_v=None, aux=None, do_mh_step=False, log_jac=False, *,
             init_v_backward=None, dir_bits=None, u=None):
-    """:28-55 -> (Lx, Lv, px, outputs)."""
+    """:28-55 -> (Lx, Lv, px, outputs).  Differentiable (torch.autograd, l2hmc_amd/autograd_toy.py) when grad mode
+    is on and x, init_v, init_v_backward, dynamics.alpha or a network weight requires grad: Lx, Lv, px and
+    outputs[0] then carry a graph.  The draws are the ones the no-grad call takes.  Each chain's gradient flows
+    through the direction its bit picks only; the other direction is multiplied by an exact 0 (:35-41)."""
     x = _lib.as_dev(x, dynamics._device)
+    if _autograd.wants_grad(dynamics, x, init_v, init_v_backward):
+        _autograd.check_differentiable(dynamics)          # before any draw
+        if aux is not None:
+            raise NotImplementedError("aux inputs are only used by the out-of-scope VAE scripts")
+        return _propose_grad(x, dynamics, init_v, do_mh_step, log_jac, init_v_backward, dir_bits, u)
     if dynamics.hmc:
         Lx, Lv, px = dynamics.forward(x, init_v=init_v, aux=aux)
         return Lx, Lv, px, [tf_accept(x, Lx, px, u, dynamics)]
@@ -71,3 +80,22 @@ def propose(x, dynamics, init_v=None, aux=None, do_mh_step=False, log_jac=False,
     Lv = Lvm if init_v is not None else None       # :43-45 (quirk Q6)
     outputs = [out] if do_mh_step else []
     return Lx, Lv, px, outputs
+
+
+def _propose_grad(x, dynamics, init_v, do_mh_step, log_jac, init_v_backward, dir_bits, u):
+    """The L2HMC branch with an autograd graph.  Draws in the order of the piecewise path below, which are the
+    Philox streams of l2hmc_small_propose: direction bits (draw0), forward momenta (draw0 + 1), backward momenta
+    (draw0 + 2), MH uniforms (draw0 + 3)."""
+    dev = dynamics._device
+    x = x.reshape(-1, dynamics.x_dim)
+    B = x.shape[0]
+    mask = (_uniform(dynamics, B) >= 0.5).to(torch.float32) if dir_bits is None else _lib.as_dev(dir_bits, dev)
+    vf = _lib.as_dev(init_v, dev) if init_v is not None else dynamics._normal(tuple(x.shape))
+    vb = init_v_backward if init_v_backward is not None else init_v
+    vb = _lib.as_dev(vb, dev) if vb is not None else dynamics._normal(tuple(x.shape))
+    if do_mh_step and u is None:
+        u = _uniform(dynamics, B)
+    Lx, Lvm, px, out = _autograd.propose(dynamics, x, vf, vb, mask, _lib.as_dev(u, dev) if do_mh_step else None,
+                                         log_jac)
+    Lv = Lvm if init_v is not None else None       # :43-45 (quirk Q6)
+    return Lx, Lv, px, ([out] if do_mh_step else [])

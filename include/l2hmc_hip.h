@@ -469,6 +469,60 @@ int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, const float* 
                     float* dx0, float* dv0, float* grads, float* x_out, float* v_out, float* sumlogdet,
                     float* p_accept, void* ws, size_t ws_bytes, l2hmc_stream_t stream);
 
+/* Hessian-vector product of the packed target's tempered energy: out[r] = Hess(energy / temperature)(x[r]) . u[r],
+ * x, u, out [rows][dim] (the closed form of the second derivative of distributions.py:151-158 / :63-68).  What a
+ * reverse pass through VNet([x, grad E(x), t]) needs for the gradient input. */
+int l2hmc_mog_energy_hvp(const l2hmc_mog_target* tgt, const float* x, const float* u, int64_t rows, float* out,
+                         l2hmc_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Training of the layer-by-layer generic Dynamics (any x_dim, num_nodes, energy; mog_model.py:324-363 through
+ * utils/dynamics.py:120-225): the building blocks of a taped reverse pass, orchestrated by
+ * l2hmc_amd/layered_train.py.  Every entry takes ANY positive D, H, Ka, Kb (bounds-checked loads where widths are
+ * not multiples of 32 or rows are not 16-byte aligned); rows = 0 is a no-op.
+ * ------------------------------------------------------------------------ */
+/* l2hmc_stq_dense with the post-relu activations h1, h2 [rows][H] written to caller buffers instead of the
+ * workspace: same kernels, so S, T, Q are bit-identical to l2hmc_stq_dense. */
+int l2hmc_stq_dense_taped(const l2hmc_dense_net* net, const float* a, const float* b, const float* bmask,
+                          float t_cos, float t_sin, int64_t rows, float* S, float* T, float* Q, float* h1, float* h2,
+                          l2hmc_stream_t stream);
+
+/* Vector-Jacobian products of l2hmc_lf_update_v / l2hmc_lf_update_x (utils/dynamics.py:123-223, both directions).
+ * dv_out / dx_out [rows][D]: cotangent of the output state; dlogdet [rows]: cotangent of the per-row log-det (may be
+ * NULL = 0).  Outputs (overwritten): the cotangents of the input state (dv / dx), of the gradient input (dgrad, v
+ * update) or of v (dv, x update: the part through this update only), of S, T, Q [rows][D], and deps [rows], each
+ * row's partial d/d eps.  Outputs must not alias inputs. */
+int l2hmc_lf_update_v_vjp(const float* v, const float* grad, const float* S, const float* T, const float* Q,
+                          float eps, int32_t dir, int64_t rows, int32_t D, const float* dv_out, const float* dlogdet,
+                          float* dv, float* dgrad, float* dS, float* dT, float* dQ, float* deps,
+                          l2hmc_stream_t stream);
+int l2hmc_lf_update_x_vjp(const float* x, const float* v, const float* keep, const float* S, const float* T,
+                          const float* Q, float eps, int32_t dir, int64_t rows, int32_t D, const float* dx_out,
+                          const float* dlogdet, float* dx, float* dv, float* dS, float* dT, float* dQ, float* deps,
+                          l2hmc_stream_t stream);
+
+/* Backward-data of one network call.  Input: the call's S, Q, the cotangents dS, dT, dQ [rows][D] and its taped
+ * h1, h2 [rows][H].  Outputs: dpre [rows][3D] the head pre-activation cotangents (tanh' and exp(coeff) applied),
+ * dsq [rows][2D] = [dS * S | dQ * Q] (the per-row coefficient gradients; may be NULL), dz2, dz1 [rows][H] the
+ * pre-activation cotangents of the hidden layers (relu-gated), din [rows][Ka+Kb] = [d/da | d/db] of the network
+ * inputs.  Workspace (transposed weights): l2hmc_dense_backward_data_ws_bytes(net). */
+size_t l2hmc_dense_backward_data_ws_bytes(const l2hmc_dense_net* net);
+int l2hmc_dense_backward_data(const l2hmc_dense_net* net, const float* S, const float* Q, const float* dS,
+                              const float* dT, const float* dQ, const float* h1, const float* h2, int64_t rows,
+                              float* dpre, float* dsq, float* dz2, float* dz1, float* din, void* ws, size_t ws_bytes,
+                              l2hmc_stream_t stream);
+
+/* Weight gradients of one network over R taped rows (all its calls stacked along rows): in [R][Ka+Kb] the network
+ * inputs [a | b], h1, h2, dz1, dz2 [R][H], dpre [R][3D], dsq [R][2D] as above, tcs [R][2] each row's (cos, sin) time
+ * input.  g (overwritten) gets w1_t, wt, b1, wh_t, bh, whd_t, bhd, coeff_s, coeff_q in the layout of struct
+ * l2hmc_dense_net.  Split-k products and column sums, every reduction in a fixed order (no float atomics): two calls
+ * give the same bits.  Workspace: l2hmc_dense_weight_grads_ws_bytes(net, R). */
+size_t l2hmc_dense_weight_grads_ws_bytes(const l2hmc_dense_net* net, int64_t R);
+int l2hmc_dense_weight_grads(const l2hmc_dense_net* net, int64_t R, const float* in, const float* h1,
+                             const float* h2, const float* dz1, const float* dz2, const float* dpre, const float* dsq,
+                             const float* tcs, const l2hmc_dense_grads* g, void* ws, size_t ws_bytes,
+                             l2hmc_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * Counter-based RNG (Philox4x32-10) standing in for tf.random_normal /
  * tf.random_uniform (gauge_dynamics.py:223,246,269).  Same (seed, offset, n)

@@ -119,6 +119,15 @@ _PROTOS = {
     "l2hmc_small_train_step": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64, _F, _F, _P, _P, _P, _P, _P, _P, _SZ,
                                          _P]),
     "l2hmc_small_vjp": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64] + [_P] * 11 + [_P, _SZ, _P]),
+    "l2hmc_mog_energy_hvp": (C.c_int, [C.POINTER(MogTarget), _P, _P, _I64, _P, _P]),
+    "l2hmc_stq_dense_taped": (C.c_int, [C.POINTER(DenseNet), _P, _P, _P, _F, _F, _I64, _P, _P, _P, _P, _P, _P]),
+    "l2hmc_lf_update_v_vjp": (C.c_int, [_P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P] + [_P] * 6 + [_P]),
+    "l2hmc_lf_update_x_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P] + [_P] * 6 + [_P]),
+    "l2hmc_dense_backward_data_ws_bytes": (_SZ, [C.POINTER(DenseNet)]),
+    "l2hmc_dense_backward_data": (C.c_int, [C.POINTER(DenseNet)] + [_P] * 7 + [_I64] + [_P] * 6 + [_SZ, _P]),
+    "l2hmc_dense_weight_grads_ws_bytes": (_SZ, [C.POINTER(DenseNet), _I64]),
+    "l2hmc_dense_weight_grads": (C.c_int, [C.POINTER(DenseNet), _I64] + [_P] * 8 + [C.POINTER(DenseGrads), _P, _SZ,
+                                                                                      _P]),
     "l2hmc_profile_begin": (C.c_int, [_I32]),
     "l2hmc_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "l2hmc_fill_normal": (C.c_int, [_P, _I64, _U64, _U64, _P]),

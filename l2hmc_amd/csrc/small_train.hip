@@ -340,6 +340,27 @@ __device__ inline void energy_hvp(const float* Lt, int dim, int K, int is_gaussi
   }
 }
 
+// l2hmc_mog_energy_hvp: one thread per row, the target in LDS (as mog_energy_grad_kernel)
+__global__ __launch_bounds__(kSmallThreads) void mog_energy_hvp_kernel(l2hmc_mog_target t, const float* __restrict__ x,
+                                                                       const float* __restrict__ u, int64_t rows,
+                                                                       float* __restrict__ out) {
+  extern __shared__ float lds[];
+  load_target(t, lds);
+  __syncthreads();
+  const int64_t r = (int64_t)blockIdx.x * kSmallThreads + threadIdx.x;
+  if (r >= rows) return;
+  float xv[kMaxDim], uv[kMaxDim], hv[kMaxDim];
+#pragma unroll
+  for (int d = 0; d < kMaxDim; ++d) {
+    xv[d] = d < t.dim ? x[r * t.dim + d] : 0.f;
+    uv[d] = d < t.dim ? u[r * t.dim + d] : 0.f;
+  }
+  energy_hvp<kMaxDim>(lds, t.dim, t.K, t.is_gaussian, 1.f / t.temperature, xv, uv, hv);
+#pragma unroll
+  for (int d = 0; d < kMaxDim; ++d)
+    if (d < t.dim) out[r * t.dim + d] = hv[d];
+}
+
 struct SmallTrainArgs {
   l2hmc_small_plan plan;
   const float* x0; const float* v0; const int* dir; int64_t rows;
@@ -915,4 +936,22 @@ extern "C" int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, co
   SmallTrainArgs a{*plan, x0, v0, dir, rows, 0.f, 0.f, x_out, v_out, p_accept, nullptr, static_cast<float*>(ws),
                    nullptr, g_x, g_v, g_logdet, g_p, dx0, dv0, sumlogdet};
   return small_train_launch<true>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
+}
+
+extern "C" int l2hmc_mog_energy_hvp(const l2hmc_mog_target* tgt, const float* x, const float* u, int64_t rows,
+                                    float* out, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(tgt != nullptr, "mog_energy_hvp: target is NULL");
+  L2HMC_REQUIRE(tgt->dim > 0 && tgt->dim <= kMaxDim && tgt->K > 0 && tgt->K <= kMaxMix,
+                "mog_energy_hvp: target dim=%d (max %d), K=%d (max %d)", tgt->dim, kMaxDim, tgt->K, kMaxMix);
+  L2HMC_REQUIRE(tgt->mu && tgt->prec && (tgt->is_gaussian || tgt->log_const), "mog_energy_hvp: NULL target parameter");
+  L2HMC_REQUIRE(!tgt->is_gaussian || tgt->K == 1, "mog_energy_hvp: gaussian needs K == 1");
+  L2HMC_REQUIRE(tgt->temperature > 0.f, "mog_energy_hvp: temperature must be > 0");
+  L2HMC_REQUIRE(rows >= 0, "mog_energy_hvp: rows = %lld < 0", (long long)rows);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x && u && out, "mog_energy_hvp: NULL pointer");
+  const size_t lds = sizeof(float) * target_view(tgt->dim, tgt->K).size;
+  hipLaunchKernelGGL(mog_energy_hvp_kernel, dim3((unsigned)ceil_div(rows, kSmallThreads)), dim3(kSmallThreads), lds,
+                     (hipStream_t)stream, *tgt, x, u, rows, out);
+  L2HMC_CHECK_LAUNCH("mog_energy_hvp");
+  return L2HMC_OK;
 }

@@ -2,14 +2,17 @@
   l2hmc/mog_model.py:324-355  _create_loss   (squared jump distance of the x and z chains)
   l2hmc/mog_model.py:357-363  _create_optimizer (AdamOptimizer.minimize)
   l2hmc/mog_model.py:183-192  exponential_decay learning rate
-Forward, loss and the whole reverse pass run in ONE library call (l2hmc_small_train_step); Adam is the same
-flat-buffer kernel the lattice trainer uses.  Chains run in the direction `propose` picks for them
+Forward, loss and the whole reverse pass run in ONE library call (l2hmc_small_train_step); a layer-by-layer dynamics
+(`Dynamics.layered`: any x_dim, num_nodes or energy) runs a taped forward and a hand-written reverse pass through the
+layered kernels instead (l2hmc_amd/layered_train.py), into the same gradient buffer.  Adam is the same flat-buffer
+kernel the lattice trainer uses.  Chains run in the direction `propose` picks for them
 (sampler.py:35-41 multiplies the other direction by an exact 0)."""
 import ctypes as C
 
 import torch
 
 from . import _lib
+from . import layered_train as _layered_train
 from .dist import active as _active_dist
 
 
@@ -34,6 +37,7 @@ class DynamicsTrainer:
         self._m, self._v = torch.zeros_like(self.grads), torch.zeros_like(self.grads)
         self._alpha_dev = dyn.alpha.detach().to(dev, torch.float32).reshape(1).clone()
         self._ws = _lib.Workspace()
+        self._layered = None
 
     def grad_views(self):
         out, off = {}, 0
@@ -72,13 +76,19 @@ class DynamicsTrainer:
         v0 = torch.where(fwd[:, None], torch.cat([vf_x, vf_z]), torch.cat([vb_x, vb_z])).contiguous()
         dirs = (~fwd).to(torch.int32).contiguous()
         R = 2 * B
-        xN, vN = torch.empty_like(x0), torch.empty_like(x0)
-        p, terms = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
-        plan, L = dyn._plan(), _lib.lib()
-        ws, nb = self._ws.get(L.l2hmc_small_train_ws_bytes(C.byref(plan), R), dev)
-        _lib.check(L.l2hmc_small_train_step(C.byref(plan), x0.data_ptr(), v0.data_ptr(), dirs.data_ptr(), R, self.scale,
-                                            1.0 / (B * self.world), xN.data_ptr(), vN.data_ptr(), p.data_ptr(),
-                                            terms.data_ptr(), self.grads.data_ptr(), ws, nb, _lib.stream_ptr(self.dynamics._device)))
+        if dyn.layered:          # decided per call: a test (or a caller) may switch a dynamics to the layered path
+            if self._layered is None:
+                self._layered = _layered_train.LayeredStep(self)
+            xN, p, terms = self._layered(x0, v0, fwd, 1.0 / (B * self.world))
+        else:
+            xN, vN = torch.empty_like(x0), torch.empty_like(x0)
+            p, terms = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
+            plan, L = dyn._plan(), _lib.lib()
+            ws, nb = self._ws.get(L.l2hmc_small_train_ws_bytes(C.byref(plan), R), dev)
+            _lib.check(L.l2hmc_small_train_step(C.byref(plan), x0.data_ptr(), v0.data_ptr(), dirs.data_ptr(), R,
+                                                self.scale, 1.0 / (B * self.world), xN.data_ptr(), vN.data_ptr(),
+                                                p.data_ptr(), terms.data_ptr(), self.grads.data_ptr(), ws, nb,
+                                                _lib.stream_ptr(self.dynamics._device)))
         self.grads[-1] *= float(dyn.eps)              # d/d alpha = eps * d/d eps  (utils/dynamics.py:51-60)
         buf = torch.stack([terms.sum(dtype=torch.float32), torch.full((), float(B), dtype=torch.float32, device=dev)])
         if self.dist is not None:

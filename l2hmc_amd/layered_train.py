@@ -1,0 +1,243 @@
+"""Training step of a layer-by-layer `Dynamics` (any x_dim, num_nodes or energy; `Dynamics.layered`): the loss of
+mog_model.py:336-355 and its gradient with respect to both networks and eps (mog_model.py:357-363,
+tf.gradients(loss, dynamics.variables)), by hand-written reverse mode over a tape.
+
+Forward: the 2B stacked chains are split by the direction `propose` picked for them; each direction runs ONE taped
+layered trajectory (step masks and the time input depend on the direction), through the same kernels as
+`Dynamics.forward` / `.backward` -- l2hmc_stq_dense_taped is l2hmc_stq_dense with its activations kept --, so the
+proposals and p are those bits.  Per sub-update the tape holds the network inputs [a | b] (VNet: x, grad E(x);
+XNet: v, keep * x), h1, h2, S, T, Q, and references to the state the update consumed.
+
+Reverse: sub-updates in reverse order.  l2hmc_lf_update_{v,x}_vjp give the cotangents of the input state, of S, T, Q
+(and of grad E for a momentum update) and per-row d/d eps partials; l2hmc_dense_backward_data carries (dS, dT, dQ)
+through the network to its inputs.  VNet's inputs are (x, grad E(x)), so d/dx gains d/da + Hess(E)(x) . (dg + d/db):
+the closed form (l2hmc_mog_energy_hvp) for the packed targets, torch double-backward of the caller's energy
+otherwise -- the reference's tf.gradients semantics, so a callable energy must be twice differentiable in torch.
+The weight gradients are formed once per network, over all its calls' tapes stacked along rows
+(l2hmc_dense_weight_grads), straight into the trainer's flat buffer [xnet | vnet | d/d eps].
+
+Tape size per network: 2 N_LF calls x 2B rows x (Ka+Kb + 4H + 3D (S, T, Q) + 3D + 2D + 2) floats; with both
+networks about 4 N_LF 2B (2D + 2H + 3D) 4 bytes for the forward part, and as much again for the reverse-pass
+cotangents (at x_dim 50, H 100, N_LF 10, 2B = 8192: about 1.2 GB in all)."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+
+class _NetTape:
+    """Row-stacked tape of every call of one network: call c of a trajectory over n rows owns rows [off, off + n)."""
+
+    def __init__(self, net, rows, dev):
+        st = net.pack()
+        self.D, self.H, self.Kin = st.D, st.H, st.Ka + st.Kb
+        D, H = self.D, self.H
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)   # noqa: E731
+        self.rows = rows
+        self.inp, self.h1, self.h2 = f(rows, self.Kin), f(rows, H), f(rows, H)
+        self.S, self.T, self.Q = f(rows, D), f(rows, D), f(rows, D)
+        self.dz1, self.dz2, self.dpre, self.dsq = f(rows, H), f(rows, H), f(rows, 3 * D), f(rows, 2 * D)
+        self.tcs = f(rows, 2)
+        self.off = 0
+
+    def take(self, n):
+        sl = slice(self.off, self.off + n)
+        self.off += n
+        return sl
+
+
+def energy_hvp(dyn, x, u):
+    """Hess(energy / temperature)(x) . u per row: l2hmc_mog_energy_hvp for a packed target, torch double-backward of
+    the caller's energy otherwise."""
+    if x.shape[0] == 0:
+        return torch.zeros_like(x)
+    if dyn._target is not None:
+        out = torch.empty_like(x)
+        st = dyn._target.struct(dyn._temp())
+        _lib.check(_lib.lib().l2hmc_mog_energy_hvp(C.byref(st), x.data_ptr(), u.contiguous().data_ptr(), x.shape[0],
+                                                   out.data_ptr(), _lib.stream_ptr(dyn._device)))
+        return out
+    with torch.enable_grad():
+        xg = x.detach().clone().requires_grad_(True)
+        e = dyn._fn(xg)
+        if e.shape != (xg.shape[0],):
+            raise ValueError(f"energy_function must return one energy per row: got {tuple(e.shape)}")
+        (g,) = torch.autograd.grad(e.sum(), xg, create_graph=True)
+        if not g.requires_grad:          # an energy linear in x: zero Hessian
+            return torch.zeros_like(x)
+        (hv,) = torch.autograd.grad(g, xg, grad_outputs=u, allow_unused=True)
+    if hv is None:
+        return torch.zeros_like(x)
+    return (hv.to(torch.float32) / dyn._temp()).contiguous()
+
+
+class LayeredStep:
+    """One `DynamicsTrainer.calc_loss_and_grads` of a layered dynamics (held by the trainer for its workspaces)."""
+
+    def __init__(self, trainer):
+        self.tr = trainer
+        self._ws_bwd, self._ws_wg = _lib.Workspace(), _lib.Workspace()
+
+    # ---- forward ---------------------------------------------------------------------------------------------
+    def _sub_v(self, x, v, tc, ts, d, lj, tape, subs):
+        dyn, L, s = self.tr.dynamics, _lib.lib(), _lib.stream_ptr(self.tr.dynamics._device)
+        n, D = x.shape
+        g = dyn.grad_energy(x)
+        sl = tape.take(n)
+        tape.inp[sl, :D] = x
+        tape.inp[sl, D:] = g
+        tape.tcs[sl, 0], tape.tcs[sl, 1] = tc, ts
+        S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
+        _lib.check(L.l2hmc_stq_dense_taped(C.byref(dyn.VNet.pack()), x.data_ptr(), g.data_ptr(), None, tc, ts, n,
+                                           S.data_ptr(), T.data_ptr(), Q.data_ptr(), tape.h1[sl].data_ptr(),
+                                           tape.h2[sl].data_ptr(), s))
+        out, ld = torch.empty_like(v), torch.empty(n, dtype=torch.float32, device=v.device)
+        _lib.check(L.l2hmc_lf_update_v(v.data_ptr(), g.data_ptr(), S.data_ptr(), T.data_ptr(), Q.data_ptr(),
+                                       float(dyn.eps), d, n, D, out.data_ptr(), ld.data_ptr(), s))
+        lj += ld
+        subs.append(("v", sl, x, v, g, None))
+        return out
+
+    def _sub_x(self, x, v, keep, tc, ts, d, lj, tape, subs):
+        dyn, L, s = self.tr.dynamics, _lib.lib(), _lib.stream_ptr(self.tr.dynamics._device)
+        n, D = x.shape
+        b = keep * x
+        sl = tape.take(n)
+        tape.inp[sl, :D] = v
+        tape.inp[sl, D:] = b
+        tape.tcs[sl, 0], tape.tcs[sl, 1] = tc, ts
+        S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
+        _lib.check(L.l2hmc_stq_dense_taped(C.byref(dyn.XNet.pack()), v.data_ptr(), b.data_ptr(), None, tc, ts, n,
+                                           S.data_ptr(), T.data_ptr(), Q.data_ptr(), tape.h1[sl].data_ptr(),
+                                           tape.h2[sl].data_ptr(), s))
+        out, ld = torch.empty_like(x), torch.empty(n, dtype=torch.float32, device=x.device)
+        _lib.check(L.l2hmc_lf_update_x(x.data_ptr(), v.data_ptr(), keep.data_ptr(), S.data_ptr(), T.data_ptr(),
+                                       Q.data_ptr(), float(dyn.eps), d, n, D, out.data_ptr(), ld.data_ptr(), s))
+        lj += ld
+        subs.append(("x", sl, x, v, None, keep))
+        return out
+
+    def _trajectory(self, x0, v0, d, tx, tv):
+        """Dynamics._layered_run with every intermediate taped: -> (x_N, v_N, sumlogdet, p, subs)."""
+        dyn = self.tr.dynamics
+        N = dyn.trajectory_length
+        x, v = x0, v0
+        lj = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
+        subs = []
+        for i in range(N):
+            step = N - i - 1 if d else i
+            t = dyn._format_time(step)
+            tc, ts = float(t[0, 0]), float(t[0, 1])
+            m, mb = dyn._get_mask(step)
+            first, second = (mb, m) if d else (m, mb)
+            v = self._sub_v(x, v, tc, ts, d, lj, tv, subs)
+            x = self._sub_x(x, v, first, tc, ts, d, lj, tx, subs)
+            x = self._sub_x(x, v, second, tc, ts, d, lj, tx, subs)
+            v = self._sub_v(x, v, tc, ts, d, lj, tv, subs)
+        return x, v, lj, dyn.p_accept(x0, v0, x, v, lj), subs
+
+    # ---- reverse ---------------------------------------------------------------------------------------------
+    def _backward_data(self, net, tape, sl, dS, dT, dQ):
+        L, dev = _lib.lib(), self.tr.dynamics._device
+        st = net.pack()
+        n = dS.shape[0]
+        din = torch.empty(n, tape.Kin, dtype=torch.float32, device=dev)
+        ws, nb = self._ws_bwd.get(L.l2hmc_dense_backward_data_ws_bytes(C.byref(st)), dev)
+        _lib.check(L.l2hmc_dense_backward_data(
+            C.byref(st), tape.S[sl].data_ptr(), tape.Q[sl].data_ptr(), dS.data_ptr(), dT.data_ptr(), dQ.data_ptr(),
+            tape.h1[sl].data_ptr(), tape.h2[sl].data_ptr(), n, tape.dpre[sl].data_ptr(), tape.dsq[sl].data_ptr(),
+            tape.dz2[sl].data_ptr(), tape.dz1[sl].data_ptr(), din.data_ptr(), ws, nb, _lib.stream_ptr(dev)))
+        return din
+
+    def _reverse(self, subs, d, dx, dv, dld, tx, tv):
+        """Walk one trajectory's sub-updates backwards from the cotangents of (x_N, v_N, sumlogdet); fills the tapes'
+        cotangent slices and returns the per-row d/d eps partials of every sub-update."""
+        dyn, L, s = self.tr.dynamics, _lib.lib(), _lib.stream_ptr(self.tr.dynamics._device)
+        eps = float(dyn.eps)
+        parts = []
+        for kind, sl, xin, vin, g, keep in reversed(subs):
+            tape = tv if kind == "v" else tx
+            n, D = xin.shape
+            S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
+            dS, dT, dQ = torch.empty_like(S), torch.empty_like(S), torch.empty_like(S)
+            de = torch.empty(n, dtype=torch.float32, device=xin.device)
+            if kind == "v":
+                dv_in, dg = torch.empty_like(dv), torch.empty_like(dv)
+                _lib.check(L.l2hmc_lf_update_v_vjp(vin.data_ptr(), g.data_ptr(), S.data_ptr(), T.data_ptr(),
+                                                   Q.data_ptr(), eps, d, n, D, dv.data_ptr(), dld.data_ptr(),
+                                                   dv_in.data_ptr(), dg.data_ptr(), dS.data_ptr(), dT.data_ptr(),
+                                                   dQ.data_ptr(), de.data_ptr(), s))
+                din = self._backward_data(dyn.VNet, tape, sl, dS, dT, dQ)
+                dx = dx + din[:, :D] + energy_hvp(dyn, xin, (dg + din[:, D:]).contiguous())
+                dv = dv_in
+            else:
+                dx_in, dv_part = torch.empty_like(dx), torch.empty_like(dx)
+                _lib.check(L.l2hmc_lf_update_x_vjp(xin.data_ptr(), vin.data_ptr(), keep.data_ptr(), S.data_ptr(),
+                                                   T.data_ptr(), Q.data_ptr(), eps, d, n, D, dx.data_ptr(),
+                                                   dld.data_ptr(), dx_in.data_ptr(), dv_part.data_ptr(), dS.data_ptr(),
+                                                   dT.data_ptr(), dQ.data_ptr(), de.data_ptr(), s))
+                din = self._backward_data(dyn.XNet, tape, sl, dS, dT, dQ)
+                dx = (dx_in + keep * din[:, D:]).contiguous()
+                dv = (dv + dv_part + din[:, :D]).contiguous()
+            dx, dv = dx.contiguous(), dv.contiguous()
+            parts.append(de)
+        return parts
+
+    def _weight_grads(self, net, tape, gv):
+        L, dev = _lib.lib(), self.tr.dynamics._device
+        st = net.pack()
+        R = tape.off
+        g = _lib.DenseGrads(**{f[0]: gv[f[0]].data_ptr() for f in _lib.DenseGrads._fields_})
+        ws, nb = self._ws_wg.get(L.l2hmc_dense_weight_grads_ws_bytes(C.byref(st), R), dev)
+        _lib.check(L.l2hmc_dense_weight_grads(
+            C.byref(st), R, tape.inp.data_ptr(), tape.h1.data_ptr(), tape.h2.data_ptr(), tape.dz1.data_ptr(),
+            tape.dz2.data_ptr(), tape.dpre.data_ptr(), tape.dsq.data_ptr(), tape.tcs.data_ptr(), C.byref(g), ws, nb,
+            _lib.stream_ptr(dev)))
+
+    # ---- the step --------------------------------------------------------------------------------------------
+    def __call__(self, x0, v0, fwd, inv_count):
+        """x0, v0 [2B][D] stacked start states, fwd [2B] bool (True = forward).  Writes the trainer's gradient buffer
+        ([xnet | vnet | d/d eps]) and returns (x_N, p, terms) in the stacked row order."""
+        tr = self.tr
+        dyn, dev = tr.dynamics, tr.dynamics._device
+        R, D = x0.shape
+        N = dyn.trajectory_length
+        groups = [(0, torch.nonzero(fwd).reshape(-1)), (1, torch.nonzero(~fwd).reshape(-1))]
+        tx = _NetTape(dyn.XNet, 2 * N * R, dev)
+        tv = _NetTape(dyn.VNet, 2 * N * R, dev)
+        xN, vN = torch.empty_like(x0), torch.empty_like(x0)
+        lj, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
+        runs = []
+        for d, idx in groups:
+            if idx.numel() == 0:
+                continue
+            xs, vs = x0[idx].contiguous(), v0[idx].contiguous()
+            X, V, J, P, subs = self._trajectory(xs, vs, d, tx, tv)
+            xN[idx], vN[idx], lj[idx], p[idx] = X, V, J, P
+            runs.append((d, idx, subs))
+        # loss (mog_model.py:336-355) and its cotangents at (x_N, v_N, sumlogdet)
+        scale = tr.scale
+        sq = ((x0 - xN) ** 2).sum(1)
+        vv = sq * p + 1e-4
+        terms = scale / vv - vv / scale
+        dvv = inv_count * (-scale / (vv * vv) - 1.0 / scale)
+        # p = exp(min(H0 - H1 + sumlogdet, 0)): d p / d(H0 - H1 + sumlogdet) = p where p < 1, else 0
+        dD = torch.where(p < 1, dvv * sq * p, torch.zeros_like(p))
+        live = (p > 0)[:, None]
+        zero = torch.zeros_like(x0)
+        gE = torch.zeros_like(x0)
+        if bool(live.any()):
+            gE = dyn.grad_energy(xN)
+        dxN = torch.where(live, (dvv * p)[:, None] * 2.0 * (xN - x0) - dD[:, None] * gE, zero)
+        dvN = torch.where(live, -dD[:, None] * vN, zero)
+        dld = dD.contiguous()
+        parts = []
+        for d, idx, subs in runs:
+            parts += self._reverse(subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(), dld[idx].contiguous(), tx, tv)
+        gv = tr.grad_views()
+        self._weight_grads(dyn.XNet, tx, gv["xnet"])
+        self._weight_grads(dyn.VNet, tv, gv["vnet"])
+        deps = torch.cat(parts).sum() if parts else torch.zeros((), dtype=torch.float32, device=dev)
+        tr.grads[-1] = deps
+        return xN, p, terms

@@ -2,6 +2,12 @@
 """Throughput of the L2HMC hot path on MI355X: chain-leapfrog-steps per second.
 
     python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--scaling {weak,strong}] [--dump-outputs DIR]
+                    [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line: nothing else.
+Everything beyond the headline figure -- roofline and per-kernel timings, ESS, the CPU baseline, the other
+architectures / batch sizes / direction modes, the one-rank RCCL and training-step legs and the `configs` table --
+runs only with `--full` (each of them can still be left out there with its --no-* option).
 
 One "step" is one pass of the hot path over one batch of synthetic chains, everything resident in HBM:
   * lattice configs (3, 4, 5): one `apply_transition` (dynamics/gauge_dynamics.py:195-259) -- momenta, direction
@@ -10,8 +16,8 @@ One "step" is one pass of the hot path over one batch of synthetic chains, every
   * toy configs (1, 2): one `propose(x, dynamics, do_mh_step=True)` (utils/sampler.py:28-59).
 
 `--config c` selects BASELINE.json configs[c-1]; the default (3) is the configuration the metric is quoted on
-(2D U(1) 8x8, beta 2.0, batch 2048 per GPU, 10 leapfrog steps, GenericNet H=512, fp32) and its line also
-carries a compact `configs` table with the other four workloads at their per-GPU size.
+(2D U(1) 8x8, beta 2.0, batch 2048 per GPU, 10 leapfrog steps, GenericNet H=512, fp32); with --full its line
+also carries a compact `configs` table with the other four workloads at their per-GPU size.
 
 N > 1: a bare `python bench.py --gpus N` starts its own N ranks (child processes through
 torch.distributed.run, before this process touches the GPU); under torch.distributed.run (WORLD_SIZE set) the
@@ -29,8 +35,8 @@ executed count is twice that (both directions) and is what the roofline FLOPs us
 sub-updates form only the columns their mask lets move: `executed_macs_per_lf`) and can therefore never exceed 1;
 the reference graph's own count (every first layer and every head column formed anew) divided
 by the same time is reported beside it as `reference_flops_equiv_tflops` / `reference_flops_equiv_frac`.
-A secondary leg that fails is reported under an "error" key AND makes the process exit non-zero after the line is
-printed.
+A secondary leg (--full) that fails is reported under an "error" key AND makes the process exit non-zero after the
+line is printed.
 """
 import argparse
 import ctypes as C
@@ -548,13 +554,18 @@ def main():
     ap.add_argument("--selected-only", action="store_true",
                     help="integrate only the direction each chain's coin selects (not the reference's work)")
     ap.add_argument("--layered", action="store_true", help="use the layer-by-layer kernels (no fused trajectory)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every secondary measurement (roofline, ESS, CPU baseline, other "
+                         "architectures / batches / modes, training legs, configs table); the --no-* options below "
+                         "leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the roofline and the legs timed beside it (config 3)")
     ap.add_argument("--no-configs-table", action="store_true",
-                    help="skip the compact table of the other BASELINE configs in the default line")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary training-step timing")
+                    help="with --full: skip the compact table of the other BASELINE configs")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the secondary training-step timing")
     ap.add_argument("--no-trained-ess", action="store_true",
-                    help="skip the 250-step training run + ESS/sec of the trained sampler (N = 1 only)")
+                    help="with --full: skip the 250-step training run + ESS/sec of the trained sampler (N = 1 only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the arrays the last timed step returned (rank 0's chains) as "
                          "DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed seeded sample of chains "
@@ -613,8 +624,11 @@ def main():
     both = not args.selected_only
     failed = []                                   # secondary legs that threw: reported AND a non-zero exit
 
+    full = args.full
+    # keep: config 3's timed steps hold on to their outputs in plain runs as well (the ESS of --full is computed from
+    # them), so that the timed loop, and with it ms_per_step, is the same with and without --full
     res, st = run_workload(job, cfg, scaling, steps, warmup, both=both, layered=args.layered,
-                           roofline=not args.no_roofline, keep=(c["kind"] == "gauge" and cfg == 3),
+                           roofline=full and not args.no_roofline, keep=(c["kind"] == "gauge" and cfg == 3),
                            dump=args.dump_outputs is not None and rank == 0)
     lo, hi = res["chains_this_rank"]
     dumped = dump_outputs(st.pop("outputs"), args.dump_outputs, lo) if "outputs" in st else None
@@ -643,7 +657,7 @@ def main():
         out["dump_outputs"] = dumped
     x, step, dyn = st["x"], st["step"], st["dyn"]
 
-    if cfg == 3:
+    if cfg == 3 and full:
         sampler, stats, BATCH = st["sampler"], st["stats"], st["B"]
         beta, n_lf = c["beta"], c["N"]
         dt = st["dt"]
@@ -931,7 +945,7 @@ def main():
             del tr
 
     # ---- CPU baseline: op-for-op torch-CPU port of the reference graph, bounded sample, rank 0 at N = 1 ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_for(cfg, st)
         # BASELINE.md publishes no number for this metric (the reference has no benchmark): the only baseline that can
         # exist here is the one timed beside it, so the ratio is against THAT and labelled as such
@@ -940,8 +954,8 @@ def main():
                                    f"{out['cpu_baseline']['cores']} host threads of this box (north_star target >= 50x at "
                                    "1 GPU); BASELINE.md holds no published number for this metric")
 
-    # ---- the other BASELINE configs at their per-GPU size (N = 1, default line only): compact table ----
-    if cfg == 3 and world == 1 and not args.no_configs_table and not args.layered and both:
+    # ---- the other BASELINE configs at their per-GPU size (N = 1, config 3 only): compact table ----
+    if cfg == 3 and world == 1 and full and not args.no_configs_table and not args.layered and both:
         table = [{"cfg": 3, "workload": c["name"], "chains": st["B"], "ms_per_step": out["ms_per_step"],
                   "value": out["value"], "tflops": res["whole_step_tflops"], "frac": res["whole_step_frac"],
                   "reference_flops_equiv_frac": res["reference_flops_equiv_frac"],

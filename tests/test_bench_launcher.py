@@ -167,3 +167,26 @@ def test_dump_outputs_of_two_runs_are_identical(tmp_path):
             assert a.dtype == np.float32 and a.shape[0] == lines[0]["config"]["global_batch"]
             assert np.isfinite(a).all()
             np.testing.assert_array_equal(a, b)
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone():
+    """Without --full the line carries the headline figure and nothing measured beside it (config 3 at 8 steps
+    would add ESS, roofline, CPU baseline and the configs table with --full); --full brings the secondary
+    measurements back."""
+    r = _run(["--gpus", "1", "--steps", "8", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["metric"] == bench.HEADLINE_METRIC and out["unit"] == "chain-leapfrog-steps/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 8 and out["warmup"] == 1
+    c = bench.CONFIGS[3]
+    assert out["value"] == pytest.approx(c["per_gpu"] * c["N"] / (out["ms_per_step"] * 1e-3), rel=1e-9)
+    assert not {"roofline", "cpu_baseline", "configs", "vs_baseline_what"} & set(out), sorted(out)
+    assert out["vs_baseline"] is None
+    assert not {"ess_per_mcmc_step", "conv3D_arch", "twice_the_chains", "selected_only", "world1_rccl",
+                "train_step", "after_260_train_steps"} & set(out["config"]), sorted(out["config"])
+
+    r = _run(["--gpus", "1", "--config", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["roofline"]["all_kernels"] and "cpu_baseline" not in out

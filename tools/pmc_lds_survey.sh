@@ -12,7 +12,7 @@ rocprofv3 --kernel-trace --pmc $CTR -d $OUT/cfg4 -o pmc --output-format csv -- p
 rocprofv3 --kernel-trace --pmc $CTR -d $OUT/train -o pmc --output-format csv -- python3 $ROOT/tools/train_perf.py 2048 10 2 > $OUT/train.log 2>&1 || { tail -5 $OUT/train.log; exit 1; }
 rocprofv3 --kernel-trace --pmc $CTR -d $OUT/trainc -o pmc --output-format csv -- python3 $ROOT/tools/train_perf.py 2048 10 2 conv3D > $OUT/trainc.log 2>&1 || { tail -5 $OUT/trainc.log; exit 1; }
 rocprofv3 --kernel-trace --pmc $CTR -d $OUT/toy -o pmc --output-format csv -- python3 $ROOT/bench.py --config 2 --steps 5 --warmup 2 --no-cpu-baseline --no-roofline > $OUT/toy.log 2>&1 || { tail -5 $OUT/toy.log; exit 1; }
-rocprofv3 --kernel-trace --pmc $CTR -d $OUT/cfg3 -o pmc --output-format csv -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-configs-table --no-trained-ess > $OUT/cfg3.log 2>&1 || { tail -5 $OUT/cfg3.log; exit 1; }
+rocprofv3 --kernel-trace --pmc $CTR -d $OUT/cfg3 -o pmc --output-format csv -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-configs-table --no-trained-ess > $OUT/cfg3.log 2>&1 || { tail -5 $OUT/cfg3.log; exit 1; }
 python3 - <<'PY'
 import csv, glob, collections, os
 base=os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r03lds'

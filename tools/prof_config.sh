@@ -9,6 +9,6 @@ OUT="$ROOT/gpurun_out/$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d "$OUT/prof_cfg$CFG" -o bench --output-format csv -- \
-  python3 "$ROOT/bench.py" --config "$CFG" --scaling weak --no-cpu-baseline "$@" > "$OUT/cfg${CFG}_bench.json" 2> "$OUT/cfg${CFG}_bench.err"
+  python3 "$ROOT/bench.py" --full --config "$CFG" --scaling weak --no-cpu-baseline "$@" > "$OUT/cfg${CFG}_bench.json" 2> "$OUT/cfg${CFG}_bench.err"
 cp "$(find "$OUT/prof_cfg$CFG" -name '*kernel_stats.csv' | head -1)" "$OUT/cfg${CFG}_kernel_stats.csv"
 echo "done: $OUT/cfg${CFG}_kernel_stats.csv"

@@ -91,7 +91,9 @@ int l2hmc_kinetic_energy(const float* v, int64_t rows, int32_t D, float* out, l2
  *     kernels -- identical arithmetic, slower loads;
  *   - the whole-trajectory kernels exist for D = 128 (T*X = 64, X a power of two): GenericNet H = 512 and
  *     ConvNet3D F = 8 / H = 256; other shapes run layer by layer (l2hmc_dense_pack_bytes() == 0 says which);
- *   - the TRAINING entry points (l2hmc_gauge_train_*) need D, H, Ka, Kb multiples of 32;
+ *   - the TRAINING entry points (l2hmc_gauge_train_*) need D, H, Ka, Kb multiples of 32; GaugeTrainer trains
+ *     GenericNet plans of other widths through the layered-training entries below (l2hmc_stq_dense_taped, ...,
+ *     l2hmc_u1_force_hvp);
  *   - ConvNet3D needs T and X multiples of 4 (two 2x2 poolings) and filter sizes (3,3,2), (2,2,2).
  * ------------------------------------------------------------------------ */
 typedef struct l2hmc_dense_net {
@@ -474,6 +476,14 @@ int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, const float* 
  * reverse pass through VNet([x, grad E(x), t]) needs for the gradient input. */
 int l2hmc_mog_energy_hvp(const l2hmc_mog_target* tgt, const float* x, const float* u, int64_t rows, float* out,
                          l2hmc_stream_t stream);
+
+/* out[r] = beta * Hess(S)(x[r]) . u[r] for the 2-D U(1) action S of l2hmc_u1_action_force (whose `force` is
+ * beta * dS/dx): the force's stencil with sin(P) replaced by cos(P) * P[u].  x, u, out [rows][2*T*X].  What a reverse
+ * pass through VNet([x, force(x), t]) needs for the force input, at any T x X.  One wave per row, the chain and the
+ * per-plaquette cos(P) * P[u] staged in LDS (20 bytes per site): a lattice whose row does not fit one workgroup's
+ * LDS (more than 8192 sites) is refused.  rows = 0 is a no-op; out must not alias x or u. */
+int l2hmc_u1_force_hvp(const float* x, const float* u, int64_t rows, int32_t T, int32_t X, float beta, float* out,
+                       l2hmc_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Training of the layer-by-layer generic Dynamics (any x_dim, num_nodes, energy; mog_model.py:324-363 through

@@ -120,6 +120,7 @@ _PROTOS = {
                                          _P]),
     "l2hmc_small_vjp": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64] + [_P] * 11 + [_P, _SZ, _P]),
     "l2hmc_mog_energy_hvp": (C.c_int, [C.POINTER(MogTarget), _P, _P, _I64, _P, _P]),
+    "l2hmc_u1_force_hvp": (C.c_int, [_P, _P, _I64, _I32, _I32, _F, _P, _P]),
     "l2hmc_stq_dense_taped": (C.c_int, [C.POINTER(DenseNet), _P, _P, _P, _F, _F, _I64, _P, _P, _P, _P, _P, _P]),
     "l2hmc_lf_update_v_vjp": (C.c_int, [_P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P] + [_P] * 6 + [_P]),
     "l2hmc_lf_update_x_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P] + [_P] * 6 + [_P]),

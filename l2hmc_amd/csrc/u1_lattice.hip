@@ -255,6 +255,56 @@ __global__ __launch_bounds__(256) void kinetic_kernel(const float* __restrict__ 
   if (lane == 0) out[r] = 0.5f * acc;
 }
 
+// l2hmc_u1_force_hvp: out = beta * Hess(S)(x) . u, one wave per row.  The force's stencil with sin(P) replaced by
+// cos(P) * P[u] (lattice.py:246-262 differentiated once more; the scheme of train.hip's vnet_in_bwd_kernel, on plain
+// [rows][D] arrays).  Per wave the chain x, u [D] and the per-plaquette cos(P) * P[u] [sites] sit in LDS: 20 bytes per
+// site.  `wpg` waves (rows) per workgroup, chosen on the host from T * X.
+constexpr int kHvpLdsPerGroup = 64 * 1024;    // target: two or more workgroups per CU where the lattice allows
+constexpr int kHvpLdsMax = 160 * 1024;        // one workgroup may take the whole LDS of a CU
+
+__global__ __launch_bounds__(256) void u1_force_hvp_kernel(const float* __restrict__ x, const float* __restrict__ u,
+                                                           int64_t rows, int T, int X, float beta, int wpg,
+                                                           float* __restrict__ out) {
+  extern __shared__ float lds[];
+  const int sites = T * X, D = 2 * sites;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * wpg + wave;
+  const bool live = row < rows;
+  float* xs = lds + (size_t)wave * (2 * D + sites);
+  float* us = xs + D;
+  float* cp = us + D;
+  if (live) {
+    const float* xr = x + row * D;
+    const float* ur = u + row * D;
+    for (int c = lane; c < D; c += kWave) {
+      xs[c] = xr[c];
+      us[c] = ur[c];
+    }
+  }
+  __syncthreads();
+  if (live) {
+    for (int s = lane; s < sites; s += kWave) {
+      const int i = s / X, j = s - i * X;
+      const int jr = (j + 1 == X) ? 0 : j + 1, id = (i + 1 == T) ? 0 : i + 1;
+      const int e = 2 * s, er = 2 * (i * X + jr), ed = 2 * (id * X + j);
+      const float P = xs[e] - xs[e + 1] - xs[er] + xs[ed + 1];
+      const float Pu = us[e] - us[e + 1] - us[er] + us[ed + 1];
+      cp[s] = cosf(P) * Pu;
+    }
+  }
+  __syncthreads();
+  if (live) {
+    float* o = out + row * D;
+    for (int s = lane; s < sites; s += kWave) {
+      const int i = s / X, j = s - i * X;
+      const int jl = (j == 0) ? X - 1 : j - 1, iu = (i == 0) ? T - 1 : i - 1;
+      const float c = cp[s];
+      o[2 * s] = beta * (c - cp[i * X + jl]);         // d/dx0[i,j]
+      o[2 * s + 1] = beta * (-c + cp[iu * X + j]);    // d/dx1[i,j]
+    }
+  }
+}
+
 int launch_u1_action_force(const float* x, int64_t rows, int T, int X, float beta, float* action,
                            float* force, float* avg_plaq, float* top_charge, hipStream_t stream) {
   const int sites = T * X;
@@ -308,6 +358,31 @@ extern "C" int l2hmc_u1_action_force(const float* x, int64_t rows, int32_t T, in
   L2HMC_REQUIRE(ceil_div(rows, 1) < (1ll << 31), "u1_action_force: too many rows");
   return launch_u1_action_force(x, rows, T, X, beta, action, force, avg_plaq, top_charge,
                                 (hipStream_t)stream);
+}
+
+extern "C" int l2hmc_u1_force_hvp(const float* x, const float* u, int64_t rows, int32_t T, int32_t X, float beta,
+                                  float* out, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(rows >= 0 && T > 0 && X > 0, "u1_force_hvp: bad shape rows=%lld T=%d X=%d", (long long)rows, T, X);
+  const int64_t per_wave = (int64_t)sizeof(float) * 5 * (int64_t)T * X;     // x, u [2*T*X] + cos(P) * P[u] [T*X]
+  L2HMC_REQUIRE(per_wave <= kHvpLdsMax, "u1_force_hvp: lattice %dx%d does not fit LDS (%lld B per row, max %d)", T, X,
+                (long long)per_wave, kHvpLdsMax);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x && u && out, "u1_force_hvp: NULL pointer");
+  const int64_t fit = kHvpLdsPerGroup / per_wave;
+  const int wpg = fit >= 4 ? 4 : fit <= 1 ? 1 : (int)fit;
+  const int64_t grid = ceil_div(rows, wpg);
+  L2HMC_REQUIRE(grid < (1ll << 31), "u1_force_hvp: too many rows");
+  const size_t lds = (size_t)per_wave * wpg;
+  static DeviceOnce attr_once;     // dynamic LDS beyond 64 KiB needs the opt-in
+  if (lds > 64 * 1024 && attr_once.pending()) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&u1_force_hvp_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kHvpLdsMax);
+    attr_once.done();
+  }
+  hipLaunchKernelGGL(u1_force_hvp_kernel, dim3((unsigned)grid), dim3(kWave * wpg), lds, (hipStream_t)stream, x, u,
+                     rows, T, X, beta, wpg, out);
+  L2HMC_CHECK_LAUNCH("u1_force_hvp");
+  return L2HMC_OK;
 }
 
 extern "C" int l2hmc_u1_plaq_sums(const float* x, int64_t rows, int32_t T, int32_t X, float* plaq,

@@ -12,12 +12,18 @@ hvd.DistributedOptimizer.compute_gradients: its ranks never exchange gradients. 
 reproduces that; the default does what the Horovod wrapper is there for.)
 
 Chains are integrated only in the direction their coin selects: the reference's mask multiplies the other
-direction's outputs by exactly 0, so it contributes exactly 0 to every gradient."""
+direction's outputs by exactly 0, so it contributes exactly 0 to every gradient.
+
+The tiled training entries (l2hmc_gauge_train_*) need every network width to be a multiple of 32; GenericNet
+networks of other widths (lattices whose T * X is not a multiple of 16: 6x6, 3x5, 4x6, ...) are trained through the
+layered-training entries instead (taped forward, reverse walk of l2hmc_amd/layered_train.py), into the same flat
+buffer, with the same draws, optimiser and data-parallel exchange."""
 import ctypes as C
 
 import torch
 
 from . import _lib
+from . import layered_train as _layered_train
 from .dist import active as _active_dist
 from .lattice import u1_observables
 
@@ -81,6 +87,11 @@ class GaugeTrainer:
             off += flat.numel()
         self._buckets = self._bucket_ranges()
         self._side = torch.cuda.Stream(device=dev) if (self.dist is not None and dev.type == "cuda") else None
+        # Which kernels a step runs through, decided per call: None = by shape (the tiled training entries where every
+        # width of both GenericNets is a multiple of 32, the layered-training entries otherwise); True = the layered
+        # path at any shape; False = the tiled entries (which refuse other widths).
+        self.layered = None
+        self._walk = None
 
     def _bucket_ranges(self):
         """{bucket id of l2hmc_gauge_train_backward_buckets: [(lo, hi), ...]} over the flat gradient buffer
@@ -150,6 +161,9 @@ class GaugeTrainer:
         x0 = torch.cat([x, z]).contiguous()
         v0 = torch.where(fwd[:, None], torch.cat([vf_x, vf_z]), torch.cat([vb_x, vb_z])).contiguous()
         dirs = (~fwd).to(torch.int32).contiguous()
+        if self._use_layered():
+            xN, p, terms, buf = self._layered_loss_and_grads(x0, v0, fwd, float(beta), B)
+            return self._step_outputs(x, u_x, xN, p, terms, buf)
         R = 2 * B
         xN, vN = torch.empty_like(x0), torch.empty_like(x0)
         sld, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
@@ -181,16 +195,7 @@ class GaugeTrainer:
 
             def on_bucket(_user, b):           # host thread, right after bucket b's producers were enqueued
                 try:
-                    if self._side is not None:
-                        self._side.wait_stream(cur)
-                        with torch.cuda.stream(self._side):
-                            for lo, hi in self._buckets[int(b)]:
-                                works.append(self.dist.all_reduce(self.grads[lo:hi], op=self.dist.ReduceOp.SUM,
-                                                                  async_op=True))
-                    else:
-                        for lo, hi in self._buckets[int(b)]:
-                            works.append(self.dist.all_reduce(self.grads[lo:hi], op=self.dist.ReduceOp.SUM,
-                                                              async_op=True))
+                    self._all_reduce_ranges(self._buckets[int(b)], works, cur)
                 except Exception as e:          # noqa: BLE001 -- a ctypes callback cannot raise: re-raised below
                     errors.append(e)
             cb = _lib.BUCKET_FN(on_bucket)
@@ -209,6 +214,12 @@ class GaugeTrainer:
                 self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
                 if self.allreduce_grads:
                     self.dist.all_reduce(self.grads, op=self.dist.ReduceOp.SUM)
+        return self._step_outputs(x, u_x, xN, p, terms, buf)
+
+    def _step_outputs(self, x, u_x, xN, p, terms, buf):
+        """(loss, x_out, accept_prob, x_dq) of a step from its proposals, accept probabilities and loss sums."""
+        T, X = self.dynamics.lattice.time_size, self.dynamics.lattice.space_size
+        B = x.shape[0]
         loss = buf[0] / buf[1]
         px = p[:B]
         x_prop = xN[:B]
@@ -218,6 +229,108 @@ class GaugeTrainer:
         x_dq = torch.abs(q0 - q1).to(torch.int32)                  # gauge_model.py:762-763
         self.last_loss_terms, self.last_pz = terms, p[B:]
         return loss, x_out, px, x_dq
+
+    def _use_layered(self):
+        if self.layered is not None:
+            use = bool(self.layered)
+        else:
+            packs = [net.pack() for net in self._nets]
+            use = not all(w % 32 == 0 for st in packs for w in (st.D, st.H, st.Ka, st.Kb))
+        if use and self.dynamics.network_arch != 'generic':
+            raise NotImplementedError("the layered training path takes GenericNet networks only; ConvNet3D training "
+                                      "needs network widths that are multiples of 32")
+        return use
+
+    def _all_reduce_ranges(self, ranges, works, cur):
+        """Start async all-reduces(SUM) of the given ranges of the flat gradient buffer, on the side stream after
+        everything enqueued so far on `cur`."""
+        if self._side is not None:
+            self._side.wait_stream(cur)
+            with torch.cuda.stream(self._side):
+                for lo, hi in ranges:
+                    works.append(self.dist.all_reduce(self.grads[lo:hi], op=self.dist.ReduceOp.SUM, async_op=True))
+        else:
+            for lo, hi in ranges:
+                works.append(self.dist.all_reduce(self.grads[lo:hi], op=self.dist.ReduceOp.SUM, async_op=True))
+
+    def _layered_loss_and_grads(self, x0, v0, fwd, beta, B):
+        """The training step through the layered-training entries (any lattice shape, GenericNet): one taped layered
+        trajectory per direction on the rows that run it, the loss reverse of l2hmc_gauge_loss_backward, the reverse
+        walk of l2hmc_amd/layered_train.py with beta * force and l2hmc_u1_force_hvp, and the weight gradients straight
+        into the flat buffer [xnet | vnet | eps].  -> (x_N, p, terms, [loss sum, chain count]) with the gradients
+        (and, data-parallel, the loss sums) combined across ranks."""
+        dyn = self.dynamics
+        dev, L, s = dyn._device, _lib.lib(), _lib.stream_ptr(dyn._device)
+        T, X = dyn.lattice.time_size, dyn.lattice.space_size
+        R = x0.shape[0]
+        if self._walk is None:
+            self._walk = _layered_train.LayeredWalk(dev)
+
+        def force(x):
+            out = torch.empty_like(x)
+            _lib.check(L.l2hmc_u1_action_force(x.data_ptr(), x.shape[0], T, X, beta, None, out.data_ptr(), None, None,
+                                               s))
+            return out
+
+        def hvp(x, u):
+            out = torch.empty_like(x)
+            _lib.check(L.l2hmc_u1_force_hvp(x.data_ptr(), u.data_ptr(), x.shape[0], T, X, beta, out.data_ptr(), s))
+            return out
+
+        def time(step):
+            t = dyn._format_time(step)
+            return float(t[0, 0]), float(t[0, 1])
+        w = _layered_train.Walk(dyn.position_fn, dyn.momentum_fn, dyn.eps, dyn.num_steps, time, dyn._get_mask_while,
+                                force, hvp)
+        walk = self._walk
+        tx, tv = walk.tapes(w, R)
+        xN, vN = torch.empty_like(x0), torch.empty_like(x0)
+        sld, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
+        runs = []
+        for d, idx in ((0, torch.nonzero(fwd).reshape(-1)), (1, torch.nonzero(~fwd).reshape(-1))):
+            if idx.numel() == 0:
+                continue
+            xs, vs = x0[idx].contiguous(), v0[idx].contiguous()
+            xe, ve, lj, subs = walk.trajectory(w, xs, vs, d, tx, tv)
+            xN[idx], vN[idx], sld[idx] = xe, ve, lj
+            p[idx] = dyn._compute_accept_prob(xs, vs, xe, ve, lj, beta)
+            runs.append((d, idx, subs))
+        terms = torch.empty(B, dtype=torch.float32, device=dev)
+        dxN, dvN = torch.empty_like(x0), torch.empty_like(x0)
+        dld = torch.empty(R, dtype=torch.float32, device=dev)
+        wt = self.weights
+        _lib.check(L.l2hmc_gauge_loss_backward(T, X, beta, x0.data_ptr(), xN.data_ptr(), vN.data_ptr(), p.data_ptr(),
+                                               B, METRICS[self.metric], self.loss_scale, wt['aux_weight'],
+                                               wt['std_weight'], wt['charge_weight'], 1.0 / (B * self.world),
+                                               terms.data_ptr(), dxN.data_ptr(), dvN.data_ptr(), dld.data_ptr(), s))
+        parts = []
+        for d, idx, subs in runs:
+            parts += walk.reverse(w, subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(), dld[idx].contiguous(),
+                                  tx, tv)
+        buf = torch.stack([terms.sum(dtype=torch.float32), torch.full((), float(B), dtype=torch.float32, device=dev)])
+        n0, n1 = self._sizes
+        bucketed = self.dist is not None and self.allreduce_grads and self.bucketed
+        works = []
+        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+        for k, (net, tape) in enumerate(((dyn.position_fn, tx), (dyn.momentum_fn, tv))):
+            walk.weight_grads(net, tape, self._grad_structs[k])
+            if bucketed:             # this network's range goes on the wire while the next one's products run
+                lo = 0 if k == 0 else n0
+                self._all_reduce_ranges([(lo, lo + self._sizes[k])], works, cur)
+        self.grads[n0 + n1] = torch.cat(parts).sum() if parts else 0.
+        if bucketed:
+            self._all_reduce_ranges([(n0 + n1, n0 + n1 + 1)], works, cur)
+            self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
+            for wk in works:
+                wk.wait()
+            if self._side is not None:
+                cur.wait_stream(self._side)
+            self.last_bucket_count = len(works)
+        elif self.dist is not None:
+            self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
+            if self.allreduce_grads:
+                self.dist.all_reduce(self.grads, op=self.dist.ReduceOp.SUM)
+        return xN, p, terms, buf
 
     # ---- optimiser --------------------------------------------------------------
     def apply_gradients(self):

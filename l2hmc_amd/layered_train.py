@@ -18,7 +18,12 @@ The weight gradients are formed once per network, over all its calls' tapes stac
 
 Tape size per network: 2 N_LF calls x 2B rows x (Ka+Kb + 4H + 3D (S, T, Q) + 3D + 2D + 2) floats; with both
 networks about 4 N_LF 2B (2D + 2H + 3D) 4 bytes for the forward part, and as much again for the reverse-pass
-cotangents (at x_dim 50, H 100, N_LF 10, 2B = 8192: about 1.2 GB in all)."""
+cotangents (at x_dim 50, H 100, N_LF 10, 2B = 8192: about 1.2 GB in all).
+
+The taped forward, the reverse walk and the weight gradients (LayeredWalk) depend on no loss and no trainer: a `Walk`
+gives them the networks, eps, the per-step masks and time input, and the energy gradient with its Hessian-vector
+product.  `GaugeTrainer` runs them on the lattice (beta * force, l2hmc_u1_force_hvp) where its tiled training entries
+do not take the network widths."""
 import ctypes as C
 
 import torch
@@ -72,35 +77,54 @@ def energy_hvp(dyn, x, u):
     return (hv.to(torch.float32) / dyn._temp()).contiguous()
 
 
-class LayeredStep:
-    """One `DynamicsTrainer.calc_loss_and_grads` of a layered dynamics (held by the trainer for its workspaces)."""
+class Walk:
+    """What a taped layered trajectory and its reverse walk need of a target, and nothing of any loss or trainer:
+    the two networks, eps, the trajectory length, per step the time input `time(step) -> (t_cos, t_sin)` and the
+    masks `masks(step) -> (m, 1 - m)` ([D] device tensors), and the gradient that feeds the momentum update and
+    VNet's second input, `grad(x)`, with its Hessian-vector product `hvp(x, u)` (toy targets: grad E / temperature
+    and energy_hvp; the lattice: beta * force and l2hmc_u1_force_hvp)."""
 
-    def __init__(self, trainer):
-        self.tr = trainer
+    def __init__(self, xnet, vnet, eps, num_steps, time, masks, grad, hvp):
+        self.xnet, self.vnet, self.eps, self.num_steps = xnet, vnet, float(eps), int(num_steps)
+        self.time, self.masks, self.grad, self.hvp = time, masks, grad, hvp
+
+
+class LayeredWalk:
+    """The target-independent stages of a layered training step (holds their workspaces): the taped forward of one
+    direction, the reverse walk from given cotangents of (x_N, v_N, sumlogdet), and one network's weight gradients
+    into caller-given l2hmc_dense_grads."""
+
+    def __init__(self, device):
+        self.device = device
         self._ws_bwd, self._ws_wg = _lib.Workspace(), _lib.Workspace()
 
+    def tapes(self, w, rows):
+        """(XNet tape, VNet tape) for trajectories over `rows` rows in all."""
+        n = 2 * w.num_steps * rows
+        return _NetTape(w.xnet, n, self.device), _NetTape(w.vnet, n, self.device)
+
     # ---- forward ---------------------------------------------------------------------------------------------
-    def _sub_v(self, x, v, tc, ts, d, lj, tape, subs):
-        dyn, L, s = self.tr.dynamics, _lib.lib(), _lib.stream_ptr(self.tr.dynamics._device)
+    def _sub_v(self, w, x, v, tc, ts, d, lj, tape, subs):
+        L, s = _lib.lib(), _lib.stream_ptr(self.device)
         n, D = x.shape
-        g = dyn.grad_energy(x)
+        g = w.grad(x)
         sl = tape.take(n)
         tape.inp[sl, :D] = x
         tape.inp[sl, D:] = g
         tape.tcs[sl, 0], tape.tcs[sl, 1] = tc, ts
         S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
-        _lib.check(L.l2hmc_stq_dense_taped(C.byref(dyn.VNet.pack()), x.data_ptr(), g.data_ptr(), None, tc, ts, n,
+        _lib.check(L.l2hmc_stq_dense_taped(C.byref(w.vnet.pack()), x.data_ptr(), g.data_ptr(), None, tc, ts, n,
                                            S.data_ptr(), T.data_ptr(), Q.data_ptr(), tape.h1[sl].data_ptr(),
                                            tape.h2[sl].data_ptr(), s))
         out, ld = torch.empty_like(v), torch.empty(n, dtype=torch.float32, device=v.device)
         _lib.check(L.l2hmc_lf_update_v(v.data_ptr(), g.data_ptr(), S.data_ptr(), T.data_ptr(), Q.data_ptr(),
-                                       float(dyn.eps), d, n, D, out.data_ptr(), ld.data_ptr(), s))
+                                       w.eps, d, n, D, out.data_ptr(), ld.data_ptr(), s))
         lj += ld
         subs.append(("v", sl, x, v, g, None))
         return out
 
-    def _sub_x(self, x, v, keep, tc, ts, d, lj, tape, subs):
-        dyn, L, s = self.tr.dynamics, _lib.lib(), _lib.stream_ptr(self.tr.dynamics._device)
+    def _sub_x(self, w, x, v, keep, tc, ts, d, lj, tape, subs):
+        L, s = _lib.lib(), _lib.stream_ptr(self.device)
         n, D = x.shape
         b = keep * x
         sl = tape.take(n)
@@ -108,38 +132,37 @@ class LayeredStep:
         tape.inp[sl, D:] = b
         tape.tcs[sl, 0], tape.tcs[sl, 1] = tc, ts
         S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
-        _lib.check(L.l2hmc_stq_dense_taped(C.byref(dyn.XNet.pack()), v.data_ptr(), b.data_ptr(), None, tc, ts, n,
+        _lib.check(L.l2hmc_stq_dense_taped(C.byref(w.xnet.pack()), v.data_ptr(), b.data_ptr(), None, tc, ts, n,
                                            S.data_ptr(), T.data_ptr(), Q.data_ptr(), tape.h1[sl].data_ptr(),
                                            tape.h2[sl].data_ptr(), s))
         out, ld = torch.empty_like(x), torch.empty(n, dtype=torch.float32, device=x.device)
         _lib.check(L.l2hmc_lf_update_x(x.data_ptr(), v.data_ptr(), keep.data_ptr(), S.data_ptr(), T.data_ptr(),
-                                       Q.data_ptr(), float(dyn.eps), d, n, D, out.data_ptr(), ld.data_ptr(), s))
+                                       Q.data_ptr(), w.eps, d, n, D, out.data_ptr(), ld.data_ptr(), s))
         lj += ld
         subs.append(("x", sl, x, v, None, keep))
         return out
 
-    def _trajectory(self, x0, v0, d, tx, tv):
-        """Dynamics._layered_run with every intermediate taped: -> (x_N, v_N, sumlogdet, p, subs)."""
-        dyn = self.tr.dynamics
-        N = dyn.trajectory_length
+    def trajectory(self, w, x0, v0, d, tx, tv):
+        """One layered trajectory in direction d (0 forward, 1 backward) with every intermediate taped:
+        -> (x_N, v_N, sumlogdet, subs)."""
+        N = w.num_steps
         x, v = x0, v0
         lj = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
         subs = []
         for i in range(N):
             step = N - i - 1 if d else i
-            t = dyn._format_time(step)
-            tc, ts = float(t[0, 0]), float(t[0, 1])
-            m, mb = dyn._get_mask(step)
+            tc, ts = w.time(step)
+            m, mb = w.masks(step)
             first, second = (mb, m) if d else (m, mb)
-            v = self._sub_v(x, v, tc, ts, d, lj, tv, subs)
-            x = self._sub_x(x, v, first, tc, ts, d, lj, tx, subs)
-            x = self._sub_x(x, v, second, tc, ts, d, lj, tx, subs)
-            v = self._sub_v(x, v, tc, ts, d, lj, tv, subs)
-        return x, v, lj, dyn.p_accept(x0, v0, x, v, lj), subs
+            v = self._sub_v(w, x, v, tc, ts, d, lj, tv, subs)
+            x = self._sub_x(w, x, v, first, tc, ts, d, lj, tx, subs)
+            x = self._sub_x(w, x, v, second, tc, ts, d, lj, tx, subs)
+            v = self._sub_v(w, x, v, tc, ts, d, lj, tv, subs)
+        return x, v, lj, subs
 
     # ---- reverse ---------------------------------------------------------------------------------------------
     def _backward_data(self, net, tape, sl, dS, dT, dQ):
-        L, dev = _lib.lib(), self.tr.dynamics._device
+        L, dev = _lib.lib(), self.device
         st = net.pack()
         n = dS.shape[0]
         din = torch.empty(n, tape.Kin, dtype=torch.float32, device=dev)
@@ -150,11 +173,11 @@ class LayeredStep:
             tape.dz2[sl].data_ptr(), tape.dz1[sl].data_ptr(), din.data_ptr(), ws, nb, _lib.stream_ptr(dev)))
         return din
 
-    def _reverse(self, subs, d, dx, dv, dld, tx, tv):
+    def reverse(self, w, subs, d, dx, dv, dld, tx, tv):
         """Walk one trajectory's sub-updates backwards from the cotangents of (x_N, v_N, sumlogdet); fills the tapes'
         cotangent slices and returns the per-row d/d eps partials of every sub-update."""
-        dyn, L, s = self.tr.dynamics, _lib.lib(), _lib.stream_ptr(self.tr.dynamics._device)
-        eps = float(dyn.eps)
+        L, s = _lib.lib(), _lib.stream_ptr(self.device)
+        eps = w.eps
         parts = []
         for kind, sl, xin, vin, g, keep in reversed(subs):
             tape = tv if kind == "v" else tx
@@ -168,8 +191,8 @@ class LayeredStep:
                                                    Q.data_ptr(), eps, d, n, D, dv.data_ptr(), dld.data_ptr(),
                                                    dv_in.data_ptr(), dg.data_ptr(), dS.data_ptr(), dT.data_ptr(),
                                                    dQ.data_ptr(), de.data_ptr(), s))
-                din = self._backward_data(dyn.VNet, tape, sl, dS, dT, dQ)
-                dx = dx + din[:, :D] + energy_hvp(dyn, xin, (dg + din[:, D:]).contiguous())
+                din = self._backward_data(w.vnet, tape, sl, dS, dT, dQ)
+                dx = dx + din[:, :D] + w.hvp(xin, (dg + din[:, D:]).contiguous())
                 dv = dv_in
             else:
                 dx_in, dv_part = torch.empty_like(dx), torch.empty_like(dx)
@@ -177,35 +200,55 @@ class LayeredStep:
                                                    T.data_ptr(), Q.data_ptr(), eps, d, n, D, dx.data_ptr(),
                                                    dld.data_ptr(), dx_in.data_ptr(), dv_part.data_ptr(), dS.data_ptr(),
                                                    dT.data_ptr(), dQ.data_ptr(), de.data_ptr(), s))
-                din = self._backward_data(dyn.XNet, tape, sl, dS, dT, dQ)
+                din = self._backward_data(w.xnet, tape, sl, dS, dT, dQ)
                 dx = (dx_in + keep * din[:, D:]).contiguous()
                 dv = (dv + dv_part + din[:, :D]).contiguous()
             dx, dv = dx.contiguous(), dv.contiguous()
             parts.append(de)
         return parts
 
-    def _weight_grads(self, net, tape, gv):
-        L, dev = _lib.lib(), self.tr.dynamics._device
+    def weight_grads(self, net, tape, g):
+        """Weight gradients of `net` over every row of its tape into the l2hmc_dense_grads `g` (overwritten)."""
+        L, dev = _lib.lib(), self.device
         st = net.pack()
         R = tape.off
-        g = _lib.DenseGrads(**{f[0]: gv[f[0]].data_ptr() for f in _lib.DenseGrads._fields_})
         ws, nb = self._ws_wg.get(L.l2hmc_dense_weight_grads_ws_bytes(C.byref(st), R), dev)
         _lib.check(L.l2hmc_dense_weight_grads(
             C.byref(st), R, tape.inp.data_ptr(), tape.h1.data_ptr(), tape.h2.data_ptr(), tape.dz1.data_ptr(),
             tape.dz2.data_ptr(), tape.dpre.data_ptr(), tape.dsq.data_ptr(), tape.tcs.data_ptr(), C.byref(g), ws, nb,
             _lib.stream_ptr(dev)))
 
-    # ---- the step --------------------------------------------------------------------------------------------
+
+def dense_grads(views):
+    """l2hmc_dense_grads over a network's gradient views ({segment: tensor})."""
+    return _lib.DenseGrads(**{f[0]: views[f[0]].data_ptr() for f in _lib.DenseGrads._fields_})
+
+
+class LayeredStep:
+    """One `DynamicsTrainer.calc_loss_and_grads` of a layered dynamics (held by the trainer for its workspaces)."""
+
+    def __init__(self, trainer):
+        self.tr = trainer
+        self.walk = LayeredWalk(trainer.dynamics._device)
+
+    def _walk(self):
+        dyn = self.tr.dynamics
+
+        def time(step):
+            t = dyn._format_time(step)
+            return float(t[0, 0]), float(t[0, 1])
+        return Walk(dyn.XNet, dyn.VNet, dyn.eps, dyn.trajectory_length, time, dyn._get_mask, dyn.grad_energy,
+                    lambda x, u: energy_hvp(dyn, x, u))
+
     def __call__(self, x0, v0, fwd, inv_count):
         """x0, v0 [2B][D] stacked start states, fwd [2B] bool (True = forward).  Writes the trainer's gradient buffer
         ([xnet | vnet | d/d eps]) and returns (x_N, p, terms) in the stacked row order."""
         tr = self.tr
         dyn, dev = tr.dynamics, tr.dynamics._device
         R, D = x0.shape
-        N = dyn.trajectory_length
+        w = self._walk()
         groups = [(0, torch.nonzero(fwd).reshape(-1)), (1, torch.nonzero(~fwd).reshape(-1))]
-        tx = _NetTape(dyn.XNet, 2 * N * R, dev)
-        tv = _NetTape(dyn.VNet, 2 * N * R, dev)
+        tx, tv = self.walk.tapes(w, R)
         xN, vN = torch.empty_like(x0), torch.empty_like(x0)
         lj, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
         runs = []
@@ -213,8 +256,8 @@ class LayeredStep:
             if idx.numel() == 0:
                 continue
             xs, vs = x0[idx].contiguous(), v0[idx].contiguous()
-            X, V, J, P, subs = self._trajectory(xs, vs, d, tx, tv)
-            xN[idx], vN[idx], lj[idx], p[idx] = X, V, J, P
+            X, V, J, subs = self.walk.trajectory(w, xs, vs, d, tx, tv)
+            xN[idx], vN[idx], lj[idx], p[idx] = X, V, J, dyn.p_accept(xs, vs, X, V, J)
             runs.append((d, idx, subs))
         # loss (mog_model.py:336-355) and its cotangents at (x_N, v_N, sumlogdet)
         scale = tr.scale
@@ -234,10 +277,11 @@ class LayeredStep:
         dld = dD.contiguous()
         parts = []
         for d, idx, subs in runs:
-            parts += self._reverse(subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(), dld[idx].contiguous(), tx, tv)
+            parts += self.walk.reverse(w, subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(),
+                                       dld[idx].contiguous(), tx, tv)
         gv = tr.grad_views()
-        self._weight_grads(dyn.XNet, tx, gv["xnet"])
-        self._weight_grads(dyn.VNet, tv, gv["vnet"])
+        self.walk.weight_grads(dyn.XNet, tx, dense_grads(gv["xnet"]))
+        self.walk.weight_grads(dyn.VNet, tv, dense_grads(gv["vnet"]))
         deps = torch.cat(parts).sum() if parts else torch.zeros((), dtype=torch.float32, device=dev)
         tr.grads[-1] = deps
         return xN, p, terms

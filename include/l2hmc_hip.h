@@ -195,9 +195,10 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
                                       * end of one step to the start of the next).  Same bits either way; diagnostic */
 #define L2HMC_PLAN_TILES16_ONLY 16   /* whole-trajectory kernel: every batch on the 16-row form (no sub-tile form, no 32-row
                                       * form, no launch split).  All forms give the same bits; A/B and the bit-identity test */
-#define L2HMC_PLAN_ALL_COLUMNS 32    /* layer-by-layer path: a position sub-update forms S / T / Q for EVERY column, as the
-                                      * reference's graph does, instead of only the columns its mask lets move (identical x, v
-                                      * for finite trajectories; 0 x non-finite differs: DESIGN.md D1) */
+#define L2HMC_PLAN_ALL_COLUMNS 32    /* a position sub-update forms S / T / Q for EVERY column, as the reference's graph
+                                      * does, instead of only the columns its mask lets move: on the layer-by-layer path,
+                                      * and in the whole-step kernel with plan.heads set (identical x, v for finite
+                                      * trajectories; 0 x non-finite differs: DESIGN.md D1).  A/B switch */
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */
@@ -209,7 +210,16 @@ typedef struct l2hmc_gauge_plan {
   l2hmc_dense_net vnet;    /* momentum_fn */
   l2hmc_conv3d_front xfront;   /* conv layers of position_fn (L2HMC_PLAN_CONV3D only) */
   l2hmc_conv3d_front vfront;   /* conv layers of momentum_fn */
+  const void* heads;       /* optional: l2hmc_gauge_pack_heads() image of (masks, xnet), or NULL = every column */
 } l2hmc_gauge_plan;
+
+/* Active-column heads of the whole-step kernel (GenericNet D = 128, H = 512 on an 8x8-site lattice; bytes = 0 for
+ * other plans).  For every mask row and keep sense it lists the D / 2 columns a position sub-update moves and packs
+ * XNet's S / T / Q weights of just those columns; l2hmc_gauge_mcmc_step then forms the heads of its position
+ * sub-updates on those columns only (same bits).  Rows whose mask is not exactly D / 2 zeros and D / 2 ones are
+ * recorded as such and take every column.  Re-pack after any change of plan.masks or of XNet's weights. */
+size_t l2hmc_gauge_pack_heads_bytes(const l2hmc_gauge_plan* plan);
+int l2hmc_gauge_pack_heads(const l2hmc_gauge_plan* plan, void* heads, l2hmc_stream_t stream);
 
 size_t l2hmc_gauge_ws_bytes(const l2hmc_gauge_plan* plan, int64_t rows);
 

@@ -46,7 +46,8 @@ class Conv3DFront(C.Structure):
 class GaugePlan(C.Structure):
     _fields_ = [("T", C.c_int32), ("X", C.c_int32), ("num_steps", C.c_int32), ("hmc", C.c_int32),
                 ("eps", C.c_float), ("flags", C.c_int32), ("masks", c_float_p),
-                ("xnet", DenseNet), ("vnet", DenseNet), ("xfront", Conv3DFront), ("vfront", Conv3DFront)]
+                ("xnet", DenseNet), ("vnet", DenseNet), ("xfront", Conv3DFront), ("vfront", Conv3DFront),
+                ("heads", C.c_void_p)]
 
 
 class MogTarget(C.Structure):
@@ -83,6 +84,8 @@ _PROTOS = {
     "l2hmc_gauge_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64]),
     "l2hmc_gauge_plan_fused": (C.c_int, [C.POINTER(GaugePlan)]),
     "l2hmc_gauge_step_plan": (C.c_int, [_I64, _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "l2hmc_gauge_pack_heads_bytes": (_SZ, [C.POINTER(GaugePlan)]),
+    "l2hmc_gauge_pack_heads": (C.c_int, [C.POINTER(GaugePlan), _P, _P]),
     "l2hmc_gauge_leapfrog": (C.c_int, [C.POINTER(GaugePlan), _F, _I32, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
     "l2hmc_gauge_trajectory": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _P, _P, _I64, _P, _P, _P, _P, _P,
                                          _SZ, _P]),

@@ -39,6 +39,15 @@ struct FusedArgs {
   float* step_px; float* step_act; float* step_plq; float* step_chg; float* step_dq;   // [B] each, or NULL
   float* step_sums;                      // [4] = [sum p, sum |dQ|, B, ticket] or NULL; ticket 0 on entry, left 0
   float* step_part;                      // [2 * workgroups] scratch for the fixed-order sums
+  // step_both on the 16-row GenericNet form: step_split = 1 gives every workgroup 16 chains of ONE direction --
+  // workgroup 2 i integrates chains [16 i, 16 i + 16) forward, workgroup 2 i + 1 the same chains backward -- so that a
+  // position sub-update can form its heads on the columns its (uniform) mask moves.  Both leave their rows in
+  // step_hand and take the pair's ticket; the one that arrives last mixes, accepts and measures the 16 chains.
+  int step_split;
+  float* step_hand;                      // [workgroups][2 * 16 * D + 16]: x rows, v rows, accept probabilities
+  int* step_ticket;                      // [workgroups / 2], zero on entry (a memset ahead of the launch)
+  const int* heads_meta;                 // l2hmc_gauge_pack_heads image (step_split only), or NULL = all columns:
+  const float* heads_img;                //   [N][2] eligibility, [N][2][D / 2] columns; [N][2] packed heads sections
 };
 
 // the sub-tile form (fused_traj4.hip): GenericNet 8x8 plans, sampling only

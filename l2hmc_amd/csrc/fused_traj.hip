@@ -70,9 +70,12 @@ struct FusedCfg {
   static constexpr int CXIN = (CL + 2) * (CL + 2) * 2;                      // haloed chain
   static constexpr int CP1 = (CL / 2 + 1) * (CL / 2 + 1) * CF;              // pooled conv1 map, zero halo
   static constexpr int CONV_FLOATS = CONV ? 2 * kFM * SA + 4 * CW + kFM * (CXIN + CP1) : 0;
+  // active-column heads (GenericNet, split step mode): log-det terms staged at their columns [16][SX], the two
+  // column lists of this workgroup's mask row [2][D / 2] (int) and their eligibility [2] (int, padded to 4)
+  static constexpr int ACT_FLOATS = CONV ? 0 : kFM * SX + D + 4;
   static constexpr int LDS_FLOATS = 3 * kFM * SX + 2 * kFM * SH + 2 * NC + kFM * (D / 2 + 4) /*sinP*/ +
                                     2 * D /*masks*/ + WAVES * kFM /*ldw*/ + (RW > 1 ? IMGW * 64 : 0) /*ldx*/ + kFM /*dir*/ +
-                                    8 * kFM /*step mode*/ + CONV_FLOATS;
+                                    8 * kFM /*step mode*/ + CONV_FLOATS + ACT_FLOATS;
 };
 
 // ---------------------------------------------------------------------------
@@ -112,6 +115,51 @@ __global__ void pack_fused_kernel(l2hmc_dense_net n, float* __restrict__ out, in
       val = n.whd_t[((size_t)hd * D + col) * H + k];
     }
     out[i] = val;
+  }
+}
+
+// Active-column heads sections (l2hmc_gauge_pack_heads): block (x, 2 m + sense) lists the columns of mask row m
+// that a position sub-update with keep = mask (sense 0) or keep = 1 - mask (sense 1) moves, records whether the row
+// qualifies (every entry exactly 0 or 1, D / 2 of them moving) and packs XNet's heads for those columns in the order
+// of the 4-wave image -- [section = active tile][k-chunk][head][lane][4] -- one 16-column tile per section.
+__global__ __launch_bounds__(256) void pack_heads_kernel(l2hmc_dense_net n, const float* __restrict__ masks, int N,
+                                                         int* __restrict__ meta, float* __restrict__ img) {
+  constexpr int DMAX = 128;
+  __shared__ int cols[DMAX / 2];
+  __shared__ int ok;
+  const int D = n.D, H = n.H, DA = D / 2;
+  const float* row = masks + (size_t)(blockIdx.y >> 1) * D;
+  const float sense = (float)(blockIdx.y & 1);
+  if (threadIdx.x == 0) {
+    int cnt = 0, bin = D <= DMAX;
+    for (int c = 0; c < D && bin; ++c) {
+      const float v = row[c];
+      if (!(v == 0.f || v == 1.f)) bin = 0;
+      else if (v == sense) {
+        if (cnt < DA) cols[cnt] = c;
+        ++cnt;
+      }
+    }
+    ok = bin && cnt == DA;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) meta[blockIdx.y] = ok;
+    for (int i = threadIdx.x; i < DA; i += blockDim.x) meta[2 * N + (size_t)blockIdx.y * DA + i] = ok ? cols[i] : -1;
+  }
+  if (!ok) return;
+  const size_t per = (size_t)3 * DA * H;
+  float* out = img + (size_t)blockIdx.y * per;
+  const int KC = H / 16;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (size_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i & 3), lane = (int)((i >> 2) & 63);
+    size_t rest = i >> 8;                             // ((w * KC + kc) * 3 + hd)
+    const int hd = (int)(rest % 3);
+    rest /= 3;
+    const int kc = (int)(rest % KC), w = (int)(rest / KC);
+    const int col = cols[w * 16 + (lane & 15)];
+    const int k = kc * 16 + (lane >> 4) * 4 + j;
+    out[i] = n.whd_t[((size_t)hd * D + col) * H + k];
   }
 }
 
@@ -168,6 +216,10 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   float* cwl = fb + kFM * SA;                         // [net x|v][input a|b][CW] filters
   float* cxin = cwl + 4 * Cfg::CW;                    // [16][CXIN] haloed chains
   float* cp1 = cxin + kFM * Cfg::CXIN;                // [16][CP1]  pooled conv1 maps
+  // active-column heads (GenericNet only; zero-sized otherwise)
+  float* stg = stp + 8 * kFM + Cfg::CONV_FLOATS;      // [16][SX] log-det terms of a position call at their columns
+  int* scol = reinterpret_cast<int*>(stg + kFM * SX);  // [2][D / 2] active columns of keep sense 0 / 1, ascending
+  int* sel = scol + D;                                 // [2] the two lists are usable (exactly D / 2 columns, 0 / 1 mask)
 
   // diagnostic cycle shares: 0-2 gemm L1/L2/heads, 3-5 their epilogues, 6 barriers, 7 force, 8 mask pass, 9 total
   [[maybe_unused]] unsigned long long ft[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -193,7 +245,12 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 #endif
   // ---- stage chain state and constants ------------------------------------
   const bool STEPM = p.step_B > 0;
-  const int cpw = STEPM ? (p.step_both ? kFM / 2 : kFM) : kFM;           // chains per workgroup in step mode
+  // split step mode (FusedArgs::step_split): 16 chains of one direction, the direction uniform over the workgroup
+  const bool SPLIT = !CONV && !TAPE && STEPM && p.step_both && p.step_split;
+  const bool PAIRED = STEPM && p.step_both && !SPLIT;                    // 8 chains x both directions
+  const int sdw = SPLIT ? (int)(blockIdx.x & 1) : 0;                     // (SPLIT) this workgroup's direction
+  const int cpw = PAIRED ? kFM / 2 : kFM;                                // chains per workgroup in step mode
+  const int64_t cbase = SPLIT ? (int64_t)(blockIdx.x >> 1) * kFM : (int64_t)blockIdx.x * cpw;   // its first chain
   float* scoin = stp;                    // [16] direction coin per chain slot
   float* su = stp + kFM;                 // [16] MH uniform
   float* spx = stp + 2 * kFM;            // [16] accept probability per row
@@ -206,7 +263,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   };
   if (STEPM) {
     if (tid < cpw) {
-      const int64_t chain = (int64_t)blockIdx.x * cpw + tid;
+      const int64_t chain = cbase + tid;
       const bool lv = chain < p.step_Bl;          // (streams are indexed by the chain's place in the WHOLE batch)
       scoin[tid] = lv ? philox_u01((uint64_t)(p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
       su[tid] = lv ? philox_u01((uint64_t)(p.step_B + p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
@@ -214,9 +271,9 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     __syncthreads();
     for (int i = tid; i < kFM * (D / 4); i += kFThreads) {
       const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
-      const int k = p.step_both ? (rr & (kFM / 2 - 1)) : rr;
-      const int64_t chain = (int64_t)blockIdx.x * cpw + k;
-      const int dsel = p.step_both ? (rr >= kFM / 2 ? 1 : 0) : (scoin[k] > 0.5f ? 0 : 1);   // gauge_dynamics.py:221-227
+      const int k = PAIRED ? (rr & (kFM / 2 - 1)) : rr;
+      const int64_t chain = cbase + k;
+      const int dsel = SPLIT ? sdw : PAIRED ? (rr >= kFM / 2 ? 1 : 0) : (scoin[k] > 0.5f ? 0 : 1);   // gauge_dynamics.py:221-227
       f32x4 xv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
       if (chain < p.step_Bl) {
         xv = *reinterpret_cast<const f32x4*>(p.x0 + chain * D + c4);
@@ -278,7 +335,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   }
   if (tid < kFM) {
     int d = 0;
-    if (STEPM) d = p.step_both ? (tid >= kFM / 2 ? 1 : 0) : (scoin[tid] > 0.5f ? 0 : 1);
+    if (STEPM) d = SPLIT ? sdw : PAIRED ? (tid >= kFM / 2 ? 1 : 0) : (scoin[tid] > 0.5f ? 0 : 1);
     else if (tid < nrow) d = p.dir ? p.dir[row0 + tid] : (p.dir_split > 0 && row0 + tid >= p.dir_split) ? 1 : 0;
     sdir[tid] = d;
   }
@@ -459,6 +516,13 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   //   keep_x: XNet's product with its FIRST input (v), identical for the two position sub-updates of a step.
   f32x4 keep_v[NT1], keep_x[NT1];
   bool keep_v_valid = false;
+  // Active-column heads (split step mode, l2hmc_gauge_pack_heads): a position sub-update moves only the columns whose
+  // keep is 0 -- x' = keep x + (1 - keep) upd and the log-det term carry (1 - keep) -- so S / T / Q are formed for those
+  // D / 2 columns alone, from a heads section packed per (mask row, keep sense): 4 tiles x [S | T | Q], one tile per
+  // SIMD (waves 0-3; their SIMD partners 4-7 fill in the kept columns' zeros).  Same k order per column, same
+  // epilogue expressions; the log-det terms are staged at their columns and summed in today's grouping.
+  constexpr bool ACTOK = !CONV && !TAPE && Cfg::NTH == 1 && RW == 2 && kFWaves == 8;
+  int arow = 0;                        // mask row of this workgroup's direction at the current step
 
   // l1: 0 = compute both halves; 1 = as 0 and store the raw product in keep_v; 2 = take keep_v, no GEMM;
   //     3 = compute, snapshot the first-input half into keep_x; 4 = start from keep_x, second half only.
@@ -498,6 +562,14 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     const float* wp2 = pk + Cfg::P1 + (size_t)wimg * Cfg::KC2 * NTI1 * 256;
     const float* wph = pk + Cfg::P1 + Cfg::P2 + (size_t)wimg * Cfg::KC2 * 3 * NTIH * 256;
     const int to1 = wsub * NT1, toh = wsub * NTH;             // first tile of this wave in a chunk of the section
+    int asense = 0;                                           // keep sense whose columns move: keep = mask (0) / 1 - mask (1)
+    bool actv = false;
+    const float* wpa = nullptr;
+    if (ACTOK && SPLIT && mode == 2 && p.heads_img) {
+      asense = sdw ^ sub;
+      actv = __builtin_amdgcn_readfirstlane(sel[asense]) != 0;
+      wpa = p.heads_img + ((size_t)(arow * 2 + asense) * 4 + (wv & 3)) * Cfg::KC2 * 3 * 256;
+    }
     [[maybe_unused]] float ld_k[4] = {0.f, 0.f, 0.f, 0.f}, ld_s[4] = {0.f, 0.f, 0.f, 0.f};   // (RW > 1: the odd wave's log-det terms)
 #ifndef L2HMC_DP1                                 // (A/B builds: tools/build_variant.sh)
 #define L2HMC_DP1 3
@@ -605,7 +677,11 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       [[maybe_unused]] unsigned long long t0 = FT_NOW();
       stream_layer<NT1, Cfg::KC2, DP2, NTI1>(
           R2, wp2, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acc, zig, to1);
-      ring_prime<3 * NTH, DPH, 3 * NTIH, TSH>(R3, wph, zig, Cfg::KC2, toh);
+      if (ACTOK && actv) {
+        if (wv < 4) ring_prime<3 * NTH, DPH, 3, 1>(R3, wpa, zig, Cfg::KC2, 0);
+      } else {
+        ring_prime<3 * NTH, DPH, 3 * NTIH, TSH>(R3, wph, zig, Cfg::KC2, toh);
+      }
       FT_ADD(1, t0);
       t0 = FT_NOW();
       [[maybe_unused]] unsigned gmask = 0;
@@ -642,8 +718,14 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       for (int t = 0; t < 3 * NTH; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
       const float* a = h2 + r * SH + q * 4;
       [[maybe_unused]] unsigned long long t0 = FT_NOW();
-      stream_layer<3 * NTH, Cfg::KC2, DPH, 3 * NTIH, TSH>(
-          R3, wph, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acc, zig, toh);
+      if (ACTOK && actv) {
+        if (wv < 4)
+          stream_layer<3 * NTH, Cfg::KC2, DPH, 3, 1>(
+              R3, wpa, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acc, zig, 0);
+      } else {
+        stream_layer<3 * NTH, Cfg::KC2, DPH, 3 * NTIH, TSH>(
+            R3, wph, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acc, zig, toh);
+      }
       FT_ADD(2, t0);
       t0 = FT_NOW();
       float ld = 0.f;                       // this lane's share of row r's log-det
@@ -651,6 +733,45 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       const float* es = bhd + 3 * D;
       const float* eq = es + D;
       const int d = dirl;
+      if (ACTOK && actv) {
+        // lane (q, r) of wave w < 4: row r, active columns al[16 w + 4 q + e]; wave w >= 4: kept columns il[...]
+        const int* al = scol + asense * (D / 2);
+        const int* il = scol + (asense ^ 1) * (D / 2);
+        if (wv < 4) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int c = al[wv * 16 + q * 4 + e];
+            const int idx = r * SX + c;
+            const float S = fast_tanh(acc[0][e] + bhd[c]) * es[c];
+            const float Tt = acc[1][e] + bhd[D + c];
+            const float qq = acc[2][e] + bhd[2 * D + c];
+            const float Q = (net.q_tanh ? fast_tanh(qq) : qq) * eq[c];
+            const float mf = skm[c], mb = skm[D + c];
+            const float keep = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf);
+            const float x = xs[idx], v = vs[idx];
+            const float s = (d ? -eps : eps) * S;
+            const float drift = eps * (fast_exp(eps * Q) * v + Tt);
+            const float es_ = fast_exp(s);
+            const float upd = d ? es_ * (x - drift) : x * es_ + drift;
+            const float xn = keep * x + (1.f - keep) * upd;
+            xs[idx] = xn;
+            stg[idx] = (1.f - keep) * s;
+            if (prep_next_mask) gs[idx] = (1.f - keep) * xn;
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int c = il[(wv - 4) * 16 + q * 4 + e];
+            const int idx = r * SX + c;
+            stg[idx] = 0.f;
+            if (prep_next_mask) {
+              const float mf = skm[c], mb = skm[D + c];
+              const float keep = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf);
+              gs[idx] = (1.f - keep) * xs[idx];
+            }
+          }
+        }
+      } else {
 #pragma unroll
       for (int t = 0; t < NTH; ++t) {
         const int c0 = wave * (D / kFWaves) + t * 16 + q * 4;      // row r, columns c0 .. c0 + 3
@@ -735,6 +856,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         // continues the chain with its own four terms behind the barrier below (ld_k, ld_s) and does the rest.
         if (wsub == 0) ldx[wimg * 64 + lane] = ld;
       }
+      }
       FT_ADD(5, t0);
     }
     {
@@ -742,7 +864,19 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       __syncthreads();
       FT_ADD(6, tb);
     }
-    if constexpr (RW > 1) {
+    if (ACTOK && actv) {
+      // the chain of adds of the all-columns form over both waves' columns of the section; a kept column adds +-0
+      if (wsub == 1) {
+        float ld = 0.f;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) ld += stg[r * SX + (2 * wimg + h) * 16 + q * 4 + e];
+        ld += __shfl_xor(ld, 16, 64);
+        ld += __shfl_xor(ld, 32, 64);
+        if (q == 0) ldw[wimg * kFM + r] += ld;
+      }
+    } else if constexpr (RW > 1) {
       if (wsub == 1) {
         float ld = ldx[wimg * 64 + lane];
 #pragma unroll
@@ -764,6 +898,11 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     for (int i = tid; i < D; i += kFThreads) {
       skm[i] = p.masks[(size_t)sf * D + i];
       skm[D + i] = p.masks[(size_t)sb * D + i];
+    }
+    if (ACTOK && SPLIT && p.heads_meta) {
+      arow = sdw ? sb : sf;
+      for (int i = tid; i < D; i += kFThreads) scol[i] = p.heads_meta[2 * p.num_steps + arow * D + i];
+      if (tid < 2) sel[tid] = p.heads_meta[arow * 2 + tid];
     }
     // (gs holds the force of the current x: from the prologue or the previous step's last kick)
     __syncthreads();
@@ -798,22 +937,78 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       spx[fc] = accept_from_delta(dh);
     }
     __syncthreads();
+    // forward / backward rows of chain k (x, v: row stride SX) and their accept probabilities
+    const float* xfr = xs;
+    const float* xbr = xs + (kFM / 2) * SX;
+    const float* vfr = vs;
+    const float* vbr = vs + (kFM / 2) * SX;
+    const float* pfr = spx;
+    const float* pbr = spx + kFM / 2;
+    if (SPLIT) {
+      // ---- hand-off between the two workgroups of a pair (cdna_hip_programming.md, Guideline 16, counter form):
+      //      both publish their rows, the one that draws ticket 1 takes its partner's and finishes the 16 chains.
+      //      Nobody waits: the first to arrive simply ends.
+      constexpr int HW = 2 * kFM * D + kFM;           // floats per workgroup in step_hand
+      float* mine = p.step_hand + (size_t)blockIdx.x * HW;
+      for (int i = tid; i < kFM * (D / 4); i += kFThreads) {
+        const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
+        *reinterpret_cast<f32x4*>(mine + rr * D + c4) = *reinterpret_cast<const f32x4*>(xs + rr * SX + c4);
+        if (p.step_vprop)
+          *reinterpret_cast<f32x4*>(mine + (kFM + rr) * D + c4) = *reinterpret_cast<const f32x4*>(vs + rr * SX + c4);
+      }
+      if (tid < kFM) mine[2 * kFM * D + tid] = spx[tid];
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      int* is_last = sdir;                              // (sdir is free: every lane holds its row's direction)
+      __syncthreads();
+      if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int got = __hip_atomic_fetch_add(p.step_ticket + (blockIdx.x >> 1), 1, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+        if (got == 1) {
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        is_last[0] = got == 1;
+      }
+      __syncthreads();
+      if (!is_last[0]) return;
+      // the partner's rows -> h2 (free): x [16][SX], v [16][SX], p [16]
+      const float* other = p.step_hand + (size_t)(blockIdx.x ^ 1u) * HW;
+      float* ox = h2;
+      float* ov = h2 + kFM * SX;
+      float* op = h2 + 2 * kFM * SX;
+      for (int i = tid; i < kFM * (D / 4); i += kFThreads) {
+        const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
+        *reinterpret_cast<f32x4*>(ox + rr * SX + c4) = *reinterpret_cast<const f32x4*>(other + rr * D + c4);
+        if (p.step_vprop)
+          *reinterpret_cast<f32x4*>(ov + rr * SX + c4) = *reinterpret_cast<const f32x4*>(other + (kFM + rr) * D + c4);
+      }
+      if (tid < kFM) op[tid] = other[2 * kFM * D + tid];
+      __syncthreads();
+      if (sdw == 0) {
+        xbr = ox; vbr = ov; pbr = op;
+      } else {
+        xfr = ox; vfr = ov; pfr = op;
+        xbr = xs; vbr = vs; pbr = spx;
+      }
+    }
     // ---- mix the two directions, Metropolis-Hastings (gauge_dynamics.py:221-257, arithmetic kept as
     //      mask * a + (1 - mask) * b); x_in -> gs rows, x_out -> h1 rows (both free now)
     float* gin = gs;
     float* gout = h1;
     for (int i = tid; i < cpw * (D / 4); i += kFThreads) {
       const int k = i / (D / 4), c4 = (i - k * (D / 4)) * 4;
-      const int64_t chain = (int64_t)blockIdx.x * cpw + k;
+      const int64_t chain = cbase + k;
       f32x4 xin = {0.f, 0.f, 0.f, 0.f};
       if (chain < p.step_Bl) xin = *reinterpret_cast<const f32x4*>(p.x0 + chain * D + c4);
       f32x4 xp;
       float pk;
       if (p.step_both) {
         const float fm = scoin[k] > 0.5f ? 1.f : 0.f, bm = 1.f - fm;
-        pk = fm * spx[k] + bm * spx[kFM / 2 + k];
-        const f32x4 xf = *reinterpret_cast<const f32x4*>(xs + k * SX + c4);
-        const f32x4 xb = *reinterpret_cast<const f32x4*>(xs + (kFM / 2 + k) * SX + c4);
+        pk = fm * pfr[k] + bm * pbr[k];
+        const f32x4 xf = *reinterpret_cast<const f32x4*>(xfr + k * SX + c4);
+        const f32x4 xb = *reinterpret_cast<const f32x4*>(xbr + k * SX + c4);
         xp = fm * xf + bm * xb;
       } else {
         pk = spx[k];
@@ -828,10 +1023,10 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         if (p.step_xprop) *reinterpret_cast<f32x4*>(p.step_xprop + chain * D + c4) = xp;
         if (p.step_xout) *reinterpret_cast<f32x4*>(p.step_xout + chain * D + c4) = xo;
         if (p.step_vprop) {
-          f32x4 vp = *reinterpret_cast<const f32x4*>(vs + k * SX + c4);
+          f32x4 vp = *reinterpret_cast<const f32x4*>(vfr + k * SX + c4);
           if (p.step_both) {
             const float fm = scoin[k] > 0.5f ? 1.f : 0.f, bm = 1.f - fm;
-            vp = fm * vp + bm * *reinterpret_cast<const f32x4*>(vs + (kFM / 2 + k) * SX + c4);
+            vp = fm * vp + bm * *reinterpret_cast<const f32x4*>(vbr + k * SX + c4);
           }
           *reinterpret_cast<f32x4*>(p.step_vprop + chain * D + c4) = vp;
         }
@@ -854,7 +1049,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       scos = chain_sum(a);
       sproj = chain_sum(b);
     };
-    if (p.step_both) {
+    if (PAIRED) {
       float a, b;
       plaq_sums(fc < kFM / 2 ? gin + fc * SX : gout + (fc - kFM / 2) * SX, a, b);
       if (own && fl == 0) {
@@ -870,7 +1065,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     __syncthreads();
     const float inv2pi = 0.15915494309189533577f;
     if (tid < cpw) {
-      const int64_t chain = (int64_t)blockIdx.x * cpw + tid;
+      const int64_t chain = cbase + tid;
       if (chain < p.step_Bl) {
         const float q_in = sobs[tid * 4 + 1] * inv2pi, q_out = sobs[tid * 4 + 2] * inv2pi;
         if (p.step_px) p.step_px[chain] = sobs[tid * 4 + 3];
@@ -884,24 +1079,34 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       // [sum p_accept, sum |dQ|, chains] in a fixed order and without a further launch: every workgroup leaves its
       // partial sums in step_part, the last one to arrive (ticket in step_sums[3]) adds them up and resets the ticket
       int* last = reinterpret_cast<int*>(spx);            // spx is free again
+      // (SPLIT: a pair leaves the partial sums of the two 8-chain groups the paired layout gives its workgroups --
+      //  the same entries, the same order; only the pairs' last arrivers take part)
+      const int ngrp = SPLIT ? 2 : 1, gch = cpw / ngrp;
+      const int nfin = SPLIT ? (int)(gridDim.x >> 1) : (int)gridDim.x;
+      const int npart = SPLIT ? (int)((p.step_Bl + kFM / 2 - 1) / (kFM / 2)) : (int)gridDim.x;
       if (tid == 0) {
-        float a0 = 0.f, a1 = 0.f;
-        for (int k = 0; k < cpw; ++k) {
-          if ((int64_t)blockIdx.x * cpw + k < p.step_Bl) {
-            a0 += sobs[k * 4 + 3];
-            a1 += fabsf(sobs[k * 4 + 1] * inv2pi - sobs[k * 4 + 2] * inv2pi);
+        for (int g = 0; g < ngrp; ++g) {
+          float a0 = 0.f, a1 = 0.f;
+          for (int k = g * gch; k < (g + 1) * gch; ++k) {
+            if (cbase + k < p.step_Bl) {
+              a0 += sobs[k * 4 + 3];
+              a1 += fabsf(sobs[k * 4 + 1] * inv2pi - sobs[k * 4 + 2] * inv2pi);
+            }
+          }
+          const int64_t slot = SPLIT ? (int64_t)(blockIdx.x >> 1) * 2 + g : (int64_t)blockIdx.x;
+          if (slot < npart) {
+            p.step_part[2 * slot] = a0;
+            p.step_part[2 * slot + 1] = a1;
           }
         }
-        p.step_part[2 * blockIdx.x] = a0;
-        p.step_part[2 * blockIdx.x + 1] = a1;
         __threadfence();
-        *last = atomicAdd(reinterpret_cast<int*>(p.step_sums + 3), 1) == (int)gridDim.x - 1;
+        *last = atomicAdd(reinterpret_cast<int*>(p.step_sums + 3), 1) == nfin - 1;
       }
       __syncthreads();
       if (*last) {
         __threadfence();
         float a0 = 0.f, a1 = 0.f;
-        for (int b = tid; b < (int)gridDim.x; b += kFThreads) {
+        for (int b = tid; b < npart; b += kFThreads) {
           a0 += p.step_part[2 * b];
           a1 += p.step_part[2 * b + 1];
         }
@@ -927,7 +1132,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     // ---- np.mod(x_out, 2 pi) (gauge_model.py:1388) and the write-back of the chains' new state
     for (int i = tid; p.step_x_next && i < cpw * (D / 4); i += kFThreads) {
       const int k = i / (D / 4), c4 = (i - k * (D / 4)) * 4;
-      const int64_t chain = (int64_t)blockIdx.x * cpw + k;
+      const int64_t chain = cbase + k;
       if (chain < p.step_Bl) {
         f32x4 w = *reinterpret_cast<const f32x4*>(gout + k * SX + c4);
 #pragma unroll
@@ -979,6 +1184,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+// l2hmc_gauge_pack_heads image: int eligibility [N][2], int columns [N][2][D / 2], then (256-byte aligned) the sections
+static size_t heads_meta_bytes(int N, int D) { return align_up(sizeof(int) * ((size_t)2 * N + (size_t)N * D), 256); }
 // shapes with a whole-trajectory kernel: GenericNet on D=128 (H=512), and the dense trunk of ConvNet3D on the
 // 8x8 lattice (features 64+64, H=256)
 static int fused_generic_net(const l2hmc_dense_net* n) {
@@ -1132,10 +1339,17 @@ extern "C" int l2hmc_gauge_step_plan(int64_t rows_all, int32_t cus, int64_t* row
   return n;
 }
 
+// hand-off workspace of the split 16-row form: a ticket per pair, then [workgroups][2 * 16 * D + 16] floats
+static size_t hand_ticket_bytes(int64_t pairs) { return align_up(sizeof(int) * (size_t)pairs, 256); }
+size_t fused_step_hand_bytes(int64_t B, int D) {
+  const int64_t pairs = ceil_div(B, (int64_t)kFM);
+  return hand_ticket_bytes(pairs) + sizeof(float) * (size_t)(2 * pairs) * (2 * kFM * (size_t)D + kFM);
+}
+
 int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, float* x_next, int64_t B,
                       uint64_t seed, uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges,
-                      float* dq, float* step_sums, float* part, hipStream_t stream, float* x_prop, float* v_prop,
-                      float* x_out) {
+                      float* dq, float* step_sums, float* part, void* hand, hipStream_t stream, float* x_prop,
+                      float* v_prop, float* x_out) {
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
   using CfgG = FusedCfg<128, 512, 128, false>;
   using CfgC = FusedCfg<128, 256, 64, true>;
@@ -1153,7 +1367,7 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
     }
     step_once.done();
   }
-  L2HMC_REQUIRE(x_in && (x_next || x_out) && B > 0 && (!step_sums || part), "fused step: bad arguments");
+  L2HMC_REQUIRE(x_in && (x_next || x_out) && B > 0 && (!step_sums || part) && hand, "fused step: bad arguments");
   // Which form runs which chains (GenericNet 8x8 plans; all forms give the same bits).  The 16-row form covers
   // 16 * (number of CUs) rows per round of workgroups (1.58 ms at the benchmark dynamics), so a batch one chain past a
   // round costs a whole further round.  The batch is cut into at most three parts, launched one after the other on the
@@ -1190,7 +1404,30 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
 #endif
     return a;
   };
-  auto launch16 = [&](const FusedArgs& a) {
+  // GenericNet, both directions: the split form (FusedArgs::step_split), with the active-column heads unless the plan
+  // has none or asks for all columns (L2HMC_PLAN_ALL_COLUMNS)
+  const bool split = !conv && both;
+  const int* hmeta = nullptr;
+  const float* himg = nullptr;
+  if (split && p->heads && !(p->flags & L2HMC_PLAN_ALL_COLUMNS)) {
+    hmeta = reinterpret_cast<const int*>(p->heads);
+    himg = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p->heads) +
+                                          heads_meta_bytes(p->num_steps, 2 * p->T * p->X));
+  }
+  auto launch16 = [&](FusedArgs a) {
+    if (split) {
+      const int64_t pairs = ceil_div(a.step_Bl, (int64_t)kFM);
+      a.rows = 2 * pairs * kFM;
+      a.step_split = 1;
+      a.step_ticket = static_cast<int*>(hand);
+      a.step_hand = reinterpret_cast<float*>(static_cast<char*>(hand) + hand_ticket_bytes(pairs));
+      a.heads_meta = hmeta;
+      a.heads_img = himg;
+      if (hipMemsetAsync(a.step_ticket, 0, sizeof(int) * (size_t)pairs, stream) != hipSuccess) {
+        set_error("fused step: cannot clear the hand-off tickets");
+        return L2HMC_ERR_HIP;
+      }
+    }
     const unsigned nwg = (unsigned)(a.rows / kFM);
     prof_before(kProfFused, stream);
     if (conv)
@@ -1216,6 +1453,28 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
 }  // namespace l2hmc
 
 using namespace l2hmc;
+
+extern "C" size_t l2hmc_gauge_pack_heads_bytes(const l2hmc_gauge_plan* plan) {
+  if (!plan || plan->hmc || plan->num_steps <= 0 || (plan->flags & L2HMC_PLAN_CONV3D) || 2 * plan->T * plan->X != 128 ||
+      !fused_generic_net(&plan->xnet))
+    return 0;
+  const int D = 128, H = plan->xnet.H;
+  return heads_meta_bytes(plan->num_steps, D) + sizeof(float) * (size_t)2 * plan->num_steps * 3 * (D / 2) * H;
+}
+
+extern "C" int l2hmc_gauge_pack_heads(const l2hmc_gauge_plan* plan, void* buf, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(plan != nullptr && buf != nullptr, "gauge_pack_heads: NULL pointer");
+  L2HMC_REQUIRE(l2hmc_gauge_pack_heads_bytes(plan) > 0, "gauge_pack_heads: the plan has no active-column heads "
+                "(GenericNet D = 128, H = 512 on an 8x8-site lattice, hmc = 0)");
+  L2HMC_REQUIRE(plan->masks && plan->xnet.whd_t, "gauge_pack_heads: NULL masks or heads weights");
+  const int N = plan->num_steps, D = 128;
+  int* meta = static_cast<int*>(buf);
+  float* img = reinterpret_cast<float*>(static_cast<char*>(buf) + heads_meta_bytes(N, D));
+  hipLaunchKernelGGL(pack_heads_kernel, dim3(32, (unsigned)(2 * N)), dim3(256), 0, (hipStream_t)stream, plan->xnet,
+                     plan->masks, N, meta, img);
+  L2HMC_CHECK_LAUNCH("gauge_pack_heads");
+  return L2HMC_OK;
+}
 
 extern "C" size_t l2hmc_dense_pack_bytes(const l2hmc_dense_net* net) {
   if (!net || !fused_net_supported(net)) return 0;

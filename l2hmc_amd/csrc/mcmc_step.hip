@@ -77,8 +77,11 @@ static size_t step_head_bytes(int64_t B, int D) {
 
 extern "C" size_t l2hmc_gauge_mcmc_step_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B) {
   if (!plan || B < 0) return 0;
-  return step_head_bytes(B, 2 * plan->T * plan->X) + l2hmc_gauge_transition_ws_bytes(plan, B, 1) +
-         3 * align_up(sizeof(float) * (size_t)B * 2 * plan->T * plan->X, 256);
+  // the rest behind the head: the general path's transition workspace and outputs, or the one-launch step's hand-off
+  const size_t general = l2hmc_gauge_transition_ws_bytes(plan, B, 1) +
+                         3 * align_up(sizeof(float) * (size_t)B * 2 * plan->T * plan->X, 256);
+  const size_t hand = fused_step_hand_bytes(B, 2 * plan->T * plan->X);
+  return step_head_bytes(B, 2 * plan->T * plan->X) + (general > hand ? general : hand);
 }
 
 extern "C" int l2hmc_gauge_mcmc_step(const l2hmc_gauge_plan* plan, float beta, float* x, int64_t B, uint64_t seed,
@@ -117,7 +120,7 @@ extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta
   if (fused) {
     // ONE launch: the whole-trajectory kernel draws, integrates, mixes, accepts, measures and wraps (fused_traj.hip)
     return launch_fused_step(plan, beta, x, x_next, B, seed, draw, selected ? 0 : 1, px, actions, plaqs, charges,
-                             charge_diff, step_sums, Xw /* 2 * workgroups floats of scratch */, s);
+                             charge_diff, step_sums, Xw /* 2 * workgroups floats of scratch */, rest, s);
   }
   // momenta of both directions, coin | u  (tf.random_normal :269, tf.random_uniform :223,:246)
   const int64_t nblk = (((int64_t)2 * B * D + 3) >> 2) + ((2 * B + 3) >> 2);
@@ -169,7 +172,8 @@ extern "C" int l2hmc_gauge_transition_draw(const l2hmc_gauge_plan* plan, float b
   const bool selected = (plan->flags & L2HMC_PLAN_SELECTED_ONLY) != 0;
   if (!(plan->flags & L2HMC_PLAN_LAYERED) && fused_plan_supported(plan))
     return launch_fused_step(plan, beta, x, nullptr, B, seed, draw, selected ? 0 : 1, p_accept, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, s, x_prop, v_prop, x_out);
+                             nullptr, nullptr, nullptr, nullptr, static_cast<char*>(ws) + step_head_bytes(B, D), s,
+                             x_prop, v_prop, x_out);
   // other plans: the same draws into the workspace, then the public transition
   char* base = static_cast<char*>(ws);
   const size_t xv = align_up(sizeof(float) * (size_t)2 * B * D, 256);

@@ -147,7 +147,26 @@ class GaugeDynamics:
                 p.flags |= _lib.PLAN_CONV3D
                 p.xfront = self.position_fn.pack_front()
                 p.vfront = self.momentum_fn.pack_front()
+            elif self.fused:
+                p.heads = self._heads_image(p)
         return p
+
+    def _heads_image(self, plan):
+        """l2hmc_gauge_pack_heads image of the plan's masks and XNet heads (the whole-step kernel's position
+        sub-updates form S / T / Q on the columns they move), packed again whenever the masks or the weights change
+        (set_masks, a rebuilt or refreshed XNet image: trainer steps, load_state, broadcasts); None if the plan has
+        no such form."""
+        L = _lib.lib()
+        nbytes = L.l2hmc_gauge_pack_heads_bytes(C.byref(plan))
+        if not nbytes:
+            return None
+        key = (plan.xnet.whd_t, getattr(self.position_fn, "_pack_serial", 0))
+        h = getattr(self, "_heads", None)
+        if h is None or h[0] is not self.mask or h[1] != key or h[2].numel() * 4 < nbytes:
+            buf = torch.empty(nbytes // 4, dtype=torch.float32, device=self._device)
+            _lib.check(L.l2hmc_gauge_pack_heads(C.byref(plan), buf.data_ptr(), _lib.stream_ptr(self._device)))
+            self._heads = h = (self.mask, key, buf)
+        return h[2].data_ptr()
 
     def _x(self, a):
         a = _lib.as_dev(a, self._device)

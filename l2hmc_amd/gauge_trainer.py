@@ -123,6 +123,7 @@ class GaugeTrainer:
         self.dist.broadcast(self._eps_dev, src=src)
         dyn.eps = self._eps_dev.detach().cpu().reshape(())
         self.dist.broadcast(dyn.mask, src=src)
+        dyn._heads = None                 # the masks changed in place: the active-column heads are packed again
 
     # ---- views ----------------------------------------------------------------
     def grad_views(self):

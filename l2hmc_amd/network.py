@@ -187,6 +187,7 @@ class _DenseSTQ:
         if self._packed is not None and "packed" in self._packed[1]:
             st, bufs = self._packed
             _lib.check(_lib.lib().l2hmc_dense_pack(C.byref(st), bufs["packed"].data_ptr(), _lib.stream_ptr(self._device)))
+            self._pack_serial = getattr(self, "_pack_serial", 0) + 1
 
     def sync_reference_layout(self):
         """Flat training buffer -> reference-layout layer tensors (state_dict / save_weights read those).
@@ -230,6 +231,8 @@ class _DenseSTQ:
                 _lib.check(L.l2hmc_dense_pack(C.byref(st), bufs["packed"].data_ptr(), _lib.stream_ptr(self._device)))
                 st.packed = bufs["packed"].data_ptr()
             self._packed = (st, bufs)
+            # images derived from these weights elsewhere (GaugeDynamics' active-column heads) compare this counter
+            self._pack_serial = getattr(self, "_pack_serial", 0) + 1
         return self._packed[0]
 
     def flat_tensors(self):

@@ -23,8 +23,7 @@
 // buffered one k-chunk (16 k) ahead.  The A operand (16 rows of activations) is
 // shared by the 4 waves and read from LDS with conflict-free ds_read_b128
 // (row stride = K + 8 floats).
-#include "fused_common.h"
-#include "fused_args.h"
+#include "fused_step.h"
 #include <atomic>
 #include <stdlib.h>
 
@@ -243,79 +242,16 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     while ((long long)__builtin_amdgcn_s_memtime() - t0 < delay) __builtin_amdgcn_s_sleep(16);
   }
 #endif
-  // ---- stage chain state and constants ------------------------------------
-  const bool STEPM = p.step_B > 0;
+  // ---- stage chain state and constants (fused_step.h) ----------------------------
   // split step mode (FusedArgs::step_split): 16 chains of one direction, the direction uniform over the workgroup
-  const bool SPLIT = !CONV && !TAPE && STEPM && p.step_both && p.step_split;
-  const bool PAIRED = STEPM && p.step_both && !SPLIT;                    // 8 chains x both directions
-  const int sdw = SPLIT ? (int)(blockIdx.x & 1) : 0;                     // (SPLIT) this workgroup's direction
-  const int cpw = PAIRED ? kFM / 2 : kFM;                                // chains per workgroup in step mode
-  const int64_t cbase = SPLIT ? (int64_t)(blockIdx.x >> 1) * kFM : (int64_t)blockIdx.x * cpw;   // its first chain
-  float* scoin = stp;                    // [16] direction coin per chain slot
-  float* su = stp + kFM;                 // [16] MH uniform
-  float* spx = stp + 2 * kFM;            // [16] accept probability per row
-  float* sobs = stp + 3 * kFM;           // [16][4] sum cos P (in), sum project P (in), sum project P (out), p
-  auto philox_u01 = [&](uint64_t elem, uint64_t stream) {        // element `elem` of l2hmc_fill_uniform's stream
-    const uint64_t b = elem >> 2;
-    uint32_t c[4] = {(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
-    philox4x32_10(c, (uint32_t)p.step_seed, (uint32_t)(p.step_seed >> 32));
-    return (float)(c[elem & 3] >> 8) * (1.0f / 16777216.0f);
-  };
-  if (STEPM) {
-    if (tid < cpw) {
-      const int64_t chain = cbase + tid;
-      const bool lv = chain < p.step_Bl;          // (streams are indexed by the chain's place in the WHOLE batch)
-      scoin[tid] = lv ? philox_u01((uint64_t)(p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
-      su[tid] = lv ? philox_u01((uint64_t)(p.step_B + p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
-    }
-    __syncthreads();
-    for (int i = tid; i < kFM * (D / 4); i += kFThreads) {
-      const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
-      const int k = PAIRED ? (rr & (kFM / 2 - 1)) : rr;
-      const int64_t chain = cbase + k;
-      const int dsel = SPLIT ? sdw : PAIRED ? (rr >= kFM / 2 ? 1 : 0) : (scoin[k] > 0.5f ? 0 : 1);   // gauge_dynamics.py:221-227
-      f32x4 xv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (chain < p.step_Bl) {
-        xv = *reinterpret_cast<const f32x4*>(p.x0 + chain * D + c4);
-        // momentum of (direction dsel, chain): elements [(dsel * B + chain) * D, + D) of the normal stream
-        const uint64_t nb = (((uint64_t)dsel * (uint64_t)p.step_B + (uint64_t)(p.step_chain0 + chain)) * D + c4) >> 2;
-        uint32_t c[4] = {(uint32_t)nb, (uint32_t)(nb >> 32), (uint32_t)(2 * p.step_draw), (uint32_t)((2 * p.step_draw) >> 32)};
-        philox4x32_10(c, (uint32_t)p.step_seed, (uint32_t)(p.step_seed >> 32));
-        float nv[4];
-        philox_normal4(c, nv);
-        vv = f32x4{nv[0], nv[1], nv[2], nv[3]};
-      }
-      *reinterpret_cast<f32x4*>(xs + rr * SX + c4) = xv;
-      *reinterpret_cast<f32x4*>(vs + rr * SX + c4) = vv;
-    }
-  } else {
-    for (int i = tid; i < kFM * (D / 4); i += kFThreads) {
-      const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
-      f32x4 xv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (rr < nrow) {
-        const int64_t xr = p.x_mod > 0 ? (row0 + rr) % p.x_mod : row0 + rr;
-        xv = *reinterpret_cast<const f32x4*>(p.x0 + xr * D + c4);
-        vv = *reinterpret_cast<const f32x4*>(p.v0 + (row0 + rr) * D + c4);
-      }
-      *reinterpret_cast<f32x4*>(xs + rr * SX + c4) = xv;
-      *reinterpret_cast<f32x4*>(vs + rr * SX + c4) = vv;
-    }
-  }
-  auto load_consts = [&](const l2hmc_dense_net& n, float* c) {
-    for (int i = tid; i < H; i += kFThreads) {
-      c[i] = n.b1[i];
-      c[H + i] = n.wt[i];
-      c[2 * H + i] = n.wt[H + i];
-      c[3 * H + i] = n.bh[i];
-    }
-    for (int i = tid; i < 3 * D; i += kFThreads) c[4 * H + i] = n.bhd[i];
-    for (int i = tid; i < D; i += kFThreads) {
-      c[4 * H + 3 * D + i] = expf(n.coeff_s[i]);
-      c[4 * H + 4 * D + i] = expf(n.coeff_q[i]);
-    }
-  };
-  load_consts(p.xnet, cx);
-  load_consts(p.vnet, cv);
+  const bool SPLIT = !CONV && !TAPE && p.step_B > 0 && p.step_both && p.step_split;
+  const StepWg wg = step_workgroup<kFM>(p, stp, SPLIT);
+  const bool STEPM = wg.stepm;
+  const int sdw = wg.sdw;                                               // (SPLIT) this workgroup's direction
+  float* spx = wg.spx;                                                  // [16] accept probability per row
+  stage_chains<kFM, kFThreads, D, SX>(p, wg, xs, vs, sdir);
+  load_consts<kFThreads, D, H>(p.xnet, cx, tid);
+  load_consts<kFThreads, D, H>(p.vnet, cv, tid);
   if constexpr (CONV) {
     constexpr int F = Cfg::CF, F2 = 2 * Cfg::CF;
     auto load_filters = [&](const float* w1, const float* b1, const float* w2, const float* b2, float* dst) {
@@ -333,66 +269,16 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     load_filters(p.vfront.w1_b, p.vfront.b1_b, p.vfront.w2_b, p.vfront.b2_b, cwl + 3 * Cfg::CW);
     for (int i = tid; i < kFM * (Cfg::CXIN + Cfg::CP1); i += kFThreads) cxin[i] = 0.f;   // halos stay zero
   }
-  if (tid < kFM) {
-    int d = 0;
-    if (STEPM) d = SPLIT ? sdw : PAIRED ? (tid >= kFM / 2 ? 1 : 0) : (scoin[tid] > 0.5f ? 0 : 1);
-    else if (tid < nrow) d = p.dir ? p.dir[row0 + tid] : (p.dir_split > 0 && row0 + tid >= p.dir_split) ? 1 : 0;
-    sdir[tid] = d;
-  }
   if (tid < IMGW * kFM) ldw[tid] = 0.f;
   __syncthreads();
 
   const int dirl = sdir[r];           // direction of the row this lane owns in a C fragment (fused_common.h)
 
-  // ---- chain-local passes: kTPC consecutive threads per chain ------------------
-  // (GenericNet instances: kTPC = 16 whatever the wave count; the threads beyond 16 chains x 16 walk empty loops and
-  //  take part in the barriers only)
-  const bool own = tid < kFM * kTPC;
-  const int fc = own ? tid / kTPC : 0, fl = tid % kTPC;      // chain, lane-in-chain
-  const int sites_l = own ? sites : 0, D_l = own ? D : 0;    // loop bounds of the chain-local passes
-  auto chain_sum = [&](float v) {
-#pragma unroll
-    for (int off = kTPC / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-  };
-  const int T = p.T, X = p.X;
-  const int xsh = 31 - __clz(X);       // sites = 64 and X divides it: shifts instead of run-time divisions
-  // force (beta * dS/dx) into gs; returns this chain's action (all 16 lanes of the chain)
-  auto force_pass = [&]() -> float {
-    const float* xc = xs + fc * SX;
-    float act = 0.f;
-    for (int s = fl; s < sites_l; s += kTPC) {
-      const int i = s >> xsh, j = s & (X - 1);            // X is a power of two (T * X = 64)
-      const int jp = (j + 1 == X) ? 0 : j + 1, ip = (i + 1 == T) ? 0 : i + 1;
-      const float P = xc[2 * s] - xc[2 * s + 1] - xc[2 * (i * X + jp)] + xc[2 * (ip * X + j) + 1];
-      float sn, cs;
-      fast_sincos(P, &sn, &cs);
-      sp[fc * SP + s] = sn;
-      act += 1.f - cs;
-    }
-    act = chain_sum(act);
-    __syncthreads();
-    float* gc = gs + fc * SX;
-    const float* spc = sp + fc * SP;
-    for (int s = fl; s < sites_l; s += kTPC) {
-      const int i = s >> xsh, j = s & (X - 1);            // X is a power of two (T * X = 64)
-      const int jm = (j == 0) ? X - 1 : j - 1, im = (i == 0) ? T - 1 : i - 1;
-      const float sP = spc[s];
-      gc[2 * s] = p.beta * (sP - spc[i * X + jm]);
-      gc[2 * s + 1] = p.beta * (-sP + spc[im * X + j]);
-    }
-    __syncthreads();
-    return act;
-  };
-  auto kinetic_pass = [&]() -> float {
-    const float* vc = vs + fc * SX;
-    float k = 0.f;
-    for (int d = fl; d < D_l; d += kTPC) k += vc[d] * vc[d];
-    return 0.5f * chain_sum(k);
-  };
-
-  const float act0 = force_pass();     // also leaves the force of x0 in gs
-  const float kin0 = kinetic_pass();
+  // ---- chain-local passes (fused_step.h): kTPC consecutive threads per chain, one chain per thread group
+  const ChainLanes cl = chain_lanes<kFM, kTPC, 1>(p, tid);
+  float act0[1], kin0[1];
+  force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
+  kinetic_pass<kFM, kTPC, 1, D, SX>(cl, vs, kin0);
 
   // ---- one network evaluation + fused sub-update ------------------------------
   // in1: first input rows (LDS, stride SX); second input is always gs.
@@ -913,7 +799,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       const bool is_v = call == 0 || call == 3;
       if (call == 3) {
         [[maybe_unused]] const unsigned long long tf = FT_NOW();
-        (void)force_pass();                                    // force at the new position
+        float unused[1];
+        force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, unused);   // force at the new position
         FT_ADD(7, tf);
       }
       // call 0: momentum half-kick (+ keep (.) x into gs)      call 1: position sub-update 1 (+ complement mask)
@@ -926,16 +813,11 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   }
 
   // ---- epilogue: energies, accept probability, write back -------------------------
-  const float act1 = force_pass();
-  const float kin1 = kinetic_pass();
+  float act1[1], kin1[1];
+  force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, act1);
+  kinetic_pass<kFM, kTPC, 1, D, SX>(cl, vs, kin1);
   if (STEPM) {
-    if (own && fl == 0) {
-      float sld = 0.f;
-#pragma unroll
-      for (int w = 0; w < IMGW; ++w) sld += ldw[w * kFM + fc];
-      const double dh = (double)p.beta * ((double)act0 - (double)act1) + ((double)kin0 - (double)kin1) + (double)sld;
-      spx[fc] = accept_from_delta(dh);
-    }
+    step_accept_probs<kFM, 1, IMGW>(cl, ldw, act0, act1, kin0, kin1, spx);
     __syncthreads();
     // forward / backward rows of chain k (x, v: row stride SX) and their accept probabilities
     const float* xfr = xs;
@@ -993,175 +875,22 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         xbr = xs; vbr = vs; pbr = spx;
       }
     }
-    // ---- mix the two directions, Metropolis-Hastings (gauge_dynamics.py:221-257, arithmetic kept as
-    //      mask * a + (1 - mask) * b); x_in -> gs rows, x_out -> h1 rows (both free now)
+    // ---- mix, accept, measure, sum, wrap (fused_step.h); x_in -> gs rows, x_out -> h1 rows (both free now)
     float* gin = gs;
     float* gout = h1;
-    for (int i = tid; i < cpw * (D / 4); i += kFThreads) {
-      const int k = i / (D / 4), c4 = (i - k * (D / 4)) * 4;
-      const int64_t chain = cbase + k;
-      f32x4 xin = {0.f, 0.f, 0.f, 0.f};
-      if (chain < p.step_Bl) xin = *reinterpret_cast<const f32x4*>(p.x0 + chain * D + c4);
-      f32x4 xp;
-      float pk;
-      if (p.step_both) {
-        const float fm = scoin[k] > 0.5f ? 1.f : 0.f, bm = 1.f - fm;
-        pk = fm * pfr[k] + bm * pbr[k];
-        const f32x4 xf = *reinterpret_cast<const f32x4*>(xfr + k * SX + c4);
-        const f32x4 xb = *reinterpret_cast<const f32x4*>(xbr + k * SX + c4);
-        xp = fm * xf + bm * xb;
-      } else {
-        pk = spx[k];
-        xp = *reinterpret_cast<const f32x4*>(xs + k * SX + c4);
-      }
-      const float am = pk > su[k] ? 1.f : 0.f;                       // strict >, quirk Q5
-      const f32x4 xo = am * xp + (1.f - am) * xin;
-      *reinterpret_cast<f32x4*>(gin + k * SX + c4) = xin;
-      *reinterpret_cast<f32x4*>(gout + k * SX + c4) = xo;
-      if (c4 == 0) sobs[k * 4 + 3] = pk;
-      if (chain < p.step_Bl) {                                       // apply_transition's own outputs (:259)
-        if (p.step_xprop) *reinterpret_cast<f32x4*>(p.step_xprop + chain * D + c4) = xp;
-        if (p.step_xout) *reinterpret_cast<f32x4*>(p.step_xout + chain * D + c4) = xo;
-        if (p.step_vprop) {
-          f32x4 vp = *reinterpret_cast<const f32x4*>(vfr + k * SX + c4);
-          if (p.step_both) {
-            const float fm = scoin[k] > 0.5f ? 1.f : 0.f, bm = 1.f - fm;
-            vp = fm * vp + bm * *reinterpret_cast<const f32x4*>(vbr + k * SX + c4);
-          }
-          *reinterpret_cast<f32x4*>(p.step_vprop + chain * D + c4) = vp;
-        }
-      }
-    }
-    __syncthreads();
-    // ---- observables of the step's INPUT samples (gauge_model.py:256-266) and the charge of its output (:718-725)
-    auto plaq_sums = [&](const float* xc, float& scos, float& sproj) {
-      const float inv2pi = 0.15915494309189533577f;
-      float a = 0.f, b = 0.f;
-      for (int st = fl; st < sites_l; st += kTPC) {
-        const int i = st >> xsh, j = st & (X - 1);
-        const int jp = (j + 1 == X) ? 0 : j + 1, ip = (i + 1 == T) ? 0 : i + 1;
-        const float P = xc[2 * st] - xc[2 * st + 1] - xc[2 * (i * X + jp)] + xc[2 * (ip * X + j) + 1];
-        float sn, cs;
-        fast_sincos(P, &sn, &cs);
-        a += cs;
-        b += P - 6.28318530717958647692f * floorf((P + 3.14159265358979323846f) * inv2pi);   // project_angle
-      }
-      scos = chain_sum(a);
-      sproj = chain_sum(b);
-    };
-    if (PAIRED) {
-      float a, b;
-      plaq_sums(fc < kFM / 2 ? gin + fc * SX : gout + (fc - kFM / 2) * SX, a, b);
-      if (own && fl == 0) {
-        if (fc < kFM / 2) { sobs[fc * 4 + 0] = a; sobs[fc * 4 + 1] = b; }
-        else sobs[(fc - kFM / 2) * 4 + 2] = b;
-      }
-    } else {
-      float a, b, c_, d_;
-      plaq_sums(gin + fc * SX, a, b);
-      plaq_sums(gout + fc * SX, c_, d_);
-      if (own && fl == 0) { sobs[fc * 4 + 0] = a; sobs[fc * 4 + 1] = b; sobs[fc * 4 + 2] = d_; }
-    }
-    __syncthreads();
-    const float inv2pi = 0.15915494309189533577f;
-    if (tid < cpw) {
-      const int64_t chain = cbase + tid;
-      if (chain < p.step_Bl) {
-        const float q_in = sobs[tid * 4 + 1] * inv2pi, q_out = sobs[tid * 4 + 2] * inv2pi;
-        if (p.step_px) p.step_px[chain] = sobs[tid * 4 + 3];
-        if (p.step_act) p.step_act[chain] = (float)sites - sobs[tid * 4 + 0];      // sum (1 - cos P)
-        if (p.step_plq) p.step_plq[chain] = sobs[tid * 4 + 0] / (float)sites;
-        if (p.step_chg) p.step_chg[chain] = q_in;
-        if (p.step_dq) p.step_dq[chain] = fabsf(q_in - q_out);
-      }
-    }
-    if (p.step_sums) {
-      // [sum p_accept, sum |dQ|, chains] in a fixed order and without a further launch: every workgroup leaves its
-      // partial sums in step_part, the last one to arrive (ticket in step_sums[3]) adds them up and resets the ticket
-      int* last = reinterpret_cast<int*>(spx);            // spx is free again
-      // (SPLIT: a pair leaves the partial sums of the two 8-chain groups the paired layout gives its workgroups --
-      //  the same entries, the same order; only the pairs' last arrivers take part)
-      const int ngrp = SPLIT ? 2 : 1, gch = cpw / ngrp;
-      const int nfin = SPLIT ? (int)(gridDim.x >> 1) : (int)gridDim.x;
-      const int npart = SPLIT ? (int)((p.step_Bl + kFM / 2 - 1) / (kFM / 2)) : (int)gridDim.x;
-      if (tid == 0) {
-        for (int g = 0; g < ngrp; ++g) {
-          float a0 = 0.f, a1 = 0.f;
-          for (int k = g * gch; k < (g + 1) * gch; ++k) {
-            if (cbase + k < p.step_Bl) {
-              a0 += sobs[k * 4 + 3];
-              a1 += fabsf(sobs[k * 4 + 1] * inv2pi - sobs[k * 4 + 2] * inv2pi);
-            }
-          }
-          const int64_t slot = SPLIT ? (int64_t)(blockIdx.x >> 1) * 2 + g : (int64_t)blockIdx.x;
-          if (slot < npart) {
-            p.step_part[2 * slot] = a0;
-            p.step_part[2 * slot + 1] = a1;
-          }
-        }
-        __threadfence();
-        *last = atomicAdd(reinterpret_cast<int*>(p.step_sums + 3), 1) == nfin - 1;
-      }
-      __syncthreads();
-      if (*last) {
-        __threadfence();
-        float a0 = 0.f, a1 = 0.f;
-        for (int b = tid; b < npart; b += kFThreads) {
-          a0 += p.step_part[2 * b];
-          a1 += p.step_part[2 * b + 1];
-        }
-        float* fin = vs;                                  // [2][kFThreads] scratch (vs is dead)
-        fin[tid] = a0;
-        fin[kFThreads + tid] = a1;
-        __syncthreads();
-        for (int st = kFThreads / 2; st > 0; st >>= 1) {
-          if (tid < st) {
-            fin[tid] += fin[tid + st];
-            fin[kFThreads + tid] += fin[kFThreads + tid + st];
-          }
-          __syncthreads();
-        }
-        if (tid == 0) {
-          p.step_sums[0] = p.step_sums_acc ? p.step_sums[0] + fin[0] : fin[0];          // (a batch cut into two launches)
-          p.step_sums[1] = p.step_sums_acc ? p.step_sums[1] + fin[kFThreads] : fin[kFThreads];
-          p.step_sums[2] = (float)p.step_B;
-          *reinterpret_cast<int*>(p.step_sums + 3) = 0;
-        }
-      }
-    }
-    // ---- np.mod(x_out, 2 pi) (gauge_model.py:1388) and the write-back of the chains' new state
-    for (int i = tid; p.step_x_next && i < cpw * (D / 4); i += kFThreads) {
-      const int k = i / (D / 4), c4 = (i - k * (D / 4)) * 4;
-      const int64_t chain = cbase + k;
-      if (chain < p.step_Bl) {
-        f32x4 w = *reinterpret_cast<const f32x4*>(gout + k * SX + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float tp = 6.28318530717958647692f;
-          float m_ = fmaf(-tp, floorf(w[e] * 0.15915494309189533577f), w[e]);       // w - 2 pi floor(w / 2 pi)
-          if (m_ < 0.f) m_ += tp;
-          if (m_ >= tp) m_ -= tp;
-          w[e] = m_;
-        }
-        *reinterpret_cast<f32x4*>(p.step_x_next + chain * D + c4) = w;
-      }
-    }
+    step_mix_accept<kFThreads, D, SX>(p, wg, xfr, xbr, vfr, vbr, pfr, pbr, gin, gout);
+    step_observables<kFM, kTPC, 1, D, SX>(p, wg, cl, gin, gout);
+    // (SPLIT: a pair leaves the partial sums of the two 8-chain groups the paired layout gives its workgroups --
+    //  the same entries, the same order; only the pairs' last arrivers take part)
+    const int ngrp = SPLIT ? 2 : 1;
+    const int64_t slot0 = SPLIT ? (int64_t)(blockIdx.x >> 1) * 2 : (int64_t)blockIdx.x;
+    const int nfin = SPLIT ? (int)(gridDim.x >> 1) : (int)gridDim.x;
+    const int npart = SPLIT ? (int)((p.step_Bl + kFM / 2 - 1) / (kFM / 2)) : (int)gridDim.x;
+    step_sums<kFThreads, kFThreads>(p, wg, ngrp, slot0, npart, nfin, /*fin=*/vs);     // (vs is dead)
+    step_write_next<kFThreads, D, SX>(p, wg, gout);
     return;
   }
-  if (own && fl == 0 && fc < nrow) {
-    float sld = 0.f;
-
-#pragma unroll
-    for (int w = 0; w < IMGW; ++w) sld += ldw[w * kFM + fc];      // fixed order: bit-reproducible
-    const int64_t rr = row0 + fc;
-    if (p.logdet) p.logdet[rr] = p.logdet_accumulate ? p.logdet[rr] + sld : sld;
-    if (p.p_accept) {
-      // gauge_dynamics.py:592-609; the O(100) Hamiltonians are differenced in fp64
-      const double dh = (double)p.beta * ((double)act0 - (double)act1) + ((double)kin0 - (double)kin1) +
-                        (double)sld;
-      p.p_accept[rr] = accept_from_delta(dh);
-    }
-  }
+  traj_logdet_accept<kFM, 1, IMGW>(p, wg, cl, ldw, act0, act1, kin0, kin1);
 #ifdef L2HMC_STAMPS
   if (p.stamps && tid == 0) {
     unsigned long long rt1;
@@ -1172,13 +901,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     p.stamps[blockIdx.x * 12 + 11] = rt1;
   }
 #endif
-  for (int i = tid; i < kFM * (D / 4); i += kFThreads) {
-    const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
-    if (rr < nrow) {
-      *reinterpret_cast<f32x4*>(p.x_out + (row0 + rr) * D + c4) = *reinterpret_cast<const f32x4*>(xs + rr * SX + c4);
-      *reinterpret_cast<f32x4*>(p.v_out + (row0 + rr) * D + c4) = *reinterpret_cast<const f32x4*>(vs + rr * SX + c4);
-    }
-  }
+  traj_write_back<kFM, kFThreads, D, SX>(p, wg, xs, vs);
 }
 
 // ---------------------------------------------------------------------------

@@ -10,15 +10,15 @@
 //
 // Same algorithm, same packed weight image, same arithmetic ORDER as fused_traj.hip
 // (l2hmc/dynamics/gauge_dynamics.py:261-313, :412-609; network/generic_net.py:129-146): a row's accumulators see
-// their k in the same order, epilogue expressions, log-det grouping, chain-local sums (16 lanes per chain) and the
-// Philox indexing are the 16-row form's -- results are bit-identical
+// their k in the same order, epilogue expressions and log-det grouping are the 16-row form's, and everything around
+// net_update (draws, chain-local passes, accept, observables, step sums, write-back) is the one copy in fused_step.h
+// -- results are bit-identical
 // (tests/test_gpu_parity.py::test_subtile_and_32_row_forms_equal_16_row_form).
 //
 // LDS: x, v, force rows (3 x 32 x 136), ONE hidden buffer (32 x 520; the second layer's output overwrites its input
 // behind an extra barrier -- two buffers would need 218 KB), constants, masks, scratch: 153.7 KB.  GenericNet on the
 // 8x8 lattice (D = 128, H = 512), sampling only (no tape, no ConvNet3D).
-#include "fused_common.h"
-#include "fused_args.h"
+#include "fused_step.h"
 
 namespace l2hmc {
 
@@ -117,7 +117,6 @@ __device__ __forceinline__ void stream_layer2(BRing<NT, DEPTH>& R, const float* 
 
 __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
   constexpr int ROWS = kR32, SX = kSX, SH = kSH, SP = kSP, D = kD, H = kH, NT1 = kNT1, NTH = kNTH;
-  constexpr int sites = D / 2;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* xs = lds;                         // [32][SX] position
   float* vs = xs + ROWS * SX;              // [32][SX] momentum
@@ -135,148 +134,25 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int q = lane >> 4, r = lane & 15;
-  const int64_t row0 = (int64_t)blockIdx.x * ROWS;
-  const int nrow = (int)min((int64_t)ROWS, p.rows - row0);
   const float eps = p.eps;
 
-  // ---- stage chain state and constants (as fused_traj.hip, kFM -> 32) ----
-  const bool STEPM = p.step_B > 0;
-  const int cpw = STEPM ? (p.step_both ? ROWS / 2 : ROWS) : ROWS;
-  float* scoin = stp;
-  float* su = stp + ROWS;
-  float* spx = stp + 2 * ROWS;
-  float* sobs = stp + 3 * ROWS;            // [32][4]
-  auto philox_u01 = [&](uint64_t elem, uint64_t stream) {
-    const uint64_t b = elem >> 2;
-    uint32_t c[4] = {(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
-    philox4x32_10(c, (uint32_t)p.step_seed, (uint32_t)(p.step_seed >> 32));
-    return (float)(c[elem & 3] >> 8) * (1.0f / 16777216.0f);
-  };
-  if (STEPM) {
-    if (tid < cpw) {
-      const int64_t chain = (int64_t)blockIdx.x * cpw + tid;
-      const bool lv = chain < p.step_Bl;          // (streams are indexed by the chain's place in the WHOLE batch)
-      scoin[tid] = lv ? philox_u01((uint64_t)(p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
-      su[tid] = lv ? philox_u01((uint64_t)(p.step_B + p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
-    }
-    __syncthreads();
-    for (int i = tid; i < ROWS * (D / 4); i += kT32) {
-      const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
-      const int k = p.step_both ? (rr & (ROWS / 2 - 1)) : rr;
-      const int64_t chain = (int64_t)blockIdx.x * cpw + k;
-      const int dsel = p.step_both ? (rr >= ROWS / 2 ? 1 : 0) : (scoin[k] > 0.5f ? 0 : 1);   // gauge_dynamics.py:221-227
-      f32x4 xv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (chain < p.step_Bl) {
-        xv = *reinterpret_cast<const f32x4*>(p.x0 + chain * D + c4);
-        const uint64_t nb = (((uint64_t)dsel * (uint64_t)p.step_B + (uint64_t)(p.step_chain0 + chain)) * D + c4) >> 2;
-        uint32_t c[4] = {(uint32_t)nb, (uint32_t)(nb >> 32), (uint32_t)(2 * p.step_draw), (uint32_t)((2 * p.step_draw) >> 32)};
-        philox4x32_10(c, (uint32_t)p.step_seed, (uint32_t)(p.step_seed >> 32));
-        float nv[4];
-        philox_normal4(c, nv);
-        vv = f32x4{nv[0], nv[1], nv[2], nv[3]};
-      }
-      *reinterpret_cast<f32x4*>(xs + rr * SX + c4) = xv;
-      *reinterpret_cast<f32x4*>(vs + rr * SX + c4) = vv;
-    }
-  } else {
-    for (int i = tid; i < ROWS * (D / 4); i += kT32) {
-      const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
-      f32x4 xv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (rr < nrow) {
-        const int64_t xr = p.x_mod > 0 ? (row0 + rr) % p.x_mod : row0 + rr;
-        xv = *reinterpret_cast<const f32x4*>(p.x0 + xr * D + c4);
-        vv = *reinterpret_cast<const f32x4*>(p.v0 + (row0 + rr) * D + c4);
-      }
-      *reinterpret_cast<f32x4*>(xs + rr * SX + c4) = xv;
-      *reinterpret_cast<f32x4*>(vs + rr * SX + c4) = vv;
-    }
-  }
-  auto load_consts = [&](const l2hmc_dense_net& n, float* c) {
-    for (int i = tid; i < H; i += kT32) {
-      c[i] = n.b1[i];
-      c[H + i] = n.wt[i];
-      c[2 * H + i] = n.wt[H + i];
-      c[3 * H + i] = n.bh[i];
-    }
-    for (int i = tid; i < 3 * D; i += kT32) c[4 * H + i] = n.bhd[i];
-    for (int i = tid; i < D; i += kT32) {
-      c[4 * H + 3 * D + i] = expf(n.coeff_s[i]);
-      c[4 * H + 4 * D + i] = expf(n.coeff_q[i]);
-    }
-  };
-  load_consts(p.xnet, cx);
-  load_consts(p.vnet, cv);
-  if (tid < ROWS) {
-    int d = 0;
-    if (STEPM) d = p.step_both ? (tid >= ROWS / 2 ? 1 : 0) : (scoin[tid] > 0.5f ? 0 : 1);
-    else if (tid < nrow) d = p.dir ? p.dir[row0 + tid] : (p.dir_split > 0 && row0 + tid >= p.dir_split) ? 1 : 0;
-    sdir[tid] = d;
-  }
+  // ---- stage chain state and constants (fused_step.h) ----
+  const StepWg wg = step_workgroup<ROWS>(p, stp, /*split=*/false);
+  stage_chains<ROWS, kT32, D, SX>(p, wg, xs, vs, sdir);
+  load_consts<kT32, D, H>(p.xnet, cx, tid);
+  load_consts<kT32, D, H>(p.vnet, cv, tid);
   if (tid < kIW32 * ROWS) ldw[tid] = 0.f;
   __syncthreads();
 
   // direction of the rows this lane owns in its C fragments: row 16 g + r
   const int dirl[kG32] = {sdir[r], sdir[16 + r]};
 
-  // ---- chain-local passes: 16 consecutive threads per chain, two passes of 16 chains (chain = 16 h + tid / 16);
-  //      the terms of a chain are strided by 16 and summed by a butterfly over 16 lanes, as in the 16-row form
-  // (the threads beyond 256 walk empty loops there and take part in the barriers only)
-  const bool own = tid < kCT32;
-  const int fc0 = own ? tid / kTPC : 0, fl = tid % kTPC;
-  const int sites_l = own ? sites : 0, D_l = own ? D : 0;
-  auto chain_sum = [&](float v) {
-#pragma unroll
-    for (int off = kTPC / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-  };
-  const int T = p.T, X = p.X;
-  const int xsh = 31 - __clz(X);
-  // force (beta * dS/dx) into gs; act[h] = the action of chain 16 h + fc0 (all 16 lanes of the chain)
-  auto force_pass = [&](float (&act)[kG32]) {
-#pragma unroll
-    for (int h = 0; h < kG32; ++h) {
-      const int fc = 16 * h + fc0;
-      const float* xc = xs + fc * SX;
-      float a = 0.f;
-      for (int s = fl; s < sites_l; s += kTPC) {
-        const int i = s >> xsh, j = s & (X - 1);
-        const int jp = (j + 1 == X) ? 0 : j + 1, ip = (i + 1 == T) ? 0 : i + 1;
-        const float P = xc[2 * s] - xc[2 * s + 1] - xc[2 * (i * X + jp)] + xc[2 * (ip * X + j) + 1];
-        float sn, cs;
-        fast_sincos(P, &sn, &cs);
-        sp[fc * SP + s] = sn;
-        a += 1.f - cs;
-      }
-      act[h] = chain_sum(a);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < kG32; ++h) {
-      const int fc = 16 * h + fc0;
-      float* gc = gs + fc * SX;
-      const float* spc = sp + fc * SP;
-      for (int s = fl; s < sites_l; s += kTPC) {
-        const int i = s >> xsh, j = s & (X - 1);
-        const int jm = (j == 0) ? X - 1 : j - 1, im = (i == 0) ? T - 1 : i - 1;
-        const float sP = spc[s];
-        gc[2 * s] = p.beta * (sP - spc[i * X + jm]);
-        gc[2 * s + 1] = p.beta * (-sP + spc[im * X + j]);
-      }
-    }
-    __syncthreads();
-  };
-  auto kinetic_pass = [&](float (&kin)[kG32]) {
-#pragma unroll
-    for (int h = 0; h < kG32; ++h) {
-      const float* vc = vs + (16 * h + fc0) * SX;
-      float k = 0.f;
-      for (int d = fl; d < D_l; d += kTPC) k += vc[d] * vc[d];
-      kin[h] = 0.5f * chain_sum(k);
-    }
-  };
+  // ---- chain-local passes (fused_step.h): 16 consecutive threads per chain on the first 256 threads, two chains
+  //      per thread group (chain = 16 h + tid / 16)
+  const ChainLanes cl = chain_lanes<ROWS, kTPC, kG32>(p, tid);
   float act0[kG32], kin0[kG32];
-  force_pass(act0);                        // also leaves the force of x0 in gs
-  kinetic_pass(kin0);
+  force_pass<ROWS, kTPC, kG32, D, SX, SP>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
+  kinetic_pass<ROWS, kTPC, kG32, D, SX>(cl, vs, kin0);
 
   // recurring first-layer products kept in registers (fused_traj.hip: keep_v, keep_x)
   f32x4 keep_v[kG32][NT1], keep_x[kG32][NT1];
@@ -507,8 +383,8 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
     for (int call = 0; call < 4; ++call) {
       const bool is_v = call == 0 || call == 3;
       if (call == 3) {
-        float dummy[kG32];
-        force_pass(dummy);                                     // force at the new position
+        float unused[kG32];
+        force_pass<ROWS, kTPC, kG32, D, SX, SP>(cl, xs, sp, gs, unused);   // force at the new position
       }
       const int l1 = call == 0 ? (keep_v_valid ? 2 : 0) : call == 1 ? 3 : call == 2 ? 4 : 1;
       net_update(is_v ? p.vnet : p.xnet, is_v ? cv : cx, is_v ? xs : vs, is_v ? 1 : 2, call == 2 ? 1 : 0, call < 2, l1,
@@ -517,197 +393,27 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
     keep_v_valid = true;
   }
 
-  // ---- epilogue: energies, accept probability, write back (as fused_traj.hip, kFM -> 32, two passes of 16 chains) ----
+  // ---- epilogue: energies, accept probability, write back (fused_step.h) ----
   float act1[kG32], kin1[kG32];
-  force_pass(act1);
-  kinetic_pass(kin1);
-  if (STEPM) {
-    if (own && fl == 0) {
-#pragma unroll
-      for (int h = 0; h < kG32; ++h) {
-        const int fc = 16 * h + fc0;
-        float sld = 0.f;
-#pragma unroll
-        for (int w = 0; w < kIW32; ++w) sld += ldw[w * ROWS + fc];
-        const double dh = (double)p.beta * ((double)act0[h] - (double)act1[h]) + ((double)kin0[h] - (double)kin1[h]) +
-                          (double)sld;
-        spx[fc] = accept_from_delta(dh);
-      }
-    }
+  force_pass<ROWS, kTPC, kG32, D, SX, SP>(cl, xs, sp, gs, act1);
+  kinetic_pass<ROWS, kTPC, kG32, D, SX>(cl, vs, kin1);
+  if (wg.stepm) {
+    step_accept_probs<ROWS, kG32, kIW32>(cl, ldw, act0, act1, kin0, kin1, wg.spx);
     __syncthreads();
-    // ---- mix the two directions, Metropolis-Hastings; x_in -> gs rows, x_out -> hh rows (both free now)
-    float* gin = gs;
+    // both directions: rows [0, 16) forward, [16, 32) backward of the same chains
+    float* gin = gs;                                    // x_in -> gs rows, x_out -> hh rows (both free now)
     float* gout = hh;
-    for (int i = tid; i < cpw * (D / 4); i += kT32) {
-      const int k = i / (D / 4), c4 = (i - k * (D / 4)) * 4;
-      const int64_t chain = (int64_t)blockIdx.x * cpw + k;
-      f32x4 xin = {0.f, 0.f, 0.f, 0.f};
-      if (chain < p.step_Bl) xin = *reinterpret_cast<const f32x4*>(p.x0 + chain * D + c4);
-      f32x4 xp;
-      float pk;
-      if (p.step_both) {
-        const float fm = scoin[k] > 0.5f ? 1.f : 0.f, bm = 1.f - fm;
-        pk = fm * spx[k] + bm * spx[ROWS / 2 + k];
-        const f32x4 xf = *reinterpret_cast<const f32x4*>(xs + k * SX + c4);
-        const f32x4 xb = *reinterpret_cast<const f32x4*>(xs + (ROWS / 2 + k) * SX + c4);
-        xp = fm * xf + bm * xb;
-      } else {
-        pk = spx[k];
-        xp = *reinterpret_cast<const f32x4*>(xs + k * SX + c4);
-      }
-      const float am = pk > su[k] ? 1.f : 0.f;                       // strict >, quirk Q5
-      const f32x4 xo = am * xp + (1.f - am) * xin;
-      *reinterpret_cast<f32x4*>(gin + k * SX + c4) = xin;
-      *reinterpret_cast<f32x4*>(gout + k * SX + c4) = xo;
-      if (c4 == 0) sobs[k * 4 + 3] = pk;
-      if (chain < p.step_Bl) {
-        if (p.step_xprop) *reinterpret_cast<f32x4*>(p.step_xprop + chain * D + c4) = xp;
-        if (p.step_xout) *reinterpret_cast<f32x4*>(p.step_xout + chain * D + c4) = xo;
-        if (p.step_vprop) {
-          f32x4 vp = *reinterpret_cast<const f32x4*>(vs + k * SX + c4);
-          if (p.step_both) {
-            const float fm = scoin[k] > 0.5f ? 1.f : 0.f, bm = 1.f - fm;
-            vp = fm * vp + bm * *reinterpret_cast<const f32x4*>(vs + (ROWS / 2 + k) * SX + c4);
-          }
-          *reinterpret_cast<f32x4*>(p.step_vprop + chain * D + c4) = vp;
-        }
-      }
-    }
-    __syncthreads();
-    // ---- observables of the step's INPUT samples and the charge of its output
-    auto plaq_sums = [&](const float* xc, float& scos, float& sproj) {
-      const float inv2pi = 0.15915494309189533577f;
-      float a = 0.f, b = 0.f;
-      for (int st = fl; st < sites_l; st += kTPC) {
-        const int i = st >> xsh, j = st & (X - 1);
-        const int jp = (j + 1 == X) ? 0 : j + 1, ip = (i + 1 == T) ? 0 : i + 1;
-        const float P = xc[2 * st] - xc[2 * st + 1] - xc[2 * (i * X + jp)] + xc[2 * (ip * X + j) + 1];
-        float sn, cs;
-        fast_sincos(P, &sn, &cs);
-        a += cs;
-        b += P - 6.28318530717958647692f * floorf((P + 3.14159265358979323846f) * inv2pi);   // project_angle
-      }
-      scos = chain_sum(a);
-      sproj = chain_sum(b);
-    };
-#pragma unroll
-    for (int h = 0; h < kG32; ++h) {
-      const int fc = 16 * h + fc0;
-      if (p.step_both) {
-        float a, b;
-        plaq_sums(fc < ROWS / 2 ? gin + fc * SX : gout + (fc - ROWS / 2) * SX, a, b);
-        if (own && fl == 0) {
-          if (fc < ROWS / 2) { sobs[fc * 4 + 0] = a; sobs[fc * 4 + 1] = b; }
-          else sobs[(fc - ROWS / 2) * 4 + 2] = b;
-        }
-      } else {
-        float a, b, c_, d_;
-        plaq_sums(gin + fc * SX, a, b);
-        plaq_sums(gout + fc * SX, c_, d_);
-        if (own && fl == 0) { sobs[fc * 4 + 0] = a; sobs[fc * 4 + 1] = b; sobs[fc * 4 + 2] = d_; }
-      }
-    }
-    __syncthreads();
-    const float inv2pi = 0.15915494309189533577f;
-    if (tid < cpw) {
-      const int64_t chain = (int64_t)blockIdx.x * cpw + tid;
-      if (chain < p.step_Bl) {
-        const float q_in = sobs[tid * 4 + 1] * inv2pi, q_out = sobs[tid * 4 + 2] * inv2pi;
-        if (p.step_px) p.step_px[chain] = sobs[tid * 4 + 3];
-        if (p.step_act) p.step_act[chain] = (float)sites - sobs[tid * 4 + 0];      // sum (1 - cos P)
-        if (p.step_plq) p.step_plq[chain] = sobs[tid * 4 + 0] / (float)sites;
-        if (p.step_chg) p.step_chg[chain] = q_in;
-        if (p.step_dq) p.step_dq[chain] = fabsf(q_in - q_out);
-      }
-    }
-    if (p.step_sums) {
-      int* last = reinterpret_cast<int*>(spx);            // spx is free again
-      if (tid == 0) {
-        float a0 = 0.f, a1 = 0.f;
-        for (int k = 0; k < cpw; ++k) {
-          if ((int64_t)blockIdx.x * cpw + k < p.step_Bl) {
-            a0 += sobs[k * 4 + 3];
-            a1 += fabsf(sobs[k * 4 + 1] * inv2pi - sobs[k * 4 + 2] * inv2pi);
-          }
-        }
-        p.step_part[2 * blockIdx.x] = a0;
-        p.step_part[2 * blockIdx.x + 1] = a1;
-        __threadfence();
-        *last = atomicAdd(reinterpret_cast<int*>(p.step_sums + 3), 1) == (int)gridDim.x - 1;
-      }
-      __syncthreads();
-      if (*last) {
-        __threadfence();
-        float a0 = 0.f, a1 = 0.f;                         // (256 partial sums and their tree, whatever the thread count)
-        for (int b = tid; own && b < (int)gridDim.x; b += kCT32) {
-          a0 += p.step_part[2 * b];
-          a1 += p.step_part[2 * b + 1];
-        }
-        float* fin = vs;                                  // [2][256] scratch (vs is dead)
-        if (own) {
-          fin[tid] = a0;
-          fin[kCT32 + tid] = a1;
-        }
-        __syncthreads();
-        for (int st = kCT32 / 2; st > 0; st >>= 1) {
-          if (tid < st) {
-            fin[tid] += fin[tid + st];
-            fin[kCT32 + tid] += fin[kCT32 + tid + st];
-          }
-          __syncthreads();
-        }
-        if (tid == 0) {
-          p.step_sums[0] = p.step_sums_acc ? p.step_sums[0] + fin[0] : fin[0];
-          p.step_sums[1] = p.step_sums_acc ? p.step_sums[1] + fin[kCT32] : fin[kCT32];
-          p.step_sums[2] = (float)p.step_B;
-          *reinterpret_cast<int*>(p.step_sums + 3) = 0;
-        }
-      }
-    }
-    // ---- np.mod(x_out, 2 pi) (gauge_model.py:1388) and the write-back of the chains' new state
-    for (int i = tid; p.step_x_next && i < cpw * (D / 4); i += kT32) {
-      const int k = i / (D / 4), c4 = (i - k * (D / 4)) * 4;
-      const int64_t chain = (int64_t)blockIdx.x * cpw + k;
-      if (chain < p.step_Bl) {
-        f32x4 w = *reinterpret_cast<const f32x4*>(gout + k * SX + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float tp = 6.28318530717958647692f;
-          float m_ = fmaf(-tp, floorf(w[e] * 0.15915494309189533577f), w[e]);
-          if (m_ < 0.f) m_ += tp;
-          if (m_ >= tp) m_ -= tp;
-          w[e] = m_;
-        }
-        *reinterpret_cast<f32x4*>(p.step_x_next + chain * D + c4) = w;
-      }
-    }
+    step_mix_accept<kT32, D, SX>(p, wg, /*xfr=*/xs, /*xbr=*/xs + ROWS / 2 * SX, /*vfr=*/vs, /*vbr=*/vs + ROWS / 2 * SX,
+                                 /*pfr=*/wg.spx, /*pbr=*/wg.spx + ROWS / 2, gin, gout);
+    step_observables<ROWS, kTPC, kG32, D, SX>(p, wg, cl, gin, gout);
+    // (256 partial sums and their tree, whatever the thread count)
+    step_sums<kT32, kCT32>(p, wg, /*ngrp=*/1, /*slot0=*/blockIdx.x, /*npart=*/(int)gridDim.x, /*nfin=*/(int)gridDim.x,
+                           /*fin=*/vs);                 // (vs is dead)
+    step_write_next<kT32, D, SX>(p, wg, gout);
     return;
   }
-  if (own && fl == 0) {
-#pragma unroll
-    for (int h = 0; h < kG32; ++h) {
-      const int fc = 16 * h + fc0;
-      if (fc < nrow) {
-        float sld = 0.f;
-#pragma unroll
-        for (int w = 0; w < kIW32; ++w) sld += ldw[w * ROWS + fc];
-        const int64_t rr = row0 + fc;
-        if (p.logdet) p.logdet[rr] = p.logdet_accumulate ? p.logdet[rr] + sld : sld;
-        if (p.p_accept) {
-          const double dh = (double)p.beta * ((double)act0[h] - (double)act1[h]) + ((double)kin0[h] - (double)kin1[h]) +
-                            (double)sld;
-          p.p_accept[rr] = accept_from_delta(dh);
-        }
-      }
-    }
-  }
-  for (int i = tid; i < ROWS * (D / 4); i += kT32) {
-    const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
-    if (rr < nrow) {
-      *reinterpret_cast<f32x4*>(p.x_out + (row0 + rr) * D + c4) = *reinterpret_cast<const f32x4*>(xs + rr * SX + c4);
-      *reinterpret_cast<f32x4*>(p.v_out + (row0 + rr) * D + c4) = *reinterpret_cast<const f32x4*>(vs + rr * SX + c4);
-    }
-  }
+  traj_logdet_accept<ROWS, kG32, kIW32>(p, wg, cl, ldw, act0, act1, kin0, kin1);
+  traj_write_back<ROWS, kT32, D, SX>(p, wg, xs, vs);
 }
 
 }  // namespace

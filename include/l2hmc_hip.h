@@ -91,6 +91,7 @@ int l2hmc_kinetic_energy(const float* v, int64_t rows, int32_t D, float* out, l2
  *     kernels -- identical arithmetic, slower loads;
  *   - the whole-trajectory kernels exist for D = 128 (T*X = 64, X a power of two): GenericNet H = 512 and
  *     ConvNet3D F = 8 / H = 256; other shapes run layer by layer (l2hmc_dense_pack_bytes() == 0 says which);
+ *     plans with hmc = 1 have one for any lattice of up to 1024 sites;
  *   - the TRAINING entry points (l2hmc_gauge_train_*) need D, H, Ka, Kb multiples of 32; GaugeTrainer trains
  *     GenericNet plans of other widths through the layered-training entries below (l2hmc_stq_dense_taped, ...,
  *     l2hmc_u1_force_hvp);
@@ -202,7 +203,9 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */
-  int32_t hmc;             /* 1: S=T=Q=0 (gauge_dynamics.py:102-108), nets ignored */
+  int32_t hmc;             /* 1: S=T=Q=0 (gauge_dynamics.py:102-108), nets ignored: plain HMC.  Lattices of up to 1024
+                            * sites run every entry point below in ONE launch (l2hmc_gauge_plan_fused() == 1);
+                            * larger ones, and L2HMC_PLAN_LAYERED, go layer by layer */
   float eps;
   int32_t flags;           /* L2HMC_PLAN_* bits */
   const float* masks;      /* [num_steps][D] 0/1, gauge_dynamics.py:651-661 */

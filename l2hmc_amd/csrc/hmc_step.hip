@@ -1,0 +1,471 @@
+// Plain HMC on the 2D U(1) lattice in ONE launch, at a lattice size chosen at run time: the whole MCMC step
+// (l2hmc_gauge_mcmc_step, l2hmc_gauge_transition_draw) or a whole trajectory / single leapfrog step
+// (l2hmc_gauge_trajectory, l2hmc_gauge_leapfrog) of plans with hmc = 1 (gauge_dynamics.py:102-108: S = T = Q = 0).
+//
+// Without networks a leapfrog step is a few flops and ONE sin per plaquette, so the kernel is transcendental- and
+// latency-bound and its mapping is chosen for waves in flight, not for the matrix pipe:
+//   * a ROW (chain x direction) is walked by TPC = 2^k threads, thread fl owning the SPT sites fl, fl + TPC, ...
+//     (SPT = 1 up to 256 sites, 2 up to 512, 4 up to 1024): both links of its sites and their momenta stay in
+//     REGISTERS for the whole trajectory.  The momentum and position sub-updates are link-local and never leave them;
+//   * LDS holds a row's x as two planes [2][sites] (for the two neighbour links a plaquette needs: consecutive lanes
+//     read consecutive words, no bank conflict) and sin P (for the two neighbour plaquettes a link's force needs).
+//     The force itself is never stored: the momentum half-kick forms it from sin P.  Two barriers per leapfrog step
+//     (x published, sin P published);
+//   * a workgroup of 256 threads (512 where TPC = 256) holds 256 / TPC rows: 32 rows of a 2 x 4 lattice, 2 of a
+//     32 x 32 one.  In step mode with both directions they are the forward and the backward rows of the same chains
+//     (rows [0, R / 2) forward), so mixing, Metropolis-Hastings and the observables need no other workgroup.
+// The force at the end of a step is the force at the start of the next (x has not moved): one sin P pass per leapfrog
+// step plus one, against two in the layered path -- the same values, kept.
+//
+// Arithmetic: the sub-updates are those of lf_update_v_kernel / lf_update_x_kernel with S = T = Q = 0 (exp(0) = 1
+// folded), masks and step index num_steps - 1 - step for backward rows, two masked position sub-updates per step;
+// sin / cos are fast_sincos (u1_lattice.hip's).  The Philox draws, the fp64 accept probability, the fixed-order step
+// sums and the wrap are fused_step.h's own code.  The per-row sums (action, kinetic energy, sum cos P, sum project P)
+// are grouped differently from fused_step.h's 16-lane form: a thread adds its SPT terms in ascending order, a
+// butterfly adds the threads of a wave, waves are added in ascending order.
+#include "fused_step.h"
+
+namespace l2hmc {
+
+constexpr int kHmcMaxSites = 1024;        // 4 sites per thread x 256 threads per row
+constexpr int kHmcMaxThreads = 512;
+
+struct HmcGeom {
+  int spt, tsh, threads, rows_wg;         // sites per thread, log2(threads per row), workgroup size, rows per workgroup
+  size_t lds;
+};
+
+static bool hmc_geom(int T, int X, HmcGeom* g) {
+  if (T <= 0 || X <= 0 || (int64_t)T * X > kHmcMaxSites) return false;
+  const int sites = T * X;
+  g->spt = sites <= 256 ? 1 : sites <= 512 ? 2 : 4;
+  const int per = (sites + g->spt - 1) / g->spt;
+  g->tsh = 0;
+  while ((1 << g->tsh) < per) ++g->tsh;
+  g->threads = g->tsh == 8 ? kHmcMaxThreads : 256;
+  g->rows_wg = g->threads >> g->tsh;
+  // xs, vs [R][D], sin P [R][sites], step scratch [8 R], wave partials [R][4][2], sum tree [2][256]: 42 KiB at most
+  g->lds = sizeof(float) * ((size_t)g->rows_wg * (5 * sites + 8 + 8) + 2 * 256);
+  return true;
+}
+
+int hmc_plan_supported(const l2hmc_gauge_plan* p) {
+  HmcGeom g;
+  return p->hmc && p->num_steps > 0 && hmc_geom(p->T, p->X, &g);
+}
+
+// sums a and b over the threads of a row; every thread of the workgroup calls it (barriers where a row spans waves)
+__device__ __forceinline__ void hmc_row_sum2(float& a, float& b, int tsh, int r, int fl, float* red) {
+  const int w = tsh < 6 ? 1 << tsh : 64;
+  for (int off = w >> 1; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+  }
+  if (tsh > 6) {
+    const int nw = 1 << (tsh - 6);
+    if ((fl & 63) == 0) {
+      red[(r * 4 + (fl >> 6)) * 2] = a;
+      red[(r * 4 + (fl >> 6)) * 2 + 1] = b;
+    }
+    __syncthreads();
+    a = 0.f;
+    b = 0.f;
+    for (int q = 0; q < nw; ++q) {
+      a += red[(r * 4 + q) * 2];
+      b += red[(r * 4 + q) * 2 + 1];
+    }
+    __syncthreads();
+  }
+}
+
+template <int SPT>
+__global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArgs p, const int tsh) {
+  extern __shared__ float lds[];
+  const int T = p.T, X = p.X, sites = T * X, D = 2 * sites;
+  const int tid = threadIdx.x;
+  const int tpc = 1 << tsh, R = (int)blockDim.x >> tsh;
+  const int r = tid >> tsh, fl = tid & (tpc - 1);
+  float* xs = lds;                          // [R][2][sites]: the x0 links of a row, then its x1 links
+  float* vs = xs + R * D;                   // [R][2][sites] (step epilogue only)
+  float* sp = vs + R * D;                   // [R][sites]  sin P
+  float* stp = sp + R * sites;              // [8 R]       StepWg scratch
+  float* red = stp + 8 * R;                 // [R][4][2]   per-wave partial sums of a row
+  float* fin = red + 8 * R;                 // [2][256]
+
+  StepWg w;
+  w.tid = tid;
+  w.row0 = (int64_t)blockIdx.x * R;
+  w.nrow = (int)min((int64_t)R, p.rows - w.row0);
+  w.stepm = p.step_B > 0;
+  w.split = false;
+  w.paired = w.stepm && p.step_both;
+  w.sdw = 0;
+  w.cpw = w.paired ? R / 2 : R;
+  w.cbase = (int64_t)blockIdx.x * w.cpw;
+  w.scoin = stp;
+  w.su = stp + R;
+  w.spx = stp + 2 * R;
+  w.sobs = stp + 3 * R;
+
+  // ---- the row's chain and direction; step mode draws coin and MH uniform of the workgroup's chains first ----
+  if (w.stepm) {
+    if (tid < w.cpw) {
+      const int64_t chain = w.cbase + tid;
+      const bool lv = chain < p.step_Bl;        // (streams are indexed by the chain's place in the WHOLE batch)
+      w.scoin[tid] = lv ? philox_u01(p.step_seed, (uint64_t)(p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
+      w.su[tid] = lv ? philox_u01(p.step_seed, (uint64_t)(p.step_B + p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
+    }
+    __syncthreads();
+  }
+  int k = r, d = 0;                             // chain slot of the row (step mode), direction
+  int64_t grow;                                 // chain (step mode) or row (trajectory mode) in the launch's arrays
+  bool live;
+  if (w.stepm) {
+    k = w.paired && r >= w.cpw ? r - w.cpw : r;
+    grow = w.cbase + k;
+    live = grow < p.step_Bl;
+    d = w.paired ? (r >= w.cpw ? 1 : 0) : (w.scoin[k] > 0.5f ? 0 : 1);     // gauge_dynamics.py:221-227
+  } else {
+    grow = w.row0 + r;
+    live = r < w.nrow;
+    if (live && p.dir) d = p.dir[grow];
+  }
+
+  // ---- the thread's sites and their plaquette neighbours ----
+  bool ok[SPT];
+  int nr[SPT], nu[SPT], nl[SPT], nd[SPT];
+  float x0[SPT], x1[SPT], v0[SPT], v1[SPT], xi0[SPT], xi1[SPT];
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    const int s = fl + j * tpc;
+    ok[j] = s < sites;
+    const int sc = ok[j] ? s : 0;
+    const int i = sc / X, jx = sc - i * X;
+    nr[j] = i * X + (jx + 1 == X ? 0 : jx + 1);
+    nl[j] = i * X + (jx == 0 ? X - 1 : jx - 1);
+    nu[j] = (i + 1 == T ? 0 : i + 1) * X + jx;
+    nd[j] = (i == 0 ? T - 1 : i - 1) * X + jx;
+    x0[j] = x1[j] = v0[j] = v1[j] = 0.f;
+    if (ok[j] && live) {
+      const float* xr = p.x0 + grow * D + 2 * s;
+      x0[j] = xr[0];
+      x1[j] = xr[1];
+      if (w.stepm) {
+        // momenta of (direction d, chain): elements [(d * B + chain) * D, + D) of the normal stream; D is even, so
+        // the two links of a site are one Box-Muller pair of one Philox block
+        const uint64_t e = ((uint64_t)d * (uint64_t)p.step_B + (uint64_t)(p.step_chain0 + grow)) * (uint64_t)D + 2 * s;
+        const uint64_t nb = e >> 2;
+        uint32_t c[4] = {(uint32_t)nb, (uint32_t)(nb >> 32), (uint32_t)(2 * p.step_draw), (uint32_t)((2 * p.step_draw) >> 32)};
+        philox4x32_10(c, (uint32_t)p.step_seed, (uint32_t)(p.step_seed >> 32));
+        float nv[4];
+        philox_normal4(c, nv);
+        const bool hi = (e & 2) != 0;
+        v0[j] = hi ? nv[2] : nv[0];
+        v1[j] = hi ? nv[3] : nv[1];
+      } else {
+        const float* vr = p.v0 + grow * D + 2 * s;
+        v0[j] = vr[0];
+        v1[j] = vr[1];
+      }
+    }
+    xi0[j] = x0[j];
+    xi1[j] = x1[j];
+  }
+
+  float* xrow = xs + r * D;
+  float* sprow = sp + r * sites;
+  const float beta = p.beta, eps = p.eps;
+  float sP[SPT];
+
+  auto publish_x = [&]() {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j)
+      if (ok[j]) {
+        xrow[fl + j * tpc] = x0[j];
+        xrow[sites + fl + j * tpc] = x1[j];
+      }
+    __syncthreads();
+  };
+  // sin P of the thread's sites -> sP and LDS; returns the thread's share of the action sum (1 - cos P)
+  auto sin_pass = [&]() {
+    float a = 0.f;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      sP[j] = 0.f;
+      if (ok[j]) {
+        // gauge_model.py:676-679: x0[i,j] - x1[i,j] - x0[i,j+1] + x1[i+1,j]
+        const float P = x0[j] - x1[j] - xrow[nr[j]] + xrow[sites + nu[j]];
+        float sn, cs;
+        fast_sincos(P, &sn, &cs);
+        sP[j] = sn;
+        sprow[fl + j * tpc] = sn;
+        a += 1.f - cs;
+      }
+    }
+    __syncthreads();
+    return a;
+  };
+  // momentum half-kick (lf_update_v_kernel with S = T = Q = 0): force = beta dS/dx from sin P
+  auto kick = [&]() {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      if (ok[j]) {
+        const float g0 = beta * (sP[j] - sprow[nl[j]]);
+        const float g1 = beta * (-sP[j] + sprow[nd[j]]);
+        const float k0 = 0.5f * eps * g0, k1 = 0.5f * eps * g1;
+        v0[j] = d ? v0[j] + k0 : v0[j] - k0;
+        v1[j] = d ? v1[j] + k1 : v1[j] - k1;
+      }
+    }
+  };
+  auto kinetic = [&]() {
+    float kk = 0.f;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) kk += v0[j] * v0[j] + v1[j] * v1[j];
+    return kk;
+  };
+
+  // ---- the trajectory ----
+  publish_x();
+  float act0 = sin_pass(), kin0 = kinetic();
+  const bool want_p = w.stepm || p.p_accept != nullptr;
+  if (want_p) hmc_row_sum2(act0, kin0, tsh, r, fl, red);
+  float act1 = act0;
+  const int N = p.num_steps;
+  for (int step = p.step_begin; step < p.step_end; ++step) {
+    const float* m = p.masks + (size_t)(d ? N - 1 - step : step) * D;     // gauge_dynamics.py:453-457
+    float m0[SPT], m1[SPT];
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      const int s = ok[j] ? fl + j * tpc : 0;
+      m0[j] = m[2 * s];
+      m1[j] = m[2 * s + 1];
+    }
+    kick();
+    // two masked position sub-updates (lf_update_x_kernel with S = T = Q = 0): forward keeps m, then 1 - m;
+    // backward 1 - m, then m
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+      const bool inv = (sub == 1) != (d != 0);
+#pragma unroll
+      for (int j = 0; j < SPT; ++j) {
+        const float ka = inv ? 1.f - m0[j] : m0[j], kb = inv ? 1.f - m1[j] : m1[j];
+        const float da = eps * v0[j], db = eps * v1[j];
+        const float ua = d ? x0[j] - da : x0[j] + da, ub = d ? x1[j] - db : x1[j] + db;
+        x0[j] = ka * x0[j] + (1.f - ka) * ua;
+        x1[j] = kb * x1[j] + (1.f - kb) * ub;
+      }
+    }
+    publish_x();
+    act1 = sin_pass();
+    kick();
+  }
+  float pr = 0.f;
+  if (want_p) {
+    float kin1 = kinetic();
+    hmc_row_sum2(act1, kin1, tsh, r, fl, red);
+    pr = accept_prob(beta, act0, act1, 0.5f * kin0, 0.5f * kin1, 0.f);
+  }
+
+  if (!w.stepm) {
+    // ---- trajectory mode: x, v, sumlogdet (exactly 0), p of the live rows ----
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < SPT; ++j) {
+        if (ok[j]) {
+          float* xo = p.x_out + grow * D + 2 * (fl + j * tpc);
+          float* vo = p.v_out + grow * D + 2 * (fl + j * tpc);
+          xo[0] = x0[j];
+          xo[1] = x1[j];
+          vo[0] = v0[j];
+          vo[1] = v1[j];
+        }
+      }
+      if (fl == 0) {
+        if (p.logdet && !p.logdet_accumulate) p.logdet[grow] = 0.f;
+        if (p.p_accept) p.p_accept[grow] = pr;
+      }
+    }
+    return;
+  }
+
+  // ---- step mode: mix the directions, Metropolis-Hastings (gauge_dynamics.py:221-257, mask * a + (1 - mask) * b) ----
+  // xs rows hold the final x already (published ahead of the last sin P pass); v rows and p join them
+  float* vrow = vs + r * D;
+#pragma unroll
+  for (int j = 0; j < SPT; ++j)
+    if (ok[j]) {
+      vrow[fl + j * tpc] = v0[j];
+      vrow[sites + fl + j * tpc] = v1[j];
+    }
+  if (fl == 0) w.spx[r] = pr;
+  __syncthreads();
+  const bool primary = r < w.cpw;            // the thread that finishes its links of chain k
+  float xo0[SPT], xo1[SPT];
+  if (primary) {
+    const float fm = w.scoin[k] > 0.5f ? 1.f : 0.f, bm = 1.f - fm;
+    const float pk = w.paired ? fm * w.spx[k] + bm * w.spx[k + w.cpw] : w.spx[k];
+    const float am = pk > w.su[k] ? 1.f : 0.f;                       // strict >, quirk Q5
+    if (fl == 0) w.sobs[k * 4 + 3] = pk;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      xo0[j] = xo1[j] = 0.f;
+      if (ok[j]) {
+        const int s = fl + j * tpc, c = 2 * s;
+        float xp0 = x0[j], xp1 = x1[j], vp0 = v0[j], vp1 = v1[j];
+        if (w.paired) {
+          const float* xb = xs + (k + w.cpw) * D;
+          const float* vb = vs + (k + w.cpw) * D;
+          xp0 = fm * xp0 + bm * xb[s];
+          xp1 = fm * xp1 + bm * xb[sites + s];
+          vp0 = fm * vp0 + bm * vb[s];
+          vp1 = fm * vp1 + bm * vb[sites + s];
+        }
+        xo0[j] = am * xp0 + (1.f - am) * xi0[j];
+        xo1[j] = am * xp1 + (1.f - am) * xi1[j];
+        if (live) {                                                  // apply_transition's own outputs (:259)
+          const int64_t o = grow * D + c;
+          if (p.step_xprop) { p.step_xprop[o] = xp0; p.step_xprop[o + 1] = xp1; }
+          if (p.step_vprop) { p.step_vprop[o] = vp0; p.step_vprop[o + 1] = vp1; }
+          if (p.step_xout) { p.step_xout[o] = xo0[j]; p.step_xout[o + 1] = xo1[j]; }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // ---- observables of the step's INPUT samples (gauge_model.py:256-266) and the charge of its output (:718-725):
+  //      x_in -> the chain's (forward) x row, x_out -> its backward x row, or its v row without one
+  float* gin = xs + k * D;
+  float* gout = w.paired ? xs + (k + w.cpw) * D : vs + k * D;
+  if (primary) {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      if (ok[j]) {
+        const int s = fl + j * tpc;
+        gin[s] = xi0[j];
+        gin[sites + s] = xi1[j];
+        gout[s] = xo0[j];
+        gout[sites + s] = xo1[j];
+      }
+    }
+  }
+  __syncthreads();
+  auto plaq = [&](const float* xc, float& scos, float& sproj) {
+    const float inv2pi = 0.15915494309189533577f;
+    float a = 0.f, b = 0.f;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      if (ok[j]) {
+        const int s = fl + j * tpc;
+        const float P = xc[s] - xc[sites + s] - xc[nr[j]] + xc[sites + nu[j]];
+        float sn, cs;
+        fast_sincos(P, &sn, &cs);
+        a += cs;
+        b += P - 6.28318530717958647692f * floorf((P + 3.14159265358979323846f) * inv2pi);   // project_angle
+      }
+    }
+    scos = a;
+    sproj = b;
+  };
+  if (w.paired) {
+    float a, b;
+    plaq(primary ? gin : gout, a, b);
+    hmc_row_sum2(a, b, tsh, r, fl, red);
+    if (fl == 0) {
+      if (primary) { w.sobs[k * 4 + 0] = a; w.sobs[k * 4 + 1] = b; }
+      else w.sobs[k * 4 + 2] = b;
+    }
+  } else {
+    float a, b, c_, d_;
+    plaq(gin, a, b);
+    plaq(gout, c_, d_);
+    hmc_row_sum2(a, b, tsh, r, fl, red);
+    hmc_row_sum2(c_, d_, tsh, r, fl, red);
+    if (fl == 0) { w.sobs[k * 4 + 0] = a; w.sobs[k * 4 + 1] = b; w.sobs[k * 4 + 2] = d_; }
+  }
+  __syncthreads();
+  if (tid < w.cpw) {
+    const float inv2pi = 0.15915494309189533577f;
+    const int64_t chain = w.cbase + tid;
+    if (chain < p.step_Bl) {
+      const float q_in = w.sobs[tid * 4 + 1] * inv2pi, q_out = w.sobs[tid * 4 + 2] * inv2pi;
+      if (p.step_px) p.step_px[chain] = w.sobs[tid * 4 + 3];
+      if (p.step_act) p.step_act[chain] = (float)sites - w.sobs[tid * 4 + 0];      // sum (1 - cos P)
+      if (p.step_plq) p.step_plq[chain] = w.sobs[tid * 4 + 0] / (float)sites;
+      if (p.step_chg) p.step_chg[chain] = q_in;
+      if (p.step_dq) p.step_dq[chain] = fabsf(q_in - q_out);
+    }
+  }
+  // ---- np.mod(x_out, 2 pi) (gauge_model.py:1388) and the chains' new state, then the step's sums ----
+  if (primary && live && p.step_x_next) {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      if (ok[j]) {
+        float wv[2] = {xo0[j], xo1[j]};
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const float tp = 6.28318530717958647692f;
+          float m_ = fmaf(-tp, floorf(wv[e] * 0.15915494309189533577f), wv[e]);       // w - 2 pi floor(w / 2 pi)
+          if (m_ < 0.f) m_ += tp;
+          if (m_ >= tp) m_ -= tp;
+          wv[e] = m_;
+        }
+        float* xn = p.step_x_next + grow * D + 2 * (fl + j * tpc);
+        xn[0] = wv[0];
+        xn[1] = wv[1];
+      }
+    }
+  }
+  step_sums<kHmcMaxThreads, 256>(p, w, 1, (int64_t)blockIdx.x, (int)gridDim.x, (int)gridDim.x, fin);
+}
+
+static int launch_hmc(const FusedArgs& a, const HmcGeom& g, int64_t nwg, hipStream_t stream) {
+  L2HMC_REQUIRE(nwg > 0 && nwg < (1ll << 31), "hmc step: too many rows");
+  prof_before(kProfFused, stream);
+  const dim3 grid((unsigned)nwg), block((unsigned)g.threads);
+  if (g.spt == 1)
+    hipLaunchKernelGGL((hmc_step_kernel<1>), grid, block, g.lds, stream, a, g.tsh);
+  else if (g.spt == 2)
+    hipLaunchKernelGGL((hmc_step_kernel<2>), grid, block, g.lds, stream, a, g.tsh);
+  else
+    hipLaunchKernelGGL((hmc_step_kernel<4>), grid, block, g.lds, stream, a, g.tsh);
+  prof_after(kProfFused, stream);
+  L2HMC_CHECK_LAUNCH("hmc_step");
+  return L2HMC_OK;
+}
+
+int launch_hmc_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begin, int step_end, const float* x0,
+                          const float* v0, const int* dir, int64_t rows, float* x_out, float* v_out, float* logdet,
+                          int logdet_accumulate, float* p_accept, hipStream_t stream) {
+  HmcGeom g;
+  L2HMC_REQUIRE(hmc_plan_supported(p) && hmc_geom(p->T, p->X, &g), "hmc trajectory: plan has no one-launch kernel");
+  L2HMC_REQUIRE(x0 && v0 && x_out && v_out && rows > 0, "hmc trajectory: bad arguments");
+  FusedArgs a{};
+  a.T = p->T; a.X = p->X; a.num_steps = p->num_steps; a.step_begin = step_begin; a.step_end = step_end;
+  a.eps = p->eps; a.beta = beta; a.masks = p->masks;
+  a.x0 = x0; a.v0 = v0; a.dir = dir; a.rows = rows; a.x_out = x_out; a.v_out = v_out;
+  a.logdet = logdet; a.logdet_accumulate = logdet_accumulate; a.p_accept = p_accept;
+  return launch_hmc(a, g, ceil_div(rows, g.rows_wg), stream);
+}
+
+int launch_hmc_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                    uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges, float* dq,
+                    float* step_sums, float* part, hipStream_t stream, float* x_prop, float* v_prop, float* x_out) {
+  HmcGeom g;
+  L2HMC_REQUIRE(hmc_plan_supported(p) && hmc_geom(p->T, p->X, &g), "hmc step: plan has no one-launch kernel");
+  L2HMC_REQUIRE(x_in && (x_next || x_out) && B > 0 && (!step_sums || part), "hmc step: bad arguments");
+  const int cpw = both ? g.rows_wg / 2 : g.rows_wg;
+  const int64_t nwg = ceil_div(B, cpw);
+  FusedArgs a{};
+  a.T = p->T; a.X = p->X; a.num_steps = p->num_steps; a.step_begin = 0; a.step_end = p->num_steps;
+  a.eps = p->eps; a.beta = beta; a.masks = p->masks;
+  a.x0 = x_in; a.rows = nwg * g.rows_wg;
+  a.step_x_next = x_next; a.step_xprop = x_prop; a.step_vprop = v_prop; a.step_xout = x_out;
+  a.step_B = B; a.step_Bl = B; a.step_chain0 = 0;
+  a.step_seed = seed; a.step_draw = draw; a.step_both = both;
+  a.step_px = px; a.step_act = actions; a.step_plq = plaqs; a.step_chg = charges; a.step_dq = dq;
+  a.step_sums = step_sums; a.step_part = part;       // part: 2 floats per workgroup
+  return launch_hmc(a, g, nwg, stream);
+}
+
+}  // namespace l2hmc

@@ -202,6 +202,10 @@ enum NetCarry { kCarryNone = 0, kCarryVSave, kCarryVUse, kCarryXFirst, kCarrySec
 static bool use_fused(const l2hmc_gauge_plan* p) {
   return !(p->flags & L2HMC_PLAN_LAYERED) && fused_plan_supported(p);
 }
+// plain HMC: the one-launch kernel of hmc_step.hip
+static bool use_hmc_kernel(const l2hmc_gauge_plan* p) {
+  return !(p->flags & L2HMC_PLAN_LAYERED) && hmc_plan_supported(p);
+}
 static int gauge_hmax(const l2hmc_gauge_plan* p) { return p->hmc ? 0 : hmax(p->xnet.H, p->vnet.H); }
 static int gauge_ncb(const l2hmc_gauge_plan* p) { return (int)ceil_div(2 * p->T * p->X, 32); }
 
@@ -429,6 +433,8 @@ static int trajectory_inplace(const l2hmc_gauge_plan* p, float beta, float* x, f
                               int64_t rows, float* sumlogdet, float* p_accept, const GaugeWs& w,
                               hipStream_t stream, int64_t dir_split = -1) {
   const int D = 2 * p->T * p->X;
+  if (use_hmc_kernel(p))
+    return launch_hmc_trajectory(p, beta, 0, p->num_steps, x, v, dir, rows, x, v, sumlogdet, 0, p_accept, stream);
   if (use_fused(p))
     return launch_fused_trajectory(p, beta, 0, p->num_steps, x, v, dir, rows, x, v, sumlogdet, 0, p_accept,
                                    stream);
@@ -616,7 +622,7 @@ extern "C" size_t l2hmc_gauge_ws_bytes(const l2hmc_gauge_plan* plan, int64_t row
 
 extern "C" int l2hmc_gauge_plan_fused(const l2hmc_gauge_plan* plan) {
   if (int e = check_plan(plan)) return -e;
-  return use_fused(plan) ? 1 : 0;
+  return use_fused(plan) || use_hmc_kernel(plan) ? 1 : 0;
 }
 
 extern "C" int l2hmc_gauge_leapfrog(const l2hmc_gauge_plan* plan, float beta, int32_t step, float* x, float* v,
@@ -632,6 +638,8 @@ extern "C" int l2hmc_gauge_leapfrog(const l2hmc_gauge_plan* plan, float beta, in
     return L2HMC_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
+  if (use_hmc_kernel(plan))
+    return launch_hmc_trajectory(plan, beta, step, step + 1, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
   if (use_fused(plan))
     return launch_fused_trajectory(plan, beta, step, step + 1, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
   if (int e = prepare_ws(plan, rows, w, s)) return e;

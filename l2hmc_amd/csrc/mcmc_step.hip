@@ -3,7 +3,7 @@
 //   draw momenta / direction coin / MH uniform  ->  both trajectories  ->  mix, accept/reject,
 //   per-step observables, wrap to [0, 2 pi).  Plans with a whole-trajectory kernel run the step in ONE launch
 //   (launch_fused_step, fused_traj.hip: the kernel draws its own Philox streams and finishes the step in its
-//   epilogue); other plans go through the public ops below with the draws of step_draws_kernel.
+//   epilogue; launch_hmc_step, hmc_step.hip: the same for plain HMC at any lattice shape); other plans go through the public ops below with the draws of step_draws_kernel.
 // The reference pays one session run with a host round trip of the whole batch per step.
 #include "stq_dense.h"
 
@@ -117,6 +117,10 @@ extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta
 
   const bool fused = !(plan->flags & L2HMC_PLAN_LAYERED) && fused_plan_supported(plan);
   const bool selected = (plan->flags & L2HMC_PLAN_SELECTED_ONLY) != 0;
+  if (!(plan->flags & L2HMC_PLAN_LAYERED) && hmc_plan_supported(plan))
+    // plain HMC: ONE launch as well (hmc_step.hip), at any lattice of up to 1024 sites
+    return launch_hmc_step(plan, beta, x, x_next, B, seed, draw, selected ? 0 : 1, px, actions, plaqs, charges,
+                           charge_diff, step_sums, Xw /* 2 floats per workgroup of scratch */, s);
   if (fused) {
     // ONE launch: the whole-trajectory kernel draws, integrates, mixes, accepts, measures and wraps (fused_traj.hip)
     return launch_fused_step(plan, beta, x, x_next, B, seed, draw, selected ? 0 : 1, px, actions, plaqs, charges,
@@ -170,6 +174,9 @@ extern "C" int l2hmc_gauge_transition_draw(const l2hmc_gauge_plan* plan, float b
   hipStream_t s = (hipStream_t)stream;
   const int D = 2 * plan->T * plan->X;
   const bool selected = (plan->flags & L2HMC_PLAN_SELECTED_ONLY) != 0;
+  if (!(plan->flags & L2HMC_PLAN_LAYERED) && hmc_plan_supported(plan))
+    return launch_hmc_step(plan, beta, x, nullptr, B, seed, draw, selected ? 0 : 1, p_accept, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, s, x_prop, v_prop, x_out);
   if (!(plan->flags & L2HMC_PLAN_LAYERED) && fused_plan_supported(plan))
     return launch_fused_step(plan, beta, x, nullptr, B, seed, draw, selected ? 0 : 1, p_accept, nullptr, nullptr,
                              nullptr, nullptr, nullptr, nullptr, static_cast<char*>(ws) + step_head_bytes(B, D), s,

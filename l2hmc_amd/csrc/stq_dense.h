@@ -155,6 +155,16 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
                       uint64_t seed, uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges,
                       float* dq, float* step_sums, float* part, void* hand, hipStream_t stream,
                       float* x_prop = nullptr, float* v_prop = nullptr, float* x_out = nullptr);
+// plain HMC (plan->hmc) in one launch at any lattice of up to 1024 sites (hmc_step.hip): the counterparts of
+// fused_plan_supported, launch_fused_trajectory and launch_fused_step (part: 2 floats per chain of scratch)
+int hmc_plan_supported(const l2hmc_gauge_plan* p);
+int launch_hmc_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begin, int step_end, const float* x0,
+                          const float* v0, const int* dir, int64_t rows, float* x_out, float* v_out, float* logdet,
+                          int logdet_accumulate, float* p_accept, hipStream_t stream);
+int launch_hmc_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                    uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges, float* dq,
+                    float* step_sums, float* part, hipStream_t stream, float* x_prop = nullptr,
+                    float* v_prop = nullptr, float* x_out = nullptr);
 // bytes of launch_fused_step's `hand` workspace for B chains (the hand-off of the split 16-row form)
 size_t fused_step_hand_bytes(int64_t B, int D);
 // whole-trajectory reverse pass (fused_train.hip); deltas_*: {dout, d2, d1} tapes, coef_parts: {dcs_x, dcq_x, dcs_v, dcq_v}

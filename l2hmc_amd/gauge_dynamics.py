@@ -33,7 +33,7 @@ class GaugeDynamics:
         self.hmc, self.network_arch, self.num_steps = False, 'generic', 5
         self.eps_trainable, self.data_format = True, 'channels_last'
         self.both_directions = True      # integrate fwd AND bwd like :211-218; False = selected only
-        self.fused = True                # whole-trajectory kernel where the shape has one
+        self.fused = True                # whole-trajectory kernel where the plan has one (hmc=True: up to 1024 sites)
         self.check_numerics = False      # True: raise on a non-finite trajectory like tf.check_numerics (:26-28)
         self.recompute = False           # True: layer-by-layer path forms every first-layer product anew (diagnostic)
         self.tiles16_only = False        # True: whole-step kernel on its 16-row form for every batch (A/B, bit-identity test)
@@ -205,6 +205,7 @@ class GaugeDynamics:
         if momentum_f is None and momentum_b is None and coin is None and u is None:
             # no draw injected: the library draws for itself (one stream pair from this object's counter, the
             # layout of the native MCMC step) -- one kernel launch where the plan has a whole-trajectory kernel
+            # (GenericNet / ConvNet3D on 8x8-site lattices; hmc=True on any lattice of up to 1024 sites)
             x_prop, v_prop, x_out = (torch.empty_like(x) for _ in range(3))
             p = torch.empty(B, dtype=torch.float32, device=x.device)
             plan, L = self._plan(), _lib.lib()

@@ -16,21 +16,25 @@ direction's outputs by exactly 0, so it contributes exactly 0 to every gradient.
 
 The tiled training entries (l2hmc_gauge_train_*) need every network width to be a multiple of 32; GenericNet
 networks of other widths (lattices whose T * X is not a multiple of 16: 6x6, 3x5, 4x6, ...) are trained through the
-layered-training entries instead (taped forward, reverse walk of l2hmc_amd/layered_train.py), into the same flat
-buffer, with the same draws, optimiser and data-parallel exchange."""
+layered-training entries instead (the forward and backward stages of l2hmc_amd/layered_train.py).  Both are the
+forward and the reverse of ONE step body (`calc_loss_and_grads`: stack, forward, loss reverse, reverse, exchange), so
+they share the draws, the flat buffer, the data-parallel exchange and the optimiser (l2hmc_amd/_flat_trainer.py)."""
 import ctypes as C
 
 import torch
 
 from . import _lib
 from . import layered_train as _layered_train
+from ._flat_trainer import FlatTrainer, stack_chains
 from .dist import active as _active_dist
 from .lattice import u1_observables
 
 METRICS = {'l1': 0, 'l2': 1, 'cos': 2, 'cos2': 3, 'cos_diff': 4}
 
 
-class GaugeTrainer:
+class GaugeTrainer(FlatTrainer):
+    STEP_NAME = 'eps'
+
     def __init__(self, dynamics, lr_init=1e-3, lr_decay_steps=1000, lr_decay_rate=0.96, clip_value=None,
                  metric='cos_diff', loss_scale=1., aux_weight=1., std_weight=1., charge_weight=1., dist=None,
                  allreduce_grads=True, beta1=0.9, beta2=0.999, epsilon=1e-8, eager_variables=False,
@@ -42,7 +46,7 @@ class GaugeTrainer:
                              "sampler only)")
         if dynamics.network_arch not in ('generic', 'conv3D'):
             raise NotImplementedError("training is implemented for network_arch 'generic' and 'conv3D'")
-        self.dynamics = dyn = dynamics
+        dyn = dynamics
         self.metric, self.loss_scale = metric, float(loss_scale)
         self.weights = dict(aux_weight=float(aux_weight), std_weight=float(std_weight),
                             charge_weight=float(charge_weight))
@@ -62,29 +66,12 @@ class GaugeTrainer:
         # REGARDLESS of `eps_trainable`.  Eager mode uses `trainable_variables` (:820) and respects the flag.
         # Default = graph mode, as the reference's sessions run; eager_variables=True = the eager branch.
         self.eager_variables = bool(eager_variables)
-        self.global_step = 0
         self.last_bucket_count = 0       # gradient groups the last step put on the wire (0: nothing to exchange)
         dev = dyn._device
-        self._nets = (dyn.position_fn, dyn.momentum_fn)
-        flats = [n.flat_params() for n in self._nets]
-        self._sizes = [f[0].numel() for f in flats]
-        n_all = sum(self._sizes) + 1
         # one bucket: [xnet | vnet | eps]
-        self.grads = torch.zeros(n_all, dtype=torch.float32, device=dev)
-        self._m = torch.zeros_like(self.grads)
-        self._v = torch.zeros_like(self.grads)
-        self._eps_dev = torch.tensor([float(dyn.eps)], dtype=torch.float32, device=dev)
-        self._gnorm = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._ws = _lib.Workspace()
+        super().__init__(dyn, (dyn.position_fn, dyn.momentum_fn),
+                         torch.tensor([float(dyn.eps)], dtype=torch.float32, device=dev))
         self.broadcast_weights()
-        self._grad_structs, self._conv_grad_structs = [], []
-        off = 0
-        for net, (flat, views, offsets) in zip(self._nets, flats):
-            at = lambda k: self.grads.data_ptr() + 4 * (off + offsets[k][0])     # noqa: E731
-            self._grad_structs.append(_lib.DenseGrads(**{k: at(k) for k in net.SEGMENTS}))
-            conv = [k for k in offsets if k not in net.SEGMENTS]
-            self._conv_grad_structs.append(_lib.Conv3DGrads(**{k: at(k) for k in conv}) if conv else None)
-            off += flat.numel()
         self._buckets = self._bucket_ranges()
         self._side = torch.cuda.Stream(device=dev) if (self.dist is not None and dev.type == "cuda") else None
         # Which kernels a step runs through, decided per call: None = by shape (the tiled training entries where every
@@ -120,21 +107,17 @@ class GaugeTrainer:
         for net in self._nets:
             self.dist.broadcast(net.flat_params()[0], src=src)
             net.refresh_packed()
-        self.dist.broadcast(self._eps_dev, src=src)
-        dyn.eps = self._eps_dev.detach().cpu().reshape(())
+        self.dist.broadcast(self._step_dev, src=src)
+        self._write_step()
         self.dist.broadcast(dyn.mask, src=src)
         dyn._heads = None                 # the masks changed in place: the active-column heads are packed again
 
-    # ---- views ----------------------------------------------------------------
-    def grad_views(self):
-        """{'xnet': {segment: tensor}, 'vnet': {...}, 'eps': tensor} over the flat gradient bucket."""
-        out, off = {}, 0
-        for name, net in zip(("xnet", "vnet"), self._nets):
-            flat, views, offsets = net.flat_params()
-            out[name] = {k: self.grads[off + a:off + b].view(views[k].shape) for k, (a, b) in offsets.items()}
-            off += flat.numel()
-        out["eps"] = self.grads[off:off + 1]
-        return out
+    # ---- what the shared optimiser step asks of a trainer ---------------------------------------------------
+    def _write_step(self):
+        self.dynamics.eps = self._step_dev.detach().cpu().reshape(())      # the plan carries eps by value
+
+    def _step_trainable(self):
+        return bool(self.dynamics.eps_trainable) or not self.eager_variables
 
     def learning_rate(self):
         """tf.train.exponential_decay(staircase=True) times the rank count (gauge_model.py:934-942)."""
@@ -155,25 +138,23 @@ class GaugeTrainer:
             if d is None:
                 return dyn._normal((B, D)), dyn._normal((B, D)), dyn._uniform((B,)), dyn._uniform((B,))
             return tuple(_lib.as_dev(a, dev) for a in d)
-        vf_x, vb_x, coin_x, u_x = draw(draws_x)
-        vf_z, vb_z, coin_z, _ = draw(draws_z)
-        coin = torch.cat([coin_x, coin_z])
-        fwd = coin > 0.5
-        x0 = torch.cat([x, z]).contiguous()
-        v0 = torch.where(fwd[:, None], torch.cat([vf_x, vf_z]), torch.cat([vb_x, vb_z])).contiguous()
-        dirs = (~fwd).to(torch.int32).contiguous()
-        if self._use_layered():
-            xN, p, terms, buf = self._layered_loss_and_grads(x0, v0, fwd, float(beta), B)
-            return self._step_outputs(x, u_x, xN, p, terms, buf)
+        x0, v0, fwd, dirs, u_x = stack_chains(x, z, draw(draws_x), draw(draws_z))
         R = 2 * B
-        xN, vN = torch.empty_like(x0), torch.empty_like(x0)
-        sld, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
-        plan, L = dyn._plan(), _lib.lib()
-        ws, nb = self._ws.get(L.l2hmc_gauge_train_ws_bytes(C.byref(plan), R), dev)
-        s = _lib.stream_ptr(self.dynamics._device)
-        _lib.check(L.l2hmc_gauge_train_forward(C.byref(plan), float(beta), x0.data_ptr(), v0.data_ptr(),
-                                               dirs.data_ptr(), R, xN.data_ptr(), vN.data_ptr(), sld.data_ptr(),
-                                               p.data_ptr(), ws, nb, s))
+        L, s, layered = _lib.lib(), _lib.stream_ptr(dev), self._use_layered()
+        if layered:          # one taped layered trajectory per direction, on the rows that run it
+            if self._walk is None:
+                self._walk = _layered_train.LayeredWalk(dev)
+            fw = self._walk.forward(self._lattice_walk(float(beta)), x0, v0, fwd,
+                                    lambda *a: dyn._compute_accept_prob(*a, float(beta)))
+            xN, vN, p = fw.xN, fw.vN, fw.p
+        else:
+            xN, vN = torch.empty_like(x0), torch.empty_like(x0)
+            sld, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
+            plan = dyn._plan()
+            ws, nb = self._ws.get(L.l2hmc_gauge_train_ws_bytes(C.byref(plan), R), dev)
+            _lib.check(L.l2hmc_gauge_train_forward(C.byref(plan), float(beta), x0.data_ptr(), v0.data_ptr(),
+                                                   dirs.data_ptr(), R, xN.data_ptr(), vN.data_ptr(), sld.data_ptr(),
+                                                   p.data_ptr(), ws, nb, s))
         terms = torch.empty(B, dtype=torch.float32, device=dev)
         dxN, dvN = torch.empty_like(x0), torch.empty_like(x0)
         dld = torch.empty(R, dtype=torch.float32, device=dev)
@@ -183,38 +164,52 @@ class GaugeTrainer:
                                                w['aux_weight'], w['std_weight'], w['charge_weight'],
                                                1.0 / (B * self.world), terms.data_ptr(), dxN.data_ptr(),
                                                dvN.data_ptr(), dld.data_ptr(), s))
-        n0, n1 = self._sizes
-        bargs = (C.byref(plan), float(beta), dirs.data_ptr(), R, dxN.data_ptr(), dvN.data_ptr(), dld.data_ptr(),
-                 C.byref(self._grad_structs[0]), C.byref(self._grad_structs[1]),
-                 *(C.byref(g) if g is not None else None for g in self._conv_grad_structs),
-                 self.grads.data_ptr() + 4 * (n0 + n1), ws, nb, s)
         buf = torch.stack([terms.sum(dtype=torch.float32),
                            torch.full((), float(B), dtype=torch.float32, device=dev)])
-        if self.dist is not None and self.allreduce_grads and self.bucketed:
-            works, errors = [], []
-            cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+        # Bucketed exchange: `send(ranges)` puts ranges of the flat buffer on the wire as soon as the reverse has
+        # enqueued their producers -- each network's range right after its products, the eps slot last.
+        n0, n1 = self._sizes
+        bucketed = self.dist is not None and self.allreduce_grads and self.bucketed
+        works = []
+        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+        send = (lambda ranges: self._all_reduce_ranges(ranges, works, cur)) if bucketed else None
+        if layered:
+            lo = (0, n0)
+            self.grads[n0 + n1] = self._walk.backward(
+                fw, dxN, dvN, dld, *self._grad_structs,
+                (lambda k: send([(lo[k], lo[k] + self._sizes[k])])) if bucketed else None)
+            if bucketed:
+                send([(n0 + n1, n0 + n1 + 1)])
+        else:
+            bargs = (C.byref(plan), float(beta), dirs.data_ptr(), R, dxN.data_ptr(), dvN.data_ptr(), dld.data_ptr(),
+                     C.byref(self._grad_structs[0]), C.byref(self._grad_structs[1]),
+                     *(C.byref(g) if g is not None else None for g in self._conv_grad_structs),
+                     self.grads.data_ptr() + 4 * (n0 + n1), ws, nb, s)
+            if bucketed:
+                errors = []
 
-            def on_bucket(_user, b):           # host thread, right after bucket b's producers were enqueued
-                try:
-                    self._all_reduce_ranges(self._buckets[int(b)], works, cur)
-                except Exception as e:          # noqa: BLE001 -- a ctypes callback cannot raise: re-raised below
-                    errors.append(e)
-            cb = _lib.BUCKET_FN(on_bucket)
-            _lib.check(L.l2hmc_gauge_train_backward_buckets(*bargs, cb, None))
-            if errors:
-                raise errors[0]
+                def on_bucket(_user, b):           # host thread, right after bucket b's producers were enqueued
+                    try:
+                        send(self._buckets[int(b)])
+                    except Exception as e:          # noqa: BLE001 -- a ctypes callback cannot raise: re-raised below
+                        errors.append(e)
+                cb = _lib.BUCKET_FN(on_bucket)
+                _lib.check(L.l2hmc_gauge_train_backward_buckets(*bargs, cb, None))
+                if errors:
+                    raise errors[0]
+            else:
+                _lib.check(L.l2hmc_gauge_train_backward(*bargs))
+        if bucketed:
             self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
             for wk in works:
                 wk.wait()
             if self._side is not None:
                 cur.wait_stream(self._side)
             self.last_bucket_count = len(works)
-        else:
-            _lib.check(L.l2hmc_gauge_train_backward(*bargs))
-            if self.dist is not None:
-                self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
-                if self.allreduce_grads:
-                    self.dist.all_reduce(self.grads, op=self.dist.ReduceOp.SUM)
+        elif self.dist is not None:
+            self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
+            if self.allreduce_grads:
+                self.dist.all_reduce(self.grads, op=self.dist.ReduceOp.SUM)
         return self._step_outputs(x, u_x, xN, p, terms, buf)
 
     def _step_outputs(self, x, u_x, xN, p, terms, buf):
@@ -254,18 +249,12 @@ class GaugeTrainer:
             for lo, hi in ranges:
                 works.append(self.dist.all_reduce(self.grads[lo:hi], op=self.dist.ReduceOp.SUM, async_op=True))
 
-    def _layered_loss_and_grads(self, x0, v0, fwd, beta, B):
-        """The training step through the layered-training entries (any lattice shape, GenericNet): one taped layered
-        trajectory per direction on the rows that run it, the loss reverse of l2hmc_gauge_loss_backward, the reverse
-        walk of l2hmc_amd/layered_train.py with beta * force and l2hmc_u1_force_hvp, and the weight gradients straight
-        into the flat buffer [xnet | vnet | eps].  -> (x_N, p, terms, [loss sum, chain count]) with the gradients
-        (and, data-parallel, the loss sums) combined across ranks."""
+    def _lattice_walk(self, beta):
+        """The lattice as l2hmc_amd/layered_train.py sees it: beta * force feeds the momentum update and VNet, with
+        l2hmc_u1_force_hvp as its Hessian-vector product."""
         dyn = self.dynamics
-        dev, L, s = dyn._device, _lib.lib(), _lib.stream_ptr(dyn._device)
+        L, s = _lib.lib(), _lib.stream_ptr(dyn._device)
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
-        R = x0.shape[0]
-        if self._walk is None:
-            self._walk = _layered_train.LayeredWalk(dev)
 
         def force(x):
             out = torch.empty_like(x)
@@ -277,103 +266,8 @@ class GaugeTrainer:
             out = torch.empty_like(x)
             _lib.check(L.l2hmc_u1_force_hvp(x.data_ptr(), u.data_ptr(), x.shape[0], T, X, beta, out.data_ptr(), s))
             return out
-
-        def time(step):
-            t = dyn._format_time(step)
-            return float(t[0, 0]), float(t[0, 1])
-        w = _layered_train.Walk(dyn.position_fn, dyn.momentum_fn, dyn.eps, dyn.num_steps, time, dyn._get_mask_while,
-                                force, hvp)
-        walk = self._walk
-        tx, tv = walk.tapes(w, R)
-        xN, vN = torch.empty_like(x0), torch.empty_like(x0)
-        sld, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
-        runs = []
-        for d, idx in ((0, torch.nonzero(fwd).reshape(-1)), (1, torch.nonzero(~fwd).reshape(-1))):
-            if idx.numel() == 0:
-                continue
-            xs, vs = x0[idx].contiguous(), v0[idx].contiguous()
-            xe, ve, lj, subs = walk.trajectory(w, xs, vs, d, tx, tv)
-            xN[idx], vN[idx], sld[idx] = xe, ve, lj
-            p[idx] = dyn._compute_accept_prob(xs, vs, xe, ve, lj, beta)
-            runs.append((d, idx, subs))
-        terms = torch.empty(B, dtype=torch.float32, device=dev)
-        dxN, dvN = torch.empty_like(x0), torch.empty_like(x0)
-        dld = torch.empty(R, dtype=torch.float32, device=dev)
-        wt = self.weights
-        _lib.check(L.l2hmc_gauge_loss_backward(T, X, beta, x0.data_ptr(), xN.data_ptr(), vN.data_ptr(), p.data_ptr(),
-                                               B, METRICS[self.metric], self.loss_scale, wt['aux_weight'],
-                                               wt['std_weight'], wt['charge_weight'], 1.0 / (B * self.world),
-                                               terms.data_ptr(), dxN.data_ptr(), dvN.data_ptr(), dld.data_ptr(), s))
-        parts = []
-        for d, idx, subs in runs:
-            parts += walk.reverse(w, subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(), dld[idx].contiguous(),
-                                  tx, tv)
-        buf = torch.stack([terms.sum(dtype=torch.float32), torch.full((), float(B), dtype=torch.float32, device=dev)])
-        n0, n1 = self._sizes
-        bucketed = self.dist is not None and self.allreduce_grads and self.bucketed
-        works = []
-        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        for k, (net, tape) in enumerate(((dyn.position_fn, tx), (dyn.momentum_fn, tv))):
-            walk.weight_grads(net, tape, self._grad_structs[k])
-            if bucketed:             # this network's range goes on the wire while the next one's products run
-                lo = 0 if k == 0 else n0
-                self._all_reduce_ranges([(lo, lo + self._sizes[k])], works, cur)
-        self.grads[n0 + n1] = torch.cat(parts).sum() if parts else 0.
-        if bucketed:
-            self._all_reduce_ranges([(n0 + n1, n0 + n1 + 1)], works, cur)
-            self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
-            for wk in works:
-                wk.wait()
-            if self._side is not None:
-                cur.wait_stream(self._side)
-            self.last_bucket_count = len(works)
-        elif self.dist is not None:
-            self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
-            if self.allreduce_grads:
-                self.dist.all_reduce(self.grads, op=self.dist.ReduceOp.SUM)
-        return xN, p, terms, buf
-
-    # ---- optimiser --------------------------------------------------------------
-    def apply_gradients(self):
-        """clip_by_global_norm (if clip_value) + Adam on [xnet | vnet | eps]; bumps global_step."""
-        dyn, L, s = self.dynamics, _lib.lib(), _lib.stream_ptr(self.dynamics._device)
-        lr = self.learning_rate()
-        self._adam_t = getattr(self, "_adam_t", 0) + 1
-        t = self._adam_t
-        lr_t = lr * (1. - self.beta2 ** t) ** 0.5 / (1. - self.beta1 ** t)
-        n0, n1 = self._sizes
-        gp, mp, vp = self.grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr()
-        segs = []
-        off = 0
-        for net in self._nets:
-            flat, _, offsets = net.flat_params()
-            segs.append((flat.data_ptr(), off, flat.numel(), offsets["b1"]))
-            off += flat.numel()
-        trainable_eps = bool(dyn.eps_trainable) or not self.eager_variables
-        gnorm = None
-        if self.clip_value is not None:
-            for i, (_, o, n, tri) in enumerate(segs):
-                _lib.check(L.l2hmc_grad_sumsq(gp + 4 * o, n, tri[0], tri[1], self._gnorm.data_ptr(), int(i > 0), s))
-            if trainable_eps:
-                _lib.check(L.l2hmc_grad_sumsq(gp + 4 * off, 1, 0, 0, self._gnorm.data_ptr(), 1, s))
-            gnorm = self._gnorm.data_ptr()
-        clip = self.clip_value if self.clip_value is not None else 0.
-        for (wp, o, n, tri) in segs:
-            _lib.check(L.l2hmc_adam_step(wp, gp + 4 * o, mp + 4 * o, vp + 4 * o, n, lr_t, self.beta1, self.beta2,
-                                         self.epsilon, gnorm, clip, tri[0], tri[1], s))
-        if trainable_eps:
-            _lib.check(L.l2hmc_adam_step(self._eps_dev.data_ptr(), gp + 4 * off, mp + 4 * off, vp + 4 * off, 1, lr_t,
-                                         self.beta1, self.beta2, self.epsilon, gnorm, clip, 0, 0, s))
-            dyn.eps = self._eps_dev.detach().cpu().reshape(())     # the plan carries eps by value
-        for net in self._nets:
-            net.refresh_packed()
-        self.global_step += 1
-
-    def train_step(self, x, beta, **kw):
-        """One evaluation of the reference's train_op: (loss, x_out, px, x_dq)."""
-        out = self.calc_loss_and_grads(x, beta, **kw)
-        self.apply_gradients()
-        return out
+        return _layered_train.Walk(dyn.position_fn, dyn.momentum_fn, dyn.eps, dyn.num_steps, dyn._format_time,
+                                   dyn._get_mask_while, force, hvp)
 
     def update_beta(self, step, beta_init=2., beta_final=4., train_steps=10000):
         """gauge_model.py:1039-1046: linear annealing of 1/beta."""
@@ -423,10 +317,10 @@ class GaugeTrainer:
         masks, and optionally the chain state and beta of `_current_state`."""
         import numpy as np
         d = {"xnet": self._nets[0].flat_params()[0], "vnet": self._nets[1].flat_params()[0], "adam_m": self._m,
-             "adam_v": self._v, "eps": self._eps_dev, "masks": self.dynamics.mask}
+             "adam_v": self._v, "eps": self._step_dev, "masks": self.dynamics.mask}
         out = {k: v.detach().cpu().numpy() for k, v in d.items()}
         out.update(global_step=np.int64(self.global_step), step=np.int64(self.global_step),
-                   adam_t=np.int64(getattr(self, "_adam_t", 0)),
+                   adam_t=np.int64(self._adam_t),
                    lr=np.float64(self.learning_rate()), draws=np.int64(self.dynamics._draws))
         if samples is not None:
             out["samples"] = samples.detach().cpu().numpy() if isinstance(samples, torch.Tensor) else np.asarray(samples)
@@ -448,8 +342,8 @@ class GaugeTrainer:
                 net.refresh_packed()
             self._m.copy_(torch.from_numpy(f["adam_m"]))
             self._v.copy_(torch.from_numpy(f["adam_v"]))
-            self._eps_dev.copy_(torch.from_numpy(f["eps"]))
-            dyn.eps = self._eps_dev.detach().cpu().reshape(())
+            self._step_dev.copy_(torch.from_numpy(f["eps"]))
+            self._write_step()
             dyn.set_masks(f["masks"])
             self.global_step, self._adam_t = int(f["global_step"]), int(f["adam_t"])
             dyn._draws = int(f["draws"])
@@ -474,8 +368,3 @@ class GaugeTrainer:
         keys = [(initial_step + i, float(b)) for i, b in enumerate(out['beta'])]
         return {name: {k: out[name][i] for i, k in enumerate(keys)}
                 for name in ('loss', 'actions', 'plaqs', 'charges', 'charge_diff', 'accept_prob')}
-
-    def sync_weights(self):
-        """Bring the reference-layout layer tensors (state_dict / save_weights) up to date."""
-        for net in self._nets:
-            net.sync_reference_layout()

@@ -20,10 +20,14 @@ Tape size per network: 2 N_LF calls x 2B rows x (Ka+Kb + 4H + 3D (S, T, Q) + 3D 
 networks about 4 N_LF 2B (2D + 2H + 3D) 4 bytes for the forward part, and as much again for the reverse-pass
 cotangents (at x_dim 50, H 100, N_LF 10, 2B = 8192: about 1.2 GB in all).
 
-The taped forward, the reverse walk and the weight gradients (LayeredWalk) depend on no loss and no trainer: a `Walk`
-gives them the networks, eps, the per-step masks and time input, and the energy gradient with its Hessian-vector
-product.  `GaugeTrainer` runs them on the lattice (beta * force, l2hmc_u1_force_hvp) where its tiled training entries
+The two stages (LayeredWalk.forward: split by direction, taped trajectories, scatter into the stacked row order;
+LayeredWalk.backward: reverse walk, weight gradients network by network, summed d/d eps) depend on no loss and no
+trainer: a `Walk` gives them the networks, eps, the per-step masks and time input, and the energy gradient with its
+Hessian-vector product; the caller gives the accept probability and, between the stages, the cotangents of
+(x_N, v_N, sumlogdet).  `LayeredStep` is the toy targets' caller (squared-jump loss); `GaugeTrainer` runs the same
+stages on the lattice (beta * force, l2hmc_u1_force_hvp, l2hmc_gauge_loss_backward) where its tiled training entries
 do not take the network widths."""
+import collections
 import ctypes as C
 
 import torch
@@ -79,20 +83,29 @@ def energy_hvp(dyn, x, u):
 
 class Walk:
     """What a taped layered trajectory and its reverse walk need of a target, and nothing of any loss or trainer:
-    the two networks, eps, the trajectory length, per step the time input `time(step) -> (t_cos, t_sin)` and the
-    masks `masks(step) -> (m, 1 - m)` ([D] device tensors), and the gradient that feeds the momentum update and
-    VNet's second input, `grad(x)`, with its Hessian-vector product `hvp(x, u)` (toy targets: grad E / temperature
-    and energy_hvp; the lattice: beta * force and l2hmc_u1_force_hvp)."""
+    the two networks, eps, the trajectory length, per step the time input `format_time(step) -> [[t_cos, t_sin]]`
+    (the dynamics' `_format_time`) and the masks `masks(step) -> (m, 1 - m)` ([D] device tensors), and the gradient
+    that feeds the momentum update and VNet's second input, `grad(x)`, with its Hessian-vector product `hvp(x, u)`
+    (toy targets: grad E / temperature and energy_hvp; the lattice: beta * force and l2hmc_u1_force_hvp)."""
 
-    def __init__(self, xnet, vnet, eps, num_steps, time, masks, grad, hvp):
+    def __init__(self, xnet, vnet, eps, num_steps, format_time, masks, grad, hvp):
         self.xnet, self.vnet, self.eps, self.num_steps = xnet, vnet, float(eps), int(num_steps)
-        self.time, self.masks, self.grad, self.hvp = time, masks, grad, hvp
+        self.format_time, self.masks, self.grad, self.hvp = format_time, masks, grad, hvp
+
+    def time(self, step):
+        t = self.format_time(step)
+        return float(t[0, 0]), float(t[0, 1])
+
+
+# What LayeredWalk.forward hands to LayeredWalk.backward: the Walk, both tapes, per direction run (d, row indices,
+# sub-updates), and x_N, v_N, sumlogdet, p in the stacked row order.
+Forward = collections.namedtuple("Forward", "w tx tv runs xN vN sld p")
 
 
 class LayeredWalk:
-    """The target-independent stages of a layered training step (holds their workspaces): the taped forward of one
-    direction, the reverse walk from given cotangents of (x_N, v_N, sumlogdet), and one network's weight gradients
-    into caller-given l2hmc_dense_grads."""
+    """The target-independent stages of a layered training step (holds their workspaces): `forward`, taped
+    trajectories of the stacked chains in the direction each runs, and `backward`, the reverse walk from given
+    cotangents of (x_N, v_N, sumlogdet) with the weight gradients into caller-given l2hmc_dense_grads."""
 
     def __init__(self, device):
         self.device = device
@@ -160,6 +173,25 @@ class LayeredWalk:
             v = self._sub_v(w, x, v, tc, ts, d, lj, tv, subs)
         return x, v, lj, subs
 
+    def forward(self, w, x0, v0, fwd, accept):
+        """The stacked chains x0, v0 [R][D], each in the direction fwd [R] (bool, True = forward) gives it: one taped
+        trajectory per direction over the rows that run it, scattered back into the stacked order, with
+        p = accept(x_start, v_start, x_end, v_end, sumlogdet) of those rows.  -> Forward."""
+        R = x0.shape[0]
+        tx, tv = self.tapes(w, R)
+        xN, vN = torch.empty_like(x0), torch.empty_like(x0)
+        sld, p = (torch.empty(R, dtype=torch.float32, device=self.device) for _ in range(2))
+        runs = []
+        for d, idx in ((0, torch.nonzero(fwd).reshape(-1)), (1, torch.nonzero(~fwd).reshape(-1))):
+            if idx.numel() == 0:
+                continue
+            xs, vs = x0[idx].contiguous(), v0[idx].contiguous()
+            xe, ve, lj, subs = self.trajectory(w, xs, vs, d, tx, tv)
+            xN[idx], vN[idx], sld[idx] = xe, ve, lj
+            p[idx] = accept(xs, vs, xe, ve, lj)
+            runs.append((d, idx, subs))
+        return Forward(w, tx, tv, runs, xN, vN, sld, p)
+
     # ---- reverse ---------------------------------------------------------------------------------------------
     def _backward_data(self, net, tape, sl, dS, dT, dQ):
         L, dev = _lib.lib(), self.device
@@ -218,47 +250,39 @@ class LayeredWalk:
             tape.dz2.data_ptr(), tape.dpre.data_ptr(), tape.dsq.data_ptr(), tape.tcs.data_ptr(), C.byref(g), ws, nb,
             _lib.stream_ptr(dev)))
 
-
-def dense_grads(views):
-    """l2hmc_dense_grads over a network's gradient views ({segment: tensor})."""
-    return _lib.DenseGrads(**{f[0]: views[f[0]].data_ptr() for f in _lib.DenseGrads._fields_})
+    def backward(self, fw, dxN, dvN, dld, gx, gv, after_net=None):
+        """From the cotangents of (x_N, v_N, sumlogdet) in the stacked row order: the reverse walk of every run of
+        `fw`, then the weight gradients of XNet into the l2hmc_dense_grads `gx` and of VNet into `gv`;
+        `after_net(k)` is called right after network k's products were enqueued.  -> d/d eps summed over all
+        sub-updates (a device scalar)."""
+        parts = []
+        for d, idx, subs in fw.runs:
+            parts += self.reverse(fw.w, subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(), dld[idx].contiguous(),
+                                  fw.tx, fw.tv)
+        for k, (net, tape, g) in enumerate(((fw.w.xnet, fw.tx, gx), (fw.w.vnet, fw.tv, gv))):
+            self.weight_grads(net, tape, g)
+            if after_net is not None:
+                after_net(k)
+        return torch.cat(parts).sum() if parts else torch.zeros((), dtype=torch.float32, device=self.device)
 
 
 class LayeredStep:
-    """One `DynamicsTrainer.calc_loss_and_grads` of a layered dynamics (held by the trainer for its workspaces)."""
+    """One `DynamicsTrainer.calc_loss_and_grads` of a layered dynamics (held by the trainer for its workspaces): the
+    `Walk` over the toy target and the squared-jump loss with its cotangents."""
 
     def __init__(self, trainer):
         self.tr = trainer
         self.walk = LayeredWalk(trainer.dynamics._device)
 
-    def _walk(self):
-        dyn = self.tr.dynamics
-
-        def time(step):
-            t = dyn._format_time(step)
-            return float(t[0, 0]), float(t[0, 1])
-        return Walk(dyn.XNet, dyn.VNet, dyn.eps, dyn.trajectory_length, time, dyn._get_mask, dyn.grad_energy,
-                    lambda x, u: energy_hvp(dyn, x, u))
-
     def __call__(self, x0, v0, fwd, inv_count):
         """x0, v0 [2B][D] stacked start states, fwd [2B] bool (True = forward).  Writes the trainer's gradient buffer
         ([xnet | vnet | d/d eps]) and returns (x_N, p, terms) in the stacked row order."""
         tr = self.tr
-        dyn, dev = tr.dynamics, tr.dynamics._device
-        R, D = x0.shape
-        w = self._walk()
-        groups = [(0, torch.nonzero(fwd).reshape(-1)), (1, torch.nonzero(~fwd).reshape(-1))]
-        tx, tv = self.walk.tapes(w, R)
-        xN, vN = torch.empty_like(x0), torch.empty_like(x0)
-        lj, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
-        runs = []
-        for d, idx in groups:
-            if idx.numel() == 0:
-                continue
-            xs, vs = x0[idx].contiguous(), v0[idx].contiguous()
-            X, V, J, subs = self.walk.trajectory(w, xs, vs, d, tx, tv)
-            xN[idx], vN[idx], lj[idx], p[idx] = X, V, J, dyn.p_accept(xs, vs, X, V, J)
-            runs.append((d, idx, subs))
+        dyn = tr.dynamics
+        w = Walk(dyn.XNet, dyn.VNet, dyn.eps, dyn.trajectory_length, dyn._format_time, dyn._get_mask, dyn.grad_energy,
+                 lambda x, u: energy_hvp(dyn, x, u))
+        fw = self.walk.forward(w, x0, v0, fwd, dyn.p_accept)
+        xN, vN, p = fw.xN, fw.vN, fw.p
         # loss (mog_model.py:336-355) and its cotangents at (x_N, v_N, sumlogdet)
         scale = tr.scale
         sq = ((x0 - xN) ** 2).sum(1)
@@ -275,13 +299,5 @@ class LayeredStep:
         dxN = torch.where(live, (dvv * p)[:, None] * 2.0 * (xN - x0) - dD[:, None] * gE, zero)
         dvN = torch.where(live, -dD[:, None] * vN, zero)
         dld = dD.contiguous()
-        parts = []
-        for d, idx, subs in runs:
-            parts += self.walk.reverse(w, subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(),
-                                       dld[idx].contiguous(), tx, tv)
-        gv = tr.grad_views()
-        self.walk.weight_grads(dyn.XNet, tx, dense_grads(gv["xnet"]))
-        self.walk.weight_grads(dyn.VNet, tv, dense_grads(gv["vnet"]))
-        deps = torch.cat(parts).sum() if parts else torch.zeros((), dtype=torch.float32, device=dev)
-        tr.grads[-1] = deps
+        tr.grads[-1] = self.walk.backward(fw, dxN, dvN, dld, *tr._grad_structs)
         return xN, p, terms

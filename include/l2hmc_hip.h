@@ -292,6 +292,30 @@ int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta, const flo
                              float* charge_diff, float* step_sums, void* ws, size_t ws_bytes,
                              l2hmc_stream_t stream);
 
+/* A RUN of n_steps consecutive MCMC steps of a plain-HMC plan (plan.hmc = 1; hmc = 0 is an error), with the results
+ * of n_steps calls of l2hmc_gauge_mcmc_step_ex, bit for bit.  Step s (0 <= s < n_steps) draws with index draw0 + s
+ * (Philox streams (seed, 2*(draw0 + s)) and (seed, 2*(draw0 + s) + 1), the element layout of the step), runs at
+ * betas[s] (a DEVICE array, so an annealed thermalisation is one call; constant beta = equal values) and starts from
+ * the wrapped output of step s - 1.  Histories (each may be NULL) are [n_steps][B]: row s is what the step writes.
+ * samples (or NULL) is [n_steps][B][D] and receives every step's wrapped output; the final state always goes to x_next,
+ * which may alias x_in.  step_sums (or NULL) is [n_steps][4], row s = that step's [sum p_accept, sum |dQ|, B, ticket]:
+ * ALL ticket words MUST BE 0 ON ENTRY and are left at 0; step_sums needs the workspace.
+ * Plans for which l2hmc_gauge_plan_fused() is 1 take ONE launch: a workgroup walks its own chains through the whole
+ * run with their state in registers, and every step has its own ticket and its own slice of the workspace for the
+ * sums, so workgroups never wait for each other.  Other hmc plans (more than 1024 sites, L2HMC_PLAN_LAYERED) run the
+ * same run as a host loop over the step; that loop reads betas back and so waits for the stream once.
+ * draw0 + n_steps must not exceed 2^63 (an error otherwise): the one-launch kernel relies on bit 63 of every draw
+ * index being 0.  Workspace: plans that take one launch need it only with step_sums; the host loop of the other plans
+ * ALWAYS needs ws of at least l2hmc_gauge_hmc_run_ws_bytes (L2HMC_ERR_WORKSPACE otherwise), and because it
+ * synchronises the stream to read betas it cannot be captured into a HIP graph (the one-launch form can).
+ * n_steps <= 0 and NULL betas / x_in / x_next are errors.  l2hmc_gauge_hmc_run_ws_bytes is 0 for bad arguments and for
+ * hmc = 0 (l2hmc_last_error then says so). */
+size_t l2hmc_gauge_hmc_run_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps);
+int l2hmc_gauge_hmc_run(const l2hmc_gauge_plan* plan, const float* betas, const float* x_in, float* x_next, int64_t B,
+                        uint64_t seed, uint64_t draw0, int32_t n_steps, float* px, float* actions, float* plaqs,
+                        float* charges, float* charge_diff, float* step_sums, float* samples, void* ws,
+                        size_t ws_bytes, l2hmc_stream_t stream);
+
 /* Forward value of the training loss, per chain (gauge_model.py:766-795): terms[b] = std_loss + charge_loss;
  * the scalar loss is their mean over ALL chains of all ranks.  x, x_prop, z: [B][2*T*X]; px, pz: [B].
  * metric: 0 'l1', 1 'l2', 2 'cos', 3 'cos2', 4 'cos_diff' (:632-657).  Both auxiliary terms compare z with

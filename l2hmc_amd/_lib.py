@@ -99,6 +99,9 @@ _PROTOS = {
                                         _SZ, _P]),
     "l2hmc_gauge_mcmc_step_ex": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _P, _I64, _U64, _U64, _P, _P, _P, _P, _P, _P, _P,
                                            _SZ, _P]),
+    "l2hmc_gauge_hmc_run_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64, _I32]),
+    "l2hmc_gauge_hmc_run": (C.c_int, [C.POINTER(GaugePlan), _P, _P, _P, _I64, _U64, _U64, _I32, _P, _P, _P, _P, _P, _P,
+                                      _P, _P, _SZ, _P]),
     "l2hmc_gauge_loss_terms": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P]),
     "l2hmc_gauge_train_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64]),
     "l2hmc_gauge_train_forward": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _SZ,
@@ -215,6 +218,13 @@ def step_draw_index(draws):
     both: the step takes the next even-aligned pair at or after `draws`.  Returns (d, new_draws)."""
     d = (int(draws) + 1) // 2
     return d, 2 * d + 2
+
+
+def run_draw_index(draws, n_steps):
+    """The draw indices of `n_steps` consecutive native steps (l2hmc_gauge_hmc_run) are draw0, draw0 + 1, ...:
+    what `n_steps` calls of step_draw_index hand out.  Returns (draw0, new_draws)."""
+    d, _ = step_draw_index(draws)
+    return d, 2 * (d + int(n_steps) - 1) + 2
 
 
 def as_dev(a, device=None, dtype=torch.float32):

@@ -1,6 +1,7 @@
 // Plain HMC on the 2D U(1) lattice in ONE launch, at a lattice size chosen at run time: the whole MCMC step
 // (l2hmc_gauge_mcmc_step, l2hmc_gauge_transition_draw) or a whole trajectory / single leapfrog step
-// (l2hmc_gauge_trajectory, l2hmc_gauge_leapfrog) of plans with hmc = 1 (gauge_dynamics.py:102-108: S = T = Q = 0).
+// (l2hmc_gauge_trajectory, l2hmc_gauge_leapfrog) of plans with hmc = 1 (gauge_dynamics.py:102-108: S = T = Q = 0), and
+// a whole RUN of MCMC steps in one launch (l2hmc_gauge_hmc_run: hmc_run_kernel loops over the one copy of the step).
 //
 // Without networks a leapfrog step is a few flops and ONE sin per plaquette, so the kernel is transcendental- and
 // latency-bound and its mapping is chosen for waves in flight, not for the matrix pipe:
@@ -78,22 +79,63 @@ __device__ __forceinline__ void hmc_row_sum2(float& a, float& b, int tsh, int r,
   }
 }
 
+// What a thread keeps for a whole launch: its place in the workgroup, the carve-up of LDS, its SPT sites and their
+// plaquette neighbours.  Nothing of it depends on the MCMC step, so the run kernel forms it once ahead of its step loop.
 template <int SPT>
-__global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArgs p, const int tsh) {
-  extern __shared__ float lds[];
-  const int T = p.T, X = p.X, sites = T * X, D = 2 * sites;
-  const int tid = threadIdx.x;
-  const int tpc = 1 << tsh, R = (int)blockDim.x >> tsh;
-  const int r = tid >> tsh, fl = tid & (tpc - 1);
-  float* xs = lds;                          // [R][2][sites]: the x0 links of a row, then its x1 links
-  float* vs = xs + R * D;                   // [R][2][sites] (step epilogue only)
-  float* sp = vs + R * D;                   // [R][sites]  sin P
-  float* stp = sp + R * sites;              // [8 R]       StepWg scratch
-  float* red = stp + 8 * R;                 // [R][4][2]   per-wave partial sums of a row
-  float* fin = red + 8 * R;                 // [2][256]
+struct HmcLanes {
+  int T, X, sites, D, tsh, tpc, R, r, fl;
+  float* xs;                                // [R][2][sites]: the x0 links of a row, then its x1 links
+  float* vs;                                // [R][2][sites] (step epilogue only)
+  float* sp;                                // [R][sites]  sin P
+  float* stp;                               // [8 R]       StepWg scratch
+  float* red;                               // [R][4][2]   per-wave partial sums of a row
+  float* fin;                               // [2][256]
+  float* xrow;                              // the thread's row of xs
+  float* sprow;                             //   and of sp
+  bool ok[SPT];
+  int nr[SPT], nu[SPT], nl[SPT], nd[SPT];
+};
 
+template <int SPT>
+__device__ __forceinline__ HmcLanes<SPT> hmc_lanes(const FusedArgs& p, int tsh, float* lds, int tid) {
+  HmcLanes<SPT> g;
+  g.T = p.T;
+  g.X = p.X;
+  g.sites = p.T * p.X;
+  g.D = 2 * g.sites;
+  g.tsh = tsh;
+  g.tpc = 1 << tsh;
+  g.R = (int)blockDim.x >> tsh;
+  g.r = tid >> tsh;
+  g.fl = tid & (g.tpc - 1);
+  g.xs = lds;
+  g.vs = g.xs + g.R * g.D;
+  g.sp = g.vs + g.R * g.D;
+  g.stp = g.sp + g.R * g.sites;
+  g.red = g.stp + 8 * g.R;
+  g.fin = g.red + 8 * g.R;
+  g.xrow = g.xs + g.r * g.D;
+  g.sprow = g.sp + g.r * g.sites;
+  const int T = g.T, X = g.X;
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    const int s = g.fl + j * g.tpc;
+    g.ok[j] = s < g.sites;
+    const int sc = g.ok[j] ? s : 0;
+    const int i = sc / X, jx = sc - i * X;
+    g.nr[j] = i * X + (jx + 1 == X ? 0 : jx + 1);
+    g.nl[j] = i * X + (jx == 0 ? X - 1 : jx - 1);
+    g.nu[j] = (i + 1 == T ? 0 : i + 1) * X + jx;
+    g.nd[j] = (i == 0 ? T - 1 : i - 1) * X + jx;
+  }
+  return g;
+}
+
+template <int SPT>
+__device__ __forceinline__ StepWg hmc_workgroup(const FusedArgs& p, const HmcLanes<SPT>& g) {
+  const int R = g.R;
   StepWg w;
-  w.tid = tid;
+  w.tid = threadIdx.x;
   w.row0 = (int64_t)blockIdx.x * R;
   w.nrow = (int)min((int64_t)R, p.rows - w.row0);
   w.stepm = p.step_B > 0;
@@ -102,85 +144,30 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
   w.sdw = 0;
   w.cpw = w.paired ? R / 2 : R;
   w.cbase = (int64_t)blockIdx.x * w.cpw;
-  w.scoin = stp;
-  w.su = stp + R;
-  w.spx = stp + 2 * R;
-  w.sobs = stp + 3 * R;
+  w.scoin = g.stp;
+  w.su = g.stp + R;
+  w.spx = g.stp + 2 * R;
+  w.sobs = g.stp + 3 * R;
+  return w;
+}
 
-  // ---- the row's chain and direction; step mode draws coin and MH uniform of the workgroup's chains first ----
-  if (w.stepm) {
-    if (tid < w.cpw) {
-      const int64_t chain = w.cbase + tid;
-      const bool lv = chain < p.step_Bl;        // (streams are indexed by the chain's place in the WHOLE batch)
-      w.scoin[tid] = lv ? philox_u01(p.step_seed, (uint64_t)(p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
-      w.su[tid] = lv ? philox_u01(p.step_seed, (uint64_t)(p.step_B + p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
-    }
-    __syncthreads();
-  }
-  int k = r, d = 0;                             // chain slot of the row (step mode), direction
-  int64_t grow;                                 // chain (step mode) or row (trajectory mode) in the launch's arrays
-  bool live;
-  if (w.stepm) {
-    k = w.paired && r >= w.cpw ? r - w.cpw : r;
-    grow = w.cbase + k;
-    live = grow < p.step_Bl;
-    d = w.paired ? (r >= w.cpw ? 1 : 0) : (w.scoin[k] > 0.5f ? 0 : 1);     // gauge_dynamics.py:221-227
-  } else {
-    grow = w.row0 + r;
-    live = r < w.nrow;
-    if (live && p.dir) d = p.dir[grow];
-  }
-
-  // ---- the thread's sites and their plaquette neighbours ----
-  bool ok[SPT];
-  int nr[SPT], nu[SPT], nl[SPT], nd[SPT];
-  float x0[SPT], x1[SPT], v0[SPT], v1[SPT], xi0[SPT], xi1[SPT];
-#pragma unroll
-  for (int j = 0; j < SPT; ++j) {
-    const int s = fl + j * tpc;
-    ok[j] = s < sites;
-    const int sc = ok[j] ? s : 0;
-    const int i = sc / X, jx = sc - i * X;
-    nr[j] = i * X + (jx + 1 == X ? 0 : jx + 1);
-    nl[j] = i * X + (jx == 0 ? X - 1 : jx - 1);
-    nu[j] = (i + 1 == T ? 0 : i + 1) * X + jx;
-    nd[j] = (i == 0 ? T - 1 : i - 1) * X + jx;
-    x0[j] = x1[j] = v0[j] = v1[j] = 0.f;
-    if (ok[j] && live) {
-      const float* xr = p.x0 + grow * D + 2 * s;
-      x0[j] = xr[0];
-      x1[j] = xr[1];
-      if (w.stepm) {
-        // momenta of (direction d, chain): elements [(d * B + chain) * D, + D) of the normal stream; D is even, so
-        // the two links of a site are one Box-Muller pair of one Philox block
-        const uint64_t e = ((uint64_t)d * (uint64_t)p.step_B + (uint64_t)(p.step_chain0 + grow)) * (uint64_t)D + 2 * s;
-        const uint64_t nb = e >> 2;
-        uint32_t c[4] = {(uint32_t)nb, (uint32_t)(nb >> 32), (uint32_t)(2 * p.step_draw), (uint32_t)((2 * p.step_draw) >> 32)};
-        philox4x32_10(c, (uint32_t)p.step_seed, (uint32_t)(p.step_seed >> 32));
-        float nv[4];
-        philox_normal4(c, nv);
-        const bool hi = (e & 2) != 0;
-        v0[j] = hi ? nv[2] : nv[0];
-        v1[j] = hi ? nv[3] : nv[1];
-      } else {
-        const float* vr = p.v0 + grow * D + 2 * s;
-        v0[j] = vr[0];
-        v1[j] = vr[1];
-      }
-    }
-    xi0[j] = x0[j];
-    xi1[j] = x1[j];
-  }
-
-  float* xrow = xs + r * D;
-  float* sprow = sp + r * sites;
+// The trajectory of the thread's row from (x, v) in registers, direction d (0 forward, 1 backward), steps
+// [p.step_begin, p.step_end) at p.beta; returns the row's accept probability (0 unless want_p).  Every thread of the
+// workgroup calls it.  On return the row's x is also in its xs row (published ahead of the last sin P pass).
+template <int SPT>
+__device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLanes<SPT>& g, const int d,
+                                                const bool want_p, float (&x0)[SPT], float (&x1)[SPT],
+                                                float (&v0)[SPT], float (&v1)[SPT]) {
+  const int sites = g.sites, D = g.D, tpc = g.tpc, fl = g.fl;
+  float* xrow = g.xrow;
+  float* sprow = g.sprow;
   const float beta = p.beta, eps = p.eps;
   float sP[SPT];
 
   auto publish_x = [&]() {
 #pragma unroll
     for (int j = 0; j < SPT; ++j)
-      if (ok[j]) {
+      if (g.ok[j]) {
         xrow[fl + j * tpc] = x0[j];
         xrow[sites + fl + j * tpc] = x1[j];
       }
@@ -192,9 +179,9 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
       sP[j] = 0.f;
-      if (ok[j]) {
+      if (g.ok[j]) {
         // gauge_model.py:676-679: x0[i,j] - x1[i,j] - x0[i,j+1] + x1[i+1,j]
-        const float P = x0[j] - x1[j] - xrow[nr[j]] + xrow[sites + nu[j]];
+        const float P = x0[j] - x1[j] - xrow[g.nr[j]] + xrow[sites + g.nu[j]];
         float sn, cs;
         fast_sincos(P, &sn, &cs);
         sP[j] = sn;
@@ -209,9 +196,9 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
   auto kick = [&]() {
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
-      if (ok[j]) {
-        const float g0 = beta * (sP[j] - sprow[nl[j]]);
-        const float g1 = beta * (-sP[j] + sprow[nd[j]]);
+      if (g.ok[j]) {
+        const float g0 = beta * (sP[j] - sprow[g.nl[j]]);
+        const float g1 = beta * (-sP[j] + sprow[g.nd[j]]);
         const float k0 = 0.5f * eps * g0, k1 = 0.5f * eps * g1;
         v0[j] = d ? v0[j] + k0 : v0[j] - k0;
         v1[j] = d ? v1[j] + k1 : v1[j] - k1;
@@ -225,11 +212,9 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
     return kk;
   };
 
-  // ---- the trajectory ----
   publish_x();
   float act0 = sin_pass(), kin0 = kinetic();
-  const bool want_p = w.stepm || p.p_accept != nullptr;
-  if (want_p) hmc_row_sum2(act0, kin0, tsh, r, fl, red);
+  if (want_p) hmc_row_sum2(act0, kin0, g.tsh, g.r, fl, g.red);
   float act1 = act0;
   const int N = p.num_steps;
   for (int step = p.step_begin; step < p.step_end; ++step) {
@@ -237,7 +222,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
     float m0[SPT], m1[SPT];
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
-      const int s = ok[j] ? fl + j * tpc : 0;
+      const int s = g.ok[j] ? fl + j * tpc : 0;
       m0[j] = m[2 * s];
       m1[j] = m[2 * s + 1];
     }
@@ -263,38 +248,92 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
   float pr = 0.f;
   if (want_p) {
     float kin1 = kinetic();
-    hmc_row_sum2(act1, kin1, tsh, r, fl, red);
+    hmc_row_sum2(act1, kin1, g.tsh, g.r, fl, g.red);
     pr = accept_prob(beta, act0, act1, 0.5f * kin0, 0.5f * kin1, 0.f);
   }
+  return pr;
+}
 
-  if (!w.stepm) {
-    // ---- trajectory mode: x, v, sumlogdet (exactly 0), p of the live rows ----
-    if (live) {
+// The chain slot and the chain of the thread's row in step mode (they do not change from step to step); a row of
+// the paired layout keeps its direction too.
+template <int SPT>
+__device__ __forceinline__ void hmc_step_row(const FusedArgs& p, const HmcLanes<SPT>& g, const StepWg& w, int& k,
+                                             int64_t& grow, bool& live) {
+  k = w.paired && g.r >= w.cpw ? g.r - w.cpw : g.r;
+  grow = w.cbase + k;
+  live = grow < p.step_Bl;
+}
+
+// x of chain `grow` -> the thread's registers (zeros for a dead row and for sites beyond the lattice)
+template <int SPT>
+__device__ __forceinline__ void hmc_load_x(const FusedArgs& p, const HmcLanes<SPT>& g, int64_t grow, bool live,
+                                           float (&x0)[SPT], float (&x1)[SPT]) {
 #pragma unroll
-      for (int j = 0; j < SPT; ++j) {
-        if (ok[j]) {
-          float* xo = p.x_out + grow * D + 2 * (fl + j * tpc);
-          float* vo = p.v_out + grow * D + 2 * (fl + j * tpc);
-          xo[0] = x0[j];
-          xo[1] = x1[j];
-          vo[0] = v0[j];
-          vo[1] = v1[j];
-        }
-      }
-      if (fl == 0) {
-        if (p.logdet && !p.logdet_accumulate) p.logdet[grow] = 0.f;
-        if (p.p_accept) p.p_accept[grow] = pr;
-      }
+  for (int j = 0; j < SPT; ++j) {
+    x0[j] = x1[j] = 0.f;
+    if (g.ok[j] && live) {
+      const float* xr = p.x0 + grow * g.D + 2 * (g.fl + j * g.tpc);
+      x0[j] = xr[0];
+      x1[j] = xr[1];
     }
-    return;
+  }
+}
+
+// ONE MCMC step, the only copy (hmc_step_kernel runs it once, hmc_run_kernel once per step of its loop): the coin /
+// MH uniform / momentum draws of draw index p.step_draw, the trajectory at p.beta with its fp64 accept probability,
+// the mix of the directions with Metropolis-Hastings, the observables of the step's input, |dQ|, the wrap and the
+// step's sums.  In: x0 / x1 = the step's input x of the row's chain (every row, whatever its direction).  Out, in the
+// threads of the chains' primary rows (r < w.cpw): x0 / x1 = the wrapped output, the very fp32 values that go to
+// p.step_x_next; the other rows' x0 / x1 are left over from their trajectory.  Every per-step pointer of p (step_px
+// ... step_dq, step_x_next, step_xprop / _vprop / _xout, step_sums, step_part) is that of THIS step.  p.x0 is not read.
+template <int SPT>
+__device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>& g, const StepWg& w, const int k,
+                                         const int64_t grow, const bool live, float (&x0)[SPT], float (&x1)[SPT]) {
+  const int sites = g.sites, D = g.D, tpc = g.tpc, r = g.r, fl = g.fl, tid = w.tid, tsh = g.tsh;
+  float* xs = g.xs;
+  float* vs = g.vs;
+  float* red = g.red;
+  // ---- coin and MH uniform of the workgroup's chains, then the row's direction ----
+  if (tid < w.cpw) {
+    const int64_t chain = w.cbase + tid;
+    const bool lv = chain < p.step_Bl;        // (streams are indexed by the chain's place in the WHOLE batch)
+    w.scoin[tid] = lv ? philox_u01(p.step_seed, (uint64_t)(p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
+    w.su[tid] = lv ? philox_u01(p.step_seed, (uint64_t)(p.step_B + p.step_chain0 + chain), 2 * p.step_draw + 1) : 1.f;
+  }
+  __syncthreads();
+  const int d = w.paired ? (r >= w.cpw ? 1 : 0) : (w.scoin[k] > 0.5f ? 0 : 1);     // gauge_dynamics.py:221-227
+
+  // ---- the momenta of the thread's links; the step's input is kept for the reject branch and the observables ----
+  float v0[SPT], v1[SPT], xi0[SPT], xi1[SPT];
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    v0[j] = v1[j] = 0.f;
+    if (g.ok[j] && live) {
+      const int s = fl + j * tpc;
+      // momenta of (direction d, chain): elements [(d * B + chain) * D, + D) of the normal stream; D is even, so
+      // the two links of a site are one Box-Muller pair of one Philox block
+      const uint64_t e = ((uint64_t)d * (uint64_t)p.step_B + (uint64_t)(p.step_chain0 + grow)) * (uint64_t)D + 2 * s;
+      const uint64_t nb = e >> 2;
+      uint32_t c[4] = {(uint32_t)nb, (uint32_t)(nb >> 32), (uint32_t)(2 * p.step_draw), (uint32_t)((2 * p.step_draw) >> 32)};
+      philox4x32_10(c, (uint32_t)p.step_seed, (uint32_t)(p.step_seed >> 32));
+      float nv[4];
+      philox_normal4(c, nv);
+      const bool hi = (e & 2) != 0;
+      v0[j] = hi ? nv[2] : nv[0];
+      v1[j] = hi ? nv[3] : nv[1];
+    }
+    xi0[j] = x0[j];
+    xi1[j] = x1[j];
   }
 
-  // ---- step mode: mix the directions, Metropolis-Hastings (gauge_dynamics.py:221-257, mask * a + (1 - mask) * b) ----
+  const float pr = hmc_trajectory<SPT>(p, g, d, true, x0, x1, v0, v1);
+
+  // ---- mix the directions, Metropolis-Hastings (gauge_dynamics.py:221-257, mask * a + (1 - mask) * b) ----
   // xs rows hold the final x already (published ahead of the last sin P pass); v rows and p join them
   float* vrow = vs + r * D;
 #pragma unroll
   for (int j = 0; j < SPT; ++j)
-    if (ok[j]) {
+    if (g.ok[j]) {
       vrow[fl + j * tpc] = v0[j];
       vrow[sites + fl + j * tpc] = v1[j];
     }
@@ -310,7 +349,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
       xo0[j] = xo1[j] = 0.f;
-      if (ok[j]) {
+      if (g.ok[j]) {
         const int s = fl + j * tpc, c = 2 * s;
         float xp0 = x0[j], xp1 = x1[j], vp0 = v0[j], vp1 = v1[j];
         if (w.paired) {
@@ -340,7 +379,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
   if (primary) {
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
-      if (ok[j]) {
+      if (g.ok[j]) {
         const int s = fl + j * tpc;
         gin[s] = xi0[j];
         gin[sites + s] = xi1[j];
@@ -355,9 +394,9 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
     float a = 0.f, b = 0.f;
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
-      if (ok[j]) {
+      if (g.ok[j]) {
         const int s = fl + j * tpc;
-        const float P = xc[s] - xc[sites + s] - xc[nr[j]] + xc[sites + nu[j]];
+        const float P = xc[s] - xc[sites + s] - xc[g.nr[j]] + xc[sites + g.nu[j]];
         float sn, cs;
         fast_sincos(P, &sn, &cs);
         a += cs;
@@ -396,11 +435,13 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
       if (p.step_dq) p.step_dq[chain] = fabsf(q_in - q_out);
     }
   }
-  // ---- np.mod(x_out, 2 pi) (gauge_model.py:1388) and the chains' new state, then the step's sums ----
-  if (primary && live && p.step_x_next) {
+  // ---- np.mod(x_out, 2 pi) (gauge_model.py:1388): the chains' new state, to registers and to step_x_next; then
+  //      the step's sums ----
+  if (primary) {
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
-      if (ok[j]) {
+      x0[j] = x1[j] = 0.f;
+      if (g.ok[j]) {
         float wv[2] = {xo0[j], xo1[j]};
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -410,20 +451,186 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
           if (m_ >= tp) m_ -= tp;
           wv[e] = m_;
         }
-        float* xn = p.step_x_next + grow * D + 2 * (fl + j * tpc);
-        xn[0] = wv[0];
-        xn[1] = wv[1];
+        x0[j] = wv[0];
+        x1[j] = wv[1];
+        if (live && p.step_x_next) {
+          float* xn = p.step_x_next + grow * D + 2 * (fl + j * tpc);
+          xn[0] = wv[0];
+          xn[1] = wv[1];
+        }
       }
     }
   }
-  step_sums<kHmcMaxThreads, 256>(p, w, 1, (int64_t)blockIdx.x, (int)gridDim.x, (int)gridDim.x, fin);
+  step_sums<kHmcMaxThreads, 256>(p, w, 1, (int64_t)blockIdx.x, (int)gridDim.x, (int)gridDim.x, g.fin);
 }
 
-static int launch_hmc(const FusedArgs& a, const HmcGeom& g, int64_t nwg, hipStream_t stream) {
+template <int SPT>
+__global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArgs p, const int tsh) {
+  extern __shared__ float lds[];
+  const HmcLanes<SPT> g = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x);
+  const StepWg w = hmc_workgroup<SPT>(p, g);
+  float x0[SPT], x1[SPT];
+  if (w.stepm) {
+    int k;
+    int64_t grow;
+    bool live;
+    hmc_step_row<SPT>(p, g, w, k, grow, live);
+    hmc_load_x<SPT>(p, g, grow, live, x0, x1);
+    hmc_step<SPT>(p, g, w, k, grow, live, x0, x1);
+    return;
+  }
+  // ---- trajectory mode: x, v, sumlogdet (exactly 0), p of the live rows ----
+  const int64_t grow = w.row0 + g.r;
+  const bool live = g.r < w.nrow;
+  const int d = live && p.dir ? p.dir[grow] : 0;
+  float v0[SPT], v1[SPT];
+  hmc_load_x<SPT>(p, g, grow, live, x0, x1);
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    v0[j] = v1[j] = 0.f;
+    if (g.ok[j] && live) {
+      const float* vr = p.v0 + grow * g.D + 2 * (g.fl + j * g.tpc);
+      v0[j] = vr[0];
+      v1[j] = vr[1];
+    }
+  }
+  const float pr = hmc_trajectory<SPT>(p, g, d, p.p_accept != nullptr, x0, x1, v0, v1);
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+      if (g.ok[j]) {
+        float* xo = p.x_out + grow * g.D + 2 * (g.fl + j * g.tpc);
+        float* vo = p.v_out + grow * g.D + 2 * (g.fl + j * g.tpc);
+        xo[0] = x0[j];
+        xo[1] = x1[j];
+        vo[0] = v0[j];
+        vo[1] = v1[j];
+      }
+    }
+    if (g.fl == 0) {
+      if (p.logdet && !p.logdet_accumulate) p.logdet[grow] = 0.f;
+      if (p.p_accept) p.p_accept[grow] = pr;
+    }
+  }
+}
+
+// What a RUN of MCMC steps adds to FusedArgs (l2hmc_gauge_hmc_run).  FusedArgs holds the run's first draw index
+// (step_draw), the first row of every history (step_px ... step_dq, step_sums, step_part) and the final state
+// (step_x_next); step s of the run uses draw step_draw + s, betas[s] and the rows s of the histories.
+// PRECONDITION, checked on the host by l2hmc_gauge_hmc_run and launch_hmc_run before the launch:
+// step_draw + n_steps <= 2^63, i.e. bit 63 of every step's draw index is 0.  hmc_run_kernel adds that bit to the
+// thread's lane, row and chain indices as a zero the compiler cannot fold (see its step loop); were it 1, every
+// index would be one too far.
+struct HmcRunArgs {
+  int n_steps;
+  const float* betas;                    // [n_steps]
+  int64_t hist_stride;                   // floats between two steps' rows of px / actions / plaqs / charges / charge_diff
+  int64_t part_stride;                   // floats between two steps' slices of step_part
+  float* samples;                        // [n_steps][sample_stride]: every step's wrapped output, or NULL
+  int64_t sample_stride;
+};
+
+// n_steps MCMC steps in ONE launch: chains never meet, so a workgroup walks its own chains through the whole run with
+// their state in registers.  Step s + 1 starts from the wrapped output of step s -- the fp32 values the step kernel
+// stores and its next launch reloads -- and forms everything else anew, so the run gives the bits of n_steps launches
+// of hmc_step_kernel.  Workgroups drift apart freely: the only thing that crosses them is a step's sums, and every
+// step has a ticket (step_sums[s][3]) and a slice of step_part of its own, so nobody waits for anybody.
+template <int SPT>
+__global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(const FusedArgs p, const HmcRunArgs ra, const int tsh) {
+  extern __shared__ float lds[];
+  const HmcLanes<SPT> g = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x);
+  const StepWg w = hmc_workgroup<SPT>(p, g);
+  int k;
+  int64_t grow;
+  bool live;
+  hmc_step_row<SPT>(p, g, w, k, grow, live);
+  float x0[SPT], x1[SPT];
+  hmc_load_x<SPT>(p, g, grow, live, x0, x1);
+  const bool primary = g.r < w.cpw;
+  FusedArgs q = p;
+  q.step_xprop = q.step_vprop = q.step_xout = nullptr;       // a run has no use for apply_transition's own outputs
+  q.step_sums_acc = 0;
+  for (int s = 0; s < ra.n_steps; ++s) {
+    q.beta = ra.betas[s];
+    q.step_draw = p.step_draw + (unsigned long long)s;
+    q.step_x_next = ra.samples ? ra.samples + s * ra.sample_stride : nullptr;
+    q.step_px = p.step_px ? p.step_px + s * ra.hist_stride : nullptr;
+    q.step_act = p.step_act ? p.step_act + s * ra.hist_stride : nullptr;
+    q.step_plq = p.step_plq ? p.step_plq + s * ra.hist_stride : nullptr;
+    q.step_chg = p.step_chg ? p.step_chg + s * ra.hist_stride : nullptr;
+    q.step_dq = p.step_dq ? p.step_dq + s * ra.hist_stride : nullptr;
+    q.step_sums = p.step_sums ? p.step_sums + 4 * (int64_t)s : nullptr;
+    q.step_part = p.step_part ? p.step_part + s * ra.part_stride : nullptr;
+    // The step's LDS and global addresses are all formed from the thread's lane and row.  Left to itself the compiler
+    // forms every one of them ahead of the loop and keeps them in registers across it: twice the step kernel's
+    // VGPRs, half its workgroups per CU.  z is 0 (a draw index does not reach 2^63), which the compiler cannot know,
+    // so the addresses are formed where they are used, as in the step kernel; the neighbour tables stay hoisted.
+    // The host refuses a run whose draw indices reach 2^63 (HmcRunArgs).  The register counts depend on the compiler:
+    // 78 / 96 / 127 VGPRs (SPT 1 / 2 / 4), no scratch, with hipcc of ROCm 7.2.0 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0) at -O3.
+    const int z = (int)(q.step_draw >> 63);
+    HmcLanes<SPT> gs = g;
+    if (SPT == 4) {
+      // four sites per thread: the 20 registers of the neighbour tables would cost the second workgroup of a CU
+      // (136 VGPRs with them hoisted, 127 without), so this instance forms them per step as well
+      gs = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x + z);
+    } else {
+      gs.fl = g.fl + z;
+      gs.r = g.r + z;
+      gs.xrow = g.xs + gs.r * g.D;
+      gs.sprow = g.sp + gs.r * g.sites;
+    }
+    StepWg ws = w;
+    ws.tid = w.tid + z;
+    hmc_step<SPT>(q, gs, ws, k + z, grow + z, live, x0, x1);
+    if (w.paired) {
+      // the chain's new state is in its forward row's registers: hand it to the backward row through that row's
+      // own (free) x row.  The next write there is the backward row's own publish of the same values.
+      if (primary) {
+        float* xb = gs.xs + (k + z + w.cpw) * gs.D;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+          if (gs.ok[j]) {
+            xb[gs.fl + j * gs.tpc] = x0[j];
+            xb[gs.sites + gs.fl + j * gs.tpc] = x1[j];
+          }
+      }
+      __syncthreads();
+      if (!primary) {
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+          x0[j] = x1[j] = 0.f;
+          if (gs.ok[j]) {
+            x0[j] = gs.xrow[gs.fl + j * gs.tpc];
+            x1[j] = gs.xrow[gs.sites + gs.fl + j * gs.tpc];
+          }
+        }
+      }
+    }
+  }
+  if (primary && live && p.step_x_next) {
+#pragma unroll
+    for (int j = 0; j < SPT; ++j)
+      if (g.ok[j]) {
+        float* xn = p.step_x_next + grow * g.D + 2 * (g.fl + j * g.tpc);
+        xn[0] = x0[j];
+        xn[1] = x1[j];
+      }
+  }
+}
+
+static int launch_hmc(const FusedArgs& a, const HmcGeom& g, int64_t nwg, hipStream_t stream,
+                      const HmcRunArgs* run = nullptr) {
   L2HMC_REQUIRE(nwg > 0 && nwg < (1ll << 31), "hmc step: too many rows");
   prof_before(kProfFused, stream);
   const dim3 grid((unsigned)nwg), block((unsigned)g.threads);
-  if (g.spt == 1)
+  if (run) {
+    if (g.spt == 1)
+      hipLaunchKernelGGL((hmc_run_kernel<1>), grid, block, g.lds, stream, a, *run, g.tsh);
+    else if (g.spt == 2)
+      hipLaunchKernelGGL((hmc_run_kernel<2>), grid, block, g.lds, stream, a, *run, g.tsh);
+    else
+      hipLaunchKernelGGL((hmc_run_kernel<4>), grid, block, g.lds, stream, a, *run, g.tsh);
+  } else if (g.spt == 1)
     hipLaunchKernelGGL((hmc_step_kernel<1>), grid, block, g.lds, stream, a, g.tsh);
   else if (g.spt == 2)
     hipLaunchKernelGGL((hmc_step_kernel<2>), grid, block, g.lds, stream, a, g.tsh);
@@ -466,6 +673,34 @@ int launch_hmc_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, fl
   a.step_px = px; a.step_act = actions; a.step_plq = plaqs; a.step_chg = charges; a.step_dq = dq;
   a.step_sums = step_sums; a.step_part = part;       // part: 2 floats per workgroup
   return launch_hmc(a, g, nwg, stream);
+}
+
+size_t hmc_run_part_bytes(int64_t B) { return align_up(sizeof(float) * 2 * (size_t)B, 256); }
+
+int launch_hmc_run(const l2hmc_gauge_plan* p, const float* betas, const float* x_in, float* x_next, int64_t B,
+                   uint64_t seed, uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
+                   float* charges, float* dq, float* step_sums, float* samples, float* part, hipStream_t stream) {
+  HmcGeom g;
+  L2HMC_REQUIRE(hmc_plan_supported(p) && hmc_geom(p->T, p->X, &g), "hmc run: plan has no one-launch kernel");
+  L2HMC_REQUIRE(betas && x_in && x_next && B > 0 && n_steps > 0 && (!step_sums || part), "hmc run: bad arguments");
+  L2HMC_REQUIRE(draw0 <= (1ull << 63) - (uint64_t)n_steps, "hmc run: draw0 + n_steps exceeds 2^63");   // HmcRunArgs
+  const int cpw = both ? g.rows_wg / 2 : g.rows_wg;
+  const int64_t nwg = ceil_div(B, cpw);
+  const int64_t D = 2 * (int64_t)p->T * p->X;
+  FusedArgs a{};
+  a.T = p->T; a.X = p->X; a.num_steps = p->num_steps; a.step_begin = 0; a.step_end = p->num_steps;
+  a.eps = p->eps; a.masks = p->masks;
+  a.x0 = x_in; a.rows = nwg * g.rows_wg;
+  a.step_x_next = x_next;
+  a.step_B = B; a.step_Bl = B; a.step_chain0 = 0;
+  a.step_seed = seed; a.step_draw = draw0; a.step_both = both;
+  a.step_px = px; a.step_act = actions; a.step_plq = plaqs; a.step_chg = charges; a.step_dq = dq;
+  a.step_sums = step_sums; a.step_part = part;       // part: hmc_run_part_bytes(B) per step (2 floats per workgroup)
+  HmcRunArgs r{};
+  r.n_steps = n_steps; r.betas = betas; r.hist_stride = B;
+  r.part_stride = (int64_t)(hmc_run_part_bytes(B) / sizeof(float));
+  r.samples = samples; r.sample_stride = B * D;
+  return launch_hmc(a, g, nwg, stream, &r);
 }
 
 }  // namespace l2hmc

@@ -5,6 +5,8 @@
 //   (launch_fused_step, fused_traj.hip: the kernel draws its own Philox streams and finishes the step in its
 //   epilogue; launch_hmc_step, hmc_step.hip: the same for plain HMC at any lattice shape); other plans go through the public ops below with the draws of step_draws_kernel.
 // The reference pays one session run with a host round trip of the whole batch per step.
+#include <vector>
+
 #include "stq_dense.h"
 
 namespace l2hmc {
@@ -193,4 +195,77 @@ extern "C" int l2hmc_gauge_transition_draw(const l2hmc_gauge_plan* plan, float b
   char* rest = base + step_head_bytes(B, D);
   return l2hmc_gauge_transition(plan, beta, x, Vw, Vw + (size_t)B * D, cu, cu + B, B, selected ? 0 : 1, x_prop, v_prop,
                                 p_accept, x_out, rest, ws_bytes - step_head_bytes(B, D), stream);
+}
+
+// ---- a run of plain-HMC steps: one launch where the plan has the one-launch kernel, the loop over the step otherwise
+static bool hmc_run_one_launch(const l2hmc_gauge_plan* plan) {
+  return !(plan->flags & L2HMC_PLAN_LAYERED) && hmc_plan_supported(plan);
+}
+
+static size_t hmc_run_loop_scratch(int64_t B) { return align_up(sizeof(float) * (size_t)B, 256); }
+
+extern "C" size_t l2hmc_gauge_hmc_run_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps) {
+  if (!plan || B < 0 || n_steps <= 0) return 0;
+  if (!plan->hmc) {
+    set_error("gauge_hmc_run_ws_bytes: plan.hmc = 0 (a run is steps of plain HMC)");
+    return 0;
+  }
+  if (hmc_run_one_launch(plan)) return (size_t)n_steps * hmc_run_part_bytes(B > 0 ? B : 1);
+  // the loop: one step's workspace, and px / charge_diff rows for a caller that keeps no histories but wants sums
+  return l2hmc_gauge_mcmc_step_ws_bytes(plan, B) + 2 * hmc_run_loop_scratch(B);
+}
+
+extern "C" int l2hmc_gauge_hmc_run(const l2hmc_gauge_plan* plan, const float* betas, const float* x_in, float* x_next,
+                                   int64_t B, uint64_t seed, uint64_t draw0, int32_t n_steps, float* px,
+                                   float* actions, float* plaqs, float* charges, float* charge_diff, float* step_sums,
+                                   float* samples, void* ws, size_t ws_bytes, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(plan != nullptr && B >= 0, "gauge_hmc_run: bad arguments");
+  L2HMC_REQUIRE(plan->hmc, "gauge_hmc_run: plan.hmc = 0 (a run is steps of plain HMC)");
+  L2HMC_REQUIRE(n_steps > 0, "gauge_hmc_run: n_steps = %d, expected at least 1", (int)n_steps);
+  L2HMC_REQUIRE(betas != nullptr, "gauge_hmc_run: NULL betas");
+  // the run kernel relies on bit 63 of every draw index being 0 (hmc_step.hip: HmcRunArgs)
+  L2HMC_REQUIRE(draw0 <= (1ull << 63) - (uint64_t)n_steps, "gauge_hmc_run: draw0 + n_steps exceeds 2^63");
+  L2HMC_REQUIRE(x_in && x_next, "gauge_hmc_run: NULL x_in / x_next");
+  L2HMC_REQUIRE(!step_sums || ws, "gauge_hmc_run: step_sums needs the workspace");
+  if (B == 0) return L2HMC_OK;
+  const size_t need = l2hmc_gauge_hmc_run_ws_bytes(plan, B, n_steps);
+  if ((step_sums || !hmc_run_one_launch(plan)) && (!ws || ws_bytes < need)) {
+    set_error("gauge_hmc_run: workspace %zu < %zu bytes", ws ? ws_bytes : (size_t)0, need);
+    return L2HMC_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const bool selected = (plan->flags & L2HMC_PLAN_SELECTED_ONLY) != 0;
+  if (hmc_run_one_launch(plan))
+    return launch_hmc_run(plan, betas, x_in, x_next, B, seed, draw0, n_steps, selected ? 0 : 1, px, actions, plaqs,
+                          charges, charge_diff, step_sums, samples, step_sums ? static_cast<float*>(ws) : nullptr, s);
+  // no one-launch kernel (more than 1024 sites, or L2HMC_PLAN_LAYERED): the same run, step by step.  The loop needs
+  // the betas on the host, so it waits for the stream once.
+  std::vector<float> hb((size_t)n_steps);
+  if (hipMemcpyAsync(hb.data(), betas, sizeof(float) * (size_t)n_steps, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    set_error("gauge_hmc_run: reading betas: %s", hipGetErrorString(hipGetLastError()));
+    return L2HMC_ERR_HIP;
+  }
+  const size_t D = 2 * (size_t)plan->T * plan->X, sc = hmc_run_loop_scratch(B);
+  char* base = static_cast<char*>(ws);
+  float* px_s = reinterpret_cast<float*>(base);
+  float* dq_s = reinterpret_cast<float*>(base + sc);
+  const float* xi = x_in;
+  for (int32_t i = 0; i < n_steps; ++i) {
+    const size_t row = (size_t)i * (size_t)B;
+    float* xo = samples ? samples + row * D : x_next;
+    float* sums = step_sums ? step_sums + 4 * (size_t)i : nullptr;
+    if (int e = l2hmc_gauge_mcmc_step_ex(plan, hb[i], xi, xo, B, seed, draw0 + (uint64_t)i, px ? px + row : (sums ? px_s : nullptr),
+                                         actions ? actions + row : nullptr, plaqs ? plaqs + row : nullptr,
+                                         charges ? charges + row : nullptr,
+                                         charge_diff ? charge_diff + row : (sums ? dq_s : nullptr), sums, base + 2 * sc,
+                                         ws_bytes - 2 * sc, stream))
+      return e;
+    xi = xo;
+  }
+  if (samples && hipMemcpyAsync(x_next, xi, sizeof(float) * (size_t)B * D, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    set_error("gauge_hmc_run: copying the final state: %s", hipGetErrorString(hipGetLastError()));
+    return L2HMC_ERR_HIP;
+  }
+  return L2HMC_OK;
 }

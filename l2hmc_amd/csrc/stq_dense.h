@@ -165,6 +165,13 @@ int launch_hmc_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, fl
                     uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges, float* dq,
                     float* step_sums, float* part, hipStream_t stream, float* x_prop = nullptr,
                     float* v_prop = nullptr, float* x_out = nullptr);
+// n_steps consecutive steps in ONE launch (l2hmc_gauge_hmc_run): step s draws with index draw0 + s at betas[s] and
+// fills row s of the [n_steps][B] histories, of step_sums [n_steps][4] and of samples [n_steps][B][D]; part:
+// n_steps x hmc_run_part_bytes(B) of scratch
+size_t hmc_run_part_bytes(int64_t B);
+int launch_hmc_run(const l2hmc_gauge_plan* p, const float* betas, const float* x_in, float* x_next, int64_t B,
+                   uint64_t seed, uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
+                   float* charges, float* dq, float* step_sums, float* samples, float* part, hipStream_t stream);
 // bytes of launch_fused_step's `hand` workspace for B chains (the hand-off of the split 16-row form)
 size_t fused_step_hand_bytes(int64_t B, int D);
 // whole-trajectory reverse pass (fused_train.hip); deltas_*: {dout, d2, d1} tapes, coef_parts: {dcs_x, dcq_x, dcs_v, dcq_v}

@@ -24,6 +24,10 @@ class GaugeSampler:
         # at 0, so the rows of one zero-initialised ring are handed out in turn (longer than StepStats' backlog)
         self._sums_ring = torch.zeros(256, 4, dtype=torch.float32, device=dynamics._device)
         self._sums_next = 0
+        # plain-HMC runs on a plan with the one-launch kernel: MCMC steps per launch of l2hmc_gauge_hmc_run
+        # (1 = one launch per step through `step`, the cross-check)
+        self.steps_per_launch = 256
+        self._run_sums = None        # [steps][4] like _sums_ring: zeroed once, the kernel leaves the tickets at 0
 
     def update_beta(self, step):
         """gauge_model.py:1039-1046: linear annealing of 1/beta."""
@@ -107,16 +111,26 @@ class GaugeSampler:
 
     def run(self, run_steps, beta, x=None, keep_samples=False):
         """:1304-1460 without the file/plot side effects.  Starts from N(0,1) samples like the reference
-        (:1354) unless `x` is given.  Returns per-step histories as NumPy arrays [steps, B]."""
+        (:1354) unless `x` is given.  Returns per-step histories as NumPy arrays [steps, B].  `beta`: a float, or a
+        sequence of `run_steps` values (one per step; `plaq_exact` is then taken at the last).  Plain HMC on a plan
+        with the one-launch kernel runs `steps_per_launch` steps per launch (`_run_launches`): the same values."""
+        import ctypes as C
         dyn = self.dynamics
         if x is None:
             x = _lib.as_dev(np.random.randn(dyn.batch_size, dyn.x_dim), dyn._device)
         else:
             x = _lib.as_dev(x, dyn._device)
+        per_step = (beta.ndim if isinstance(beta, torch.Tensor) else np.ndim(beta)) > 0
+        betas = [float(b) for b in beta] if per_step else [beta] * run_steps
+        if len(betas) != run_steps:
+            raise ValueError(f"beta: expected a float or {run_steps} values, got {len(betas)}")
+        if (run_steps > 0 and dyn.hmc and int(self.steps_per_launch) > 1
+                and _lib.lib().l2hmc_gauge_plan_fused(C.byref(dyn._plan())) == 1):
+            return self._run_launches(run_steps, betas, x, keep_samples)
         hist = {k: [] for k in ("px", "actions", "plaqs", "charges", "charge_diff")}
         samples = []
-        for _ in range(run_steps):
-            x, px, obs, dq = self.step(x, beta)
+        for i in range(run_steps):
+            x, px, obs, dq = self.step(x, betas[i])
             hist["px"].append(px)
             hist["actions"].append(obs["action"])
             hist["plaqs"].append(obs["avg_plaq"])
@@ -125,13 +139,55 @@ class GaugeSampler:
             if keep_samples:
                 samples.append(x)
         out = {k: torch.stack(v).cpu().numpy() for k, v in hist.items()}
-        out["plaq_exact"] = u1_plaq_exact(beta)
+        out["plaq_exact"] = u1_plaq_exact(betas[-1] if per_step else beta)
         out["samples_out"] = x
         out["mean_accept"] = self.stats.mean_accept()
         if keep_samples:
             out["samples"] = torch.stack(samples).cpu().numpy()
         return out
 
+    def _run_launches(self, run_steps, betas, x, keep_samples):
+        """`run` for plain HMC through l2hmc_gauge_hmc_run: chunks of at most `steps_per_launch` MCMC steps, ONE launch
+        each, the chains' state in registers from step to step.  The same draws (consecutive draw indices from the
+        dynamics' counter), histories, sums and samples as the loop over `step`, bit for bit.  The chunks bound the
+        workspace and, with `keep_samples`, the device buffer of the samples (copied to the host chunk by chunk)."""
+        import ctypes as C
+        dyn = self.dynamics
+        B, D, dev = x.shape[0], x.shape[1], x.device
+        plan, L = dyn._plan(), _lib.lib()
+        chunk = min(int(self.steps_per_launch), run_steps)
+        names = ("px", "actions", "plaqs", "charges", "charge_diff")
+        hist = {k: torch.empty(run_steps, B, dtype=torch.float32, device=dev) for k in names}
+        beta_dev = torch.tensor(betas, dtype=torch.float32, device=dev)
+        if self._run_sums is None or self._run_sums.shape[0] < run_steps or self._run_sums.device != dev:
+            self._run_sums = torch.zeros(run_steps, 4, dtype=torch.float32, device=dev)
+        sums = self._run_sums
+        ws, nb = dyn._ws.get(L.l2hmc_gauge_hmc_run_ws_bytes(C.byref(plan), B, chunk), dev)
+        samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
+        samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
+        # the steps' random streams come from the dynamics' own draw counter, as in `step`
+        draw0, _ = _lib.run_draw_index(dyn._draws, run_steps)
+        x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
+        x_in = _lib.dev_ptr(x, name="x")
+        for s0 in range(0, run_steps, chunk):
+            n = min(chunk, run_steps - s0)
+            _lib.check(L.l2hmc_gauge_hmc_run(
+                C.byref(plan), beta_dev[s0:].data_ptr(), x_in, x_next.data_ptr(), B, dyn._seed, draw0 + s0, n,
+                *(hist[k][s0:].data_ptr() for k in names), sums[s0:].data_ptr(),
+                samples_dev.data_ptr() if keep_samples else None, ws, nb, _lib.stream_ptr(dyn._device)))
+            _, dyn._draws = _lib.run_draw_index(2 * draw0, s0 + n)      # the counter moves with the completed steps
+            x_in = x_next.data_ptr()                       # later chunks advance the state in place
+            for i in range(s0, s0 + n):
+                self.stats.push_sums(sums[i, :3])
+            if keep_samples:
+                samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
+        out = {k: v.cpu().numpy() for k, v in hist.items()}
+        out["plaq_exact"] = u1_plaq_exact(betas[-1])
+        out["samples_out"] = x_next
+        out["mean_accept"] = self.stats.mean_accept()
+        if keep_samples:
+            out["samples"] = samples
+        return out
 
     @staticmethod
     def run_dicts(out, beta):

@@ -200,6 +200,9 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
                                       * does, instead of only the columns its mask lets move: on the layer-by-layer path,
                                       * and in the whole-step kernel with plan.heads set (identical x, v for finite
                                       * trajectories; 0 x non-finite differs: DESIGN.md D1).  A/B switch */
+#define L2HMC_PLAN_FULL_L1 64        /* whole-step kernel with plan.heads set: a position sub-update forms XNet's first-layer
+                                      * product with keep (.) x over all D columns instead of the D / 2 it keeps (same bits;
+                                      * the active-column heads stay on; L2HMC_PLAN_ALL_COLUMNS switches off both).  A/B switch */
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */
@@ -219,8 +222,22 @@ typedef struct l2hmc_gauge_plan {
 /* Active-column heads of the whole-step kernel (GenericNet D = 128, H = 512 on an 8x8-site lattice; bytes = 0 for
  * other plans).  For every mask row and keep sense it lists the D / 2 columns a position sub-update moves and packs
  * XNet's S / T / Q weights of just those columns; l2hmc_gauge_mcmc_step then forms the heads of its position
- * sub-updates on those columns only (same bits).  Rows whose mask is not exactly D / 2 zeros and D / 2 ones are
- * recorded as such and take every column.  Re-pack after any change of plan.masks or of XNet's weights. */
+ * sub-updates on those columns only (same bits).  It also packs the rows D + c of XNet's first-layer weights for the
+ * D / 2 columns c the sub-update KEEPS: its second input keep (.) x is zero everywhere else, so the kernel forms that
+ * product over D / 2 k instead of D (same bits; a row in which a moving column holds 0 x non-finite = NaN comes out
+ * NaN as before).  Rows whose mask is not exactly D / 2 zeros and D / 2 ones are recorded as such and take every
+ * column and the full first layer.  Re-pack after any change of plan.masks or of XNet's weights.
+ * Layout (N = num_steps, pair = 2 * mask row + keep sense whose columns move; everything int32 / float32):
+ *   int   ok[N][2]             1 = the pair is eligible
+ *   int   cols[N][2][D / 2]    the columns the pair moves, ascending (-1 if not eligible)
+ *   int   compact_k[N][D]      column -> its k in the first-layer section of the pair that keeps it (-1 if not eligible)
+ *   (padding to 256 bytes)
+ *   float heads[N][2][4 sections][H / 16 chunks][S | T | Q][64 lanes][4]       3 * (D / 2) * H floats per pair
+ *   float l1[N][2][4 sections][D / 32 chunks][H / 64 tiles][64 lanes][4]       (D / 2) * H floats per pair
+ * Both images are in the fragment order of the 4-wave weight image (l2hmc_dense_pack): lane = 16 q + r holds column
+ * tile * 16 + r, k = chunk * 16 + 4 q + j.  The matrix instruction takes the 16 k of a chunk in the order 4 q + e,
+ * e = 0..3 outer, q = 0..3 inner; the n-th kept column in THAT order over all D columns sits at the compact k whose
+ * turn is n-th in the same order, so every accumulator adds its kept terms in the order of the full walk. */
 size_t l2hmc_gauge_pack_heads_bytes(const l2hmc_gauge_plan* plan);
 int l2hmc_gauge_pack_heads(const l2hmc_gauge_plan* plan, void* heads, l2hmc_stream_t stream);
 

@@ -47,7 +47,8 @@ struct FusedArgs {
   float* step_hand;                      // [workgroups][2 * 16 * D + 16]: x rows, v rows, accept probabilities
   int* step_ticket;                      // [workgroups / 2], zero on entry (a memset ahead of the launch)
   const int* heads_meta;                 // l2hmc_gauge_pack_heads image (step_split only), or NULL = all columns:
-  const float* heads_img;                //   [N][2] eligibility, [N][2][D / 2] columns; [N][2] packed heads sections
+  const float* heads_img;                //   [N][2] eligibility, [N][2][D / 2] columns, [N][D] compact k; [N][2] packed heads sections
+  const float* l1_img;                   // its [N][2] kept-column first-layer sections (needs heads_img), or NULL = full K
 };
 
 // the sub-tile form (fused_traj4.hip): GenericNet 8x8 plans, sampling only

@@ -70,8 +70,9 @@ struct FusedCfg {
   static constexpr int CP1 = (CL / 2 + 1) * (CL / 2 + 1) * CF;              // pooled conv1 map, zero halo
   static constexpr int CONV_FLOATS = CONV ? 2 * kFM * SA + 4 * CW + kFM * (CXIN + CP1) : 0;
   // active-column heads (GenericNet, split step mode): log-det terms staged at their columns [16][SX], the two
-  // column lists of this workgroup's mask row [2][D / 2] (int) and their eligibility [2] (int, padded to 4)
-  static constexpr int ACT_FLOATS = CONV ? 0 : kFM * SX + D + 4;
+  // column lists of this workgroup's mask row [2][D / 2] (int) and their eligibility [2] (int, padded to 4); the
+  // kept-column first layer's column -> compact k map [D] (int) and its per-row poison values [2][16]
+  static constexpr int ACT_FLOATS = CONV ? 0 : kFM * SX + D + 4 + D + 2 * kFM;
   static constexpr int LDS_FLOATS = 3 * kFM * SX + 2 * kFM * SH + 2 * NC + kFM * (D / 2 + 4) /*sinP*/ +
                                     2 * D /*masks*/ + WAVES * kFM /*ldw*/ + (RW > 1 ? IMGW * 64 : 0) /*ldx*/ + kFM /*dir*/ +
                                     8 * kFM /*step mode*/ + CONV_FLOATS + ACT_FLOATS;
@@ -121,12 +122,21 @@ __global__ void pack_fused_kernel(l2hmc_dense_net n, float* __restrict__ out, in
 // that a position sub-update with keep = mask (sense 0) or keep = 1 - mask (sense 1) moves, records whether the row
 // qualifies (every entry exactly 0 or 1, D / 2 of them moving) and packs XNet's heads for those columns in the order
 // of the 4-wave image -- [section = active tile][k-chunk][head][lane][4] -- one 16-column tile per section.
+// Kept-column first layer: the same block packs the x-half of XNet's W1 for the D / 2 columns that sub-update KEEPS
+// (its second input keep (.) x is exactly zero everywhere else) as a first-layer image of D / 2 k -- [section]
+// [chunk 0..D/32-1][tile][lane][4].  A 16-k chunk is walked e-major (k = 4 q + e: e = 0..3 outer, q = 0..3 inner), so
+// the n-th kept column of that walk over all D columns takes the compact k whose turn is n-th in the compact walk:
+// every accumulator meets its kept columns in today's order (kept_compact_k).
+__host__ __device__ inline int kept_compact_k(int n) { return (n & ~15) + 4 * (n & 3) + ((n >> 2) & 3); }
+
 __global__ __launch_bounds__(256) void pack_heads_kernel(l2hmc_dense_net n, const float* __restrict__ masks, int N,
-                                                         int* __restrict__ meta, float* __restrict__ img) {
+                                                         int* __restrict__ meta, float* __restrict__ img,
+                                                         int* __restrict__ cpos, float* __restrict__ img1) {
   constexpr int DMAX = 128;
   __shared__ int cols[DMAX / 2];
+  __shared__ int kcol[DMAX / 2];          // compact k -> kept column
   __shared__ int ok;
-  const int D = n.D, H = n.H, DA = D / 2;
+  const int D = n.D, H = n.H, DA = D / 2, K1 = n.Ka + n.Kb;
   const float* row = masks + (size_t)(blockIdx.y >> 1) * D;
   const float sense = (float)(blockIdx.y & 1);
   if (threadIdx.x == 0) {
@@ -140,11 +150,25 @@ __global__ __launch_bounds__(256) void pack_heads_kernel(l2hmc_dense_net n, cons
       }
     }
     ok = bin && cnt == DA;
+    if (ok) {
+      int nk = 0;
+      for (int w = 0; w < D; ++w) {                   // the full walk: chunk, e, q
+        const int c = (w & ~15) + 4 * (w & 3) + ((w >> 2) & 3);
+        if (row[c] != sense) kcol[kept_compact_k(nk++)] = c;
+      }
+    }
   }
   __syncthreads();
   if (blockIdx.x == 0) {
     if (threadIdx.x == 0) meta[blockIdx.y] = ok;
     for (int i = threadIdx.x; i < DA; i += blockDim.x) meta[2 * N + (size_t)blockIdx.y * DA + i] = ok ? cols[i] : -1;
+    // column -> compact k of the sub-update that keeps it (each block fills in the columns it keeps)
+    int* cp = cpos + (size_t)(blockIdx.y >> 1) * D;
+    if (ok) {
+      for (int i = threadIdx.x; i < DA; i += blockDim.x) cp[kcol[i]] = i;
+    } else {
+      for (int i = threadIdx.x; i < D; i += blockDim.x) cp[i] = -1;
+    }
   }
   if (!ok) return;
   const size_t per = (size_t)3 * DA * H;
@@ -159,6 +183,19 @@ __global__ __launch_bounds__(256) void pack_heads_kernel(l2hmc_dense_net n, cons
     const int col = cols[w * 16 + (lane & 15)];
     const int k = kc * 16 + (lane >> 4) * 4 + j;
     out[i] = n.whd_t[((size_t)hd * D + col) * H + k];
+  }
+  const size_t per1 = (size_t)DA * H;
+  float* out1 = img1 + (size_t)blockIdx.y * per1;
+  const int KC1 = DA / 16, NT = H / (16 * 4);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < per1; i += (size_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i & 3), lane = (int)((i >> 2) & 63);
+    size_t rest = i >> 8;                             // ((w * KC1 + kc) * NT + t)
+    const int t = (int)(rest % NT);
+    rest /= NT;
+    const int kc = (int)(rest % KC1), w = (int)(rest / KC1);
+    const int col = (w * NT + t) * 16 + (lane & 15);
+    const int k = kc * 16 + (lane >> 4) * 4 + j;
+    out1[i] = n.w1_t[(size_t)col * K1 + n.Ka + kcol[k]];
   }
 }
 
@@ -219,6 +256,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   float* stg = stp + 8 * kFM + Cfg::CONV_FLOATS;      // [16][SX] log-det terms of a position call at their columns
   int* scol = reinterpret_cast<int*>(stg + kFM * SX);  // [2][D / 2] active columns of keep sense 0 / 1, ascending
   int* sel = scol + D;                                 // [2] the two lists are usable (exactly D / 2 columns, 0 / 1 mask)
+  int* scp = sel + 4;                                  // [D] column -> compact k of the position sub-update that keeps it
+  float* spz = reinterpret_cast<float*>(scp + D);      // [2][16] NaN: the row's next sub-update (1st, 2nd) sees 0 x non-finite
 
   // diagnostic cycle shares: 0-2 gemm L1/L2/heads, 3-5 their epilogues, 6 barriers, 7 force, 8 mask pass, 9 total
   [[maybe_unused]] unsigned long long ft[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -270,6 +309,9 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     for (int i = tid; i < kFM * (Cfg::CXIN + Cfg::CP1); i += kFThreads) cxin[i] = 0.f;   // halos stay zero
   }
   if (tid < IMGW * kFM) ldw[tid] = 0.f;
+  if constexpr (!CONV) {
+    if (tid < 2 * kFM) spz[tid] = 0.f;
+  }
   __syncthreads();
 
   const int dirl = sdir[r];           // direction of the row this lane owns in a C fragment (fused_common.h)
@@ -456,6 +498,12 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       actv = __builtin_amdgcn_readfirstlane(sel[asense]) != 0;
       wpa = p.heads_img + ((size_t)(arow * 2 + asense) * 4 + (wv & 3)) * Cfg::KC2 * 3 * 256;
     }
+    // Kept-column first layer (split step mode, eligible mask row, l2hmc_gauge_pack_heads): the second input of a
+    // position sub-update, keep (.) x, is exactly zero in the D / 2 columns the sub-update moves, so its product is
+    // formed over the D / 2 kept columns alone, from a first-layer section packed per (mask row, keep sense).  The
+    // kept values sit at compact k (scp) in stg (first sub-update; gs still holds the force when they are written) or
+    // gs (second); a moving column that would have put 0 x non-finite = NaN into the product raises the row's poison.
+    const bool l1c = ACTOK && SPLIT && p.l1_img && p.heads_img && __builtin_amdgcn_readfirstlane(sel[0] & sel[1]) != 0;
     [[maybe_unused]] float ld_k[4] = {0.f, 0.f, 0.f, 0.f}, ld_s[4] = {0.f, 0.f, 0.f, 0.f};   // (RW > 1: the odd wave's log-det terms)
 #ifndef L2HMC_DP1                                 // (A/B builds: tools/build_variant.sh)
 #define L2HMC_DP1 3
@@ -497,7 +545,9 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         for (int t = 0; t < NT1; ++t) acc[t] = keep_v[t];
       } else {
         BRing<NT1, DP1> RA, RB;
+        const bool cmp = l1c && mode == 2;
         const float* wpb = wp1 + (size_t)KH * NTI1 * 256;
+        if (cmp) wpb = p.l1_img + ((size_t)(arow * 2 + asense) * IMGW + wimg) * (KH / 2) * NTI1 * 256;
         ring_prime<NT1, DP1, NTI1>(RB, wpb, false, 0, to1);          // both halves' first fragments are requested up front
         if (l1 == 4) {
 #pragma unroll
@@ -514,9 +564,30 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
             for (int t = 0; t < NT1; ++t) keep_x[t] = acc[t];
           }
         }
-        const float* a2 = src2 + r * s1 + q * 4;
-        stream_layer<NT1, KH, DP1, NTI1>(
-            RB, wpb, [&](int kc) { return *reinterpret_cast<const f32x4*>(a2 + kc * 16); }, acc, false, to1);
+        bool x_done = false;
+        if constexpr (ACTOK) {
+          if (cmp) {
+            x_done = true;
+            const float* a2 = (sub == 0 ? stg : gs) + r * SX + q * 4;
+            const bool bad = spz[sub * kFM + r] != 0.f;
+            stream_layer<NT1, KH / 2, DP1, NTI1>(
+                RB, wpb,
+                [&](int kc) {
+                  f32x4 a = *reinterpret_cast<const f32x4*>(a2 + kc * 16);
+                  if (kc == 0) {       // a select, not an add: finite rows keep their bits
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) a[e] = bad ? __builtin_nanf("") : a[e];
+                  }
+                  return a;
+                },
+                acc, false, to1);
+          }
+        }
+        if (!x_done) {
+          const float* a2 = src2 + r * s1 + q * 4;
+          stream_layer<NT1, KH, DP1, NTI1>(
+              RB, wpb, [&](int kc) { return *reinterpret_cast<const f32x4*>(a2 + kc * 16); }, acc, false, to1);
+        }
         if (l1 == 1) {
 #pragma unroll
           for (int t = 0; t < NT1; ++t) keep_v[t] = acc[t];
@@ -642,7 +713,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
             const float xn = keep * x + (1.f - keep) * upd;
             xs[idx] = xn;
             stg[idx] = (1.f - keep) * s;
-            if (prep_next_mask) gs[idx] = (1.f - keep) * xn;
+            // (the columns this sub-update moves are the ones the next one keeps)
+            if (prep_next_mask) gs[l1c ? r * SX + scp[c] : idx] = (1.f - keep) * xn;
           }
         } else {
 #pragma unroll
@@ -653,9 +725,12 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
             if (prep_next_mask) {
               const float mf = skm[c], mb = skm[D + c];
               const float keep = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf);
-              gs[idx] = (1.f - keep) * xs[idx];
+              const float kx = (1.f - keep) * xs[idx];
+              if (!l1c) gs[idx] = kx;
+              else if (kx != kx) spz[kFM + r] = kx;
             }
           }
+          if (l1c && wv == 4 && q == 0) spz[sub * kFM + r] = 0.f;      // this call's poison is spent
         }
       } else {
 #pragma unroll
@@ -707,7 +782,15 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
             f32x4 kx;
 #pragma unroll
             for (int e = 0; e < 4; ++e) kx[e] = (d ? 1.f - mb[e] : mf[e]) * x[e];
-            *reinterpret_cast<f32x4*>(gs + idx) = kx;
+            if (l1c) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                if ((d ? 1.f - mb[e] : mf[e]) != 0.f) stg[r * SX + scp[c0 + e]] = kx[e];
+                else if (kx[e] != kx[e]) spz[r] = kx[e];
+              }
+            } else {
+              *reinterpret_cast<f32x4*>(gs + idx) = kx;
+            }
           }
         } else {
           // gauge_dynamics.py:519-531 (fwd), :574-584 (bwd); keep mask per direction and sub-update
@@ -789,6 +872,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       arow = sdw ? sb : sf;
       for (int i = tid; i < D; i += kFThreads) scol[i] = p.heads_meta[2 * p.num_steps + arow * D + i];
       if (tid < 2) sel[tid] = p.heads_meta[arow * 2 + tid];
+      if (p.l1_img)
+        for (int i = tid; i < D; i += kFThreads) scp[i] = p.heads_meta[2 * p.num_steps + (p.num_steps + arow) * D + i];
     }
     // (gs holds the force of the current x: from the prologue or the previous step's last kick)
     __syncthreads();
@@ -907,8 +992,11 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// l2hmc_gauge_pack_heads image: int eligibility [N][2], int columns [N][2][D / 2], then (256-byte aligned) the sections
-static size_t heads_meta_bytes(int N, int D) { return align_up(sizeof(int) * ((size_t)2 * N + (size_t)N * D), 256); }
+// l2hmc_gauge_pack_heads image: int eligibility [N][2], int columns [N][2][D / 2], int compact first-layer k [N][D],
+// then (256-byte aligned) the heads sections and, behind them, the kept-column first-layer sections
+static size_t heads_meta_bytes(int N, int D) { return align_up(sizeof(int) * ((size_t)2 * N + (size_t)2 * N * D), 256); }
+static size_t heads_sections_bytes(int N, int D, int H) { return sizeof(float) * (size_t)2 * N * 3 * (D / 2) * H; }
+static size_t l1_sections_bytes(int N, int D, int H) { return sizeof(float) * (size_t)2 * N * (D / 2) * H; }
 // shapes with a whole-trajectory kernel: GenericNet on D=128 (H=512), and the dense trunk of ConvNet3D on the
 // 8x8 lattice (features 64+64, H=256)
 static int fused_generic_net(const l2hmc_dense_net* n) {
@@ -1130,12 +1218,17 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
   // GenericNet, both directions: the split form (FusedArgs::step_split), with the active-column heads unless the plan
   // has none or asks for all columns (L2HMC_PLAN_ALL_COLUMNS)
   const bool split = !conv && both;
+  // ... and the first layer's x product of a position sub-update on the kept columns unless L2HMC_PLAN_FULL_L1
   const int* hmeta = nullptr;
   const float* himg = nullptr;
+  const float* l1img = nullptr;
   if (split && p->heads && !(p->flags & L2HMC_PLAN_ALL_COLUMNS)) {
+    const int Dp = 2 * p->T * p->X;
     hmeta = reinterpret_cast<const int*>(p->heads);
-    himg = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p->heads) +
-                                          heads_meta_bytes(p->num_steps, 2 * p->T * p->X));
+    himg = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p->heads) + heads_meta_bytes(p->num_steps, Dp));
+    if (!(p->flags & L2HMC_PLAN_FULL_L1))
+      l1img = reinterpret_cast<const float*>(reinterpret_cast<const char*>(himg) +
+                                             heads_sections_bytes(p->num_steps, Dp, p->xnet.H));
   }
   auto launch16 = [&](FusedArgs a) {
     if (split) {
@@ -1146,6 +1239,7 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
       a.step_hand = reinterpret_cast<float*>(static_cast<char*>(hand) + hand_ticket_bytes(pairs));
       a.heads_meta = hmeta;
       a.heads_img = himg;
+      a.l1_img = l1img;
       if (hipMemsetAsync(a.step_ticket, 0, sizeof(int) * (size_t)pairs, stream) != hipSuccess) {
         set_error("fused step: cannot clear the hand-off tickets");
         return L2HMC_ERR_HIP;
@@ -1182,19 +1276,21 @@ extern "C" size_t l2hmc_gauge_pack_heads_bytes(const l2hmc_gauge_plan* plan) {
       !fused_generic_net(&plan->xnet))
     return 0;
   const int D = 128, H = plan->xnet.H;
-  return heads_meta_bytes(plan->num_steps, D) + sizeof(float) * (size_t)2 * plan->num_steps * 3 * (D / 2) * H;
+  return heads_meta_bytes(plan->num_steps, D) + heads_sections_bytes(plan->num_steps, D, H) +
+         l1_sections_bytes(plan->num_steps, D, H);
 }
 
 extern "C" int l2hmc_gauge_pack_heads(const l2hmc_gauge_plan* plan, void* buf, l2hmc_stream_t stream) {
   L2HMC_REQUIRE(plan != nullptr && buf != nullptr, "gauge_pack_heads: NULL pointer");
   L2HMC_REQUIRE(l2hmc_gauge_pack_heads_bytes(plan) > 0, "gauge_pack_heads: the plan has no active-column heads "
                 "(GenericNet D = 128, H = 512 on an 8x8-site lattice, hmc = 0)");
-  L2HMC_REQUIRE(plan->masks && plan->xnet.whd_t, "gauge_pack_heads: NULL masks or heads weights");
+  L2HMC_REQUIRE(plan->masks && plan->xnet.whd_t && plan->xnet.w1_t, "gauge_pack_heads: NULL masks or weights");
   const int N = plan->num_steps, D = 128;
   int* meta = static_cast<int*>(buf);
   float* img = reinterpret_cast<float*>(static_cast<char*>(buf) + heads_meta_bytes(N, D));
+  float* img1 = reinterpret_cast<float*>(reinterpret_cast<char*>(img) + heads_sections_bytes(N, D, plan->xnet.H));
   hipLaunchKernelGGL(pack_heads_kernel, dim3(32, (unsigned)(2 * N)), dim3(256), 0, (hipStream_t)stream, plan->xnet,
-                     plan->masks, N, meta, img);
+                     plan->masks, N, meta, img, meta + 2 * N + N * D, img1);
   L2HMC_CHECK_LAUNCH("gauge_pack_heads");
   return L2HMC_OK;
 }

@@ -495,6 +495,22 @@ int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float* x0, const 
 int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x, int64_t B, uint64_t seed, uint64_t draw0,
                         float* Lx, float* Lv, float* px, float* x_out, l2hmc_stream_t stream);
 
+/* A RUN of n_steps consecutive sampler steps of an L2HMC plan (plan->hmc == 0; hmc != 0 is refused as by
+ * l2hmc_small_propose), with the results of n_steps calls of l2hmc_small_propose(plan, x, B, seed, draw0 + 4 s, NULL,
+ * NULL, px + s B, x_out) chained through x_out, bit for bit.  Step s (0 <= s < n_steps) takes its direction bits,
+ * forward momenta, backward momenta and Metropolis-Hastings uniforms from the Philox streams (seed, draw0 + 4 s) ..
+ * (seed, draw0 + 4 s + 3) and starts from the output of step s - 1 (step 0 from x_in).  px (or NULL) is [n_steps][B]:
+ * row s holds the step's accept probabilities.  samples (or NULL) is [n_steps][B][x_dim] and receives every step's
+ * output; the final state always goes to x_next [B][x_dim], which may alias x_in.
+ * ONE launch, of the kernel and in the form l2hmc_small_propose takes for the same B: a wave keeps both directions of
+ * its eight chains in registers from step to step and stages the weights, the target, the masks and the time table
+ * once.  Waves never wait for each other, so there is no workspace, no ticket and no host synchronisation, and the call
+ * can be captured into a HIP graph.
+ * draw0 + 4 n_steps must not exceed 2^64 - 1 (an error otherwise).  n_steps <= 0 and NULL plan / x_in / x_next are
+ * errors, as is everything l2hmc_small_propose refuses; all are reported before any device call.  B == 0 is a no-op. */
+int l2hmc_small_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                    uint64_t draw0, int32_t n_steps, float* px, float* samples, l2hmc_stream_t stream);
+
 /* One training evaluation on the toy targets (mog_model.py:324-363): `rows` = 2B stacked chains (B started at
  * x, B at z ~ N(0,1); sampler.py:28-55 picks a direction per chain, passed in `dir`), each integrated in its
  * direction; per chain v = |x0 - x_N|^2 * p + 1e-4, term = scale / v - v / scale, loss = inv_count * sum of all

@@ -10,4 +10,5 @@ from .distributions import GMM, Gaussian, gen_ring, quadratic_gaussian  # noqa: 
 from .gauge_sampler import GaugeSampler  # noqa: F401
 from .gauge_trainer import GaugeTrainer  # noqa: F401
 from .dynamics_trainer import DynamicsTrainer  # noqa: F401
+from .dynamics_sampler import DynamicsSampler  # noqa: F401
 from . import stats  # noqa: F401

@@ -49,6 +49,11 @@ struct SmallTrajArgs {
   // utils/sampler.py:28-59 (mix by the direction bit, Metropolis-Hastings) in its epilogue
   int64_t prop_B; uint64_t seed, draw0;
   float* Lx; float* Lv; float* px; float* mh_out;
+  // a run of propose steps (l2hmc_small_run; n_steps > 0 selects the kernel's RUN instance, 0 is the single pass of
+  // the other entries): step s draws from streams draw0 + 4 s .. draw0 + 4 s + 3 and starts from the Metropolis-Hastings
+  // output of step s - 1; px is [n_steps][prop_B], samples (or NULL) [n_steps][prop_B][x_dim] takes every step's
+  // output, and Lx / Lv / mh_out are written by the last step
+  int32_t n_steps; float* samples;
   unsigned long long* stamps;            // diagnostic builds only (-DL2HMC_STAMPS, class 7), else NULL
 };
 
@@ -540,7 +545,10 @@ struct TargetRegs {
   }
 };
 
-template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false>
+// RUN: the propose-mode body loops over a.n_steps sampler steps (l2hmc_small_run).  The single pass is the same code
+// with the back edge compiled out, so that holding the weights across the epilogue costs the one-step entries nothing
+// (registers per instance: profiles/small_run.txt).
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false, bool RUN = false>
 __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTrajArgs a) {
   using V = MfmaNet<HP, MD, KS_, KSH_>;
   static_assert(!TW || (L1M && V::NT == 4), "the twin form is a latency form of the 64-unit instances");
@@ -585,7 +593,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   [[maybe_unused]] f32x4s* xch = reinterpret_cast<f32x4s*>(scr_all + (kSmallThreads / 64) * 16 * V::NTH * 16) +
                                  (wave >> 1) * 4 * V::NTH * 64;          // [group][2 parities][2 parts][NTH][64]
   [[maybe_unused]] int ncall = 0;
-  const bool prop = a.prop_B > 0;
+  const bool prop = RUN || a.prop_B > 0;
   const int64_t gw = TW ? (int64_t)blockIdx.x * (kSmallThreads / 128) + (wave >> 1)
                         : (int64_t)blockIdx.x * (kSmallThreads / 64) + wave;
   // trajectory mode: row r of [rows]; propose mode: chain r, direction (lane & 15) >> 3
@@ -598,18 +606,9 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   [[maybe_unused]] unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   [[maybe_unused]] const unsigned long long st_begin = ST_NOW();
 
-  float x[MD], v[MD];
+  float x[MD], v[MD], x_init[MD];
 #pragma unroll
-  for (int d = 0; d < MD; ++d) {
-    x[d] = (d < dim && live) ? a.x0[r * dim + d] : 0.f;
-    if (prop)      // streams draw0 + 1 (forward momenta) and draw0 + 2 (backward), element chain * dim + d
-      v[d] = (d < dim && live) ? philox_normal_at(a.seed, a.draw0 + 1 + bwd, r * dim + d) : 0.f;
-    else
-      v[d] = (d < dim && live) ? a.v0[r * dim + d] : 0.f;
-  }
-  float x_init[MD];
-#pragma unroll
-  for (int d = 0; d < MD; ++d) x_init[d] = x[d];
+  for (int d = 0; d < MD; ++d) x[d] = (d < dim && live) ? a.x0[r * dim + d] : 0.f;
   TargetRegs<MD> tregs;
   const bool treg = TargetRegs<MD>::kFits && K <= TargetRegs<MD>::KM;       // uniform
   if (treg) tregs.load(Lt, dim, K);
@@ -623,90 +622,115 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
 #endif
     ST_ADD(4, tt);
   };
-  float g[MD], E0, E1;
-  target(x, &E0, g);
-  float kin0 = 0.f;
-#pragma unroll
-  for (int d = 0; d < MD; ++d) kin0 += v[d] * v[d];
-  const float H0 = E0 + 0.5f * kin0;
-
-  float logdet = 0.f;
+  float g[MD], E0, E1, H0, H1, logdet;
   float S[MD], T[MD], Q[MD], bin[MD];
 #pragma unroll
   for (int d = 0; d < MD; ++d) S[d] = T[d] = Q[d] = 0.f;
-  for (int it = 0; it < N; ++it) {
-    const int step = bwd ? N - 1 - it : it;       // utils/dynamics.py:294-296
-    const float tc = Lts[2 * step], ts = Lts[2 * step + 1];
-    const float* m = Lm + step * dim;
-    for (int half = 0; half < 2; ++half) {
-      if (half == 1) {
-        for (int sub = 0; sub < 2; ++sub) {       // keep mask m then 1 - m (fwd) / 1 - m then m (bwd)
-          const bool keep_is_m = (sub == 0) != (bwd != 0);
+  // The RUN instance walks a.n_steps sampler steps (l2hmc_small_run) with everything above -- weights, target, masks,
+  // time table -- staged once and the chains' state in registers from step to step; waves never meet (the twin form's
+  // two waves hold the same state and take the same steps).  The other entries leave after the first pass.  Every
+  // lane, those of rows beyond the batch included, walks the whole loop: all of them take part in the matrix
+  // instructions and the lane permutes, and only the stores are predicated.
+  float* const samples = RUN ? a.samples : nullptr;
+  for (int sidx = 0;; ++sidx) {
+    const uint64_t draw = a.draw0 + 4 * (uint64_t)sidx;
+    if (prop) {
+      // streams draw + 1 (forward momenta) and draw + 2 (backward), element chain * dim + d.  The four lanes of a row
+      // share the work: lane q draws components q and q + 4, and every lane fetches the others' by lane permute
+      float pv[(MD + 3) / 4];
 #pragma unroll
-          for (int d = 0; d < MD; ++d) {
-            const float k = d < dim ? (keep_is_m ? m[d] : 1.f - m[d]) : 1.f;
-            bin[d] = k * x[d];
-          }
-          if (!P.hmc) {
-            if constexpr (TW) net_eval_twin<HP, MD, KS_, KSH_>(Wx, dim, P.xnet.q_tanh, v, bin, tc, ts, lane, part, xch, ncall++ & 1, S, T, Q);
-            else net_eval_mfma<HP, MD, KS_, KSH_, L1M>(Lx, Wx, dim, P.xnet.q_tanh, v, bin, tc, ts, lane, S, T, Q, st);
-          }
-          [[maybe_unused]] const unsigned long long tu = ST_NOW();
+      for (int j = 0; j < (MD + 3) / 4; ++j) {
+        const int d = 4 * j + (lane >> 4);
+        pv[j] = (d < dim && live) ? philox_normal_at(a.seed, draw + 1 + bwd, r * dim + d) : 0.f;
+      }
 #pragma unroll
-          for (int d = 0; d < MD; ++d) {
-            if (d < dim) {
-              const float k = keep_is_m ? m[d] : 1.f - m[d];
-              const float s = (bwd ? -eps : eps) * S[d];
-              const float drift = eps * (fast_exp(eps * Q[d]) * v[d] + T[d]);
-              const float es_ = fast_exp(s);
-              const float upd = bwd ? es_ * (x[d] - drift) : x[d] * es_ + drift;
-              x[d] = k * x[d] + (1.f - k) * upd;
-              logdet += (1.f - k) * s;
-            }
-          }
-#ifdef L2HMC_STAMPS
-          asm volatile("" :: "v"(x[0]), "v"(logdet));
-#endif
-          ST_ADD(5, tu);
-        }
-        target(x, nullptr, g);         // (the energy itself is needed only after the last step: below)
-      }
-      if (!P.hmc) {
-        if constexpr (TW) net_eval_twin<HP, MD, KS_, KSH_>(Wv, dim, P.vnet.q_tanh, x, g, tc, ts, lane, part, xch, ncall++ & 1, S, T, Q);
-        else net_eval_mfma<HP, MD, KS_, KSH_, L1M>(Lv, Wv, dim, P.vnet.q_tanh, x, g, tc, ts, lane, S, T, Q, st);
-      }
-      [[maybe_unused]] const unsigned long long tu2 = ST_NOW();
+      for (int d = 0; d < MD; ++d)
+        v[d] = __int_as_float(__builtin_amdgcn_ds_bpermute((16 * (d & 3) + (lane & 15)) << 2, __float_as_int(pv[d >> 2])));
+    } else {
 #pragma unroll
-      for (int d = 0; d < MD; ++d) {
-        if (d < dim) {
-          const float s = (bwd ? -0.5f : 0.5f) * eps * S[d];
-          const float kick = 0.5f * eps * (fast_exp(eps * Q[d]) * g[d] - T[d]);
-          const float es_ = fast_exp(s);
-          v[d] = bwd ? es_ * (v[d] + kick) : v[d] * es_ - kick;
-          logdet += s;
-        }
-      }
-#ifdef L2HMC_STAMPS
-      asm volatile("" :: "v"(v[0]), "v"(logdet));
-#endif
-      ST_ADD(5, tu2);
+      for (int d = 0; d < MD; ++d) v[d] = (d < dim && live) ? a.v0[r * dim + d] : 0.f;
     }
-  }
-#ifdef L2HMC_STAMPS
-  if (a.stamps && lane == 0 && part == 0) {
-    st[6] = ST_NOW() - st_begin;
-    for (int i = 0; i < 8; ++i) a.stamps[gw * 8 + i] = st[i];
-  }
-#endif
-  if (TW && part) return;             // both waves of a group hold the same state: the first one finishes (no barrier follows)
-  target(x, &E1, g);
-  float kin1 = 0.f;
 #pragma unroll
-  for (int d = 0; d < MD; ++d) kin1 += v[d] * v[d];
-  const float H1 = E1 + 0.5f * kin1;
-  if (prop) {
-    // the backward half (lanes 8..15) hands its result to the forward half through the wave's LDS patch; lanes
-    // 0..7 then mix and accept exactly as l2hmc_mix_accept(strict = 0) does
+    for (int d = 0; d < MD; ++d) x_init[d] = x[d];
+    target(x, &E0, g);
+    float kin0 = 0.f;
+#pragma unroll
+    for (int d = 0; d < MD; ++d) kin0 += v[d] * v[d];
+    H0 = E0 + 0.5f * kin0;
+    logdet = 0.f;
+    for (int it = 0; it < N; ++it) {
+      const int step = bwd ? N - 1 - it : it;       // utils/dynamics.py:294-296
+      const float tc = Lts[2 * step], ts = Lts[2 * step + 1];
+      const float* m = Lm + step * dim;
+      for (int half = 0; half < 2; ++half) {
+        if (half == 1) {
+          for (int sub = 0; sub < 2; ++sub) {       // keep mask m then 1 - m (fwd) / 1 - m then m (bwd)
+            const bool keep_is_m = (sub == 0) != (bwd != 0);
+#pragma unroll
+            for (int d = 0; d < MD; ++d) {
+              const float k = d < dim ? (keep_is_m ? m[d] : 1.f - m[d]) : 1.f;
+              bin[d] = k * x[d];
+            }
+            if (!P.hmc) {
+              if constexpr (TW) net_eval_twin<HP, MD, KS_, KSH_>(Wx, dim, P.xnet.q_tanh, v, bin, tc, ts, lane, part, xch, ncall++ & 1, S, T, Q);
+              else net_eval_mfma<HP, MD, KS_, KSH_, L1M>(Lx, Wx, dim, P.xnet.q_tanh, v, bin, tc, ts, lane, S, T, Q, st);
+            }
+            [[maybe_unused]] const unsigned long long tu = ST_NOW();
+#pragma unroll
+            for (int d = 0; d < MD; ++d) {
+              if (d < dim) {
+                const float k = keep_is_m ? m[d] : 1.f - m[d];
+                const float s = (bwd ? -eps : eps) * S[d];
+                const float drift = eps * (fast_exp(eps * Q[d]) * v[d] + T[d]);
+                const float es_ = fast_exp(s);
+                const float upd = bwd ? es_ * (x[d] - drift) : x[d] * es_ + drift;
+                x[d] = k * x[d] + (1.f - k) * upd;
+                logdet += (1.f - k) * s;
+              }
+            }
+#ifdef L2HMC_STAMPS
+            asm volatile("" :: "v"(x[0]), "v"(logdet));
+#endif
+            ST_ADD(5, tu);
+          }
+          target(x, nullptr, g);         // (the energy itself is needed only after the last step: below)
+        }
+        if (!P.hmc) {
+          if constexpr (TW) net_eval_twin<HP, MD, KS_, KSH_>(Wv, dim, P.vnet.q_tanh, x, g, tc, ts, lane, part, xch, ncall++ & 1, S, T, Q);
+          else net_eval_mfma<HP, MD, KS_, KSH_, L1M>(Lv, Wv, dim, P.vnet.q_tanh, x, g, tc, ts, lane, S, T, Q, st);
+        }
+        [[maybe_unused]] const unsigned long long tu2 = ST_NOW();
+#pragma unroll
+        for (int d = 0; d < MD; ++d) {
+          if (d < dim) {
+            const float s = (bwd ? -0.5f : 0.5f) * eps * S[d];
+            const float kick = 0.5f * eps * (fast_exp(eps * Q[d]) * g[d] - T[d]);
+            const float es_ = fast_exp(s);
+            v[d] = bwd ? es_ * (v[d] + kick) : v[d] * es_ - kick;
+            logdet += s;
+          }
+        }
+#ifdef L2HMC_STAMPS
+        asm volatile("" :: "v"(v[0]), "v"(logdet));
+#endif
+        ST_ADD(5, tu2);
+      }
+    }
+#ifdef L2HMC_STAMPS
+    if (a.stamps && lane == 0 && part == 0) {        // (totals so far: a run leaves those of all its steps)
+      st[6] = ST_NOW() - st_begin;
+      for (int i = 0; i < 8; ++i) a.stamps[gw * 8 + i] = st[i];
+    }
+#endif
+    target(x, &E1, g);
+    float kin1 = 0.f;
+#pragma unroll
+    for (int d = 0; d < MD; ++d) kin1 += v[d] * v[d];
+    H1 = E1 + 0.5f * kin1;
+    if (!prop) break;
+    // the backward half (lanes 8..15) hands its result to the forward half through the wave's LDS patch; the forward
+    // lanes then mix and accept exactly as l2hmc_mix_accept(strict = 0) does.  (All lanes do the arithmetic; lanes
+    // 0..7 of a group's first wave hold the chains' results and store them.)
     const float pacc = accept_from_delta(H0 - H1 + logdet);
     float* slot = scr + (lane & 7) * (2 * MD + 1);
     if (lane >= 8 && lane < 16) {
@@ -720,23 +744,39 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (!live || lane >= 8) return;
-    const bool fwd = philox_uniform_at(a.seed, a.draw0, r) >= 0.5f;          // sampler.py:33 randint {0, 1}
+    const bool last = !RUN || sidx + 1 == a.n_steps;                          // uniform
+    const bool writer = live && lane < 8 && !(TW && part);
+    const bool fwd = philox_uniform_at(a.seed, draw, r) >= 0.5f;              // sampler.py:33 randint {0, 1}
     const float fm = fwd ? 1.f : 0.f, bm = 1.f - fm;
     const float pm = fm * pacc + bm * slot[2 * MD];
-    const bool acc = a.mh_out ? (pm - philox_uniform_at(a.seed, a.draw0 + 3, r) >= 0.f) : false;   // :57-59
-    if (a.px) a.px[r] = pm;
+    const bool want_mh = a.mh_out || samples || !last;
+    const bool acc = want_mh ? (pm - philox_uniform_at(a.seed, draw + 3, r) >= 0.f) : false;   // :57-59
+    if (writer && a.px) a.px[(int64_t)sidx * a.prop_B + r] = pm;
+    float xn[MD];
 #pragma unroll
     for (int d = 0; d < MD; ++d) {
-      if (d < dim) {
-        const float xp = fm * x[d] + bm * slot[d];
-        if (a.Lx) a.Lx[r * dim + d] = xp;
-        if (a.Lv) a.Lv[r * dim + d] = fm * v[d] + bm * slot[MD + d];
-        if (a.mh_out) a.mh_out[r * dim + d] = acc ? xp : x_init[d];
+      const float xp = fm * x[d] + bm * slot[d];
+      xn[d] = acc ? xp : x_init[d];
+      if (writer && d < dim) {
+        if (samples) samples[((int64_t)sidx * a.prop_B + r) * dim + d] = xn[d];
+        if (last) {
+          if (a.Lx) a.Lx[r * dim + d] = xp;
+          if (a.Lv) a.Lv[r * dim + d] = fm * v[d] + bm * slot[MD + d];
+          if (a.mh_out) a.mh_out[r * dim + d] = xn[d];
+        }
       }
     }
-    return;
+    if (last) return;
+    // the accepted state of chain c, in lane c, becomes the start of every lane with (lane & 7) == c: both direction
+    // halves and the four lanes of each row.  The patch is free again once every lane has read it.
+#pragma unroll
+    for (int d = 0; d < MD; ++d)
+      x[d] = __int_as_float(__builtin_amdgcn_ds_bpermute((lane & 7) << 2, __float_as_int(xn[d])));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
+  if (TW && part) return;             // both waves of a group hold the same state: the first one finishes (no barrier follows)
   if (!live || lane >= 16) return;                 // the four lanes of a chain hold the same result
 #pragma unroll
   for (int d = 0; d < MD; ++d) {
@@ -757,14 +797,14 @@ static size_t small_mfma_lds(int dim, int K, int N) {
                           (size_t)(kSmallThreads / 128) * 4 * MfmaNet<HP, MD, KS_, KSH_>::NTH * 64 * 4);   // twin exchange patches
 }
 
-template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false>
-static int launch_small_mfma_form(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN>
+static int launch_small_mfma_kernel(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
   const l2hmc_small_plan& P = a.plan;
   const size_t lds = small_mfma_lds<HP, MD, KS_, KSH_>(P.x_dim, P.target.K, P.trajectory_length);
   L2HMC_REQUIRE(lds <= 160 * 1024, "small_trajectory: LDS image %zu B too large", lds);
   static DeviceOnce attr_once;   // dynamic LDS beyond 64 KiB needs the opt-in (host-side, not a stream op)
   if (attr_once.pending()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_once.done();
   }
@@ -772,13 +812,20 @@ static int launch_small_mfma_form(const SmallTrajArgs& a, dim3 grid, hipStream_t
 #ifdef L2HMC_STAMPS
   SmallTrajArgs b = a;
   b.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW>), grid, dim3(kSmallThreads), lds, st, b);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN>), grid, dim3(kSmallThreads), lds, st, b);
 #else
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW>), grid, dim3(kSmallThreads), lds, st, a);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN>), grid, dim3(kSmallThreads), lds, st, a);
 #endif
   prof_after(kProfSmall, st);
   L2HMC_CHECK_LAUNCH("small_trajectory");
   return L2HMC_OK;
+}
+
+// (a run, a.n_steps > 0, takes the RUN instance of the same form)
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false>
+static int launch_small_mfma_form(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
+  return a.n_steps > 0 ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true>(a, grid, st)
+                       : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false>(a, grid, st);
 }
 
 // Three forms, chosen by the number of 16-row groups (l2hmc_small_plan::first_layer_form forces one; they walk sums in
@@ -843,6 +890,26 @@ extern "C" int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x,
   SmallTrajArgs a{};
   a.plan = *plan; a.x0 = x; a.rows = 2 * B;
   a.prop_B = B; a.seed = seed; a.draw0 = draw0; a.Lx = Lx; a.Lv = Lv; a.px = px; a.mh_out = x_out;
+  return small_launch(plan, a, stream);
+}
+
+extern "C" int l2hmc_small_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                               uint64_t seed, uint64_t draw0, int32_t n_steps, float* px, float* samples,
+                               l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(plan != nullptr, "small_run: plan is NULL");
+  L2HMC_REQUIRE(x_in != nullptr && x_next != nullptr, "small_run: x_in / x_next is NULL");
+  L2HMC_REQUIRE(B >= 0, "small_run: B < 0");
+  L2HMC_REQUIRE(n_steps > 0, "small_run: n_steps=%d must be positive", n_steps);
+  L2HMC_REQUIRE(!plan->hmc, "small_run: the hmc sampler proposes with the forward trajectory only "
+                            "(utils/sampler.py:30-32): use l2hmc_small_trajectory + l2hmc_mix_accept");
+  L2HMC_REQUIRE(4 * (uint64_t)n_steps <= UINT64_MAX - draw0,
+                "small_run: draw0 + 4 * n_steps overflows 64 bits (draw0=%llu, n_steps=%d)",
+                (unsigned long long)draw0, n_steps);
+  if (B == 0) return L2HMC_OK;
+  SmallTrajArgs a{};
+  a.plan = *plan; a.x0 = x_in; a.rows = 2 * B;
+  a.prop_B = B; a.seed = seed; a.draw0 = draw0; a.px = px; a.mh_out = x_next;
+  a.n_steps = n_steps; a.samples = samples;
   return small_launch(plan, a, stream);
 }
 

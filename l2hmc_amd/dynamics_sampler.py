@@ -1,0 +1,128 @@
+"""Device-resident sampling loop for the toy-target `Dynamics`: what l2hmc/mog_model.py:394-421
+(`GaussianMixtureModel.generate_trajectories`) does with one `sess.run` per MCMC step -- chains started from the target's
+own samples, positions and accept probabilities of every step kept -- and the tunnelling-rate / autocorrelation
+evaluation of the paper is made of.
+
+An L2HMC dynamics the one-launch kernel holds (packed target, x_dim <= 8, at most 64 hidden units) hands
+`steps_per_launch` steps at a time to l2hmc_small_run: ONE launch per chunk, the chains in registers from step to step,
+the weights, target, masks and time table staged once.  The values are those of the loop over
+`propose(x, dynamics, do_mh_step=True)`, bit for bit, and that loop is what every other dynamics (`hmc`, `layered`) and
+`steps_per_launch = 1` run."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .sampler import propose
+
+
+class DynamicsSampler:
+    def __init__(self, dynamics, distribution=None, batch_size=None):
+        """`distribution`: anything with `get_samples(n)` (l2hmc_amd.distributions), the start of
+        `generate_trajectories`.  `batch_size`: the number of chains `run` starts when no `x` is given."""
+        self.dynamics = dynamics
+        self.distribution = distribution
+        self.batch_size = batch_size
+        # MCMC steps per launch of l2hmc_small_run (1 = one launch per step through `propose`, the cross-check)
+        self.steps_per_launch = 256
+
+    def _one_launch(self):
+        dyn = self.dynamics
+        return int(self.steps_per_launch) > 1 and not dyn.hmc and not dyn.layered
+
+    def run(self, run_steps, x=None, keep_samples=True):
+        """`run_steps` MCMC steps (utils/sampler.py:28-59 with the Metropolis-Hastings step) from `x` [B, x_dim], or
+        from N(0, 1) samples for `batch_size` chains.  Returns {"px": [steps, B] accept probabilities, "samples":
+        [steps, B, x_dim] with samples[s] the OUTPUT of step s (if kept), "samples_out": the final state on the
+        device, "mean_accept": the mean of this run's px (NaN for an empty run)}.  The caller's `x` is not advanced in
+        place.  The draws come from the dynamics' own counter (`_draws`, 4 streams per L2HMC step) and the temperature
+        is the dynamics' (`use_temperature` / `temperature`)."""
+        dyn = self.dynamics
+        run_steps = int(run_steps)
+        if run_steps < 0:
+            raise ValueError(f"run_steps={run_steps} must not be negative")
+        if x is None:
+            if self.batch_size is None:
+                raise ValueError("run: pass the start `x`, or give the sampler a batch_size to start from N(0, 1)")
+            x = np.random.randn(int(self.batch_size), dyn.x_dim)
+        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        B, D = x.shape
+        if run_steps == 0:
+            out = {"px": np.empty((0, B), dtype=np.float32), "samples_out": x.clone()}
+            if keep_samples:
+                out["samples"] = np.empty((0, B, D), dtype=np.float32)
+        elif self._one_launch():
+            out = self._run_launches(run_steps, x, keep_samples)
+        else:
+            out = self._run_loop(run_steps, x, keep_samples)
+        px = out["px"]
+        out["mean_accept"] = float(px.mean(dtype=np.float64)) if px.size else float("nan")
+        return out
+
+    def _run_loop(self, run_steps, x, keep_samples):
+        """One `propose` per step: any dynamics."""
+        dyn = self.dynamics
+        px_hist, samples = [], []
+        for _ in range(run_steps):
+            _, _, px, (x,) = propose(x, dyn, do_mh_step=True)
+            px_hist.append(px)
+            if keep_samples:
+                samples.append(x)
+        out = {"px": torch.stack(px_hist).cpu().numpy(), "samples_out": x}
+        if keep_samples:
+            out["samples"] = torch.stack(samples).cpu().numpy()
+        return out
+
+    def _run_launches(self, run_steps, x, keep_samples):
+        """Chunks of at most `steps_per_launch` steps through l2hmc_small_run, ONE launch each.  The same draws (four
+        consecutive streams per step from the dynamics' counter), accept probabilities and samples as `_run_loop`, bit
+        for bit.  With `keep_samples` the device buffer of the samples is one chunk long and is copied to the host
+        chunk by chunk."""
+        dyn = self.dynamics
+        B, D, dev = x.shape[0], x.shape[1], x.device
+        plan, L = dyn._plan(), _lib.lib()
+        chunk = min(int(self.steps_per_launch), run_steps)
+        px = torch.empty(run_steps, B, dtype=torch.float32, device=dev)
+        samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
+        samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
+        x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
+        x_in = _lib.dev_ptr(x, name="x")
+        for s0 in range(0, run_steps, chunk):
+            n = min(chunk, run_steps - s0)
+            _lib.check(L.l2hmc_small_run(
+                C.byref(plan), x_in, x_next.data_ptr(), B, dyn._seed, dyn._draws, n, px[s0:].data_ptr(),
+                samples_dev.data_ptr() if keep_samples else None, _lib.stream_ptr(dyn._device)))
+            dyn._draws += 4 * n                            # the counter moves with the completed steps
+            x_in = x_next.data_ptr()                       # later chunks advance the state in place
+            if keep_samples:
+                samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
+        out = {"px": px.cpu().numpy(), "samples_out": x_next}
+        if keep_samples:
+            out["samples"] = samples
+        return out
+
+    def generate_trajectories(self, temp=1., num_samples=500, num_steps=100, x=None):
+        """mog_model.py:394-421 -> (trajectories [num_steps, num_samples, x_dim], px [num_steps, num_samples]).  As in
+        the reference trajectories[s] is the INPUT of step s (:410), so trajectories[0] is the start: `x`, or
+        `num_samples` samples of the sampler's distribution (:399).  `temp` is set on `dynamics.temperature` for the
+        run and restored afterwards; it takes effect on a dynamics built with use_temperature=True, which is how the
+        reference builds its own (:385-387).  The reference's third return value, the training loss of every step, is
+        the trainer's business (DynamicsTrainer) and is not produced here.  `num_steps=None`: the trajectory length
+        (:396-398)."""
+        dyn = self.dynamics
+        if num_steps is None:
+            num_steps = int(dyn.trajectory_length)
+        if x is None:
+            if self.distribution is None:
+                raise ValueError("generate_trajectories: pass the start `x`, or give the sampler a distribution")
+            x = self.distribution.get_samples(int(num_samples))
+        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        saved = dyn.temperature
+        dyn.temperature = temp
+        try:
+            out = self.run(num_steps, x, keep_samples=True)
+        finally:
+            dyn.temperature = saved
+        start = x.cpu().numpy()[None]
+        return np.concatenate([start, out["samples"]])[:int(num_steps)], out["px"]

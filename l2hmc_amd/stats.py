@@ -2,6 +2,7 @@
   l2hmc/utils/func_utils.py:45-54   autocovariance (uncentred, normalised by the number of chains)
   l2hmc/utils/func_utils.py:114-116 acl_spectrum
   l2hmc/utils/func_utils.py:118-120 ESS
+  l2hmc/utils/trajectories.py:47-95  tunnelling rate among the modes of a mixture
 BASELINE.json's secondary metric (ESS/sec) is reported with these estimators."""
 import numpy as np
 
@@ -53,6 +54,23 @@ def ESS(A):
     A = np.asarray(A, dtype=np.float64)
     A = A * (A > 0.05)
     return 1. / (1. + 2 * np.sum(A[1:]))
+
+
+def calc_tunneling_rate(trajectories, means):
+    """l2hmc/utils/trajectories.py:47-95.  A point belongs to the mean it is nearest to (Euclidean distance, the first
+    of equally near ones, :39-60); a tunnelling event is a change of membership between consecutive steps, and the rate
+    is the number of events divided by steps - 1 (:83-95).  `trajectories` [steps, dim] gives a float, [steps, chains,
+    dim] one rate per chain (the loop of mog_model.py:423-429 at once); `means` is [modes, dim].  The reference's
+    third argument is the number of rows of `means`."""
+    X = np.asarray(trajectories, dtype=np.float64)
+    M = np.asarray(means, dtype=np.float64)
+    if X.ndim not in (2, 3) or M.ndim != 2 or X.shape[-1] != M.shape[1]:
+        raise ValueError(f"trajectories {X.shape} must be [steps, dim] or [steps, chains, dim] with the dim of means {M.shape}")
+    if X.shape[0] < 2:
+        raise ValueError("a tunnelling rate needs at least two steps")
+    member = np.argmin(np.sqrt(((X[..., None, :] - M) ** 2).sum(axis=-1)), axis=-1)       # [steps(, chains)]
+    rate = (member[1:] != member[:-1]).sum(axis=0) / (X.shape[0] - 1)
+    return float(rate) if X.ndim == 2 else rate
 
 
 # ---------------------------------------------------------------------------------------------

@@ -444,25 +444,50 @@ int l2hmc_adam_step(float* w, const float* g, float* m, float* v, int64_t n, flo
 /* ------------------------------------------------------------------------
  * Generic integrator on 2-D toy targets (MoG / SCG):
  *   utils/dynamics.py:120-225,255-319; utils/sampler.py:28-59;
- *   utils/distributions.py:32-39,63-68,151-158.
- * Target: mixture of K Gaussians (K=1, log_const ignored => plain Gaussian).
- *   energy(x) = -logsumexp_k( -0.5 (x-mu_k)^T P_k (x-mu_k) + log_const[k] ) / temperature
+ *   utils/distributions.py:32-39,63-68,151-158 (mixture, Gaussian), :101-121 (rough well), :184-211 (funnel).
+ * Target kinds (l2hmc_mog_target::is_gaussian holds the kind; 0 and 1 mean what they always did):
+ *   L2HMC_TARGET_MIXTURE     mixture of K Gaussians:
+ *       energy(x) = -logsumexp_k( -0.5 (x-mu_k)^T P_k (x-mu_k) + log_const[k] )
+ *   L2HMC_TARGET_GAUSSIAN    K = 1, log_const ignored: energy(x) = 0.5 (x-mu)^T P (x-mu)
+ *   L2HMC_TARGET_ROUGH_WELL  energy(x) = 0.5 sum_i x_i^2 + eps sum_i cos(x_i / a), a = eps^2, or a = eps when `easy`;
+ *       x_i / a is a division by the fp32 product eps * eps (the reference's operation order)
+ *   L2HMC_TARGET_FUNNEL      v = x_0, n = dim - 1, s = exp(v):
+ *       energy(x) = 0.5 (v^2 / 4 + sum_{i>=1} x_i^2 / s + n log(2 pi s)),
+ *       with s the constant exp(8) where v > 8 and exp(-8) where v < -8 (strict comparisons: v = +-8 is unclipped);
+ *       gradient and Hessian follow the selected branch, as tf.gradients of tf.where does.  sigma = 2 and the clip
+ *       4 sigma = 8 are the reference's constants (its constructor ignores its `clip` argument).  dim >= 2.
+ * Every kind's energy, gradient and Hessian are divided by `temperature`.
+ * The two analytic kinds take no device memory: K = 1, prec and log_const are ignored (may be NULL), and the rough
+ * well's two scalars travel by value in the slot of `mu` (same size and offset: the layout and L2HMC_ABI_VERSION are
+ * unchanged).  An unknown kind, a funnel with dim < 2 and a rough well with eps <= 0 (or not finite) are refused with
+ * L2HMC_ERR_ARG before any launch by every entry that takes a target or a plan.
  * ------------------------------------------------------------------------ */
 /* Limits of this path (utils/network.py:89-114 takes any x_dim / num_nodes; the reference's own configurations are
- * 2-D targets with num_nodes 10 (SCGExperiment.ipynb) and 50 (mog_model.py, network.py:89)): x_dim <= 8 with at most
- * 8 mixture components (the closed-form energy, its gradient and Hessian-vector product live in registers), and
- * num_nodes <= 64 (both networks' weights stay in LDS for the whole trajectory).  Larger values are refused with
- * L2HMC_ERR_ARG; wider toy networks belong on the MFMA path above. */
+ * 2-D targets with num_nodes 10 (SCGExperiment.ipynb) and 50 (mog_model.py, network.py:89)): x_dim <= 8 for every
+ * target kind, with at most 8 mixture components (the closed-form energy, its gradient and Hessian-vector product
+ * live in registers; the rough well and the funnel have no parameter arrays at all), and num_nodes <= 64 (both
+ * networks' weights stay in LDS for the whole trajectory).  Larger values are refused with L2HMC_ERR_ARG; wider toy
+ * networks, higher dimensions and any other energy belong on the layer-by-layer path above. */
 #define L2HMC_MAX_MIX 8
 #define L2HMC_MAX_SMALL_DIM 8
+#define L2HMC_TARGET_MIXTURE 0
+#define L2HMC_TARGET_GAUSSIAN 1
+#define L2HMC_TARGET_ROUGH_WELL 2
+#define L2HMC_TARGET_FUNNEL 3
 typedef struct l2hmc_mog_target {
   int32_t dim;                     /* <= L2HMC_MAX_SMALL_DIM */
-  int32_t K;                       /* <= L2HMC_MAX_MIX */
-  int32_t is_gaussian;             /* 1: energy = 0.5 (x-mu)^T P (x-mu) (distributions.py:63-68) */
+  int32_t K;                       /* <= L2HMC_MAX_MIX; 1 for every kind but the mixture */
+  int32_t is_gaussian;             /* the kind: one of L2HMC_TARGET_* (1: energy = 0.5 (x-mu)^T P (x-mu)) */
   float temperature;
-  const float* mu;                 /* [K][dim] */
-  const float* prec;               /* [K][dim][dim] inverse covariances */
-  const float* log_const;          /* [K] log(pi_k / sqrt((2pi)^dim det Sigma_k)) */
+  union {
+    const float* mu;               /* mixture, Gaussian: [K][dim] */
+    struct {
+      float eps;                   /* rough well: > 0 */
+      int32_t easy;                /* rough well: 0: a = eps^2; otherwise a = eps */
+    } rough_well;
+  };
+  const float* prec;               /* mixture, Gaussian: [K][dim][dim] inverse covariances */
+  const float* log_const;          /* mixture: [K] log(pi_k / sqrt((2pi)^dim det Sigma_k)) */
 } l2hmc_mog_target;
 
 typedef struct l2hmc_small_plan {

@@ -6,7 +6,8 @@ from .network import ConvNet3D, GenericNet, MLPNet, network  # noqa: F401
 from .gauge_dynamics import GaugeDynamics  # noqa: F401
 from .dynamics import Dynamics  # noqa: F401
 from .sampler import propose, tf_accept  # noqa: F401
-from .distributions import GMM, Gaussian, gen_ring, quadratic_gaussian  # noqa: F401
+from .distributions import (GMM, Gaussian, GaussianFunnel, RoughWell, TiltedGaussian, gen_ring,  # noqa: F401
+                            quadratic_gaussian, random_tilted_gaussian)
 from .gauge_sampler import GaugeSampler  # noqa: F401
 from .gauge_trainer import GaugeTrainer  # noqa: F401
 from .dynamics_trainer import DynamicsTrainer  # noqa: F401

@@ -51,9 +51,21 @@ class GaugePlan(C.Structure):
                 ("heads", C.c_void_p)]
 
 
+TARGET_MIXTURE, TARGET_GAUSSIAN, TARGET_ROUGH_WELL, TARGET_FUNNEL = 0, 1, 2, 3     # l2hmc_mog_target::is_gaussian
+
+
+class RoughWellParams(C.Structure):
+    _fields_ = [("eps", C.c_float), ("easy", C.c_int32)]
+
+
+class _MuSlot(C.Union):      # the rough well's scalars travel by value in the slot of `mu`
+    _fields_ = [("mu", c_float_p), ("rough_well", RoughWellParams)]
+
+
 class MogTarget(C.Structure):
+    _anonymous_ = ("_slot",)
     _fields_ = [("dim", C.c_int32), ("K", C.c_int32), ("is_gaussian", C.c_int32),
-                ("temperature", C.c_float), ("mu", c_float_p), ("prec", c_float_p),
+                ("temperature", C.c_float), ("_slot", _MuSlot), ("prec", c_float_p),
                 ("log_const", c_float_p)]
 
 

@@ -44,7 +44,7 @@ def check_differentiable(dyn):
     if dyn.layered:
         raise NotImplementedError("autograd through Dynamics: this Dynamics runs layer by layer (arbitrary energy "
                                   "function, x_dim > 8 or more than 64 hidden units); only the one-launch toy targets "
-                                  "(l2hmc_amd.GMM / Gaussian, x_dim <= 8, num_nodes <= 64) are differentiable")
+                                  "(l2hmc_amd.GMM / Gaussian / RoughWell / GaussianFunnel, x_dim <= 8, num_nodes <= 64) are differentiable")
     for name, net in _nets(dyn):
         if getattr(net, "_flat", None) is not None:
             raise ValueError(f"autograd through Dynamics: a DynamicsTrainer owns the weights of {name} (flat master "

@@ -140,11 +140,119 @@ __host__ __device__ inline TargetView target_view(int dim, int K) {
   return t;
 }
 
+// The target's kind and the scalars of the analytic kinds (wave-uniform: they come from the kernel's arguments).
+struct TargetKind {
+  int kind;            // L2HMC_TARGET_*
+  float eps, a;        // rough well: a = eps * eps, or eps when `easy` (distributions.py:110-116)
+};
+__host__ __device__ inline TargetKind target_kind(const l2hmc_mog_target& t) {
+  TargetKind k;
+  k.kind = t.is_gaussian;
+  k.eps = k.a = 1.f;
+  if (t.is_gaussian == L2HMC_TARGET_ROUGH_WELL) {
+    k.eps = t.rough_well.eps;
+    k.a = t.rough_well.easy ? k.eps : k.eps * k.eps;
+  }
+  return k;
+}
+__host__ __device__ inline bool target_is_analytic(int kind) { return kind >= L2HMC_TARGET_ROUGH_WELL; }
+
+// The funnel's constants (distributions.py:185-188: sigma = 2, clip = 4 sigma whatever the constructor is given)
+constexpr float kFunnelInvVar = 0.25f, kFunnelClip = 8.f;
+constexpr float kFunnelSMax = 2980.9579870417283f, kFunnelSMin = 3.3546262790251185e-4f;   // exp(+-clip)
+constexpr float kLog2Pi = 1.8378770664093453f;
+
+// s = exp(v) of the funnel, or the constant of the clipped branch (tf.where on tf.greater: v == +-clip is unclipped);
+// *inv_s = 1 / s, *log_s = log(s), *clipped tells which
+__device__ __forceinline__ void funnel_scale(float v, float* inv_s, float* log_s, bool* clipped) {
+  const bool hi = v > kFunnelClip, lo = -kFunnelClip > v;
+  *clipped = hi || lo;
+  *log_s = hi ? kFunnelClip : lo ? -kFunnelClip : v;
+  *inv_s = hi ? kFunnelSMin : lo ? kFunnelSMax : expf(-v);
+}
+
+// Rough well (distributions.py:101-121) and Gaussian funnel (:184-211), gradient in closed form.  E == nullptr:
+// gradient only (the rough well then needs no cosine, the funnel no logarithm term).
+template <int MD>
+__device__ __forceinline__ void analytic_energy_grad(const TargetKind& tk, int dim, float inv_temp, const float* x,
+                                                     float* E, float* g) {
+  if (tk.kind == L2HMC_TARGET_ROUGH_WELL) {
+    const float c1 = tk.eps / tk.a;
+    float n = 0.f, sc = 0.f;
+#pragma unroll
+    for (int i = 0; i < MD; ++i) {
+      g[i] = 0.f;
+      if (i < dim) {
+        const float t = x[i] / tk.a;
+        g[i] = (x[i] - c1 * sinf(t)) * inv_temp;
+        if (E) {
+          n += x[i] * x[i];
+          sc += cosf(t);
+        }
+      }
+    }
+    if (E) *E = (0.5f * n + tk.eps * sc) * inv_temp;
+  } else {
+    float inv_s, log_s, ss = 0.f;
+    bool clipped;
+    funnel_scale(x[0], &inv_s, &log_s, &clipped);
+    const float nn = (float)(dim - 1);
+#pragma unroll
+    for (int i = 1; i < MD; ++i) {
+      g[i] = 0.f;
+      if (i < dim) {
+        ss += x[i] * x[i];
+        g[i] = x[i] * inv_s * inv_temp;
+      }
+    }
+    const float q = ss * inv_s;
+    g[0] = (x[0] * kFunnelInvVar + (clipped ? 0.f : 0.5f * (nn - q))) * inv_temp;
+    if (E) *E = 0.5f * (x[0] * x[0] * kFunnelInvVar + q + nn * (kLog2Pi + log_s)) * inv_temp;
+  }
+}
+
+// Hessian(energy)(x) . u of the two analytic kinds: diagonal for the rough well; for the funnel the arrow matrix of
+// the selected branch (clipped: diagonal)
+template <int MD>
+__device__ __forceinline__ void analytic_hvp(const TargetKind& tk, int dim, float inv_temp, const float* x,
+                                             const float* u, float* out) {
+  if (tk.kind == L2HMC_TARGET_ROUGH_WELL) {
+    const float c2 = tk.eps / (tk.a * tk.a);
+#pragma unroll
+    for (int i = 0; i < MD; ++i) out[i] = i < dim ? (1.f - c2 * cosf(x[i] / tk.a)) * u[i] * inv_temp : 0.f;
+  } else {
+    float inv_s, log_s, ss = 0.f, xu = 0.f;
+    bool clipped;
+    funnel_scale(x[0], &inv_s, &log_s, &clipped);
+    (void)log_s;
+#pragma unroll
+    for (int i = 1; i < MD; ++i) {
+      out[i] = 0.f;
+      if (i < dim) {
+        ss += x[i] * x[i];
+        xu += x[i] * u[i];
+        out[i] = (u[i] - (clipped ? 0.f : x[i] * u[0])) * inv_s * inv_temp;
+      }
+    }
+    const float h00 = kFunnelInvVar + (clipped ? 0.f : 0.5f * ss * inv_s);
+    out[0] = (h00 * u[0] - (clipped ? 0.f : xu * inv_s)) * inv_temp;
+  }
+}
+
 // distributions.py:151-158 (GMM), :63-68 (Gaussian); gradient in closed form.  All loops over the dimension run
 // to the compile-time bound MD with a guard, so x / g stay in registers (no dynamically indexed arrays).
-template <int MD = L2HMC_MAX_SMALL_DIM>
-__device__ inline void energy_grad(const float* Lt, int dim, int K, int is_gaussian, float inv_temp, const float* x,
+// AN: the instance of the analytic kinds (rough well, funnel).  A compile-time flag, not a branch on the kind: sinf /
+// cosf carry their large-argument reduction (16 bytes of scratch and about ten registers), which as a run-time branch
+// cost four of the mixture's kernel instances a wave per SIMD (profiles/analytic_targets.txt); the AN = false
+// instances are the code they were.
+template <int MD = L2HMC_MAX_SMALL_DIM, bool AN = false>
+__device__ inline void energy_grad(const float* Lt, int dim, int K, const TargetKind& tk, float inv_temp, const float* x,
                                    float* E, float* g) {
+  if constexpr (AN) {
+    analytic_energy_grad<MD>(tk, dim, inv_temp, x, E, g);
+    return;
+  }
+  const int is_gaussian = tk.kind;
   const TargetView tv = target_view(dim, K);
   float V[kMaxMix];
   float vmax = -INFINITY;
@@ -196,12 +304,36 @@ __device__ inline void energy_grad(const float* Lt, int dim, int K, int is_gauss
   for (int d = 0; d < MD; ++d) g[d] = g[d] / sw * inv_temp;
 }
 
+// (the analytic kinds have no parameter arrays: nothing is staged, and mu / prec / log_const are not pointers to read)
 __device__ inline void load_target(const l2hmc_mog_target& t, float* Lt) {
+  if (target_is_analytic(t.is_gaussian)) return;
   const TargetView tv = target_view(t.dim, t.K);
   for (int i = threadIdx.x; i < t.K * t.dim; i += blockDim.x) Lt[tv.mu + i] = t.mu[i];
   for (int i = threadIdx.x; i < t.K * t.dim * t.dim; i += blockDim.x) Lt[tv.prec + i] = t.prec[i];
   for (int i = threadIdx.x; i < t.K; i += blockDim.x) Lt[tv.logc + i] = t.is_gaussian ? 0.f : t.log_const[i];
 }
 
+// What every entry that takes a target checks before any launch.
+inline int check_target_args(const l2hmc_mog_target* t, const char* who) {
+  L2HMC_REQUIRE(t != nullptr, "%s: target is NULL", who);
+  L2HMC_REQUIRE(t->dim > 0 && t->dim <= kMaxDim && t->K > 0 && t->K <= kMaxMix,
+                "%s: target dim=%d (max %d), K=%d (max %d)", who, t->dim, kMaxDim, t->K, kMaxMix);
+  const int kind = t->is_gaussian;
+  L2HMC_REQUIRE(kind >= L2HMC_TARGET_MIXTURE && kind <= L2HMC_TARGET_FUNNEL,
+                "%s: target kind %d unknown (0 mixture, 1 gaussian, 2 rough well, 3 funnel)", who, kind);
+  L2HMC_REQUIRE(t->temperature > 0.f, "%s: target temperature must be > 0", who);
+  if (kind == L2HMC_TARGET_ROUGH_WELL) {
+    L2HMC_REQUIRE(t->K == 1, "%s: rough-well target needs K == 1", who);
+    L2HMC_REQUIRE(t->rough_well.eps > 0.f && t->rough_well.eps <= 3.0e38f,
+                  "%s: rough-well target needs a finite eps > 0 (eps=%g)", who, (double)t->rough_well.eps);
+  } else if (kind == L2HMC_TARGET_FUNNEL) {
+    L2HMC_REQUIRE(t->K == 1, "%s: funnel target needs K == 1", who);
+    L2HMC_REQUIRE(t->dim >= 2, "%s: funnel target needs dim >= 2 (dim=%d)", who, t->dim);
+  } else {
+    L2HMC_REQUIRE(t->mu && t->prec && (kind == L2HMC_TARGET_GAUSSIAN || t->log_const), "%s: target has a NULL parameter pointer", who);
+    L2HMC_REQUIRE(kind != L2HMC_TARGET_GAUSSIAN || t->K == 1, "%s: gaussian target needs K == 1", who);
+  }
+  return L2HMC_OK;
+}
 
 }  // namespace l2hmc

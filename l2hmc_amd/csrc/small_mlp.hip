@@ -18,6 +18,7 @@
 
 namespace l2hmc {
 
+template <bool AN>
 __global__ __launch_bounds__(kSmallThreads) void mog_energy_grad_kernel(l2hmc_mog_target t,
                                                                         const float* __restrict__ x,
                                                                         int64_t rows,
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(kSmallThreads) void mog_energy_grad_kernel(l2hmc_mo
   float xv[kMaxDim], g[kMaxDim], E;
 #pragma unroll
   for (int d = 0; d < kMaxDim; ++d) xv[d] = d < t.dim ? x[r * t.dim + d] : 0.f;
-  energy_grad(lds, t.dim, t.K, t.is_gaussian, 1.f / t.temperature, xv, &E, g);
+  energy_grad<kMaxDim, AN>(lds, t.dim, t.K, target_kind(t), 1.f / t.temperature, xv, &E, g);
   if (energy) energy[r] = E;
   if (grad) {
 #pragma unroll
@@ -548,7 +549,8 @@ struct TargetRegs {
 // RUN: the propose-mode body loops over a.n_steps sampler steps (l2hmc_small_run).  The single pass is the same code
 // with the back edge compiled out, so that holding the weights across the epilogue costs the one-step entries nothing
 // (registers per instance: profiles/small_run.txt).
-template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false, bool RUN = false>
+// AN: the instance of the analytic target kinds (small_mlp.h: energy_grad).
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false, bool RUN = false, bool AN = false>
 __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTrajArgs a) {
   using V = MfmaNet<HP, MD, KS_, KSH_>;
   static_assert(!TW || (L1M && V::NT == 4), "the twin form is a latency form of the 64-unit instances");
@@ -602,7 +604,8 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   const int bwd = prop ? ((lane >> 3) & 1) : ((a.dir && live) ? a.dir[r] : 0);
   const float eps = P.eps;
   const float inv_temp = 1.f / P.target.temperature;
-  const int isg = P.target.is_gaussian, K = P.target.K;
+  const TargetKind tk = target_kind(P.target);
+  const int K = P.target.K;
   [[maybe_unused]] unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   [[maybe_unused]] const unsigned long long st_begin = ST_NOW();
 
@@ -611,12 +614,14 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   for (int d = 0; d < MD; ++d) x[d] = (d < dim && live) ? a.x0[r * dim + d] : 0.f;
   TargetRegs<MD> tregs;
   const bool treg = TargetRegs<MD>::kFits && K <= TargetRegs<MD>::KM;       // uniform
-  if (treg) tregs.load(Lt, dim, K);
+  if (treg && !AN) tregs.load(Lt, dim, K);
   auto target = [&](const float (&xx)[MD], float* E, float (&gg)[MD]) {
     [[maybe_unused]] const unsigned long long tt = ST_NOW();
     float dummy;
-    if (treg) tregs.eval(dim, K, isg, inv_temp, xx, E, gg);
-    else energy_grad<MD>(Lt, dim, K, isg, inv_temp, xx, E ? E : &dummy, gg);
+    // rough well / funnel: no parameter arrays, the scalars are kernel arguments -- register-resident at any MD
+    if constexpr (AN) analytic_energy_grad<MD>(tk, dim, inv_temp, xx, E, gg);
+    else if (treg) tregs.eval(dim, K, tk.kind, inv_temp, xx, E, gg);
+    else energy_grad<MD>(Lt, dim, K, tk, inv_temp, xx, E ? E : &dummy, gg);
 #ifdef L2HMC_STAMPS
     asm volatile("" :: "v"(gg[0]));
 #endif
@@ -797,14 +802,14 @@ static size_t small_mfma_lds(int dim, int K, int N) {
                           (size_t)(kSmallThreads / 128) * 4 * MfmaNet<HP, MD, KS_, KSH_>::NTH * 64 * 4);   // twin exchange patches
 }
 
-template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN>
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN, bool AN>
 static int launch_small_mfma_kernel(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
   const l2hmc_small_plan& P = a.plan;
   const size_t lds = small_mfma_lds<HP, MD, KS_, KSH_>(P.x_dim, P.target.K, P.trajectory_length);
   L2HMC_REQUIRE(lds <= 160 * 1024, "small_trajectory: LDS image %zu B too large", lds);
   static DeviceOnce attr_once;   // dynamic LDS beyond 64 KiB needs the opt-in (host-side, not a stream op)
   if (attr_once.pending()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_once.done();
   }
@@ -812,20 +817,23 @@ static int launch_small_mfma_kernel(const SmallTrajArgs& a, dim3 grid, hipStream
 #ifdef L2HMC_STAMPS
   SmallTrajArgs b = a;
   b.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN>), grid, dim3(kSmallThreads), lds, st, b);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN>), grid, dim3(kSmallThreads), lds, st, b);
 #else
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN>), grid, dim3(kSmallThreads), lds, st, a);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN>), grid, dim3(kSmallThreads), lds, st, a);
 #endif
   prof_after(kProfSmall, st);
   L2HMC_CHECK_LAUNCH("small_trajectory");
   return L2HMC_OK;
 }
 
-// (a run, a.n_steps > 0, takes the RUN instance of the same form)
+// (a run, a.n_steps > 0, takes the RUN instance of the same form; a rough well or a funnel the AN instance)
 template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false>
 static int launch_small_mfma_form(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
-  return a.n_steps > 0 ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true>(a, grid, st)
-                       : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false>(a, grid, st);
+  if (target_is_analytic(a.plan.target.is_gaussian))
+    return a.n_steps > 0 ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, true>(a, grid, st)
+                         : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false, true>(a, grid, st);
+  return a.n_steps > 0 ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, false>(a, grid, st)
+                       : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false, false>(a, grid, st);
 }
 
 // Three forms, chosen by the number of 16-row groups (l2hmc_small_plan::first_layer_form forces one; they walk sums in
@@ -849,15 +857,7 @@ static int launch_small_mfma(const SmallTrajArgs& a, dim3 grid, hipStream_t st) 
              : launch_small_mfma_form<HP, MD, KS_, KSH_, false>(a, grid, st);
 }
 
-static int check_target(const l2hmc_mog_target* t) {
-  L2HMC_REQUIRE(t != nullptr, "target is NULL");
-  L2HMC_REQUIRE(t->dim > 0 && t->dim <= kMaxDim && t->K > 0 && t->K <= kMaxMix,
-                "target: dim=%d (max %d), K=%d (max %d)", t->dim, kMaxDim, t->K, kMaxMix);
-  L2HMC_REQUIRE(t->mu && t->prec && (t->is_gaussian || t->log_const), "target: NULL parameter pointer");
-  L2HMC_REQUIRE(!t->is_gaussian || t->K == 1, "target: gaussian needs K == 1");
-  L2HMC_REQUIRE(t->temperature > 0.f, "target: temperature must be > 0");
-  return L2HMC_OK;
-}
+static int check_target(const l2hmc_mog_target* t) { return check_target_args(t, "target"); }
 
 }  // namespace l2hmc
 
@@ -870,8 +870,13 @@ extern "C" int l2hmc_mog_energy_grad(const l2hmc_mog_target* tgt, const float* x
   if (rows == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x != nullptr, "mog_energy_grad: x is NULL");
   const size_t lds = sizeof(float) * target_view(tgt->dim, tgt->K).size;
-  hipLaunchKernelGGL(mog_energy_grad_kernel, dim3((unsigned)ceil_div(rows, kSmallThreads)), dim3(kSmallThreads),
-                     lds, (hipStream_t)stream, *tgt, x, rows, energy, grad);
+  const dim3 grid((unsigned)ceil_div(rows, kSmallThreads));
+  if (target_is_analytic(tgt->is_gaussian))
+    hipLaunchKernelGGL(mog_energy_grad_kernel<true>, grid, dim3(kSmallThreads), lds, (hipStream_t)stream, *tgt, x, rows,
+                       energy, grad);
+  else
+    hipLaunchKernelGGL(mog_energy_grad_kernel<false>, grid, dim3(kSmallThreads), lds, (hipStream_t)stream, *tgt, x, rows,
+                       energy, grad);
   L2HMC_CHECK_LAUNCH("mog_energy_grad");
   return L2HMC_OK;
 }

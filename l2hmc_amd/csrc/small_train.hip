@@ -270,9 +270,14 @@ __device__ void net_eval_keep(const float* L, int dim, int q_tanh, const float* 
 // Hessian(energy)(x) . u for the mixture / Gaussian target (second derivative of distributions.py:151-158):
 //   H = sum_k r_k P_k - sum_k r_k g_k g_k^T + gbar gbar^T,   g_k = P_k (x - mu_k), r = softmax(V), gbar = sum r_k g_k
 // with P_k the symmetrised precision; everything divided by the temperature.
-template <int MD>
-__device__ inline void energy_hvp(const float* Lt, int dim, int K, int is_gaussian, float inv_temp, const float* x,
+template <int MD, bool AN = false>
+__device__ inline void energy_hvp(const float* Lt, int dim, int K, const TargetKind& tk, float inv_temp, const float* x,
                                   const float* u, float* out) {
+  if constexpr (AN) {
+    analytic_hvp<MD>(tk, dim, inv_temp, x, u, out);
+    return;
+  }
+  const int is_gaussian = tk.kind;
   constexpr int kMaxDim = MD;
   const TargetView tv = target_view(dim, K);
   float V[kMaxMix];
@@ -341,6 +346,7 @@ __device__ inline void energy_hvp(const float* Lt, int dim, int K, int is_gaussi
 }
 
 // l2hmc_mog_energy_hvp: one thread per row, the target in LDS (as mog_energy_grad_kernel)
+template <bool AN>
 __global__ __launch_bounds__(kSmallThreads) void mog_energy_hvp_kernel(l2hmc_mog_target t, const float* __restrict__ x,
                                                                        const float* __restrict__ u, int64_t rows,
                                                                        float* __restrict__ out) {
@@ -355,7 +361,7 @@ __global__ __launch_bounds__(kSmallThreads) void mog_energy_hvp_kernel(l2hmc_mog
     xv[d] = d < t.dim ? x[r * t.dim + d] : 0.f;
     uv[d] = d < t.dim ? u[r * t.dim + d] : 0.f;
   }
-  energy_hvp<kMaxDim>(lds, t.dim, t.K, t.is_gaussian, 1.f / t.temperature, xv, uv, hv);
+  energy_hvp<kMaxDim, AN>(lds, t.dim, t.K, target_kind(t), 1.f / t.temperature, xv, uv, hv);
 #pragma unroll
   for (int d = 0; d < kMaxDim; ++d)
     if (d < t.dim) out[r * t.dim + d] = hv[d];
@@ -391,7 +397,8 @@ struct SmallTrainArgs {
 // VJP = false: the reverse pass is seeded by the squared-jump-distance loss (l2hmc_small_train_step);
 // VJP = true: by the caller's cotangents of (x_N, v_N, sumlogdet, p) (l2hmc_small_vjp), and the gradient with
 // respect to the start state is written out.  Everything else is the same code.
-template <int HP, int MD, int TH, bool VJP>
+// AN: the instance of the analytic target kinds (small_mlp.h: energy_grad).
+template <int HP, int MD, int TH, bool VJP, bool AN>
 __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   constexpr int kSlots = TH / kLPC, kSmallThreads = TH, SS = kSlots + 4;
   // diagnostic cycle shares (class 7): 0 prologue, 1 forward, 2 loss, 3 net re-evaluation, 4 sub-update + head deltas,
@@ -438,7 +445,8 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   const int bwd = (a.dir && live) ? a.dir[r] : 0;
   const float eps = P.eps;
   const float inv_temp = 1.f / P.target.temperature;
-  const int isg = P.target.is_gaussian, K = P.target.K;
+  const TargetKind tk = target_kind(P.target);
+  const int K = P.target.K;
   const int n0 = lsub * UPL;
 
   float x[kMaxDim], v[kMaxDim], xs[kMaxDim];
@@ -449,7 +457,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
     xs[d] = x[d];
   }
   float g[kMaxDim], E0, E1;
-  energy_grad<MD>(Lt, dim, K, isg, inv_temp, x, &E0, g);
+  energy_grad<MD, AN>(Lt, dim, K, tk, inv_temp, x, &E0, g);
   float kin0 = 0.f;
 #pragma unroll
   for (int d = 0; d < kMaxDim; ++d) kin0 += v[d] * v[d];
@@ -493,7 +501,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
             }
           }
         }
-        energy_grad<MD>(Lt, dim, K, isg, inv_temp, x, &E1, g);
+        energy_grad<MD, AN>(Lt, dim, K, tk, inv_temp, x, &E1, g);
       }
       float* tp = mytape + (size_t)(it * 4 + (half ? 3 : 0)) * 3 * dim;
       if (lsub == 0) {
@@ -517,7 +525,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       }
     }
   }
-  energy_grad<MD>(Lt, dim, K, isg, inv_temp, x, &E1, g);
+  energy_grad<MD, AN>(Lt, dim, K, tk, inv_temp, x, &E1, g);
   float kin1 = 0.f;
 #pragma unroll
   for (int d = 0; d < kMaxDim; ++d) kin1 += v[d] * v[d];
@@ -757,7 +765,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       float u[kMaxDim], hv[kMaxDim];
 #pragma unroll
       for (int d = 0; d < kMaxDim; ++d) u[d] = dgd[d] + db[d];
-      energy_hvp<MD>(Lt, dim, K, isg, inv_temp, ain, u, hv);
+      energy_hvp<MD, AN>(Lt, dim, K, tk, inv_temp, ain, u, hv);
 #pragma unroll
       for (int d = 0; d < kMaxDim; ++d) dx[d] += da[d] + hv[d];
     } else {
@@ -774,7 +782,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       float x0r[kMaxDim], g0[kMaxDim], e0;
 #pragma unroll
       for (int d = 0; d < kMaxDim; ++d) x0r[d] = d < dim ? a.x0[r * dim + d] : 0.f;
-      energy_grad<MD>(Lt, dim, K, isg, inv_temp, x0r, &e0, g0);
+      energy_grad<MD, AN>(Lt, dim, K, tk, inv_temp, x0r, &e0, g0);
 #pragma unroll
       for (int d = 0; d < kMaxDim; ++d)
         if (d < dim) {
@@ -840,11 +848,8 @@ static int small_train_check(const l2hmc_small_plan* plan, int64_t rows, const c
   L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
   L2HMC_REQUIRE(!plan->hmc, "%s: hmc plans have no trainable networks", who);
   const int dim = plan->x_dim, H = plan->num_nodes, N = plan->trajectory_length;
-  L2HMC_REQUIRE(plan->target.dim == dim && dim > 0 && dim <= kMaxDim && plan->target.K > 0 && plan->target.K <= kMaxMix,
-                "%s: bad target / x_dim", who);
-  L2HMC_REQUIRE(plan->target.mu && plan->target.prec && (plan->target.is_gaussian || plan->target.log_const) &&
-                    plan->target.temperature > 0.f,
-                "%s: bad target parameters", who);
+  L2HMC_REQUIRE(plan->target.dim == dim, "%s: x_dim=%d != target dim=%d", who, dim, plan->target.dim);
+  if (int rc = check_target_args(&plan->target, who)) return rc;
   L2HMC_REQUIRE(N > 0 && plan->masks != nullptr && H > 0 && H <= 64, "%s: bad plan (num_nodes 1..64)", who);
   L2HMC_REQUIRE(rows >= 0, "%s: bad rows", who);
   return L2HMC_OK;
@@ -876,13 +881,14 @@ static int small_train_launch(const l2hmc_small_plan* plan, SmallTrainArgs a, fl
   int nwg = 0;
   // (TH = 512 -- 32 chains, two waves per SIMD, one round of workgroups for 8192 chains -- was measured: 1.59 ms per
   //  step against 1.46 for two rounds of 16-chain workgroups: the kernel is bound by LDS throughput, not latency)
-  auto run = [&](auto hp, auto md) -> int {
+  auto run_kind = [&](auto hp, auto md, auto an) -> int {
     constexpr int HPc = decltype(hp)::value, MDc = decltype(md)::value;
+    constexpr bool AN = decltype(an)::value;
     const size_t lds = small_train_lds<HPc, MDc, 256>(dim, plan->target.K, N);
     L2HMC_REQUIRE(lds <= 160 * 1024, "%s: LDS image %zu B too large (trajectory too long?)", who, lds);
     static DeviceOnce attr_once;
     if (attr_once.pending()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_train_kernel<HPc, MDc, 256, VJP>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_train_kernel<HPc, MDc, 256, VJP, AN>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr_once.done();
     }
@@ -890,8 +896,12 @@ static int small_train_launch(const l2hmc_small_plan* plan, SmallTrainArgs a, fl
     a.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
 #endif
     nwg = (int)ceil_div(rows, 256 / kLPC);
-    hipLaunchKernelGGL((small_train_kernel<HPc, MDc, 256, VJP>), dim3(nwg), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((small_train_kernel<HPc, MDc, 256, VJP, AN>), dim3(nwg), dim3(256), lds, s, a);
     return L2HMC_OK;
+  };
+  auto run = [&](auto hp, auto md) -> int {
+    return target_is_analytic(plan->target.is_gaussian) ? run_kind(hp, md, std::true_type{})
+                                                        : run_kind(hp, md, std::false_type{});
   };
   using I16 = std::integral_constant<int, 16>;
   using I64 = std::integral_constant<int, 64>;
@@ -940,18 +950,18 @@ extern "C" int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, co
 
 extern "C" int l2hmc_mog_energy_hvp(const l2hmc_mog_target* tgt, const float* x, const float* u, int64_t rows,
                                     float* out, l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(tgt != nullptr, "mog_energy_hvp: target is NULL");
-  L2HMC_REQUIRE(tgt->dim > 0 && tgt->dim <= kMaxDim && tgt->K > 0 && tgt->K <= kMaxMix,
-                "mog_energy_hvp: target dim=%d (max %d), K=%d (max %d)", tgt->dim, kMaxDim, tgt->K, kMaxMix);
-  L2HMC_REQUIRE(tgt->mu && tgt->prec && (tgt->is_gaussian || tgt->log_const), "mog_energy_hvp: NULL target parameter");
-  L2HMC_REQUIRE(!tgt->is_gaussian || tgt->K == 1, "mog_energy_hvp: gaussian needs K == 1");
-  L2HMC_REQUIRE(tgt->temperature > 0.f, "mog_energy_hvp: temperature must be > 0");
+  if (int rc = check_target_args(tgt, "mog_energy_hvp")) return rc;
   L2HMC_REQUIRE(rows >= 0, "mog_energy_hvp: rows = %lld < 0", (long long)rows);
   if (rows == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x && u && out, "mog_energy_hvp: NULL pointer");
   const size_t lds = sizeof(float) * target_view(tgt->dim, tgt->K).size;
-  hipLaunchKernelGGL(mog_energy_hvp_kernel, dim3((unsigned)ceil_div(rows, kSmallThreads)), dim3(kSmallThreads), lds,
-                     (hipStream_t)stream, *tgt, x, u, rows, out);
+  const dim3 grid((unsigned)ceil_div(rows, kSmallThreads));
+  if (target_is_analytic(tgt->is_gaussian))
+    hipLaunchKernelGGL(mog_energy_hvp_kernel<true>, grid, dim3(kSmallThreads), lds, (hipStream_t)stream, *tgt, x, u, rows,
+                       out);
+  else
+    hipLaunchKernelGGL(mog_energy_hvp_kernel<false>, grid, dim3(kSmallThreads), lds, (hipStream_t)stream, *tgt, x, u, rows,
+                       out);
   L2HMC_CHECK_LAUNCH("mog_energy_hvp");
   return L2HMC_OK;
 }

@@ -2,7 +2,7 @@
 
 Two paths behind it, chosen per instance (`Dynamics.layered`):
   * one launch per trajectory (l2hmc_small_trajectory / l2hmc_small_propose): the packed toy targets of
-    l2hmc_amd.distributions (GMM / Gaussian, x_dim <= 8, <= 8 components) with `network`-style nets of at most 64
+    l2hmc_amd.distributions (GMM / Gaussian / RoughWell / GaussianFunnel, x_dim <= 8, <= 8 components) with `network`-style nets of at most 64
     hidden units -- BASELINE configs 1 and 2;
   * layer by layer, for everything else the reference's constructor accepts (:35-43: ANY `energy_function`, any x_dim,
     `net_factory` of any `num_nodes`): per sub-update of utils/dynamics.py:120-225 one S/T/Q evaluation through

@@ -536,6 +536,28 @@ int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x, int64_t B,
 int l2hmc_small_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B, uint64_t seed,
                     uint64_t draw0, int32_t n_steps, float* px, float* samples, l2hmc_stream_t stream);
 
+/* l2hmc_small_run with a temperature per step, per chain, or both: an annealed burn-in or a ladder of temperatures in
+ * ONE launch.  The contract of l2hmc_small_run in every respect (the draws (seed, draw0 + 4 s .. + 3), px, samples,
+ * x_next that may alias x_in, one launch, no workspace, graph capture, B == 0 a no-op) but one: step s of chain c runs
+ * at temperature temps[s * step_stride + c * chain_stride], both of its directions and both ends of its Hamiltonian
+ * difference alike.  temps is a DEVICE pointer; a stride may be 0:
+ *   (step_stride, chain_stride) = (1, 0)  a schedule, temps [n_steps]
+ *                                 (0, 1)  a ladder, temps [B]
+ *                                 (B, 1)  both, temps [n_steps][B]
+ * plan->target.temperature is not used (it must still be > 0, as everywhere).  The kernel forms 1 / t as the other
+ * entries form 1 / temperature, so a run whose entries all equal T gives the bits of l2hmc_small_run on a plan with
+ * temperature = T.
+ * Refused with L2HMC_ERR_ARG before any device call: everything l2hmc_small_run refuses, NULL temps, a negative stride.
+ * The VALUES are on the device and are not checked.  An entry of 0 or NaN gives its chain a non-finite energy and
+ * gradient in that step, which by the rule of every entry here is an accept probability of 0 -- the chain stays where
+ * it is.  A negative entry is not refused either and is no temperature (finite energies of the wrong sign: the step
+ * targets exp(+E / |t|)), and +infinity is the flat target.  Callers that cannot vouch for their temperatures check
+ * them first: finite and > 0 (DynamicsSampler.run does). */
+int l2hmc_small_run_tempered(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                             uint64_t seed, uint64_t draw0, int32_t n_steps,
+                             const float* temps, int64_t step_stride, int64_t chain_stride,
+                             float* px, float* samples, l2hmc_stream_t stream);
+
 /* One training evaluation on the toy targets (mog_model.py:324-363): `rows` = 2B stacked chains (B started at
  * x, B at z ~ N(0,1); sampler.py:28-55 picks a direction per chain, passed in `dir`), each integrated in its
  * direction; per chain v = |x0 - x_N|^2 * p + 1e-4, term = scale / v - v / scale, loss = inv_count * sum of all

@@ -55,7 +55,10 @@ struct SmallTrajArgs {
   // output of step s - 1; px is [n_steps][prop_B], samples (or NULL) [n_steps][prop_B][x_dim] takes every step's
   // output, and Lx / Lv / mh_out are written by the last step
   int32_t n_steps; float* samples;
-  unsigned long long* stamps;            // diagnostic builds only (-DL2HMC_STAMPS, class 7), else NULL
+  // a tempered run (l2hmc_small_run_tempered; non-NULL selects the kernel's TEMPERED instance): step s of chain c runs
+  // at temperature temps[s * temp_step_stride + c * temp_chain_stride] instead of plan.target.temperature
+  const float* temps; int64_t temp_step_stride, temp_chain_stride;
+  unsigned long long* stamps;           // diagnostic builds only (-DL2HMC_STAMPS, class 7), else NULL
 };
 
 // Per-phase cycle counters of a wave (diagnostic build only): 0 first layer (VALU), 1 hidden layer (MFMA), 2 heads
@@ -550,9 +553,14 @@ struct TargetRegs {
 // with the back edge compiled out, so that holding the weights across the epilogue costs the one-step entries nothing
 // (registers per instance: profiles/small_run.txt).
 // AN: the instance of the analytic target kinds (small_mlp.h: energy_grad).
-template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false, bool RUN = false, bool AN = false>
+// TEMPERED (a RUN instance, l2hmc_small_run_tempered): every step reloads the chain's temperature from a.temps, where
+// the other instances hold plan.target.temperature for the launch.  A template flag as RUN is, and for its reason: the
+// untempered instances keep their code (registers per instance: profiles/small_run_tempered.txt).
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false, bool RUN = false, bool AN = false,
+          bool TEMPERED = false>
 __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTrajArgs a) {
   using V = MfmaNet<HP, MD, KS_, KSH_>;
+  static_assert(!TEMPERED || RUN, "a temperature per step is a run's");
   static_assert(!TW || (L1M && V::NT == 4), "the twin form is a latency form of the 64-unit instances");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const l2hmc_small_plan& P = a.plan;
@@ -603,7 +611,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   const bool live = r < (prop ? a.prop_B : a.rows);
   const int bwd = prop ? ((lane >> 3) & 1) : ((a.dir && live) ? a.dir[r] : 0);
   const float eps = P.eps;
-  const float inv_temp = 1.f / P.target.temperature;
+  float inv_temp = TEMPERED ? 1.f : 1.f / P.target.temperature;      // (TEMPERED: set at the head of every step)
   const TargetKind tk = target_kind(P.target);
   const int K = P.target.K;
   [[maybe_unused]] unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -639,6 +647,11 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   float* const samples = RUN ? a.samples : nullptr;
   for (int sidx = 0;; ++sidx) {
     const uint64_t draw = a.draw0 + 4 * (uint64_t)sidx;
+    // the step's temperature: one value per chain, the same in both direction halves, in the four lanes of a row and
+    // in the twin form's second wave (all of them index by r), and the same from E0 to E1 -- the step's Hamiltonian
+    // difference is taken at one temperature.  The same division as above, so equal temperatures give equal bits.
+    if constexpr (TEMPERED)
+      inv_temp = 1.f / (live ? a.temps[(int64_t)sidx * a.temp_step_stride + r * a.temp_chain_stride] : 1.f);
     if (prop) {
       // streams draw + 1 (forward momenta) and draw + 2 (backward), element chain * dim + d.  The four lanes of a row
       // share the work: lane q draws components q and q + 4, and every lane fetches the others' by lane permute
@@ -802,14 +815,14 @@ static size_t small_mfma_lds(int dim, int K, int N) {
                           (size_t)(kSmallThreads / 128) * 4 * MfmaNet<HP, MD, KS_, KSH_>::NTH * 64 * 4);   // twin exchange patches
 }
 
-template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN, bool AN>
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN, bool AN, bool TEMPERED = false>
 static int launch_small_mfma_kernel(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
   const l2hmc_small_plan& P = a.plan;
   const size_t lds = small_mfma_lds<HP, MD, KS_, KSH_>(P.x_dim, P.target.K, P.trajectory_length);
   L2HMC_REQUIRE(lds <= 160 * 1024, "small_trajectory: LDS image %zu B too large", lds);
   static DeviceOnce attr_once;   // dynamic LDS beyond 64 KiB needs the opt-in (host-side, not a stream op)
   if (attr_once.pending()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_once.done();
   }
@@ -817,18 +830,23 @@ static int launch_small_mfma_kernel(const SmallTrajArgs& a, dim3 grid, hipStream
 #ifdef L2HMC_STAMPS
   SmallTrajArgs b = a;
   b.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN>), grid, dim3(kSmallThreads), lds, st, b);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED>), grid, dim3(kSmallThreads), lds, st, b);
 #else
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN>), grid, dim3(kSmallThreads), lds, st, a);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED>), grid, dim3(kSmallThreads), lds, st, a);
 #endif
   prof_after(kProfSmall, st);
   L2HMC_CHECK_LAUNCH("small_trajectory");
   return L2HMC_OK;
 }
 
-// (a run, a.n_steps > 0, takes the RUN instance of the same form; a rough well or a funnel the AN instance)
+// (a run, a.n_steps > 0, takes the RUN instance of the same form, a tempered one its TEMPERED instance; a rough well
+// or a funnel the AN instance)
 template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false>
 static int launch_small_mfma_form(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
+  if (a.temps)
+    return target_is_analytic(a.plan.target.is_gaussian)
+               ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, true, true>(a, grid, st)
+               : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, false, true>(a, grid, st);
   if (target_is_analytic(a.plan.target.is_gaussian))
     return a.n_steps > 0 ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, true>(a, grid, st)
                          : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false, true>(a, grid, st);
@@ -882,6 +900,9 @@ extern "C" int l2hmc_mog_energy_grad(const l2hmc_mog_target* tgt, const float* x
 }
 
 static int small_launch(const l2hmc_small_plan* plan, SmallTrajArgs a, l2hmc_stream_t stream);
+static int small_run_entry(const char* who, const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                           uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride,
+                           int64_t chain_stride, bool tempered, float* px, float* samples, l2hmc_stream_t stream);
 
 extern "C" int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x, int64_t B, uint64_t seed,
                                    uint64_t draw0, float* Lx, float* Lv, float* px, float* x_out,
@@ -901,20 +922,43 @@ extern "C" int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x,
 extern "C" int l2hmc_small_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
                                uint64_t seed, uint64_t draw0, int32_t n_steps, float* px, float* samples,
                                l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(plan != nullptr, "small_run: plan is NULL");
-  L2HMC_REQUIRE(x_in != nullptr && x_next != nullptr, "small_run: x_in / x_next is NULL");
-  L2HMC_REQUIRE(B >= 0, "small_run: B < 0");
-  L2HMC_REQUIRE(n_steps > 0, "small_run: n_steps=%d must be positive", n_steps);
-  L2HMC_REQUIRE(!plan->hmc, "small_run: the hmc sampler proposes with the forward trajectory only "
-                            "(utils/sampler.py:30-32): use l2hmc_small_trajectory + l2hmc_mix_accept");
+  return small_run_entry("small_run", plan, x_in, x_next, B, seed, draw0, n_steps, nullptr, 0, 0, false, px, samples,
+                         stream);
+}
+
+extern "C" int l2hmc_small_run_tempered(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                                        uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps,
+                                        int64_t step_stride, int64_t chain_stride, float* px, float* samples,
+                                        l2hmc_stream_t stream) {
+  return small_run_entry("small_run_tempered", plan, x_in, x_next, B, seed, draw0, n_steps, temps, step_stride,
+                         chain_stride, true, px, samples, stream);
+}
+
+// The two run entries: one set of checks, all of them before any device call.  (The temperatures themselves live on the
+// device and are not looked at here.)
+static int small_run_entry(const char* who, const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                           uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride,
+                           int64_t chain_stride, bool tempered, float* px, float* samples, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  L2HMC_REQUIRE(x_in != nullptr && x_next != nullptr, "%s: x_in / x_next is NULL", who);
+  L2HMC_REQUIRE(B >= 0, "%s: B < 0", who);
+  L2HMC_REQUIRE(n_steps > 0, "%s: n_steps=%d must be positive", who, n_steps);
+  L2HMC_REQUIRE(!plan->hmc, "%s: the hmc sampler proposes with the forward trajectory only "
+                            "(utils/sampler.py:30-32): use l2hmc_small_trajectory + l2hmc_mix_accept", who);
   L2HMC_REQUIRE(4 * (uint64_t)n_steps <= UINT64_MAX - draw0,
-                "small_run: draw0 + 4 * n_steps overflows 64 bits (draw0=%llu, n_steps=%d)",
+                "%s: draw0 + 4 * n_steps overflows 64 bits (draw0=%llu, n_steps=%d)", who,
                 (unsigned long long)draw0, n_steps);
+  if (tempered) {
+    L2HMC_REQUIRE(temps != nullptr, "%s: temps is NULL", who);
+    L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0, "%s: negative stride (step_stride=%lld, chain_stride=%lld)",
+                  who, (long long)step_stride, (long long)chain_stride);
+  }
   if (B == 0) return L2HMC_OK;
   SmallTrajArgs a{};
   a.plan = *plan; a.x0 = x_in; a.rows = 2 * B;
   a.prop_B = B; a.seed = seed; a.draw0 = draw0; a.px = px; a.mh_out = x_next;
   a.n_steps = n_steps; a.samples = samples;
+  a.temps = temps; a.temp_step_stride = step_stride; a.temp_chain_stride = chain_stride;
   return small_launch(plan, a, stream);
 }
 

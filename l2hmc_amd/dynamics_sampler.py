@@ -7,7 +7,10 @@ An L2HMC dynamics the one-launch kernel holds (packed target, x_dim <= 8, at mos
 `steps_per_launch` steps at a time to l2hmc_small_run: ONE launch per chunk, the chains in registers from step to step,
 the weights, target, masks and time table staged once.  The values are those of the loop over
 `propose(x, dynamics, do_mh_step=True)`, bit for bit, and that loop is what every other dynamics (`hmc`, `layered`) and
-`steps_per_launch = 1` run."""
+`steps_per_launch = 1` run.
+
+`run(..., temperature=)` anneals or ladders the temperature inside such a run (l2hmc_small_run_tempered): one value per
+step, per chain, or both, where `dynamics.temperature` is one value for the launch."""
 import ctypes as C
 
 import numpy as np
@@ -31,13 +34,34 @@ class DynamicsSampler:
         dyn = self.dynamics
         return int(self.steps_per_launch) > 1 and not dyn.hmc and not dyn.layered
 
-    def run(self, run_steps, x=None, keep_samples=True):
+    def _temperatures(self, temperature, run_steps, B):
+        """`run`'s `temperature` as a float32 array of shape [] (the whole run), [run_steps] (a schedule), [1, B] (a
+        ladder over the chains) or [run_steps, B] (both); ValueError for any other shape, for an entry that is not
+        finite and > 0 in float32, and for a dynamics that would ignore it."""
+        if not self.dynamics.use_temperature:
+            raise ValueError("run: temperature= on a Dynamics built with use_temperature=False, which ignores "
+                             "temperatures (Dynamics._temp): build it with use_temperature=True")
+        if isinstance(temperature, torch.Tensor):
+            temperature = temperature.detach().cpu().numpy()
+        with np.errstate(over="ignore"):
+            t = np.asarray(temperature, dtype=np.float64).astype(np.float32)
+        if t.shape not in ((), (run_steps,), (1, B), (run_steps, B)):
+            raise ValueError(f"run: temperature of shape {t.shape}: expected a scalar, [{run_steps}] (one per step), "
+                             f"[1, {B}] (one per chain) or [{run_steps}, {B}]")
+        if not (np.isfinite(t) & (t > 0)).all():
+            raise ValueError("run: every temperature must be finite and > 0 (in float32)")
+        return t
+
+    def run(self, run_steps, x=None, keep_samples=True, temperature=None):
         """`run_steps` MCMC steps (utils/sampler.py:28-59 with the Metropolis-Hastings step) from `x` [B, x_dim], or
         from N(0, 1) samples for `batch_size` chains.  Returns {"px": [steps, B] accept probabilities, "samples":
         [steps, B, x_dim] with samples[s] the OUTPUT of step s (if kept), "samples_out": the final state on the
         device, "mean_accept": the mean of this run's px (NaN for an empty run)}.  The caller's `x` is not advanced in
         place.  The draws come from the dynamics' own counter (`_draws`, 4 streams per L2HMC step) and the temperature
-        is the dynamics' (`use_temperature` / `temperature`)."""
+        is the dynamics' (`use_temperature` / `temperature`), or `temperature`: a scalar (the whole run), [run_steps]
+        (a schedule: step s at temperature[s]), [1, B] (a ladder: chain c at temperature[0, c]) or [run_steps, B]
+        (both).  Chains never interact, so the columns of a ladder are independent runs at their own temperatures.
+        `dynamics.temperature` is left as it was.  Temperatures per chain need the one-launch path."""
         dyn = self.dynamics
         run_steps = int(run_steps)
         if run_steps < 0:
@@ -48,34 +72,48 @@ class DynamicsSampler:
             x = np.random.randn(int(self.batch_size), dyn.x_dim)
         x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
         B, D = x.shape
+        temps = None if temperature is None else self._temperatures(temperature, run_steps, B)
+        if temps is not None and temps.ndim == 2 and not self._one_launch():
+            raise NotImplementedError(
+                "run: temperatures per chain need the one-launch path (an L2HMC dynamics the one-launch kernel holds: "
+                "not hmc, not layer by layer, and steps_per_launch > 1); the loop over `propose` has one "
+                "`dynamics.temperature` for all chains")
         if run_steps == 0:
             out = {"px": np.empty((0, B), dtype=np.float32), "samples_out": x.clone()}
             if keep_samples:
                 out["samples"] = np.empty((0, B, D), dtype=np.float32)
         elif self._one_launch():
-            out = self._run_launches(run_steps, x, keep_samples)
+            out = self._run_launches(run_steps, x, keep_samples, temps)
         else:
-            out = self._run_loop(run_steps, x, keep_samples)
+            out = self._run_loop(run_steps, x, keep_samples, temps)
         px = out["px"]
         out["mean_accept"] = float(px.mean(dtype=np.float64)) if px.size else float("nan")
         return out
 
-    def _run_loop(self, run_steps, x, keep_samples):
-        """One `propose` per step: any dynamics."""
+    def _run_loop(self, run_steps, x, keep_samples, temps=None):
+        """One `propose` per step: any dynamics.  `temps` ([] or [run_steps]) is set on `dynamics.temperature` step by
+        step, and what was there is put back."""
         dyn = self.dynamics
         px_hist, samples = [], []
-        for _ in range(run_steps):
-            _, _, px, (x,) = propose(x, dyn, do_mh_step=True)
-            px_hist.append(px)
-            if keep_samples:
-                samples.append(x)
+        saved = dyn.temperature
+        try:
+            for s in range(run_steps):
+                if temps is not None:
+                    dyn.temperature = float(temps[s] if temps.ndim else temps)
+                _, _, px, (x,) = propose(x, dyn, do_mh_step=True)
+                px_hist.append(px)
+                if keep_samples:
+                    samples.append(x)
+        finally:
+            dyn.temperature = saved
         out = {"px": torch.stack(px_hist).cpu().numpy(), "samples_out": x}
         if keep_samples:
             out["samples"] = torch.stack(samples).cpu().numpy()
         return out
 
-    def _run_launches(self, run_steps, x, keep_samples):
-        """Chunks of at most `steps_per_launch` steps through l2hmc_small_run, ONE launch each.  The same draws (four
+    def _run_launches(self, run_steps, x, keep_samples, temps=None):
+        """Chunks of at most `steps_per_launch` steps through l2hmc_small_run, ONE launch each (l2hmc_small_run_tempered
+        with `temps`: the array goes to the device once and every chunk starts at its own row).  The same draws (four
         consecutive streams per step from the dynamics' counter), accept probabilities and samples as `_run_loop`, bit
         for bit.  With `keep_samples` the device buffer of the samples is one chunk long and is copied to the host
         chunk by chunk."""
@@ -88,11 +126,22 @@ class DynamicsSampler:
         samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
         x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
         x_in = _lib.dev_ptr(x, name="x")
+        if temps is not None:
+            # element strides of (step, chain): (0, 0) one value, (1, 0) a schedule, (0, 1) a ladder, (B, 1) both
+            step_stride, chain_stride = ((0, 0) if temps.ndim == 0 else (1, 0) if temps.ndim == 1 else
+                                         (0, 1) if temps.shape[0] == 1 else (B, 1))
+            temps_dev = _lib.as_dev(np.ascontiguousarray(temps).reshape(-1), dev)
         for s0 in range(0, run_steps, chunk):
             n = min(chunk, run_steps - s0)
-            _lib.check(L.l2hmc_small_run(
-                C.byref(plan), x_in, x_next.data_ptr(), B, dyn._seed, dyn._draws, n, px[s0:].data_ptr(),
-                samples_dev.data_ptr() if keep_samples else None, _lib.stream_ptr(dyn._device)))
+            out_ptrs = (px[s0:].data_ptr(), samples_dev.data_ptr() if keep_samples else None,
+                        _lib.stream_ptr(dyn._device))
+            if temps is None:
+                _lib.check(L.l2hmc_small_run(C.byref(plan), x_in, x_next.data_ptr(), B, dyn._seed, dyn._draws, n,
+                                             *out_ptrs))
+            else:
+                _lib.check(L.l2hmc_small_run_tempered(
+                    C.byref(plan), x_in, x_next.data_ptr(), B, dyn._seed, dyn._draws, n,
+                    temps_dev.data_ptr() + 4 * s0 * step_stride, step_stride, chain_stride, *out_ptrs))
             dyn._draws += 4 * n                            # the counter moves with the completed steps
             x_in = x_next.data_ptr()                       # later chunks advance the state in place
             if keep_samples:

@@ -58,30 +58,30 @@ class FlatTrainer:
 
     def apply_gradients(self):
         """clip_by_global_norm (if clip_value) + Adam on [xnet | vnet | step size]; bumps global_step."""
-        L, s = _lib.lib(), _lib.stream_ptr(self.dynamics._device)
+        dev = self.dynamics._device
         self._adam_t += 1
         t = self._adam_t
         lr_t = self.learning_rate() * (1. - self.beta2 ** t) ** 0.5 / (1. - self.beta1 ** t)
-        gp, mp, vp = self.grads.data_ptr(), self._m.data_ptr(), self._v.data_ptr()
+        g, m, v = self.grads, self._m, self._v
         segs, off = [], 0
         for net in self._nets:
             flat, _, offsets = net.flat_params()
-            segs.append((flat.data_ptr(), off, flat.numel(), offsets["b1"]))
+            segs.append((flat, off, flat.numel(), offsets["b1"]))
             off += flat.numel()
         step = self._step_trainable()
         gnorm, clip = None, 0.
         if self.clip_value is not None:
             for i, (_, o, n, tri) in enumerate(segs):
-                _lib.check(L.l2hmc_grad_sumsq(gp + 4 * o, n, tri[0], tri[1], self._gnorm.data_ptr(), int(i > 0), s))
+                _lib.call("l2hmc_grad_sumsq", g[o:], n, tri[0], tri[1], self._gnorm, int(i > 0), device=dev)
             if step:
-                _lib.check(L.l2hmc_grad_sumsq(gp + 4 * off, 1, 0, 0, self._gnorm.data_ptr(), 1, s))
-            gnorm, clip = self._gnorm.data_ptr(), self.clip_value
-        for (wp, o, n, tri) in segs:
-            _lib.check(L.l2hmc_adam_step(wp, gp + 4 * o, mp + 4 * o, vp + 4 * o, n, lr_t, self.beta1, self.beta2,
-                                         self.epsilon, gnorm, clip, tri[0], tri[1], s))
+                _lib.call("l2hmc_grad_sumsq", g[off:], 1, 0, 0, self._gnorm, 1, device=dev)
+            gnorm, clip = self._gnorm, self.clip_value
+        for (w, o, n, tri) in segs:
+            _lib.call("l2hmc_adam_step", w, g[o:], m[o:], v[o:], n, lr_t, self.beta1, self.beta2, self.epsilon, gnorm,
+                      clip, tri[0], tri[1], device=dev)
         if step:
-            _lib.check(L.l2hmc_adam_step(self._step_dev.data_ptr(), gp + 4 * off, mp + 4 * off, vp + 4 * off, 1, lr_t,
-                                         self.beta1, self.beta2, self.epsilon, gnorm, clip, 0, 0, s))
+            _lib.call("l2hmc_adam_step", self._step_dev, g[off:], m[off:], v[off:], 1, lr_t, self.beta1, self.beta2,
+                      self.epsilon, gnorm, clip, 0, 0, device=dev)
             self._write_step()
         for net in self._nets:
             net.refresh_packed()

@@ -216,16 +216,32 @@ def dev_ptr(t, dtype=torch.float32, name="tensor"):
 def stream_ptr(device=None):
     """Raw hipStream_t of torch's current stream on `device` (default: the current device).  Kernels are launched
     on the CURRENT device, so a tensor living elsewhere is an error, not a silent cross-device launch."""
+    cur = torch.cuda.current_device()
     if device is not None:
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("the HIP path has no CPU fallback")
-        idx = torch.cuda.current_device() if device.index is None else device.index
-        if idx != torch.cuda.current_device():
-            raise RuntimeError(f"object lives on cuda:{idx} but the current device is cuda:{torch.cuda.current_device()}; "
-                               f"wrap the call in `with torch.cuda.device({idx}):`")
-        return torch.cuda.current_stream(idx).cuda_stream
-    return torch.cuda.current_stream().cuda_stream
+        if device.index is not None and device.index != cur:
+            raise RuntimeError(f"object lives on cuda:{device.index} but the current device is cuda:{cur}; "
+                               f"wrap the call in `with torch.cuda.device({device.index}):`")
+    return torch._C._cuda_getCurrentRawStream(cur)      # current_stream(cur).cuda_stream without the Stream object
+
+
+_CALL_DTYPES = frozenset((torch.float32, torch.int32, torch.uint8))
+
+
+def call(name, *args, device=None, tail=()):
+    """Run the C entry `name` on torch's current stream of `device` and check its status.  Every tensor argument travels
+    as its device address after `dev_ptr`'s checks (on the GPU, contiguous; fp32, int32 or uint8), before the library
+    or torch.cuda is touched; None stays NULL; plans (C.byref), numbers and workspace (ptr, nbytes) pairs pass as they
+    are.  `tail`: what the entry takes after its stream."""
+    ptrs = list(args)
+    for i, a in enumerate(args):
+        if hasattr(a, "data_ptr"):          # a tensor; isinstance(a, torch.Tensor) costs 0.2 us for every plain argument
+            if not (a.is_cuda and a.dtype in _CALL_DTYPES and a.is_contiguous()):      # dev_ptr words the error
+                dev_ptr(a, a.dtype if a.dtype in _CALL_DTYPES else torch.float32, f"{name}: argument {i}")
+            ptrs[i] = a.data_ptr()
+    check(getattr(lib(), name)(*ptrs, stream_ptr(device), *tail))
 
 
 def step_draw_index(draws):

@@ -15,7 +15,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 
 def _nets(dyn):
@@ -58,12 +58,9 @@ def transition(dyn, x, beta, momentum_f=None, momentum_b=None, coin=None, u=None
     dev = x.device
     if momentum_f is None and momentum_b is None and coin is None and u is None:
         # the draws of l2hmc_gauge_transition_draw: (seed, 2d) = [v0_f; v0_b], (seed, 2d+1) = coin | u
-        L, s = _lib.lib(), _lib.stream_ptr(dyn._device)
         d, dyn._draws = _lib.step_draw_index(dyn._draws)
-        V = torch.empty(2 * B * D, dtype=torch.float32, device=dev)
-        cu = torch.empty(2 * B, dtype=torch.float32, device=dev)
-        _lib.check(L.l2hmc_fill_normal(V.data_ptr(), V.numel(), dyn._seed, 2 * d, s))
-        _lib.check(L.l2hmc_fill_uniform(cu.data_ptr(), cu.numel(), dyn._seed, 2 * d + 1, s))
+        V = ops.fill_normal(2 * B * D, dyn._seed, 2 * d, dev)
+        cu = ops.fill_uniform(2 * B, dyn._seed, 2 * d + 1, dev)
         v0f, v0b, coin, u = V[:B * D].view(B, D), V[B * D:].view(B, D), cu[:B], cu[B:]
     else:
         v0f = dyn._x(momentum_f) if momentum_f is not None else dyn._normal((B, D))
@@ -96,9 +93,8 @@ class _Transition(torch.autograd.Function):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         xN, vN = torch.empty_like(x), torch.empty_like(x)
         sld, p = (torch.empty(B, dtype=torch.float32, device=x.device) for _ in range(2))
-        _lib.check(L.l2hmc_gauge_train_forward(C.byref(plan), beta, x.data_ptr(), v0.data_ptr(), dirs.data_ptr(), B,
-                                               xN.data_ptr(), vN.data_ptr(), sld.data_ptr(), p.data_ptr(), ws.data_ptr(),
-                                               nbytes, _lib.stream_ptr(x.device)))
+        _lib.call("l2hmc_gauge_train_forward", C.byref(plan), beta, x, v0, dirs, B, xN, vN, sld, p, ws, nbytes,
+                  device=x.device)
         x_out = torch.where((p > u)[:, None], xN, x)      # strict >, gauge_dynamics.py:244-257
         ctx.save_for_backward(x, v0, xN, vN, p, u, eps, *weights)
         ctx.set_materialize_grads(False)
@@ -116,18 +112,16 @@ class _Transition(torch.autograd.Function):
                                "tape is freed by the first backward")
         saved = ctx.saved_tensors          # raises if a weight or input was modified in place since the forward
         x, v0, xN, vN, p, u, eps = saved[:7]
-        dyn, plan, L = ctx.dyn, ctx.plan, _lib.lib()
+        dyn, plan = ctx.dyn, ctx.plan
         B = x.shape[0]
-        dev, s = x.device, _lib.stream_ptr(x.device)
+        dev = x.device
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
-        ptr = lambda t: None if t is None else _lib.dev_ptr(t.contiguous(), name="cotangent")  # noqa: E731
         gs = [None if t is None else t.contiguous() for t in (g_xprop, g_vprop, g_p, g_xout)]
         dxN, dvN = torch.empty_like(x), torch.empty_like(x)
         dld = torch.empty(B, dtype=torch.float32, device=dev)
         dx0 = torch.empty_like(x) if ctx.needs_input_grad[4] else None
-        _lib.check(L.l2hmc_gauge_accept_backward(T, X, ctx.beta, B, x.data_ptr(), v0.data_ptr(), xN.data_ptr(),
-                                                 vN.data_ptr(), p.data_ptr(), u.data_ptr(), *map(ptr, gs),
-                                                 dxN.data_ptr(), dvN.data_ptr(), dld.data_ptr(), ptr(dx0), None, s))
+        _lib.call("l2hmc_gauge_accept_backward", T, X, ctx.beta, B, x, v0, xN, vN, p, u, *gs, dxN, dvN, dld, dx0, None,
+                  device=dev)
         nets = [net for _, net in _nets(dyn)]
         keys = _lib.DenseGrads._fields_
         dense = [_grad_buffers(b, [k for k, _ in keys]) for b in ctx.bufs]
@@ -136,10 +130,9 @@ class _Transition(torch.autograd.Function):
         if B > 0:
             gstruct = [_lib.DenseGrads(**{k: v.data_ptr() for k, v in g.items()}) for g in dense]
             cstruct = [None if g is None else _lib.Conv3DGrads(**{k: v.data_ptr() for k, v in g.items()}) for g in conv]
-            _lib.check(L.l2hmc_gauge_train_backward(
-                C.byref(plan), ctx.beta, ctx.dirs.data_ptr(), B, dxN.data_ptr(), dvN.data_ptr(), dld.data_ptr(),
-                C.byref(gstruct[0]), C.byref(gstruct[1]), *(None if c is None else C.byref(c) for c in cstruct),
-                deps.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), s))
+            _lib.call("l2hmc_gauge_train_backward", C.byref(plan), ctx.beta, ctx.dirs, B, dxN, dvN, dld,
+                      C.byref(gstruct[0]), C.byref(gstruct[1]), *(None if c is None else C.byref(c) for c in cstruct),
+                      deps, ctx.ws, ctx.ws.numel(), device=dev)
         else:
             dxN.zero_()
         ctx.ws = ctx.plan = ctx.bufs = ctx.front = ctx.mask = ctx.dyn = None

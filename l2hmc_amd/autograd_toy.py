@@ -71,10 +71,8 @@ def vjp_grads(dyn, plan, x0, v0, dirs, cot, want_dx0=True, want_dv0=True):
     dv0 = torch.empty_like(x0) if want_dv0 else None
     nbytes = max(int(L.l2hmc_small_train_ws_bytes(C.byref(plan), R)), 256)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else _lib.dev_ptr(t, name="cotangent")  # noqa: E731
-    _lib.check(L.l2hmc_small_vjp(C.byref(plan), x0.data_ptr(), v0.data_ptr(), _lib.dev_ptr(dirs, torch.int32), R,
-                                 *map(ptr, cot), ptr(dx0), ptr(dv0), grads.data_ptr(), None, None, None, None,
-                                 ws.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    _lib.call("l2hmc_small_vjp", C.byref(plan), x0, v0, dirs, R, *cot, dx0, dv0, grads, None, None, None, None, ws,
+              nbytes, device=dev)
     return grads, dx0, dv0
 
 
@@ -101,13 +99,11 @@ class _Trajectory(torch.autograd.Function):
     def forward(ctx, dyn, xnames, vnames, x0, v0, dirs, sel, alpha, *weights):
         x0, v0 = x0.contiguous(), v0.contiguous()
         R = x0.shape[0]
-        plan, L = dyn._plan(), _lib.lib()
+        plan = dyn._plan()
         X, V = torch.empty_like(x0), torch.empty_like(x0)
         ld = torch.empty(R, dtype=torch.float32, device=x0.device)
         p = torch.empty_like(ld)
-        _lib.check(L.l2hmc_small_trajectory(
-            C.byref(plan), x0.data_ptr(), _lib.dev_ptr(v0, name="init_v"), _lib.dev_ptr(dirs, torch.int32), R,
-            X.data_ptr(), V.data_ptr(), ld.data_ptr(), p.data_ptr(), _lib.stream_ptr(dyn._device)))
+        _lib.call("l2hmc_small_trajectory", C.byref(plan), x0, v0, dirs, R, X, V, ld, p, device=dyn._device)
         ctx.save_for_backward(x0, v0, alpha, *weights)
         ctx.set_materialize_grads(False)
         # what the plan points at stays alive until the backward
@@ -159,7 +155,7 @@ def propose(dyn, x, vf, vb, mask, u, log_jac):
     xx, vv = torch.cat([x, x]), torch.cat([vf, vb])
     dirs = torch.cat([torch.zeros(B, dtype=torch.int32, device=x.device),
                       torch.ones(B, dtype=torch.int32, device=x.device)])
-    fwd = mask != 0                        # l2hmc_mix_accept(strict = 0)
+    fwd = mask != 0                        # ops.mix_accept(strict = 0)
     sel = torch.arange(B, device=x.device) + B * (~fwd).to(torch.int64)
     Lx, Lv, ld, p = trajectory(dyn, xx, vv, dirs, sel)
     px = ld if log_jac else p

@@ -6,14 +6,14 @@ Two paths behind it, chosen per instance (`Dynamics.layered`):
     hidden units -- BASELINE configs 1 and 2;
   * layer by layer, for everything else the reference's constructor accepts (:35-43: ANY `energy_function`, any x_dim,
     `net_factory` of any `num_nodes`): per sub-update of utils/dynamics.py:120-225 one S/T/Q evaluation through
-    l2hmc_stq_dense (any width) and one l2hmc_lf_update_v / _x launch; the energy gradient comes from the packed target's
+    l2hmc_stq_dense (any width) and one ops.lf_update_v / _x launch; the energy gradient comes from the packed target's
     kernel or, for an arbitrary callable on torch tensors, from torch.autograd (the reference's tf.gradients, :241-242)."""
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from . import autograd_toy as _autograd
 
 
@@ -100,11 +100,7 @@ class Dynamics(object):
         return float(self.temperature) if self.use_temperature else 1.0
 
     def kinetic(self, v):
-        v = _lib.as_dev(v, self._device)
-        out = torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
-        _lib.check(_lib.lib().l2hmc_kinetic_energy(v.data_ptr(), v.shape[0], v.shape[1], out.data_ptr(),
-                                                   _lib.stream_ptr(self._device)))
-        return out
+        return ops.kinetic_energy(_lib.as_dev(v, self._device))
 
     def energy(self, x, aux=None):
         """:227-236."""
@@ -133,20 +129,14 @@ class Dynamics(object):
         """:123-132 / :158-166 (d = 0), :175-185 / :213-223 (d = 1): half-kick with VNet([x, grad, t])."""
         g = self.grad_energy(x)
         S, T, Q = self.VNet([x, g, t])
-        out, ld = torch.empty_like(v), torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
-        _lib.check(_lib.lib().l2hmc_lf_update_v(v.data_ptr(), g.data_ptr(), S.data_ptr(), T.data_ptr(), Q.data_ptr(),
-                                                float(self.eps), d, v.shape[0], self.x_dim, out.data_ptr(), ld.data_ptr(),
-                                                _lib.stream_ptr(self._device)))
+        out, ld = ops.lf_update_v(v, g, S, T, Q, self.eps, d)
         logdet += ld
         return out
 
     def _sub_x(self, x, v, keep, t, d, logdet):
         """:134-156 (d = 0), :187-211 (d = 1): XNet([v, keep * x, t]); the kept coordinates pass through."""
         S, T, Q = self.XNet([v, keep * x, t])
-        out, ld = torch.empty_like(x), torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().l2hmc_lf_update_x(x.data_ptr(), v.data_ptr(), keep.data_ptr(), S.data_ptr(), T.data_ptr(),
-                                                Q.data_ptr(), float(self.eps), d, x.shape[0], self.x_dim, out.data_ptr(),
-                                                ld.data_ptr(), _lib.stream_ptr(self._device)))
+        out, ld = ops.lf_update_x(x, v, keep, S, T, Q, self.eps, d)
         logdet += ld
         return out
 
@@ -185,9 +175,7 @@ class Dynamics(object):
         return p
 
     def _normal(self, shape):
-        out = torch.empty(shape, dtype=torch.float32, device=self._device)
-        _lib.check(_lib.lib().l2hmc_fill_normal(out.data_ptr(), out.numel(), self._seed, self._draws,
-                                                _lib.stream_ptr(self._device)))
+        out = ops.fill_normal(shape, self._seed, self._draws, self._device)
         self._draws += 1
         return out
 
@@ -206,9 +194,7 @@ class Dynamics(object):
         p = torch.empty_like(lj)
         dirs = torch.full((rows,), 1, dtype=torch.int32, device=x.device) if backward else None
         plan = self._plan()
-        _lib.check(_lib.lib().l2hmc_small_trajectory(
-            C.byref(plan), x.data_ptr(), _lib.dev_ptr(v, name="init_v"), _lib.dev_ptr(dirs, torch.int32), rows,
-            X.data_ptr(), V.data_ptr(), lj.data_ptr(), p.data_ptr(), _lib.stream_ptr(self._device)))
+        _lib.call("l2hmc_small_trajectory", C.byref(plan), x, v, dirs, rows, X, V, lj, p, device=self._device)
         return (X, V, lj) if log_jac else (X, V, p)
 
     def both(self, x, init_v_forward=None, init_v_backward=None, log_jac=False):
@@ -227,9 +213,7 @@ class Dynamics(object):
         lj = torch.empty(2 * B, dtype=torch.float32, device=x.device)
         p = torch.empty_like(lj)
         plan = self._plan()
-        _lib.check(_lib.lib().l2hmc_small_trajectory(
-            C.byref(plan), xx.data_ptr(), vv.data_ptr(), dirs.data_ptr(), 2 * B, X.data_ptr(), V.data_ptr(),
-            lj.data_ptr(), p.data_ptr(), _lib.stream_ptr(self._device)))
+        _lib.call("l2hmc_small_trajectory", C.byref(plan), xx, vv, dirs, 2 * B, X, V, lj, p, device=self._device)
         third = lj if log_jac else p
         return (X[:B], V[:B], third[:B]), (X[B:], V[B:], third[B:])
 
@@ -249,8 +233,4 @@ class Dynamics(object):
     def p_accept(self, x0, v0, x1, v1, log_jac, aux=None):
         """:312-319."""
         e_new, e_old = self.hamiltonian(x1, v1), self.hamiltonian(x0, v0)
-        lj = _lib.as_dev(log_jac, self._device)
-        p = torch.empty_like(e_old)
-        _lib.check(_lib.lib().l2hmc_accept_prob(e_old.data_ptr(), e_new.data_ptr(), lj.data_ptr(), p.numel(),
-                                                p.data_ptr(), _lib.stream_ptr(self._device)))
-        return p
+        return ops.accept_prob(e_old, e_new, _lib.as_dev(log_jac, self._device))

@@ -119,13 +119,13 @@ class DynamicsSampler:
         chunk by chunk."""
         dyn = self.dynamics
         B, D, dev = x.shape[0], x.shape[1], x.device
-        plan, L = dyn._plan(), _lib.lib()
+        plan = dyn._plan()
         chunk = min(int(self.steps_per_launch), run_steps)
         px = torch.empty(run_steps, B, dtype=torch.float32, device=dev)
         samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
         samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
         x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
-        x_in = _lib.dev_ptr(x, name="x")
+        x_in = x
         if temps is not None:
             # element strides of (step, chain): (0, 0) one value, (1, 0) a schedule, (0, 1) a ladder, (B, 1) both
             step_stride, chain_stride = ((0, 0) if temps.ndim == 0 else (1, 0) if temps.ndim == 1 else
@@ -133,17 +133,15 @@ class DynamicsSampler:
             temps_dev = _lib.as_dev(np.ascontiguousarray(temps).reshape(-1), dev)
         for s0 in range(0, run_steps, chunk):
             n = min(chunk, run_steps - s0)
-            out_ptrs = (px[s0:].data_ptr(), samples_dev.data_ptr() if keep_samples else None,
-                        _lib.stream_ptr(dyn._device))
             if temps is None:
-                _lib.check(L.l2hmc_small_run(C.byref(plan), x_in, x_next.data_ptr(), B, dyn._seed, dyn._draws, n,
-                                             *out_ptrs))
+                _lib.call("l2hmc_small_run", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n, px[s0:],
+                          samples_dev, device=dyn._device)
             else:
-                _lib.check(L.l2hmc_small_run_tempered(
-                    C.byref(plan), x_in, x_next.data_ptr(), B, dyn._seed, dyn._draws, n,
-                    temps_dev.data_ptr() + 4 * s0 * step_stride, step_stride, chain_stride, *out_ptrs))
+                _lib.call("l2hmc_small_run_tempered", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
+                          temps_dev[s0 * step_stride:], step_stride, chain_stride, px[s0:], samples_dev,
+                          device=dyn._device)
             dyn._draws += 4 * n                            # the counter moves with the completed steps
-            x_in = x_next.data_ptr()                       # later chunks advance the state in place
+            x_in = x_next                                  # later chunks advance the state in place
             if keep_samples:
                 samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
         out = {"px": px.cpu().numpy(), "samples_out": x_next}

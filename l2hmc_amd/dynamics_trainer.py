@@ -11,7 +11,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from . import layered_train as _layered_train
 from ._flat_trainer import FlatTrainer, stack_chains
 from .dist import active as _active_dist
@@ -52,8 +52,7 @@ class DynamicsTrainer(FlatTrainer):
         z = dyn._normal((B, D)) if z is None else _lib.as_dev(z, dev).reshape(B, D)
 
         def uniform(n):
-            out = torch.empty(n, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().l2hmc_fill_uniform(out.data_ptr(), n, dyn._seed, dyn._draws, _lib.stream_ptr(self.dynamics._device)))
+            out = ops.fill_uniform(n, dyn._seed, dyn._draws, dev)
             dyn._draws += 1
             return out
 
@@ -72,10 +71,8 @@ class DynamicsTrainer(FlatTrainer):
             p, terms = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
             plan, L = dyn._plan(), _lib.lib()
             ws, nb = self._ws.get(L.l2hmc_small_train_ws_bytes(C.byref(plan), R), dev)
-            _lib.check(L.l2hmc_small_train_step(C.byref(plan), x0.data_ptr(), v0.data_ptr(), dirs.data_ptr(), R,
-                                                self.scale, 1.0 / (B * self.world), xN.data_ptr(), vN.data_ptr(),
-                                                p.data_ptr(), terms.data_ptr(), self.grads.data_ptr(), ws, nb,
-                                                _lib.stream_ptr(self.dynamics._device)))
+            _lib.call("l2hmc_small_train_step", C.byref(plan), x0, v0, dirs, R, self.scale, 1.0 / (B * self.world), xN,
+                      vN, p, terms, self.grads, ws, nb, device=dev)
         self.grads[-1] *= float(dyn.eps)              # d/d alpha = eps * d/d eps  (utils/dynamics.py:51-60)
         buf = torch.stack([terms.sum(dtype=torch.float32), torch.full((), float(B), dtype=torch.float32, device=dev)])
         if self.dist is not None:

@@ -15,7 +15,7 @@ import numpy as np
 import numpy.random as npr
 import torch
 
-from . import _lib
+from . import _lib, ops
 from . import autograd as _autograd
 from .network import ConvNet3D, GenericNet
 
@@ -166,7 +166,7 @@ class GaugeDynamics:
         h = getattr(self, "_heads", None)
         if h is None or h[0] is not self.mask or h[1] != key or h[2].numel() * 4 < nbytes:
             buf = torch.empty(nbytes // 4, dtype=torch.float32, device=self._device)
-            _lib.check(L.l2hmc_gauge_pack_heads(C.byref(plan), buf.data_ptr(), _lib.stream_ptr(self._device)))
+            _lib.call("l2hmc_gauge_pack_heads", C.byref(plan), buf, device=self._device)
             self._heads = h = (self.mask, key, buf)
         return h[2].data_ptr()
 
@@ -175,16 +175,12 @@ class GaugeDynamics:
         return a.reshape(a.shape[0], -1)
 
     def _normal(self, shape):
-        out = torch.empty(shape, dtype=torch.float32, device=self._device)
-        _lib.check(_lib.lib().l2hmc_fill_normal(out.data_ptr(), out.numel(), self._seed, self._draws,
-                                                _lib.stream_ptr(self._device)))
+        out = ops.fill_normal(shape, self._seed, self._draws, self._device)
         self._draws += 1
         return out
 
     def _uniform(self, shape):
-        out = torch.empty(shape, dtype=torch.float32, device=self._device)
-        _lib.check(_lib.lib().l2hmc_fill_uniform(out.data_ptr(), out.numel(), self._seed, self._draws,
-                                                 _lib.stream_ptr(self._device)))
+        out = ops.fill_uniform(shape, self._seed, self._draws, self._device)
         self._draws += 1
         return out
 
@@ -213,9 +209,8 @@ class GaugeDynamics:
             plan, L = self._plan(), _lib.lib()
             ws, nb = self._ws.get(L.l2hmc_gauge_mcmc_step_ws_bytes(C.byref(plan), B), x.device)
             draw, self._draws = _lib.step_draw_index(self._draws)
-            _lib.check(L.l2hmc_gauge_transition_draw(
-                C.byref(plan), float(beta), _lib.dev_ptr(x, name="position"), B, self._seed, draw, x_prop.data_ptr(),
-                v_prop.data_ptr(), p.data_ptr(), x_out.data_ptr(), ws, nb, _lib.stream_ptr(self._device)))
+            _lib.call("l2hmc_gauge_transition_draw", C.byref(plan), float(beta), x, B, self._seed, draw, x_prop,
+                      v_prop, p, x_out, ws, nb, device=self._device)
             if self.check_numerics and not bool(torch.isfinite(x_prop).all() & torch.isfinite(v_prop).all()):
                 raise FloatingPointError("check_numerics: non-finite value in the proposed configuration")
             return x_prop, v_prop, p, x_out
@@ -228,11 +223,8 @@ class GaugeDynamics:
         plan, L = self._plan(), _lib.lib()
         both = int(bool(self.both_directions))
         ws, nb = self._ws.get(L.l2hmc_gauge_transition_ws_bytes(C.byref(plan), B, both), x.device)
-        _lib.check(L.l2hmc_gauge_transition(
-            C.byref(plan), float(beta), _lib.dev_ptr(x, name="position"), _lib.dev_ptr(v0f, name="momentum_f"),
-            _lib.dev_ptr(v0b, name="momentum_b"), _lib.dev_ptr(coin, name="coin"), _lib.dev_ptr(u, name="u"),
-            B, both, x_prop.data_ptr(), v_prop.data_ptr(), p.data_ptr(), x_out.data_ptr(), ws, nb,
-            _lib.stream_ptr(self._device)))
+        _lib.call("l2hmc_gauge_transition", C.byref(plan), float(beta), x, v0f, v0b, coin, u, B, both, x_prop, v_prop,
+                  p, x_out, ws, nb, device=self._device)
         if self.check_numerics and not bool(torch.isfinite(x_prop).all() & torch.isfinite(v_prop).all()):
             # the reference wraps every exp of the sub-updates in tf.check_numerics and aborts the step;
             # the kernels propagate NaN / inf instead, and this opt-in check (one host sync) reports it
@@ -250,10 +242,8 @@ class GaugeDynamics:
         plan, L = self._plan(), _lib.lib()
         dirs = None if forward else self._dir(rows, True)
         ws, nb = self._ws.get(L.l2hmc_gauge_ws_bytes(C.byref(plan), rows), x.device)
-        _lib.check(L.l2hmc_gauge_trajectory(
-            C.byref(plan), float(beta), _lib.dev_ptr(x, name="position"), _lib.dev_ptr(v0, name="momentum"),
-            _lib.dev_ptr(dirs, torch.int32), rows, x_out.data_ptr(), v_out.data_ptr(), sld.data_ptr(),
-            p.data_ptr(), ws, nb, _lib.stream_ptr(self._device)))
+        _lib.call("l2hmc_gauge_trajectory", C.byref(plan), float(beta), x, v0, dirs, rows, x_out, v_out, sld, p, ws, nb,
+                  device=self._device)
         if return_logdet:
             return x_out, v_out, p, sld
         return x_out, v_out, p
@@ -265,9 +255,8 @@ class GaugeDynamics:
         plan, L = self._plan(), _lib.lib()
         dirs = self._dir(rows, True) if backward else None
         ws, nb = self._ws.get(L.l2hmc_gauge_ws_bytes(C.byref(plan), rows), x.device)
-        _lib.check(L.l2hmc_gauge_leapfrog(C.byref(plan), float(beta), int(step), x.data_ptr(), v.data_ptr(),
-                                          _lib.dev_ptr(dirs, torch.int32), rows, logdet.data_ptr(), ws, nb,
-                                          _lib.stream_ptr(self._device)))
+        _lib.call("l2hmc_gauge_leapfrog", C.byref(plan), float(beta), int(step), x, v, dirs, rows, logdet, ws, nb,
+                  device=self._device)
         return x, v, logdet
 
     def _forward_lf(self, position, momentum, beta, step):
@@ -286,13 +275,7 @@ class GaugeDynamics:
         x, v = self._x(position), self._x(momentum)
         grad = self.grad_potential(x, beta)
         S, T, Q = self._stq(self.momentum_fn, x, grad, t)           # :493-495
-        v_out = torch.empty_like(v)
-        logdet = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().l2hmc_lf_update_v(
-            v.data_ptr(), grad.data_ptr(), _lib.dev_ptr(self._x(S)), _lib.dev_ptr(self._x(T)),
-            _lib.dev_ptr(self._x(Q)), float(self.eps), int(backward), x.shape[0], x.shape[1],
-            v_out.data_ptr(), logdet.data_ptr(), _lib.stream_ptr(self._device)))
-        return v_out, logdet
+        return ops.lf_update_v(v, grad, self._x(S), self._x(T), self._x(Q), self.eps, backward)
 
     def _update_momentum_forward(self, position, momentum, beta, t):
         """:486-508."""
@@ -306,13 +289,7 @@ class GaugeDynamics:
         x, v = self._x(position), self._x(momentum)
         keep = _lib.as_dev(mask, self._device).reshape(-1)
         S, T, Q = self._stq(self.position_fn, v, keep[None, :] * x, t)   # :515-517
-        x_out = torch.empty_like(x)
-        logdet = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().l2hmc_lf_update_x(
-            x.data_ptr(), v.data_ptr(), keep.data_ptr(), _lib.dev_ptr(self._x(S)), _lib.dev_ptr(self._x(T)),
-            _lib.dev_ptr(self._x(Q)), float(self.eps), int(backward), x.shape[0], x.shape[1],
-            x_out.data_ptr(), logdet.data_ptr(), _lib.stream_ptr(self._device)))
-        return x_out, logdet
+        return ops.lf_update_x(x, v, keep, self._x(S), self._x(T), self._x(Q), self.eps, backward)
 
     def _update_position_forward(self, position, momentum, t, mask, mask_inv):
         """:511-534."""
@@ -326,11 +303,7 @@ class GaugeDynamics:
         """:592-609."""
         old = self.hamiltonian(position, momentum, beta)
         new = self.hamiltonian(position_post, momentum_post, beta)
-        sld = _lib.as_dev(sumlogdet, self._device)
-        p = torch.empty_like(old)
-        _lib.check(_lib.lib().l2hmc_accept_prob(old.data_ptr(), new.data_ptr(), sld.data_ptr(), old.numel(),
-                                                p.data_ptr(), _lib.stream_ptr(self._device)))
-        return p
+        return ops.accept_prob(old, new, _lib.as_dev(sumlogdet, self._device))
 
     def _get_time(self, i):
         return self.ts[i]
@@ -352,11 +325,7 @@ class GaugeDynamics:
 
     def kinetic_energy(self, v):
         """:683-689."""
-        v = self._x(v)
-        out = torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
-        _lib.check(_lib.lib().l2hmc_kinetic_energy(v.data_ptr(), v.shape[0], v.shape[1], out.data_ptr(),
-                                                   _lib.stream_ptr(self._device)))
-        return out
+        return ops.kinetic_energy(self._x(v))
 
     def hamiltonian(self, position, momentum, beta):
         """:691-696."""

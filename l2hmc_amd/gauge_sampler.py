@@ -8,7 +8,7 @@ per-step scalars of all ranks are combined by one small asynchronous all-reduce 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .dist import StepStats
 from .lattice import u1_observables, u1_plaq_exact
 
@@ -36,9 +36,7 @@ class GaugeSampler:
         return 1. / temp
 
     def wrap(self, x):
-        out = torch.empty_like(x)
-        _lib.check(_lib.lib().l2hmc_wrap_angle(x.data_ptr(), x.numel(), out.data_ptr(), _lib.stream_ptr(self.dynamics._device)))
-        return out
+        return ops.wrap_angle(x)
 
     def step(self, x, beta):
         """One MCMC step on device state x: [B, x_dim].  Returns (x_next, px, observables of x, |dQ|);
@@ -60,11 +58,8 @@ class GaugeSampler:
         # the step's random streams come from the dynamics' own draw counter (saved / restored with the state):
         # a sampler never replays noise the dynamics, a trainer or another sampler on the same dynamics used
         draw, dyn._draws = _lib.step_draw_index(dyn._draws)
-        _lib.check(L.l2hmc_gauge_mcmc_step_ex(
-            C.byref(plan), float(beta), _lib.dev_ptr(x, name="x"), x_next.data_ptr(), B, dyn._seed, draw,
-            outs["px"].data_ptr(), outs["action"].data_ptr(), outs["avg_plaq"].data_ptr(),
-            outs["top_charge"].data_ptr(), outs["dq"].data_ptr(), sums.data_ptr(), ws, nb,
-            _lib.stream_ptr(dyn._device)))
+        _lib.call("l2hmc_gauge_mcmc_step_ex", C.byref(plan), float(beta), x, x_next, B, dyn._seed, draw, outs["px"],
+                  outs["action"], outs["avg_plaq"], outs["top_charge"], outs["dq"], sums, ws, nb, device=dyn._device)
         self.stats.push_sums(sums[:3])
         return x_next, outs["px"], outs, outs["dq"]
 
@@ -93,11 +88,9 @@ class GaugeSampler:
         z = dyn._normal(tuple(x.shape)) if z is None else _lib.as_dev(z, dyn._device)
         _, _, pz, _ = dyn(z, beta)
         terms = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().l2hmc_gauge_loss_terms(
-            x.data_ptr(), x_prop.data_ptr(), px.data_ptr(), z.data_ptr(), pz.data_ptr(), x.shape[0], T, X,
-            self.METRICS[metric], float(loss_scale), float(weights.get('aux_weight', 1.)),
-            float(weights.get('std_weight', 1.)), float(weights.get('charge_weight', 1.)), terms.data_ptr(),
-            _lib.stream_ptr(self.dynamics._device)))
+        _lib.call("l2hmc_gauge_loss_terms", x, x_prop, px, z, pz, x.shape[0], T, X, self.METRICS[metric],
+                  float(loss_scale), float(weights.get('aux_weight', 1.)), float(weights.get('std_weight', 1.)),
+                  float(weights.get('charge_weight', 1.)), terms, device=dyn._device)
         buf = torch.stack([terms.sum(dtype=torch.float32),
                            torch.full((), float(terms.numel()), dtype=torch.float32, device=x.device)])
         if self.stats.dist is not None:
@@ -168,15 +161,13 @@ class GaugeSampler:
         # the steps' random streams come from the dynamics' own draw counter, as in `step`
         draw0, _ = _lib.run_draw_index(dyn._draws, run_steps)
         x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
-        x_in = _lib.dev_ptr(x, name="x")
+        x_in = x
         for s0 in range(0, run_steps, chunk):
             n = min(chunk, run_steps - s0)
-            _lib.check(L.l2hmc_gauge_hmc_run(
-                C.byref(plan), beta_dev[s0:].data_ptr(), x_in, x_next.data_ptr(), B, dyn._seed, draw0 + s0, n,
-                *(hist[k][s0:].data_ptr() for k in names), sums[s0:].data_ptr(),
-                samples_dev.data_ptr() if keep_samples else None, ws, nb, _lib.stream_ptr(dyn._device)))
+            _lib.call("l2hmc_gauge_hmc_run", C.byref(plan), beta_dev[s0:], x_in, x_next, B, dyn._seed, draw0 + s0, n,
+                      *(hist[k][s0:] for k in names), sums[s0:], samples_dev, ws, nb, device=dyn._device)
             _, dyn._draws = _lib.run_draw_index(2 * draw0, s0 + n)      # the counter moves with the completed steps
-            x_in = x_next.data_ptr()                       # later chunks advance the state in place
+            x_in = x_next                                  # later chunks advance the state in place
             for i in range(s0, s0 + n):
                 self.stats.push_sums(sums[i, :3])
             if keep_samples:

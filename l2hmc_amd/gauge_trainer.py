@@ -23,7 +23,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from . import layered_train as _layered_train
 from ._flat_trainer import FlatTrainer, stack_chains
 from .dist import active as _active_dist
@@ -140,7 +140,7 @@ class GaugeTrainer(FlatTrainer):
             return tuple(_lib.as_dev(a, dev) for a in d)
         x0, v0, fwd, dirs, u_x = stack_chains(x, z, draw(draws_x), draw(draws_z))
         R = 2 * B
-        L, s, layered = _lib.lib(), _lib.stream_ptr(dev), self._use_layered()
+        L, layered = _lib.lib(), self._use_layered()
         if layered:          # one taped layered trajectory per direction, on the rows that run it
             if self._walk is None:
                 self._walk = _layered_train.LayeredWalk(dev)
@@ -152,18 +152,15 @@ class GaugeTrainer(FlatTrainer):
             sld, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
             plan = dyn._plan()
             ws, nb = self._ws.get(L.l2hmc_gauge_train_ws_bytes(C.byref(plan), R), dev)
-            _lib.check(L.l2hmc_gauge_train_forward(C.byref(plan), float(beta), x0.data_ptr(), v0.data_ptr(),
-                                                   dirs.data_ptr(), R, xN.data_ptr(), vN.data_ptr(), sld.data_ptr(),
-                                                   p.data_ptr(), ws, nb, s))
+            _lib.call("l2hmc_gauge_train_forward", C.byref(plan), float(beta), x0, v0, dirs, R, xN, vN, sld, p, ws, nb,
+                      device=dev)
         terms = torch.empty(B, dtype=torch.float32, device=dev)
         dxN, dvN = torch.empty_like(x0), torch.empty_like(x0)
         dld = torch.empty(R, dtype=torch.float32, device=dev)
         w = self.weights
-        _lib.check(L.l2hmc_gauge_loss_backward(T, X, float(beta), x0.data_ptr(), xN.data_ptr(), vN.data_ptr(),
-                                               p.data_ptr(), B, METRICS[self.metric], self.loss_scale,
-                                               w['aux_weight'], w['std_weight'], w['charge_weight'],
-                                               1.0 / (B * self.world), terms.data_ptr(), dxN.data_ptr(),
-                                               dvN.data_ptr(), dld.data_ptr(), s))
+        _lib.call("l2hmc_gauge_loss_backward", T, X, float(beta), x0, xN, vN, p, B, METRICS[self.metric],
+                  self.loss_scale, w['aux_weight'], w['std_weight'], w['charge_weight'], 1.0 / (B * self.world), terms,
+                  dxN, dvN, dld, device=dev)
         buf = torch.stack([terms.sum(dtype=torch.float32),
                            torch.full((), float(B), dtype=torch.float32, device=dev)])
         # Bucketed exchange: `send(ranges)` puts ranges of the flat buffer on the wire as soon as the reverse has
@@ -181,10 +178,10 @@ class GaugeTrainer(FlatTrainer):
             if bucketed:
                 send([(n0 + n1, n0 + n1 + 1)])
         else:
-            bargs = (C.byref(plan), float(beta), dirs.data_ptr(), R, dxN.data_ptr(), dvN.data_ptr(), dld.data_ptr(),
+            bargs = (C.byref(plan), float(beta), dirs, R, dxN, dvN, dld,
                      C.byref(self._grad_structs[0]), C.byref(self._grad_structs[1]),
                      *(C.byref(g) if g is not None else None for g in self._conv_grad_structs),
-                     self.grads.data_ptr() + 4 * (n0 + n1), ws, nb, s)
+                     self.grads[n0 + n1:], ws, nb)
             if bucketed:
                 errors = []
 
@@ -194,11 +191,11 @@ class GaugeTrainer(FlatTrainer):
                     except Exception as e:          # noqa: BLE001 -- a ctypes callback cannot raise: re-raised below
                         errors.append(e)
                 cb = _lib.BUCKET_FN(on_bucket)
-                _lib.check(L.l2hmc_gauge_train_backward_buckets(*bargs, cb, None))
+                _lib.call("l2hmc_gauge_train_backward_buckets", *bargs, device=dev, tail=(cb, None))
                 if errors:
                     raise errors[0]
             else:
-                _lib.check(L.l2hmc_gauge_train_backward(*bargs))
+                _lib.call("l2hmc_gauge_train_backward", *bargs, device=dev)
         if bucketed:
             self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
             for wk in works:
@@ -251,23 +248,13 @@ class GaugeTrainer(FlatTrainer):
 
     def _lattice_walk(self, beta):
         """The lattice as l2hmc_amd/layered_train.py sees it: beta * force feeds the momentum update and VNet, with
-        l2hmc_u1_force_hvp as its Hessian-vector product."""
+        ops.u1_force_hvp as its Hessian-vector product."""
         dyn = self.dynamics
-        L, s = _lib.lib(), _lib.stream_ptr(dyn._device)
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
-
-        def force(x):
-            out = torch.empty_like(x)
-            _lib.check(L.l2hmc_u1_action_force(x.data_ptr(), x.shape[0], T, X, beta, None, out.data_ptr(), None, None,
-                                               s))
-            return out
-
-        def hvp(x, u):
-            out = torch.empty_like(x)
-            _lib.check(L.l2hmc_u1_force_hvp(x.data_ptr(), u.data_ptr(), x.shape[0], T, X, beta, out.data_ptr(), s))
-            return out
         return _layered_train.Walk(dyn.position_fn, dyn.momentum_fn, dyn.eps, dyn.num_steps, dyn._format_time,
-                                   dyn._get_mask_while, force, hvp)
+                                   dyn._get_mask_while,
+                                   lambda x: ops.u1_action_force(x, T, X, beta, want_observables=False)[1],
+                                   lambda x, u: ops.u1_force_hvp(x, u, T, X, beta))
 
     def update_beta(self, step, beta_init=2., beta_final=4., train_steps=10000):
         """gauge_model.py:1039-1046: linear annealing of 1/beta."""
@@ -294,7 +281,7 @@ class GaugeTrainer(FlatTrainer):
             lr = self.learning_rate()
             obs = u1_observables(x, T, X)
             loss, x_out, px, x_dq = self.train_step(x, beta)
-            _lib.check(_lib.lib().l2hmc_wrap_angle(x_out.data_ptr(), x_out.numel(), x.data_ptr(), _lib.stream_ptr(self.dynamics._device)))
+            ops.wrap_angle(x_out, out=x)
             for k, v in (("loss", loss), ("accept_prob", px.mean()), ("actions", obs["action"].mean()),
                          ("plaqs", obs["avg_plaq"].mean()), ("charges", obs["top_charge"]),
                          ("charge_diff", x_dq.sum() / float(x_dq.numel()))):

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 from scipy.special import i0, i1
 
-from . import _lib
+from . import _lib, ops
 
 
 def u1_plaq_exact(beta):
@@ -22,16 +22,9 @@ def _x2d(x, D):
 
 def u1_observables(x, time_size, space_size, beta=1.0, want_force=False):
     """One pass over x: [rows, 2*T*X] -> dict(action, avg_plaq, top_charge[, force=beta*dS/dx])."""
-    D = 2 * time_size * space_size
-    x = _x2d(x, D)
-    rows = x.shape[0]
-    out = {k: torch.empty(rows, dtype=torch.float32, device=x.device)
-           for k in ("action", "avg_plaq", "top_charge")}
-    force = torch.empty_like(x) if want_force else None
-    _lib.check(_lib.lib().l2hmc_u1_action_force(
-        _lib.dev_ptr(x, name="x"), rows, time_size, space_size, float(beta), out["action"].data_ptr(),
-        None if force is None else force.data_ptr(), out["avg_plaq"].data_ptr(),
-        out["top_charge"].data_ptr(), _lib.stream_ptr(x.device)))
+    x = _x2d(x, 2 * time_size * space_size)
+    action, force, plaq, charge = ops.u1_action_force(x, time_size, space_size, beta, want_force=want_force)
+    out = {"action": action, "avg_plaq": plaq, "top_charge": charge}
     if want_force:
         out["force"] = force
     return out
@@ -90,8 +83,7 @@ class GaugeLattice(object):
         """gauge_model.py:659-681 -> [B, T, X]."""
         x = _x2d(samples, self.num_links)
         out = torch.empty(x.shape[0], self.time_size, self.space_size, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().l2hmc_u1_plaq_sums(_lib.dev_ptr(x, name="x"), x.shape[0], self.time_size,
-                                                 self.space_size, out.data_ptr(), _lib.stream_ptr(x.device)))
+        _lib.call("l2hmc_u1_plaq_sums", x, x.shape[0], self.time_size, self.space_size, out, device=x.device)
         return out
 
     def grad_action(self, samples, beta=1.0):

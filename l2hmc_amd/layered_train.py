@@ -25,14 +25,14 @@ LayeredWalk.backward: reverse walk, weight gradients network by network, summed 
 trainer: a `Walk` gives them the networks, eps, the per-step masks and time input, and the energy gradient with its
 Hessian-vector product; the caller gives the accept probability and, between the stages, the cotangents of
 (x_N, v_N, sumlogdet).  `LayeredStep` is the toy targets' caller (squared-jump loss); `GaugeTrainer` runs the same
-stages on the lattice (beta * force, l2hmc_u1_force_hvp, l2hmc_gauge_loss_backward) where its tiled training entries
+stages on the lattice (beta * force, ops.u1_force_hvp, l2hmc_gauge_loss_backward) where its tiled training entries
 do not take the network widths."""
 import collections
 import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 
 class _NetTape:
@@ -64,8 +64,7 @@ def energy_hvp(dyn, x, u):
     if dyn._target is not None:
         out = torch.empty_like(x)
         st = dyn._target.struct(dyn._temp())
-        _lib.check(_lib.lib().l2hmc_mog_energy_hvp(C.byref(st), x.data_ptr(), u.contiguous().data_ptr(), x.shape[0],
-                                                   out.data_ptr(), _lib.stream_ptr(dyn._device)))
+        _lib.call("l2hmc_mog_energy_hvp", C.byref(st), x, u.contiguous(), x.shape[0], out, device=dyn._device)
         return out
     with torch.enable_grad():
         xg = x.detach().clone().requires_grad_(True)
@@ -86,7 +85,7 @@ class Walk:
     the two networks, eps, the trajectory length, per step the time input `format_time(step) -> [[t_cos, t_sin]]`
     (the dynamics' `_format_time`) and the masks `masks(step) -> (m, 1 - m)` ([D] device tensors), and the gradient
     that feeds the momentum update and VNet's second input, `grad(x)`, with its Hessian-vector product `hvp(x, u)`
-    (toy targets: grad E / temperature and energy_hvp; the lattice: beta * force and l2hmc_u1_force_hvp)."""
+    (toy targets: grad E / temperature and energy_hvp; the lattice: beta * force and ops.u1_force_hvp)."""
 
     def __init__(self, xnet, vnet, eps, num_steps, format_time, masks, grad, hvp):
         self.xnet, self.vnet, self.eps, self.num_steps = xnet, vnet, float(eps), int(num_steps)
@@ -118,7 +117,6 @@ class LayeredWalk:
 
     # ---- forward ---------------------------------------------------------------------------------------------
     def _sub_v(self, w, x, v, tc, ts, d, lj, tape, subs):
-        L, s = _lib.lib(), _lib.stream_ptr(self.device)
         n, D = x.shape
         g = w.grad(x)
         sl = tape.take(n)
@@ -126,18 +124,14 @@ class LayeredWalk:
         tape.inp[sl, D:] = g
         tape.tcs[sl, 0], tape.tcs[sl, 1] = tc, ts
         S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
-        _lib.check(L.l2hmc_stq_dense_taped(C.byref(w.vnet.pack()), x.data_ptr(), g.data_ptr(), None, tc, ts, n,
-                                           S.data_ptr(), T.data_ptr(), Q.data_ptr(), tape.h1[sl].data_ptr(),
-                                           tape.h2[sl].data_ptr(), s))
-        out, ld = torch.empty_like(v), torch.empty(n, dtype=torch.float32, device=v.device)
-        _lib.check(L.l2hmc_lf_update_v(v.data_ptr(), g.data_ptr(), S.data_ptr(), T.data_ptr(), Q.data_ptr(),
-                                       w.eps, d, n, D, out.data_ptr(), ld.data_ptr(), s))
+        _lib.call("l2hmc_stq_dense_taped", C.byref(w.vnet.pack()), x, g, None, tc, ts, n, S, T, Q, tape.h1[sl],
+                  tape.h2[sl], device=self.device)
+        out, ld = ops.lf_update_v(v, g, S, T, Q, w.eps, d)
         lj += ld
         subs.append(("v", sl, x, v, g, None))
         return out
 
     def _sub_x(self, w, x, v, keep, tc, ts, d, lj, tape, subs):
-        L, s = _lib.lib(), _lib.stream_ptr(self.device)
         n, D = x.shape
         b = keep * x
         sl = tape.take(n)
@@ -145,12 +139,9 @@ class LayeredWalk:
         tape.inp[sl, D:] = b
         tape.tcs[sl, 0], tape.tcs[sl, 1] = tc, ts
         S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
-        _lib.check(L.l2hmc_stq_dense_taped(C.byref(w.xnet.pack()), v.data_ptr(), b.data_ptr(), None, tc, ts, n,
-                                           S.data_ptr(), T.data_ptr(), Q.data_ptr(), tape.h1[sl].data_ptr(),
-                                           tape.h2[sl].data_ptr(), s))
-        out, ld = torch.empty_like(x), torch.empty(n, dtype=torch.float32, device=x.device)
-        _lib.check(L.l2hmc_lf_update_x(x.data_ptr(), v.data_ptr(), keep.data_ptr(), S.data_ptr(), T.data_ptr(),
-                                       Q.data_ptr(), w.eps, d, n, D, out.data_ptr(), ld.data_ptr(), s))
+        _lib.call("l2hmc_stq_dense_taped", C.byref(w.xnet.pack()), v, b, None, tc, ts, n, S, T, Q, tape.h1[sl],
+                  tape.h2[sl], device=self.device)
+        out, ld = ops.lf_update_x(x, v, keep, S, T, Q, w.eps, d)
         lj += ld
         subs.append(("x", sl, x, v, None, keep))
         return out
@@ -199,16 +190,13 @@ class LayeredWalk:
         n = dS.shape[0]
         din = torch.empty(n, tape.Kin, dtype=torch.float32, device=dev)
         ws, nb = self._ws_bwd.get(L.l2hmc_dense_backward_data_ws_bytes(C.byref(st)), dev)
-        _lib.check(L.l2hmc_dense_backward_data(
-            C.byref(st), tape.S[sl].data_ptr(), tape.Q[sl].data_ptr(), dS.data_ptr(), dT.data_ptr(), dQ.data_ptr(),
-            tape.h1[sl].data_ptr(), tape.h2[sl].data_ptr(), n, tape.dpre[sl].data_ptr(), tape.dsq[sl].data_ptr(),
-            tape.dz2[sl].data_ptr(), tape.dz1[sl].data_ptr(), din.data_ptr(), ws, nb, _lib.stream_ptr(dev)))
+        _lib.call("l2hmc_dense_backward_data", C.byref(st), tape.S[sl], tape.Q[sl], dS, dT, dQ, tape.h1[sl], tape.h2[sl],
+                  n, tape.dpre[sl], tape.dsq[sl], tape.dz2[sl], tape.dz1[sl], din, ws, nb, device=dev)
         return din
 
     def reverse(self, w, subs, d, dx, dv, dld, tx, tv):
         """Walk one trajectory's sub-updates backwards from the cotangents of (x_N, v_N, sumlogdet); fills the tapes'
         cotangent slices and returns the per-row d/d eps partials of every sub-update."""
-        L, s = _lib.lib(), _lib.stream_ptr(self.device)
         eps = w.eps
         parts = []
         for kind, sl, xin, vin, g, keep in reversed(subs):
@@ -219,19 +207,15 @@ class LayeredWalk:
             de = torch.empty(n, dtype=torch.float32, device=xin.device)
             if kind == "v":
                 dv_in, dg = torch.empty_like(dv), torch.empty_like(dv)
-                _lib.check(L.l2hmc_lf_update_v_vjp(vin.data_ptr(), g.data_ptr(), S.data_ptr(), T.data_ptr(),
-                                                   Q.data_ptr(), eps, d, n, D, dv.data_ptr(), dld.data_ptr(),
-                                                   dv_in.data_ptr(), dg.data_ptr(), dS.data_ptr(), dT.data_ptr(),
-                                                   dQ.data_ptr(), de.data_ptr(), s))
+                _lib.call("l2hmc_lf_update_v_vjp", vin, g, S, T, Q, eps, d, n, D, dv, dld, dv_in, dg, dS, dT, dQ, de,
+                          device=self.device)
                 din = self._backward_data(w.vnet, tape, sl, dS, dT, dQ)
                 dx = dx + din[:, :D] + w.hvp(xin, (dg + din[:, D:]).contiguous())
                 dv = dv_in
             else:
                 dx_in, dv_part = torch.empty_like(dx), torch.empty_like(dx)
-                _lib.check(L.l2hmc_lf_update_x_vjp(xin.data_ptr(), vin.data_ptr(), keep.data_ptr(), S.data_ptr(),
-                                                   T.data_ptr(), Q.data_ptr(), eps, d, n, D, dx.data_ptr(),
-                                                   dld.data_ptr(), dx_in.data_ptr(), dv_part.data_ptr(), dS.data_ptr(),
-                                                   dT.data_ptr(), dQ.data_ptr(), de.data_ptr(), s))
+                _lib.call("l2hmc_lf_update_x_vjp", xin, vin, keep, S, T, Q, eps, d, n, D, dx, dld, dx_in, dv_part, dS,
+                          dT, dQ, de, device=self.device)
                 din = self._backward_data(w.xnet, tape, sl, dS, dT, dQ)
                 dx = (dx_in + keep * din[:, D:]).contiguous()
                 dv = (dv + dv_part + din[:, :D]).contiguous()
@@ -245,10 +229,8 @@ class LayeredWalk:
         st = net.pack()
         R = tape.off
         ws, nb = self._ws_wg.get(L.l2hmc_dense_weight_grads_ws_bytes(C.byref(st), R), dev)
-        _lib.check(L.l2hmc_dense_weight_grads(
-            C.byref(st), R, tape.inp.data_ptr(), tape.h1.data_ptr(), tape.h2.data_ptr(), tape.dz1.data_ptr(),
-            tape.dz2.data_ptr(), tape.dpre.data_ptr(), tape.dsq.data_ptr(), tape.tcs.data_ptr(), C.byref(g), ws, nb,
-            _lib.stream_ptr(dev)))
+        _lib.call("l2hmc_dense_weight_grads", C.byref(st), R, tape.inp, tape.h1, tape.h2, tape.dz1, tape.dz2, tape.dpre,
+                  tape.dsq, tape.tcs, C.byref(g), ws, nb, device=dev)
 
     def backward(self, fw, dxN, dvN, dld, gx, gv, after_net=None):
         """From the cotangents of (x_N, v_N, sumlogdet) in the stacked row order: the reverse walk of every run of

@@ -186,7 +186,7 @@ class _DenseSTQ:
         """After the flat buffer changed: rebuild the fragment-ordered image of the fused kernel."""
         if self._packed is not None and "packed" in self._packed[1]:
             st, bufs = self._packed
-            _lib.check(_lib.lib().l2hmc_dense_pack(C.byref(st), bufs["packed"].data_ptr(), _lib.stream_ptr(self._device)))
+            _lib.call("l2hmc_dense_pack", C.byref(st), bufs["packed"], device=self._device)
             self._pack_serial = getattr(self, "_pack_serial", 0) + 1
 
     def sync_reference_layout(self):
@@ -228,7 +228,7 @@ class _DenseSTQ:
             nbytes = L.l2hmc_dense_pack_bytes(C.byref(st))
             if nbytes:      # fragment-ordered image for the fused whole-trajectory kernel
                 bufs["packed"] = torch.empty(nbytes // 4, dtype=torch.float32, device=self._device)
-                _lib.check(L.l2hmc_dense_pack(C.byref(st), bufs["packed"].data_ptr(), _lib.stream_ptr(self._device)))
+                _lib.call("l2hmc_dense_pack", C.byref(st), bufs["packed"], device=self._device)
                 st.packed = bufs["packed"].data_ptr()
             self._packed = (st, bufs)
             # images derived from these weights elsewhere (GaugeDynamics' active-column heads) compare this counter
@@ -254,9 +254,7 @@ class _DenseSTQ:
         S, T, Q = (torch.empty(rows, st.D, dtype=torch.float32, device=a.device) for _ in range(3))
         L = _lib.lib()
         ws, nb = self._ws.get(L.l2hmc_stq_ws_bytes(rows, st.H), a.device)
-        _lib.check(L.l2hmc_stq_dense(C.byref(st), _lib.dev_ptr(a, name="a"), _lib.dev_ptr(b, name="b"), None,
-                                     tc, ts, rows, S.data_ptr(), T.data_ptr(), Q.data_ptr(), ws, nb,
-                                     _lib.stream_ptr(self._device)))
+        _lib.call("l2hmc_stq_dense", C.byref(st), a, b, None, tc, ts, rows, S, T, Q, ws, nb, device=self._device)
         return S, T, Q
 
     call = __call__
@@ -435,9 +433,8 @@ class ConvNet3D(_DenseSTQ):
         S, Tr, Q = (torch.empty(rows, st.D, dtype=torch.float32, device=a.device) for _ in range(3))
         L = _lib.lib()
         ws, nb = self._ws.get(L.l2hmc_stq_conv3d_ws_bytes(rows, st.H, T, X, fr.F), a.device)
-        _lib.check(L.l2hmc_stq_conv3d(C.byref(fr), C.byref(st), T, X, _lib.dev_ptr(a, name="a"),
-                                      _lib.dev_ptr(b, name="b"), None, float(t[0, 0]), float(t[0, 1]), rows,
-                                      S.data_ptr(), Tr.data_ptr(), Q.data_ptr(), ws, nb, _lib.stream_ptr(self._device)))
+        _lib.call("l2hmc_stq_conv3d", C.byref(fr), C.byref(st), T, X, a, b, None, float(t[0, 0]), float(t[0, 1]), rows,
+                  S, Tr, Q, ws, nb, device=self._device)
         return S, Tr, Q
 
     call = __call__

@@ -16,6 +16,7 @@
 // is the plaquette stencil with sin P -> cos P . P[u], chain-local in LDS.
 // All reductions have a fixed order: results are reproducible.
 #include "fused_common.h"
+#include "lf_update.h"
 #include <stdlib.h>
 
 namespace l2hmc {
@@ -259,8 +260,7 @@ __global__ __launch_bounds__(kFThreads) void gauge_train_bwd_fused_kernel(FusedB
             dgdr[k] = dgd;
           } else {
             // st = x before the update, ia = v; keep mask per direction and sub-update
-            const float mf = mfr[k], mb = mbr[k];
-            const float kk = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf), mi = 1.f - kk;
+            const float kk = keep_of(mfr[k], mbr[k], d, sub), mi = 1.f - kk;
             const float xx = st[k], vv = ia[k], u = udx[k];
             const float dy = mi * u;
             if (!d) {
@@ -400,8 +400,7 @@ __global__ __launch_bounds__(kFThreads) void gauge_train_bwd_fused_kernel(FusedB
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const int c = c0 + k;
-          const float mf = skm[c], mb = skm[D + c];
-          const float kk = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf);
+          const float kk = keep_of(skm[c], skm[D + c], d, sub);
           dvs[fc * SX + c] += dis[fc * SI + c];
           dxs[fc * SX + c] += kk * dis[fc * SI + D + c];
         }
@@ -525,7 +524,7 @@ __global__ __launch_bounds__(kFThreads) void gauge_trunk_bwd_kernel(TrunkBwdArgs
   const int64_t grow = row0 + (live ? fc : 0);     // (dead rows read row 0 of the tile and write nothing)
   const float dl = live ? p.dld[grow] : 0.f;
 
-  // ---- phase A: the sub-update, element-wise (gauge_dynamics.py:486-590 differentiated; update_bwd_kernel's math)
+  // ---- phase A: the sub-update, element-wise (gauge_dynamics.py:486-590 differentiated: lf_update.h)
   float acs[8], acq[8], deps = 0.f;
   {
     float S[8], Tt[8], Q[8], st[8], ia[8], ib[8], u[8], uv[8];
@@ -550,52 +549,17 @@ __global__ __launch_bounds__(kFThreads) void gauge_trunk_bwd_kernel(TrunkBwdArgs
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int c = c0 + k;
-      const float eq = expf(eps * Q[k]);
       float dS, dT, dQ;
       ndx[k] = u[k]; ndv[k] = uv[k]; ndg[k] = 0.f;
       if (is_v) {
         // st = v before the kick, ib = force
-        const float vv = st[k], gg = ib[k], uu = uv[k], he = 0.5f * eps;
-        if (!d) {
-          const float es = expf(he * S[k]);
-          const float ds = uu * vv * es + dl;
-          ndv[k] = uu * es;
-          dS = ds * he; dT = uu * he; dQ = -uu * he * eq * gg * eps;
-          ndg[k] = -uu * he * eq;
-          deps += ds * 0.5f * S[k] - uu * 0.5f * (eq * gg - Tt[k]) - uu * he * gg * eq * Q[k];
-        } else {
-          const float es = expf(-he * S[k]);
-          const float kick = he * (eq * gg - Tt[k]);
-          const float vp = es * (vv + kick);
-          const float dw = uu * es;
-          const float ds = uu * vp + dl;
-          ndv[k] = dw;
-          dS = -he * ds; dT = -dw * he; dQ = dw * he * eq * gg * eps;
-          ndg[k] = dw * he * eq;
-          deps += -0.5f * S[k] * ds + dw * 0.5f * (eq * gg - Tt[k]) + dw * he * gg * eq * Q[k];
-        }
+        lf_kick_vjp(st[k], ib[k], S[k], Tt[k], Q[k], eps, d, uv[k], dl, ndv[k], ndg[k], dS, dT, dQ, deps);
       } else {
         // st = x before the update, ia = v
-        const float kk = (d ? p.keep_b : p.keep_f)[c], mi = 1.f - kk;
-        const float xx = st[k], vv = ia[k], uu = u[k];
-        const float dy = mi * uu;
-        if (!d) {
-          const float es = expf(eps * S[k]);
-          const float ds = dy * xx * es + dl * mi;
-          ndx[k] = kk * uu + dy * es;
-          ndv[k] = uv[k] + dy * eps * eq;
-          dS = eps * ds; dT = dy * eps; dQ = dy * eps * eq * vv * eps;
-          deps += ds * S[k] + dy * (eq * vv + Tt[k]) + dy * eps * vv * eq * Q[k];
-        } else {
-          const float es = expf(-eps * S[k]);
-          const float w = xx - eps * (eq * vv + Tt[k]);
-          const float dw = dy * es;
-          const float ds = dy * (es * w) + dl * mi;
-          ndx[k] = kk * uu + dw;
-          ndv[k] = uv[k] - dw * eps * eq;
-          dS = -eps * ds; dT = -dw * eps; dQ = -dw * eps * eq * vv * eps;
-          deps += -S[k] * ds - dw * (eq * vv + Tt[k]) - dw * eps * vv * eq * Q[k];
-        }
+        float eq;
+        lf_drift_vjp(st[k], ia[k], (d ? p.keep_b : p.keep_f)[c], S[k], Tt[k], Q[k], eps, d, u[k], dl, ndx[k], dS, dT, dQ,
+                     eq, deps);
+        ndv[k] = uv[k] + dT * eq;
       }
       // through tanh(.) * exp(coeff) (generic_net.py:139-144)
       const float es_ = ec[c], eq_ = ec[D + c];

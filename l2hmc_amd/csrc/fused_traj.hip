@@ -24,6 +24,7 @@
 // shared by the 4 waves and read from LDS with conflict-free ds_read_b128
 // (row stride = K + 8 floats).
 #include "fused_step.h"
+#include "lf_update.h"
 #include <atomic>
 #include <stdlib.h>
 
@@ -699,22 +700,15 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
           for (int e = 0; e < 4; ++e) {
             const int c = al[wv * 16 + q * 4 + e];
             const int idx = r * SX + c;
-            const float S = fast_tanh(acc[0][e] + bhd[c]) * es[c];
-            const float Tt = acc[1][e] + bhd[D + c];
-            const float qq = acc[2][e] + bhd[2 * D + c];
-            const float Q = (net.q_tanh ? fast_tanh(qq) : qq) * eq[c];
-            const float mf = skm[c], mb = skm[D + c];
-            const float keep = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf);
-            const float x = xs[idx], v = vs[idx];
-            const float s = (d ? -eps : eps) * S;
-            const float drift = eps * (fast_exp(eps * Q) * v + Tt);
-            const float es_ = fast_exp(s);
-            const float upd = d ? es_ * (x - drift) : x * es_ + drift;
-            const float xn = keep * x + (1.f - keep) * upd;
+            float S, Tt, Q, s, omk;
+            heads_stq(acc[0][e], acc[1][e], acc[2][e], bhd[c], bhd[D + c], bhd[2 * D + c], es[c], eq[c], net.q_tanh, S,
+                      Tt, Q);
+            const float xn = lf_drift<ExpFast>(xs[idx], vs[idx], keep_of(skm[c], skm[D + c], d, sub), S, Tt, Q, eps, d, s,
+                                               omk);
             xs[idx] = xn;
-            stg[idx] = (1.f - keep) * s;
+            stg[idx] = omk * s;
             // (the columns this sub-update moves are the ones the next one keeps)
-            if (prep_next_mask) gs[l1c ? r * SX + scp[c] : idx] = (1.f - keep) * xn;
+            if (prep_next_mask) gs[l1c ? r * SX + scp[c] : idx] = omk * xn;
           }
         } else {
 #pragma unroll
@@ -723,9 +717,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
             const int idx = r * SX + c;
             stg[idx] = 0.f;
             if (prep_next_mask) {
-              const float mf = skm[c], mb = skm[D + c];
-              const float keep = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf);
-              const float kx = (1.f - keep) * xs[idx];
+              const float kx = (1.f - keep_of(skm[c], skm[D + c], d, sub)) * xs[idx];
               if (!l1c) gs[idx] = kx;
               else if (kx != kx) spz[kFM + r] = kx;
             }
@@ -747,10 +739,10 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         f32x4 S, Tt, Q;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          S[e] = fast_tanh(acc[0 * NTH + t][e] + b_s[e]) * e_s[e];
-          Tt[e] = acc[1 * NTH + t][e] + b_t[e];
-          const float qq = acc[2 * NTH + t][e] + b_q[e];
-          Q[e] = (net.q_tanh ? fast_tanh(qq) : qq) * e_q[e];
+          float s_, t_, q_;
+          heads_stq(acc[0 * NTH + t][e], acc[1 * NTH + t][e], acc[2 * NTH + t][e], b_s[e], b_t[e], b_q[e], e_s[e], e_q[e],
+                    net.q_tanh, s_, t_, q_);
+          S[e] = s_; Tt[e] = t_; Q[e] = q_;
         }
         if constexpr (TAPE) {
           if (r < nrow) {
@@ -768,10 +760,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
           f32x4 vn;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float s = (d ? -0.5f : 0.5f) * eps * S[e];
-            const float kick = 0.5f * eps * (fast_exp(eps * Q[e]) * g[e] - Tt[e]);
-            const float es_ = fast_exp(s);
-            vn[e] = d ? es_ * (v[e] + kick) : v[e] * es_ - kick;
+            float s;
+            vn[e] = lf_kick<ExpFast>(v[e], g[e], S[e], Tt[e], Q[e], eps, d, s);
             ld += s;
             if constexpr (RW > 1) { ld_k[e] = 1.f; ld_s[e] = s; }
           }
@@ -781,11 +771,11 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
             const f32x4 x = *reinterpret_cast<const f32x4*>(xs + idx);
             f32x4 kx;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) kx[e] = (d ? 1.f - mb[e] : mf[e]) * x[e];
+            for (int e = 0; e < 4; ++e) kx[e] = keep_of(mf[e], mb[e], d, 0) * x[e];
             if (l1c) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
-                if ((d ? 1.f - mb[e] : mf[e]) != 0.f) stg[r * SX + scp[c0 + e]] = kx[e];
+                if (keep_of(mf[e], mb[e], d, 0) != 0.f) stg[r * SX + scp[c0 + e]] = kx[e];
                 else if (kx[e] != kx[e]) spz[r] = kx[e];
               }
             } else {
@@ -799,15 +789,11 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
           f32x4 xn, kx;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float keep = sub == 0 ? (d ? 1.f - mb[e] : mf[e]) : (d ? mb[e] : 1.f - mf[e]);
-            const float s = (d ? -eps : eps) * S[e];
-            const float drift = eps * (fast_exp(eps * Q[e]) * v[e] + Tt[e]);
-            const float es_ = fast_exp(s);
-            const float upd = d ? es_ * (x[e] - drift) : x[e] * es_ + drift;
-            xn[e] = keep * x[e] + (1.f - keep) * upd;
-            ld += (1.f - keep) * s;
-            if constexpr (RW > 1) { ld_k[e] = 1.f - keep; ld_s[e] = s; }
-            kx[e] = (1.f - keep) * xn[e];
+            float s, omk;
+            xn[e] = lf_drift<ExpFast>(x[e], v[e], keep_of(mf[e], mb[e], d, sub), S[e], Tt[e], Q[e], eps, d, s, omk);
+            ld += omk * s;
+            if constexpr (RW > 1) { ld_k[e] = omk; ld_s[e] = s; }
+            kx[e] = omk * xn[e];
           }
           *reinterpret_cast<f32x4*>(xs + idx) = xn;
           // second sub-update follows: its keep mask is the complement (gauge_dynamics.py:434-437, :472-475)

@@ -10,15 +10,16 @@
 //
 // Same algorithm, same packed weight image, same arithmetic ORDER as fused_traj.hip
 // (l2hmc/dynamics/gauge_dynamics.py:261-313, :412-609; network/generic_net.py:129-146): a row's accumulators see
-// their k in the same order, epilogue expressions and log-det grouping are the 16-row form's, and everything around
-// net_update (draws, chain-local passes, accept, observables, step sums, write-back) is the one copy in fused_step.h
-// -- results are bit-identical
+// their k in the same order, the epilogue expressions are the one copy in lf_update.h, the log-det grouping is the
+// 16-row form's, and everything around net_update (draws, chain-local passes, accept, observables, step sums,
+// write-back) is the one copy in fused_step.h -- results are bit-identical
 // (tests/test_gpu_parity.py::test_subtile_and_32_row_forms_equal_16_row_form).
 //
 // LDS: x, v, force rows (3 x 32 x 136), ONE hidden buffer (32 x 520; the second layer's output overwrites its input
 // behind an extra barrier -- two buffers would need 218 KB), constants, masks, scratch: 153.7 KB.  GenericNet on the
 // 8x8 lattice (D = 128, H = 512), sampling only (no tape, no ConvNet3D).
 #include "fused_step.h"
+#include "lf_update.h"
 
 namespace l2hmc {
 
@@ -285,10 +286,10 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
           f32x4 S, Tt, Q;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            S[e] = fast_tanh(acc[g][0 * NTH + t][e] + b_s[e]) * e_s[e];
-            Tt[e] = acc[g][1 * NTH + t][e] + b_t[e];
-            const float qq = acc[g][2 * NTH + t][e] + b_q[e];
-            Q[e] = (net.q_tanh ? fast_tanh(qq) : qq) * e_q[e];
+            float s_, t_, q_;
+            heads_stq(acc[g][0 * NTH + t][e], acc[g][1 * NTH + t][e], acc[g][2 * NTH + t][e], b_s[e], b_t[e], b_q[e], e_s[e],
+                      e_q[e], net.q_tanh, s_, t_, q_);
+            S[e] = s_; Tt[e] = t_; Q[e] = q_;
           }
           if (mode == 1) {
             // gauge_dynamics.py:497-506 (fwd), :549-559 (bwd)
@@ -297,10 +298,8 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
             f32x4 vn;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float s = (d ? -0.5f : 0.5f) * eps * S[e];
-              const float kick = 0.5f * eps * (fast_exp(eps * Q[e]) * gg[e] - Tt[e]);
-              const float es_ = fast_exp(s);
-              vn[e] = d ? es_ * (v[e] + kick) : v[e] * es_ - kick;
+              float s;
+              vn[e] = lf_kick<ExpFast>(v[e], gg[e], S[e], Tt[e], Q[e], eps, d, s);
               ld += s;
               ld_s[g][e] = s;
             }
@@ -309,7 +308,7 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
               const f32x4 x = *reinterpret_cast<const f32x4*>(xs + idx);
               f32x4 kx;
 #pragma unroll
-              for (int e = 0; e < 4; ++e) kx[e] = (d ? 1.f - mb[e] : mf[e]) * x[e];
+              for (int e = 0; e < 4; ++e) kx[e] = keep_of(mf[e], mb[e], d, 0) * x[e];
               *reinterpret_cast<f32x4*>(gs + idx) = kx;
             }
           } else {
@@ -319,15 +318,14 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
             f32x4 xn, kx;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
+              // keep_of(mf[e], mb[e], d, sub) spelled out: through the helper this kernel (256 VGPRs) spills one
+              // register more; the odd wave's replay below takes the same value from keep_of
               const float keep = sub == 0 ? (d ? 1.f - mb[e] : mf[e]) : (d ? mb[e] : 1.f - mf[e]);
-              const float s = (d ? -eps : eps) * S[e];
-              const float drift = eps * (fast_exp(eps * Q[e]) * v[e] + Tt[e]);
-              const float es_ = fast_exp(s);
-              const float upd = d ? es_ * (x[e] - drift) : x[e] * es_ + drift;
-              xn[e] = keep * x[e] + (1.f - keep) * upd;
-              ld += (1.f - keep) * s;
+              float s, omk;
+              xn[e] = lf_drift<ExpFast>(x[e], v[e], keep, S[e], Tt[e], Q[e], eps, d, s, omk);
+              ld += omk * s;
               ld_s[g][e] = s;
-              kx[e] = (1.f - keep) * xn[e];
+              kx[e] = omk * xn[e];
             }
             *reinterpret_cast<f32x4*>(xs + idx) = xn;
             if (prep_next_mask) *reinterpret_cast<f32x4*>(gs + idx) = kx;
@@ -335,7 +333,8 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
         }
         // The bits of the 4-wave form are those of ONE chain of adds per lane over both waves' head columns, then the
         // cross-lane steps: the even wave hands its lane sum over, the odd wave continues the chain with its own four
-        // terms behind the barrier below (ld_k, ld_s; fused_traj.hip has the same hand-off) and does the rest.
+        // terms behind the barrier below (ld_s, the keep mask again from keep_of; fused_traj.hip hands ld_k over too)
+        // and does the rest.
         if (wsub == 0) ldx[(wimg * kG32 + g) * 64 + lane] = ld;
       }
     }
@@ -349,14 +348,10 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
         const f32x4 mf = *reinterpret_cast<const f32x4*>(skm + c0);
         const f32x4 mb = *reinterpret_cast<const f32x4*>(skm + D + c0);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {                                    // the statements of the chain above, verbatim
+        for (int e = 0; e < 4; ++e) {                                    // the `ld +=` statements of the chain above
           const float s = ld_s[g][e];
-          if (mode == 1) {
-            ld += s;
-          } else {
-            const float keep = sub == 0 ? (d ? 1.f - mb[e] : mf[e]) : (d ? mb[e] : 1.f - mf[e]);
-            ld += (1.f - keep) * s;
-          }
+          if (mode == 1) ld += s;
+          else ld += (1.f - keep_of(mf[e], mb[e], d, sub)) * s;
         }
         // the row's log-det share of this image wave: lanes r, r + 16, r + 32, r + 48 (fixed order: bit-reproducible)
         ld += __shfl_xor(ld, 16, 64);

@@ -11,9 +11,10 @@
 //
 // Same algorithm, same arithmetic ORDER as fused_traj.hip (l2hmc/dynamics/gauge_dynamics.py:261-313, :412-609;
 // network/generic_net.py:129-146): a product's k runs in the order the 16-row form's instructions take it (within a
-// 16-k chunk: k = 4 q + e for e = 0..3, q = 0..3), epilogue expressions are the same, the log-det partial sums are added
-// in the same grouping, and everything around net_update (draws, chain-local passes, accept, observables, step sums,
-// write-back) is the one copy in fused_step.h -- the results are bit-identical to the 16-row form
+// 16-k chunk: k = 4 q + e for e = 0..3, q = 0..3), the epilogue expressions are the one copy in lf_update.h, the
+// log-det partial sums are added in the same grouping, and everything around net_update (draws, chain-local passes,
+// accept, observables, step sums, write-back) is the one copy in fused_step.h -- the results are bit-identical to the
+// 16-row form
 // (tests/test_gpu_parity.py::test_subtile_and_32_row_forms_equal_16_row_form).
 //
 // Geometry: 4 waves; wave w owns output columns [128 w, 128 w + 128) of layers 1 / 2 (two 64-column blocks) and columns
@@ -21,6 +22,7 @@
 // column and 4 rows per row group (register i = row).  ROWS = 4, 8 or 12 rows per workgroup (1 to 3 row groups sharing
 // every weight fragment).  GenericNet on the 8x8 lattice (D = 128, H = 512), sampling only (no tape, no ConvNet3D).
 #include "fused_step.h"
+#include "lf_update.h"
 
 namespace l2hmc {
 
@@ -283,36 +285,24 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
         for (int i = 0; i < 4; ++i) {
           const int row = 4 * g + i;
           const float aT = __shfl(acc[g][0][i], cl + 32, 64);      // the T product of this column sits 32 lanes up
-          const float S = fast_tanh(acc[g][0][i] + b_s) * e_s;
-          const float Tt = aT + b_t;
-          const float qq = acc[g][1][i] + b_q;
-          const float Q = (net.q_tanh ? fast_tanh(qq) : qq) * e_q;
+          float S, Tt, Q;
+          heads_stq(acc[g][0][i], aT, acc[g][1][i], b_s, b_t, b_q, e_s, e_q, net.q_tanh, S, Tt, Q);
           const int d = dirr[g][i];
           const int idx = row * SX + c;
           float term;
           if (mode == 1) {
-            const float gg = gs[idx], v = vs[idx];
-            const float s = (d ? -0.5f : 0.5f) * eps * S;
-            const float kick = 0.5f * eps * (fast_exp(eps * Q) * gg - Tt);
-            const float es_ = fast_exp(s);
-            const float vn = d ? es_ * (v + kick) : v * es_ - kick;
-            term = s;
+            const float vn = lf_kick<ExpFast>(vs[idx], gs[idx], S, Tt, Q, eps, d, term);
             if (lane < 32) {
               vs[idx] = vn;
-              if (prep_next_mask) gs[idx] = (d ? 1.f - mb : mf) * xs[idx];
+              if (prep_next_mask) gs[idx] = keep_of(mf, mb, d, 0) * xs[idx];
             }
           } else {
-            const float x = xs[idx], v = vs[idx];
-            const float keep = sub == 0 ? (d ? 1.f - mb : mf) : (d ? mb : 1.f - mf);
-            const float s = (d ? -eps : eps) * S;
-            const float drift = eps * (fast_exp(eps * Q) * v + Tt);
-            const float es_ = fast_exp(s);
-            const float upd = d ? es_ * (x - drift) : x * es_ + drift;
-            const float xn = keep * x + (1.f - keep) * upd;
-            term = (1.f - keep) * s;
+            float s, omk;
+            const float xn = lf_drift<ExpFast>(xs[idx], vs[idx], keep_of(mf, mb, d, sub), S, Tt, Q, eps, d, s, omk);
+            term = omk * s;
             if (lane < 32) {
               xs[idx] = xn;
-              if (prep_next_mask) gs[idx] = (1.f - keep) * xn;
+              if (prep_next_mask) gs[idx] = omk * xn;
             }
           }
           if (lane < 32) myst[row * 32 + cl] = term;

@@ -6,21 +6,20 @@
 // The orchestration (which sub-update, which tape slice) lives in l2hmc_amd/layered_train.py; every entry here takes
 // any positive D, H, Ka, Kb and any row count:
 //   * l2hmc_stq_dense_taped: l2hmc_stq_dense with h1 / h2 in caller buffers (same launches, same bits);
-//   * l2hmc_lf_update_{v,x}_vjp: reverse of one sub-update (the algebra of train.hip's update_bwd_kernel, dense rows);
+//   * l2hmc_lf_update_{v,x}_vjp: reverse of one sub-update (lf_update.h, dense rows);
 //   * l2hmc_dense_backward_data: cotangents of (S, T, Q) -> head pre-activations -> h2 -> h1 -> network inputs, on
 //     the matrix pipe (gemm_relu_kernel KIND 3 / 4, bounds-checked when widths are ragged);
 //   * l2hmc_dense_weight_grads: once per network and step, over all calls' tapes stacked along rows: split-k "TN"
 //     MFMA products with bounds-checked staging and column sums, each reduced in a fixed order (no float atomics).
 #include "stq_dense.h"
+#include "lf_update.h"
 
 namespace l2hmc {
 
 using f32x16_lt = __attribute__((ext_vector_type(16))) float;
 
 // ---------------------------------------------------------------------------------------------------------------
-// reverse of lf_update_v_kernel (leapfrog.hip) for ANY cotangents: one wave per row.
-//   dir 0:  v' = v e^s - k,       s = eps/2 S,  k = eps/2 (e^{eps Q} g - T)
-//   dir 1:  v' = e^s (v + k),     s = -eps/2 S
+// reverse of lf_update_v_kernel (leapfrog.hip) for ANY cotangents, lf_kick_vjp of lf_update.h: one wave per row.
 // Inputs: u = d/dv', dl = d/dlogdet (logdet += sum_d s).  Outputs: dv, dg, dS, dT, dQ [rows][D], deps [rows].
 __global__ __launch_bounds__(256) void lf_update_v_vjp_kernel(
     const float* __restrict__ v, const float* __restrict__ g, const float* __restrict__ S, const float* __restrict__ T,
@@ -31,42 +30,16 @@ __global__ __launch_bounds__(256) void lf_update_v_vjp_kernel(
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float dl = dld ? dld[row] : 0.f;
-  const float he = 0.5f * eps;
   float de = 0.f;
   for (int c = lane; c < D; c += kWave) {
     const int64_t i = row * D + c;
-    const float Sv = S[i], Tv = T[i], Qv = Q[i], gv = g[i], vv = v[i], u = dvo[i];
-    const float eq = expf(eps * Qv);
-    if (!d) {
-      const float es = expf(he * Sv);
-      const float ds = u * vv * es + dl;
-      dv[i] = u * es;
-      dS[i] = ds * he;
-      dT[i] = u * he;
-      dQ[i] = -u * he * eq * gv * eps;
-      dg[i] = -u * he * eq;
-      de += ds * 0.5f * Sv - u * 0.5f * (eq * gv - Tv) - u * he * gv * eq * Qv;
-    } else {
-      const float es = expf(-he * Sv);
-      const float kick = he * (eq * gv - Tv);
-      const float vp = es * (vv + kick);
-      const float dw = u * es;
-      const float ds = u * vp + dl;
-      dv[i] = dw;
-      dS[i] = -he * ds;
-      dT[i] = -dw * he;
-      dQ[i] = dw * he * eq * gv * eps;
-      dg[i] = dw * he * eq;
-      de += -0.5f * Sv * ds + dw * 0.5f * (eq * gv - Tv) + dw * he * gv * eq * Qv;
-    }
+    lf_kick_vjp(v[i], g[i], S[i], T[i], Q[i], eps, d, dvo[i], dl, dv[i], dg[i], dS[i], dT[i], dQ[i], de);
   }
   de = wave_sum(de);
   if (lane == 0) deps[row] = de;
 }
 
-// reverse of lf_update_x_kernel: x' = k x + (1 - k) y with
-//   dir 0:  y = x e^s + eps (e^{eps Q} v + T),   s = eps S
-//   dir 1:  y = e^s (x - eps (e^{eps Q} v + T)), s = -eps S          (logdet += sum_d (1 - k) s)
+// reverse of lf_update_x_kernel (lf_drift_vjp of lf_update.h; logdet += sum_d (1 - k) s).
 // Outputs: dx, dv (the cotangent of v through this update alone), dS, dT, dQ [rows][D], deps [rows].
 __global__ __launch_bounds__(256) void lf_update_x_vjp_kernel(
     const float* __restrict__ x, const float* __restrict__ v, const float* __restrict__ keep,
@@ -81,31 +54,10 @@ __global__ __launch_bounds__(256) void lf_update_x_vjp_kernel(
   float de = 0.f;
   for (int c = lane; c < D; c += kWave) {
     const int64_t i = row * D + c;
-    const float Sv = S[i], Tv = T[i], Qv = Q[i], xv = x[i], vv = v[i], u = dxo[i];
-    const float k = keep[c], mi = 1.f - k;
-    const float eq = expf(eps * Qv);
-    const float dy = mi * u;
-    if (!d) {
-      const float es = expf(eps * Sv);
-      const float ds = dy * xv * es + dl * mi;
-      dx[i] = k * u + dy * es;
-      dv[i] = dy * eps * eq;
-      dS[i] = eps * ds;
-      dT[i] = dy * eps;
-      dQ[i] = dy * eps * eq * vv * eps;
-      de += ds * Sv + dy * (eq * vv + Tv) + dy * eps * vv * eq * Qv;
-    } else {
-      const float es = expf(-eps * Sv);
-      const float w = xv - eps * (eq * vv + Tv);
-      const float dw = dy * es;
-      const float ds = dy * (es * w) + dl * mi;
-      dx[i] = k * u + dw;
-      dv[i] = -dw * eps * eq;
-      dS[i] = -eps * ds;
-      dT[i] = -dw * eps;
-      dQ[i] = -dw * eps * eq * vv * eps;
-      de += -Sv * ds - dw * (eq * vv + Tv) - dw * eps * vv * eq * Qv;
-    }
+    float dt, eq;
+    lf_drift_vjp(x[i], v[i], keep[c], S[i], T[i], Q[i], eps, d, dxo[i], dl, dx[i], dS[i], dt, dQ[i], eq, de);
+    dT[i] = dt;
+    dv[i] = dt * eq;
   }
   de = wave_sum(de);
   if (lane == 0) deps[row] = de;

@@ -2,6 +2,7 @@
 // mixing / Metropolis-Hastings, and the host-side orchestration of the lattice
 // trajectory: l2hmc/dynamics/gauge_dynamics.py:195-313, :412-609.
 #include "stq_dense.h"
+#include "lf_update.h"
 #include <atomic>
 #include <math.h>
 
@@ -25,10 +26,8 @@ __global__ __launch_bounds__(256) void lf_update_v_kernel(
   for (int c = lane; c < D; c += kWave) {
     const int64_t i = row * D + c;
     const float Sv = S ? S[i] : 0.f, Tv = T ? T[i] : 0.f, Qv = Q ? Q[i] : 0.f;
-    const float s = (d ? -0.5f : 0.5f) * eps * Sv;
-    const float kick = 0.5f * eps * (expf(eps * Qv) * grad[i] - Tv);
-    const float vv = v[i];
-    v_out[i] = d ? expf(s) * (vv + kick) : vv * expf(s) - kick;
+    float s;
+    v_out[i] = lf_kick<ExpLibm>(v[i], grad[i], Sv, Tv, Qv, eps, d, s);
     ld += s;
   }
   ld = wave_sum(ld);
@@ -49,13 +48,9 @@ __global__ __launch_bounds__(256) void lf_update_x_kernel(
   for (int c = lane; c < D; c += kWave) {
     const int64_t i = row * D + c;
     const float Sv = S ? S[i] : 0.f, Tv = T ? T[i] : 0.f, Qv = Q ? Q[i] : 0.f;
-    const float k = keep[c];
-    const float s = (d ? -eps : eps) * Sv;
-    const float drift = eps * (expf(eps * Qv) * v[i] + Tv);
-    const float xx = x[i];
-    const float upd = d ? expf(s) * (xx - drift) : xx * expf(s) + drift;
-    x_out[i] = k * xx + (1.f - k) * upd;
-    ld += (1.f - k) * s;
+    float s, omk;
+    x_out[i] = lf_drift<ExpLibm>(x[i], v[i], keep[c], Sv, Tv, Qv, eps, d, s, omk);
+    ld += omk * s;
   }
   ld = wave_sum(ld);
   if (lane == 0 && logdet) logdet[row] = accumulate ? logdet[row] + ld : ld;

@@ -14,6 +14,7 @@
 // (small_train.hip) keeps the earlier sixteen-lanes-per-chain VALU form of
 // small_mlp.h.
 #include "small_mlp.h"
+#include "lf_update.h"
 #include <atomic>
 
 namespace l2hmc {
@@ -683,10 +684,9 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
       for (int half = 0; half < 2; ++half) {
         if (half == 1) {
           for (int sub = 0; sub < 2; ++sub) {       // keep mask m then 1 - m (fwd) / 1 - m then m (bwd)
-            const bool keep_is_m = (sub == 0) != (bwd != 0);
 #pragma unroll
             for (int d = 0; d < MD; ++d) {
-              const float k = d < dim ? (keep_is_m ? m[d] : 1.f - m[d]) : 1.f;
+              const float k = d < dim ? keep_of(m[d], m[d], bwd, sub) : 1.f;
               bin[d] = k * x[d];
             }
             if (!P.hmc) {
@@ -697,13 +697,9 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
 #pragma unroll
             for (int d = 0; d < MD; ++d) {
               if (d < dim) {
-                const float k = keep_is_m ? m[d] : 1.f - m[d];
-                const float s = (bwd ? -eps : eps) * S[d];
-                const float drift = eps * (fast_exp(eps * Q[d]) * v[d] + T[d]);
-                const float es_ = fast_exp(s);
-                const float upd = bwd ? es_ * (x[d] - drift) : x[d] * es_ + drift;
-                x[d] = k * x[d] + (1.f - k) * upd;
-                logdet += (1.f - k) * s;
+                float s, omk;
+                x[d] = lf_drift<ExpFast>(x[d], v[d], keep_of(m[d], m[d], bwd, sub), S[d], T[d], Q[d], eps, bwd, s, omk);
+                logdet += omk * s;
               }
             }
 #ifdef L2HMC_STAMPS
@@ -721,10 +717,8 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
 #pragma unroll
         for (int d = 0; d < MD; ++d) {
           if (d < dim) {
-            const float s = (bwd ? -0.5f : 0.5f) * eps * S[d];
-            const float kick = 0.5f * eps * (fast_exp(eps * Q[d]) * g[d] - T[d]);
-            const float es_ = fast_exp(s);
-            v[d] = bwd ? es_ * (v[d] + kick) : v[d] * es_ - kick;
+            float s;
+            v[d] = lf_kick<ExpFast>(v[d], g[d], S[d], T[d], Q[d], eps, bwd, s);
             logdet += s;
           }
         }

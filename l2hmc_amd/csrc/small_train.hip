@@ -21,6 +21,7 @@
 //    writes its partial gradient (same layout as the packed weights), summed in order afterwards.
 // No atomics anywhere: gradients are reproducible.
 #include "small_mlp.h"
+#include "lf_update.h"
 #include <type_traits>
 #include "stq_dense.h"      // diagnostic stamp globals
 
@@ -476,11 +477,10 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
     for (int half = 0; half < 2; ++half) {
       if (half == 1) {
         for (int sub = 0; sub < 2; ++sub) {
-          const bool keep_is_m = (sub == 0) != (bwd != 0);
           float* tp = mytape + (size_t)(it * 4 + 1 + sub) * 3 * dim;
 #pragma unroll
           for (int d = 0; d < kMaxDim; ++d) {
-            const float k = d < dim ? (keep_is_m ? m[d] : 1.f - m[d]) : 1.f;
+            const float k = d < dim ? keep_of(m[d], m[d], bwd, sub) : 1.f;
             bin[d] = k * x[d];
             if (d < dim && lsub == 0) {
               tp[d] = v[d];
@@ -492,12 +492,9 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
 #pragma unroll
           for (int d = 0; d < kMaxDim; ++d) {
             if (d < dim) {
-              const float k = keep_is_m ? m[d] : 1.f - m[d];
-              const float s = (bwd ? -eps : eps) * S[d];
-              const float drift = eps * (expf(eps * Q[d]) * v[d] + T[d]);
-              const float upd = bwd ? expf(s) * (x[d] - drift) : x[d] * expf(s) + drift;
-              x[d] = k * x[d] + (1.f - k) * upd;
-              logdet += (1.f - k) * s;
+              float s, omk;
+              x[d] = lf_drift<ExpLibm>(x[d], v[d], keep_of(m[d], m[d], bwd, sub), S[d], T[d], Q[d], eps, bwd, s, omk);
+              logdet += omk * s;
             }
           }
         }
@@ -517,9 +514,8 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
 #pragma unroll
       for (int d = 0; d < kMaxDim; ++d) {
         if (d < dim) {
-          const float s = (bwd ? -0.5f : 0.5f) * eps * S[d];
-          const float kick = 0.5f * eps * (expf(eps * Q[d]) * g[d] - T[d]);
-          v[d] = bwd ? expf(s) * (v[d] + kick) : v[d] * expf(s) - kick;
+          float s;
+          v[d] = lf_kick<ExpLibm>(v[d], g[d], S[d], T[d], Q[d], eps, bwd, s);
           logdet += s;
         }
       }
@@ -622,8 +618,8 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       dS[d] = dT[d] = dQ[d] = dgd[d] = 0.f;
       keep[d] = 1.f;
       if (d >= dim) continue;
-      const float eq = expf(eps * Q[d]);
       if (vcall) {
+        const float eq = expf(eps * Q[d]);
         const float vv = st[d], gg = bin[d], u = dv[d], he = 0.5f * eps;
         if (!bwd) {
           const float es = expf(he * S[d]);
@@ -643,28 +639,10 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
           deps += -0.5f * S[d] * ds + dw * 0.5f * (eq * gg - T[d]) + dw * he * gg * eq * Q[d];
         }
       } else {
-        const bool keep_is_m = (kind == 1) != (bwd != 0);
-        const float k = keep_is_m ? m[d] : 1.f - m[d], mi = 1.f - k;
-        keep[d] = k;
-        const float xx = st[d], vv = ain[d], u = dx[d];
-        const float dy = mi * u;
-        if (!bwd) {
-          const float es = expf(eps * S[d]);
-          const float ds = dy * xx * es + dl * mi;
-          dx[d] = k * u + dy * es;
-          dv[d] += dy * eps * eq;
-          dS[d] = eps * ds; dT[d] = dy * eps; dQ[d] = dy * eps * eq * vv * eps;
-          deps += ds * S[d] + dy * (eq * vv + T[d]) + dy * eps * vv * eq * Q[d];
-        } else {
-          const float es = expf(-eps * S[d]);
-          const float w = xx - eps * (eq * vv + T[d]);
-          const float dw = dy * es;
-          const float ds = dy * (es * w) + dl * mi;
-          dx[d] = k * u + dw;
-          dv[d] -= dw * eps * eq;
-          dS[d] = -eps * ds; dT[d] = -dw * eps; dQ[d] = -dw * eps * eq * vv * eps;
-          deps += -S[d] * ds - dw * (eq * vv + T[d]) - dw * eps * vv * eq * Q[d];
-        }
+        keep[d] = keep_of(m[d], m[d], bwd, kind - 1);
+        float eq;
+        lf_drift_vjp(st[d], ain[d], keep[d], S[d], T[d], Q[d], eps, bwd, dx[d], dl, dx[d], dS[d], dT[d], dQ[d], eq, deps);
+        dv[d] += dT[d] * eq;
       }
     }
     float dout[3][kMaxDim], dSS[kMaxDim], dQQ[kMaxDim];

@@ -23,6 +23,7 @@
 // 16-row ones).  Tile ids are remapped so tiles sharing activation rows land on
 // one XCD (shared L2).
 #include "stq_dense.h"
+#include "lf_update.h"
 
 namespace l2hmc {
 
@@ -457,10 +458,8 @@ __device__ __forceinline__ HeadsCol heads_col(const HeadsArgs& p, int col, bool 
 }
 __device__ __forceinline__ float heads_element(const HeadsArgs& p, const HeadsCol& c, int64_t row, int col, float aS,
                                                float aT, float aQ) {
-  const float S = fast_tanh(aS + c.b_s) * c.e_s;
-  const float T = aT + c.b_t;
-  float Q = aQ + c.b_q;
-  Q = (p.q_tanh ? fast_tanh(Q) : Q) * c.e_q;
+  float S, T, Q;
+  heads_stq(aS, aT, aQ, c.b_s, c.b_t, c.b_q, c.e_s, c.e_q, p.q_tanh, S, T, Q);
   const int64_t idx = row * p.D + col;
   if (p.mode == kHeadsMaterialise) {
     p.S[idx] = S;
@@ -469,25 +468,15 @@ __device__ __forceinline__ float heads_element(const HeadsArgs& p, const HeadsCo
     return 0.f;
   }
   const int d = p.dir ? p.dir[row] : 0;
-  const float eps = p.eps;
+  float s, omk;
   if (p.mode == kHeadsUpdateV) {
     // gauge_dynamics.py:497-506 (fwd), :549-559 (bwd)
-    const float g = p.g[idx], v = p.v[idx];
-    const float s = (d ? -0.5f : 0.5f) * eps * S;
-    const float tq = eps * Q;
-    const float kick = 0.5f * eps * (fast_exp(tq) * g - T);
-    p.v[idx] = d ? fast_exp(s) * (v + kick) : v * fast_exp(s) - kick;
+    p.v[idx] = lf_kick<ExpFast>(p.v[idx], p.g[idx], S, T, Q, p.eps, d, s);
     return s;
   }
   // gauge_dynamics.py:519-531 (fwd), :574-584 (bwd)
-  const float keep = d ? c.kb : c.kf;
-  const float x = p.x[idx], v = p.v[idx];
-  const float s = (d ? -eps : eps) * S;
-  const float tq = eps * Q;
-  const float drift = eps * (fast_exp(tq) * v + T);
-  const float upd = d ? fast_exp(s) * (x - drift) : x * fast_exp(s) + drift;
-  p.x[idx] = keep * x + (1.f - keep) * upd;
-  return (1.f - keep) * s;
+  p.x[idx] = lf_drift<ExpFast>(p.x[idx], p.v[idx], d ? c.kb : c.kf, S, T, Q, p.eps, d, s, omk);
+  return omk * s;
 }
 
 // BM = 32: half-height row tiles for launches with few live tiles (the active-column form of a small batch: cfg 4's

@@ -23,6 +23,7 @@
 //    one bucket per network.
 //  * every reduction runs in a fixed order (no float atomics): results are reproducible.
 #include "stq_dense.h"
+#include "lf_update.h"
 #include <math.h>
 
 namespace l2hmc {
@@ -68,20 +69,13 @@ __global__ __launch_bounds__(256) void train_update_kernel(int mode, const float
   for (int c = lane; c < D; c += kWave) {
     const int64_t i = row * D + c;
     const float S = stq[i], T = stq[plane + i], Q = stq[2 * plane + i];
+    float s, omk;
     if (mode == 1) {
-      const float s = (d ? -0.5f : 0.5f) * eps * S;
-      const float kick = 0.5f * eps * (expf(eps * Q) * g[i] - T);
-      const float vv = v[i];
-      v[i] = d ? expf(s) * (vv + kick) : vv * expf(s) - kick;
+      v[i] = lf_kick<ExpLibm>(v[i], g[i], S, T, Q, eps, d, s);
       acc += s;
     } else {
-      const float k = (d ? keep_b : keep_f)[c];
-      const float s = (d ? -eps : eps) * S;
-      const float drift = eps * (expf(eps * Q) * v[i] + T);
-      const float xx = x[i];
-      const float upd = d ? expf(s) * (xx - drift) : xx * expf(s) + drift;
-      x[i] = k * xx + (1.f - k) * upd;
-      acc += (1.f - k) * s;
+      x[i] = lf_drift<ExpLibm>(x[i], v[i], (d ? keep_b : keep_f)[c], S, T, Q, eps, d, s, omk);
+      acc += omk * s;
     }
   }
   acc = wave_sum(acc);
@@ -143,50 +137,14 @@ __global__ __launch_bounds__(256) void update_bwd_kernel(UpdBwdArgs p) {
       const int d = p.dir ? p.dir[row] : 0;
       const float S = p.stq[i], T = p.stq[p.plane + i], Q = p.stq[2 * p.plane + i];
       const float dl = p.dld[row];
-      const float eq = expf(eps * Q);
       float dS, dT, dQ;
       if (p.mode == 1) {
-        const float v = p.st[i], g = p.in[row * 2 * D + D + c], u = p.dv[i];
-        const float he = 0.5f * eps;
-        if (!d) {
-          const float es = expf(he * S);
-          const float ds = u * v * es + dl;
-          p.dv[i] = u * es;
-          dS = ds * he; dT = u * he; dQ = -u * he * eq * g * eps;
-          p.dg[i] = -u * he * eq;
-          deps += ds * 0.5f * S - u * 0.5f * (eq * g - T) - u * he * g * eq * Q;
-        } else {
-          const float es = expf(-he * S);
-          const float kick = he * (eq * g - T);
-          const float vp = es * (v + kick);
-          const float dw = u * es;
-          const float ds = u * vp + dl;
-          p.dv[i] = dw;
-          dS = -he * ds; dT = -dw * he; dQ = dw * he * eq * g * eps;
-          p.dg[i] = dw * he * eq;
-          deps += -0.5f * S * ds + dw * 0.5f * (eq * g - T) + dw * he * g * eq * Q;
-        }
+        lf_kick_vjp(p.st[i], p.in[row * 2 * D + D + c], S, T, Q, eps, d, p.dv[i], dl, p.dv[i], p.dg[i], dS, dT, dQ, deps);
       } else {
-        const float k = (d ? p.keep_b : p.keep_f)[c], mi = 1.f - k;
-        const float x = p.st[i], v = p.in[row * 2 * D + c], u = p.dx[i];
-        const float dy = mi * u;
-        if (!d) {
-          const float es = expf(eps * S);
-          const float ds = dy * x * es + dl * mi;
-          p.dx[i] = k * u + dy * es;
-          p.dv[i] += dy * eps * eq;
-          dS = eps * ds; dT = dy * eps; dQ = dy * eps * eq * v * eps;
-          deps += ds * S + dy * (eq * v + T) + dy * eps * v * eq * Q;
-        } else {
-          const float es = expf(-eps * S);
-          const float w = x - eps * (eq * v + T);
-          const float dw = dy * es;
-          const float ds = dy * (es * w) + dl * mi;
-          p.dx[i] = k * u + dw;
-          p.dv[i] -= dw * eps * eq;
-          dS = -eps * ds; dT = -dw * eps; dQ = -dw * eps * eq * v * eps;
-          deps += -S * ds - dw * (eq * v + T) - dw * eps * v * eq * Q;
-        }
+        float eq;
+        lf_drift_vjp(p.st[i], p.in[row * 2 * D + c], (d ? p.keep_b : p.keep_f)[c], S, T, Q, eps, d, p.dx[i], dl, p.dx[i],
+                     dS, dT, dQ, eq, deps);
+        p.dv[i] += dT * eq;
       }
       // through tanh(.) * exp(coeff) (generic_net.py:139-144)
       const float th = S / ecs;

@@ -558,6 +558,30 @@ int l2hmc_small_run_tempered(const l2hmc_small_plan* plan, const float* x_in, fl
                              const float* temps, int64_t step_stride, int64_t chain_stride,
                              float* px, float* samples, l2hmc_stream_t stream);
 
+/* A RUN of n_steps consecutive sampler steps of a plain-HMC plan (plan->hmc != 0: no networks, the forward trajectory
+ * only, utils/sampler.py:30-32) in ONE launch, with the results of the loop over l2hmc_fill_normal(seed, draw0 + 2 s),
+ * l2hmc_small_trajectory, l2hmc_fill_uniform(seed, draw0 + 2 s + 1) and l2hmc_mix_accept(strict = 0, coin = 1, the
+ * proposal in both slots) chained through its output, bit for bit.  Step s takes its momenta (element c * x_dim + d for
+ * chain c) and its Metropolis-Hastings uniforms (element c) from those two Philox streams and starts from the output
+ * of step s - 1 (step 0 from x_in).  px (or NULL) is [n_steps][B], samples (or NULL) [n_steps][B][x_dim] with every
+ * step's output; the final state always goes to x_next [B][x_dim], which may alias x_in.
+ * A kernel of its own (small_hmc.hip): one thread per chain with the chain in registers for the whole launch, one wave
+ * per workgroup, the target and the masks staged once.  No workspace, no host synchronisation; the call can be captured
+ * into a HIP graph.  plan->xnet / vnet / num_nodes / first_layer_form are not read.
+ * temps (DEVICE pointer, or NULL: plan->target.temperature for every step and chain) has the meaning and the strides
+ * of l2hmc_small_run_tempered: step s of chain c runs at temps[s * step_stride + c * chain_stride]; the strides are
+ * not read when temps is NULL.  eps_chain (DEVICE pointer, or NULL: plan->eps for every chain) is [B]: chain c
+ * integrates with step size eps_chain[c].  Chains never interact, so the columns of a ladder of temperatures or of
+ * step sizes are independent runs.  The VALUES of both arrays are not checked (as in l2hmc_small_run_tempered; a step
+ * size that is 0, negative or not finite is no step size: callers check, DynamicsSampler.run_hmc does).
+ * Refused with L2HMC_ERR_ARG before any device call: NULL plan / x_in / x_next, B < 0, n_steps <= 0, an L2HMC plan
+ * (hmc == 0: that is l2hmc_small_run's), draw0 + 2 n_steps beyond 2^64 - 1, a negative stride, x_dim != target.dim,
+ * trajectory_length <= 0 or NULL masks (or more masks than 64 KiB of LDS hold), and what every entry refuses of a
+ * target.  B == 0 is a no-op. */
+int l2hmc_small_hmc_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                        uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride, int64_t chain_stride,
+                        const float* eps_chain, float* px, float* samples, l2hmc_stream_t stream);
+
 /* One training evaluation on the toy targets (mog_model.py:324-363): `rows` = 2B stacked chains (B started at
  * x, B at z ~ N(0,1); sampler.py:28-55 picks a direction per chain, passed in `dir`), each integrated in its
  * direction; per chain v = |x0 - x_N|^2 * p + 1e-4, term = scale / v - v / scale, loss = inv_count * sum of all

@@ -137,6 +137,8 @@ _PROTOS = {
     "l2hmc_small_run": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _P, _P]),
     "l2hmc_small_run_tempered": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _I64, _I64, _P, _P,
                                            _P]),
+    "l2hmc_small_hmc_run": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _I64, _I64, _P, _P, _P,
+                                      _P]),
     "l2hmc_small_train_ws_bytes": (_SZ, [C.POINTER(SmallPlan), _I64]),
     "l2hmc_small_train_step": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64, _F, _F, _P, _P, _P, _P, _P, _P, _SZ,
                                          _P]),

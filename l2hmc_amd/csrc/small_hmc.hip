@@ -1,0 +1,209 @@
+// Plain HMC on the packed toy targets, a run of MCMC steps in ONE launch (l2hmc_small_hmc_run): the baseline every
+// L2HMC figure is compared against (utils/dynamics.py:75-78 -- both networks return zeros --, utils/sampler.py:30-32,
+// :57-59).
+//
+// One THREAD per chain, one wave per workgroup.  A chain without networks is a few dozen dependent VALU instructions
+// per leapfrog step: nothing to share between lanes, nothing for the matrix pipe, and a launch of 128..4096 chains is
+// bound by the latency of that one dependent chain.  So x, v and the gradient (x_dim <= 8) stay in the thread's
+// registers from the first step to the last, the target and the masks are staged into LDS once per workgroup, and
+// workgroups of 64 chains spread a batch over as many compute units as it has waves.  small_traj_mfma_kernel
+// (small_mlp.hip), which the loop over `propose` runs for an hmc plan, gives a chain four lanes, 16 chains a wave of
+// 256-thread workgroups and sizes its LDS image for two networks that are not there.
+//
+// The arithmetic is that kernel's forward body with P.hmc, statement by statement (lf_update.h with S = T = Q = 0, the
+// same target instances: MD = 2 for x_dim <= 2, kMaxDim otherwise; AN for the analytic kinds), followed by
+// mix_accept_kernel(strict = 0) as sampler.py's tf_accept calls it, so a run gives the bits of the loop over
+// fill_normal, l2hmc_small_trajectory, fill_uniform and l2hmc_mix_accept.
+#include "small_mlp.h"
+#include "lf_update.h"
+
+namespace l2hmc {
+
+constexpr int kHmcThreads = 64;      // one wave: 64 chains per workgroup
+
+struct SmallHmcArgs {
+  l2hmc_mog_target target;
+  // target_kind(target), formed on the host: read in the kernel, the rough well's scalars in the union slot of `mu`
+  // put the whole argument block on the stack (16 B of scratch per lane in the analytic instances)
+  TargetKind tk;
+  const float* masks;                // [N][dim]
+  int32_t dim, N;
+  float eps;
+  const float* eps_chain;            // [B] or NULL (eps for every chain)
+  const float* x_in; float* x_next; int64_t B;
+  uint64_t seed, draw0;
+  int32_t n_steps;
+  // TEMPERED instance: step s of chain c runs at temps[s * temp_step_stride + c * temp_chain_stride]
+  const float* temps; int64_t temp_step_stride, temp_chain_stride;
+  float* px; float* samples;         // [n_steps][B], [n_steps][B][dim]; each may be NULL
+};
+
+// TEMPERED: a template flag for the reason given at small_traj_mfma_kernel -- the untempered instances hold
+// 1 / temperature for the launch and keep their code.
+template <int MD, bool AN, bool TEMPERED>
+__global__ __launch_bounds__(kHmcThreads) void small_hmc_run_kernel(SmallHmcArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int dim = a.dim, N = a.N, K = a.target.K;
+  const TargetView tv = target_view(a.target.dim, K);
+  float* Lt = lds;
+  float* Lm = Lt + tv.size;                       // masks [N][dim]
+  load_target(a.target, Lt);
+  for (int i = threadIdx.x; i < N * dim; i += kHmcThreads) Lm[i] = a.masks[i];
+  __syncthreads();                                // the only barrier of the kernel
+
+  const int64_t r = (int64_t)blockIdx.x * kHmcThreads + threadIdx.x;
+  if (r >= a.B) return;                           // chains never meet: nothing below is collective
+  const float eps = a.eps_chain ? a.eps_chain[r] : a.eps;
+  float inv_temp = TEMPERED ? 1.f : 1.f / a.target.temperature;      // (TEMPERED: set at the head of every step)
+  const TargetKind tk = a.tk;
+
+  float x[MD], v[MD], g[MD], x_init[MD];
+#pragma unroll
+  for (int d = 0; d < MD; ++d) x[d] = d < dim ? a.x_in[r * dim + d] : 0.f;
+  TargetRegs<MD> tregs;
+  const bool treg = TargetRegs<MD>::kFits && K <= TargetRegs<MD>::KM;       // uniform
+  if (treg && !AN) tregs.load(Lt, dim, K);
+  auto target = [&](const float (&xx)[MD], float* E, float (&gg)[MD]) {
+    float dummy;
+    if constexpr (AN) analytic_energy_grad<MD>(tk, dim, inv_temp, xx, E, gg);
+    else if (treg) tregs.eval(dim, K, tk.kind, inv_temp, xx, E, gg);
+    else energy_grad<MD>(Lt, dim, K, tk, inv_temp, xx, E ? E : &dummy, gg);
+  };
+
+  for (int sidx = 0; sidx < a.n_steps; ++sidx) {
+    const uint64_t draw = a.draw0 + 2 * (uint64_t)sidx;
+    // the same division as above, so equal temperatures give equal bits; one temperature from E0 to E1
+    if constexpr (TEMPERED) inv_temp = 1.f / a.temps[(int64_t)sidx * a.temp_step_stride + r * a.temp_chain_stride];
+    // momenta: elements r * dim + d of stream `draw`.  A Philox block holds four of them, so consecutive components
+    // mostly share one
+    {
+      float nv[4] = {0.f, 0.f, 0.f, 0.f};
+      int64_t have = -1;
+#pragma unroll
+      for (int d = 0; d < MD; ++d) {
+        v[d] = 0.f;
+        if (d < dim) {
+          const int64_t i = r * dim + d;
+          if ((i >> 2) != have) {
+            uint32_t c[4];
+            philox_block_at(a.seed, draw, i, c);
+            philox_normal4(c, nv);
+            have = i >> 2;
+          }
+          const int j = (int)(i & 3);
+          v[d] = j == 0 ? nv[0] : j == 1 ? nv[1] : j == 2 ? nv[2] : nv[3];
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < MD; ++d) x_init[d] = x[d];
+    float E0, E1;
+    target(x, &E0, g);
+    float kin0 = 0.f;
+#pragma unroll
+    for (int d = 0; d < MD; ++d) kin0 += v[d] * v[d];
+    const float H0 = E0 + 0.5f * kin0;
+    float logdet = 0.f;
+    for (int it = 0; it < N; ++it) {
+      const float* m = Lm + it * dim;
+      for (int half = 0; half < 2; ++half) {
+        if (half == 1) {
+          for (int sub = 0; sub < 2; ++sub) {       // keep mask m, then 1 - m
+#pragma unroll
+            for (int d = 0; d < MD; ++d) {
+              if (d < dim) {
+                float s, omk;
+                x[d] = lf_drift<ExpFast>(x[d], v[d], keep_of(m[d], m[d], 0, sub), 0.f, 0.f, 0.f, eps, 0, s, omk);
+                logdet += omk * s;
+              }
+            }
+          }
+          target(x, nullptr, g);
+        }
+#pragma unroll
+        for (int d = 0; d < MD; ++d) {
+          if (d < dim) {
+            float s;
+            v[d] = lf_kick<ExpFast>(v[d], g[d], 0.f, 0.f, 0.f, eps, 0, s);
+            logdet += s;
+          }
+        }
+      }
+    }
+    target(x, &E1, g);
+    float kin1 = 0.f;
+#pragma unroll
+    for (int d = 0; d < MD; ++d) kin1 += v[d] * v[d];
+    const float H1 = E1 + 0.5f * kin1;
+    const float pacc = accept_from_delta(H0 - H1 + logdet);
+    // mix_accept_kernel(strict = 0) with coin = 1 and the proposal in both slots (sampler.py: tf_accept)
+    const float fm = 1.f, bm = 1.f - fm;
+    const float pm = fm * pacc + bm * pacc;
+    const bool acc = pm - philox_uniform_at(a.seed, draw + 1, r) >= 0.f;
+    if (a.px) a.px[(int64_t)sidx * a.B + r] = pm;
+#pragma unroll
+    for (int d = 0; d < MD; ++d) {
+      const float xp = fm * x[d] + bm * x[d];
+      x[d] = acc ? xp : x_init[d];
+      if (a.samples && d < dim) a.samples[((int64_t)sidx * a.B + r) * dim + d] = x[d];
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < MD; ++d)
+    if (d < dim) a.x_next[r * dim + d] = x[d];
+}
+
+template <int MD, bool AN, bool TEMPERED>
+static int launch_small_hmc(const SmallHmcArgs& a, size_t lds, hipStream_t st) {
+  const dim3 grid((unsigned)ceil_div(a.B, kHmcThreads));
+  prof_before(kProfSmall, st);
+  hipLaunchKernelGGL((small_hmc_run_kernel<MD, AN, TEMPERED>), grid, dim3(kHmcThreads), lds, st, a);
+  prof_after(kProfSmall, st);
+  L2HMC_CHECK_LAUNCH("small_hmc_run");
+  return L2HMC_OK;
+}
+
+template <int MD>
+static int launch_small_hmc_md(const SmallHmcArgs& a, size_t lds, hipStream_t st) {
+  const bool an = target_is_analytic(a.target.is_gaussian);
+  if (a.temps) return an ? launch_small_hmc<MD, true, true>(a, lds, st) : launch_small_hmc<MD, false, true>(a, lds, st);
+  return an ? launch_small_hmc<MD, true, false>(a, lds, st) : launch_small_hmc<MD, false, false>(a, lds, st);
+}
+
+}  // namespace l2hmc
+
+using namespace l2hmc;
+
+// Every check comes before any device call.  (Temperatures and step sizes live on the device and are not looked at.)
+extern "C" int l2hmc_small_hmc_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                                   uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps,
+                                   int64_t step_stride, int64_t chain_stride, const float* eps_chain, float* px,
+                                   float* samples, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(plan != nullptr, "small_hmc_run: plan is NULL");
+  L2HMC_REQUIRE(x_in != nullptr && x_next != nullptr, "small_hmc_run: x_in / x_next is NULL");
+  L2HMC_REQUIRE(B >= 0, "small_hmc_run: B < 0");
+  L2HMC_REQUIRE(n_steps > 0, "small_hmc_run: n_steps=%d must be positive", n_steps);
+  L2HMC_REQUIRE(plan->hmc, "small_hmc_run: the plan is an L2HMC sampler's (hmc == 0), which proposes in both "
+                           "directions with its networks: use l2hmc_small_run");
+  L2HMC_REQUIRE(2 * (uint64_t)n_steps <= UINT64_MAX - draw0,
+                "small_hmc_run: draw0 + 2 * n_steps overflows 64 bits (draw0=%llu, n_steps=%d)",
+                (unsigned long long)draw0, n_steps);
+  L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0,
+                "small_hmc_run: negative stride (step_stride=%lld, chain_stride=%lld)", (long long)step_stride,
+                (long long)chain_stride);
+  const int dim = plan->x_dim, N = plan->trajectory_length;
+  L2HMC_REQUIRE(dim == plan->target.dim, "small_hmc_run: x_dim=%d != target dim=%d", dim, plan->target.dim);
+  L2HMC_REQUIRE(N > 0 && plan->masks != nullptr, "small_hmc_run: bad trajectory_length / masks");
+  if (int e = check_target_args(&plan->target, "small_hmc_run")) return e;
+  const size_t lds = sizeof(float) * ((size_t)target_view(dim, plan->target.K).size + (size_t)N * dim);
+  L2HMC_REQUIRE(lds <= 64 * 1024, "small_hmc_run: trajectory_length=%d: target and masks take %zu B of LDS (max 65536)",
+                N, lds);
+  if (B == 0) return L2HMC_OK;
+  SmallHmcArgs a{};
+  a.target = plan->target; a.tk = target_kind(plan->target); a.masks = plan->masks; a.dim = dim; a.N = N; a.eps = plan->eps; a.eps_chain = eps_chain;
+  a.x_in = x_in; a.x_next = x_next; a.B = B; a.seed = seed; a.draw0 = draw0; a.n_steps = n_steps;
+  a.temps = temps; a.temp_step_stride = step_stride; a.temp_chain_stride = chain_stride;
+  a.px = px; a.samples = samples;
+  hipStream_t st = (hipStream_t)stream;
+  return dim <= 2 ? launch_small_hmc_md<2>(a, lds, st) : launch_small_hmc_md<kMaxDim>(a, lds, st);
+}

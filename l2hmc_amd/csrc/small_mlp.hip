@@ -82,25 +82,6 @@ extern int g_stamp_cls;
 #define ST_ADD(slot, t0) do {} while (0)
 #endif
 
-// element i of the stream l2hmc_fill_uniform / l2hmc_fill_normal writes for (seed, offset)   (capi.hip: fill_kernel)
-__device__ __forceinline__ void philox_block_at(uint64_t seed, uint64_t offset, int64_t i, uint32_t c[4]) {
-  const uint64_t b = (uint64_t)i >> 2;
-  c[0] = (uint32_t)b; c[1] = (uint32_t)(b >> 32); c[2] = (uint32_t)offset; c[3] = (uint32_t)(offset >> 32);
-  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-__device__ __forceinline__ float philox_uniform_at(uint64_t seed, uint64_t offset, int64_t i) {
-  uint32_t c[4];
-  philox_block_at(seed, offset, i, c);
-  return (float)(c[i & 3] >> 8) * (1.0f / 16777216.0f);
-}
-__device__ __forceinline__ float philox_normal_at(uint64_t seed, uint64_t offset, int64_t i) {
-  uint32_t c[4];
-  philox_block_at(seed, offset, i, c);
-  float v[4];
-  philox_normal4(c, v);
-  return v[i & 3];
-}
-
 // =====================================================================================================
 // The trajectory kernel.  One WAVE integrates 16 chains and never exchanges anything
 // with another wave: lane (q = lane / 16, r = lane % 16) belongs to chain r of the wave; the four lanes of a
@@ -475,80 +456,6 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
 #endif
   ST_ADD(3, t0);
 }
-
-// Target parameters in registers (x_dim <= 2 instance, the reference's toy targets): energy_grad() re-reads
-// them from LDS with run-time offsets at every one of its 2 N + 2 calls, behind the network's LDS traffic; here
-// they are read once.  Same arithmetic, same order as energy_grad (small_mlp.h).
-template <int MD>
-struct TargetRegs {
-  static constexpr int KM = 2;              // components held (mog_model.py: two; more fall back to energy_grad)
-  static constexpr bool kFits = MD <= 2;
-  float mu[KM][MD], prec[KM][MD][MD], logc[KM];
-  __device__ __forceinline__ void load(const float* Lt, int dim, int K) {
-    const TargetView tv = target_view(dim, K);
-#pragma unroll
-    for (int k = 0; k < KM; ++k) {
-      logc[k] = k < K ? Lt[tv.logc + k] : 0.f;
-#pragma unroll
-      for (int i = 0; i < MD; ++i) {
-        mu[k][i] = (k < K && i < dim) ? Lt[tv.mu + k * dim + i] : 0.f;
-#pragma unroll
-        for (int j = 0; j < MD; ++j)
-          prec[k][i][j] = (k < K && i < dim && j < dim) ? Lt[tv.prec + (k * dim + i) * dim + j] : 0.f;
-      }
-    }
-  }
-  // E == nullptr: gradient only (the energy's logf is needed at the two ends of a trajectory, not inside it)
-  __device__ __forceinline__ void eval(int dim, int K, int is_gaussian, float inv_temp, const float (&x)[MD], float* E,
-                                       float (&g)[MD]) const {
-    float V[KM];
-    float vmax = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < KM; ++k) {
-      if (k < K) {
-        float quad = 0.f;
-#pragma unroll
-        for (int i = 0; i < MD; ++i) {
-          if (i < dim) {
-            float pd = 0.f;
-#pragma unroll
-            for (int j = 0; j < MD; ++j)
-              if (j < dim) pd += prec[k][i][j] * (x[j] - mu[k][j]);
-            quad += (x[i] - mu[k][i]) * pd;
-          }
-        }
-        V[k] = -0.5f * quad + (is_gaussian ? 0.f : logc[k]);
-        vmax = fmaxf(vmax, V[k]);
-      }
-    }
-    float sw = 0.f;
-#pragma unroll
-    for (int d = 0; d < MD; ++d) g[d] = 0.f;
-#pragma unroll
-    for (int k = 0; k < KM; ++k) {
-      if (k < K) {
-        const float w = is_gaussian ? 1.f : expf(V[k] - vmax);
-        sw += w;
-#pragma unroll
-        for (int i = 0; i < MD; ++i) {
-          if (i < dim) {
-            float gi = 0.f;
-#pragma unroll
-            for (int j = 0; j < MD; ++j)
-              if (j < dim) gi += (prec[k][i][j] + prec[k][j][i]) * (x[j] - mu[k][j]);
-            g[i] += w * 0.5f * gi;
-          }
-        }
-      }
-    }
-    if (E) {
-      const float e = is_gaussian ? -V[0] : -(vmax + logf(sw));
-      *E = e * inv_temp;
-    }
-#pragma unroll
-    for (int d = 0; d < MD; ++d) g[d] = g[d] / sw * inv_temp;
-  }
-};
 
 // RUN: the propose-mode body loops over a.n_steps sampler steps (l2hmc_small_run).  The single pass is the same code
 // with the back edge compiled out, so that holding the weights across the epilogue costs the one-step entries nothing

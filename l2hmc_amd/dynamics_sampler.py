@@ -10,7 +10,11 @@ the weights, target, masks and time table staged once.  The values are those of 
 `steps_per_launch = 1` run.
 
 `run(..., temperature=)` anneals or ladders the temperature inside such a run (l2hmc_small_run_tempered): one value per
-step, per chain, or both, where `dynamics.temperature` is one value for the launch."""
+step, per chain, or both, where `dynamics.temperature` is one value for the launch.
+
+`run_hmc` is the plain-HMC baseline in one launch per chunk (l2hmc_small_hmc_run, a kernel of its own: one thread per
+chain): the values of `run` on an `hmc=True` dynamics, bit for bit, and beyond them a temperature and a step size per
+chain, so that "HMC at three eps" is one call."""
 import ctypes as C
 
 import numpy as np
@@ -111,21 +115,24 @@ class DynamicsSampler:
             out["samples"] = torch.stack(samples).cpu().numpy()
         return out
 
-    def _run_launches(self, run_steps, x, keep_samples, temps=None):
+    def _run_launches(self, run_steps, x, keep_samples, temps=None, hmc_plan=None, eps_chain=None):
         """Chunks of at most `steps_per_launch` steps through l2hmc_small_run, ONE launch each (l2hmc_small_run_tempered
         with `temps`: the array goes to the device once and every chunk starts at its own row).  The same draws (four
         consecutive streams per step from the dynamics' counter), accept probabilities and samples as `_run_loop`, bit
         for bit.  With `keep_samples` the device buffer of the samples is one chunk long and is copied to the host
-        chunk by chunk."""
+        chunk by chunk.  `hmc_plan` (`run_hmc`): the chunks go through l2hmc_small_hmc_run with that plan and
+        `eps_chain` ([B] on the device, or None), two streams per step."""
         dyn = self.dynamics
         B, D, dev = x.shape[0], x.shape[1], x.device
-        plan = dyn._plan()
+        plan = hmc_plan if hmc_plan is not None else dyn._plan()
+        streams = 4 if hmc_plan is None else 2             # per step
         chunk = min(int(self.steps_per_launch), run_steps)
         px = torch.empty(run_steps, B, dtype=torch.float32, device=dev)
         samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
         samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
         x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
         x_in = x
+        step_stride = chain_stride = 0
         if temps is not None:
             # element strides of (step, chain): (0, 0) one value, (1, 0) a schedule, (0, 1) a ladder, (B, 1) both
             step_stride, chain_stride = ((0, 0) if temps.ndim == 0 else (1, 0) if temps.ndim == 1 else
@@ -133,20 +140,81 @@ class DynamicsSampler:
             temps_dev = _lib.as_dev(np.ascontiguousarray(temps).reshape(-1), dev)
         for s0 in range(0, run_steps, chunk):
             n = min(chunk, run_steps - s0)
-            if temps is None:
+            if hmc_plan is not None:
+                _lib.call("l2hmc_small_hmc_run", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
+                          None if temps is None else temps_dev[s0 * step_stride:], step_stride, chain_stride,
+                          eps_chain, px[s0:], samples_dev, device=dyn._device)
+            elif temps is None:
                 _lib.call("l2hmc_small_run", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n, px[s0:],
                           samples_dev, device=dyn._device)
             else:
                 _lib.call("l2hmc_small_run_tempered", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
                           temps_dev[s0 * step_stride:], step_stride, chain_stride, px[s0:], samples_dev,
                           device=dyn._device)
-            dyn._draws += 4 * n                            # the counter moves with the completed steps
+            dyn._draws += streams * n                      # the counter moves with the completed steps
             x_in = x_next                                  # later chunks advance the state in place
             if keep_samples:
                 samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
         out = {"px": px.cpu().numpy(), "samples_out": x_next}
         if keep_samples:
             out["samples"] = samples
+        return out
+
+    def _step_sizes(self, eps, B):
+        """`run_hmc`'s `eps` as a float32 array of shape [] or [B]; ValueError for any other shape and for an entry that
+        is not finite and > 0 in float32."""
+        if isinstance(eps, torch.Tensor):
+            eps = eps.detach().cpu().numpy()
+        with np.errstate(over="ignore"):
+            e = np.asarray(eps, dtype=np.float64).astype(np.float32)
+        if e.shape not in ((), (B,)):
+            raise ValueError(f"run_hmc: eps of shape {e.shape}: expected a scalar or [{B}] (one per chain)")
+        if not (np.isfinite(e) & (e > 0)).all():
+            raise ValueError("run_hmc: every eps must be finite and > 0 (in float32)")
+        return e
+
+    def run_hmc(self, run_steps, x=None, keep_samples=True, temperature=None, eps=None):
+        """`run` for a plain-HMC dynamics (`hmc=True`) on a packed toy target, `steps_per_launch` steps per launch
+        (l2hmc_small_hmc_run): the same dictionary, the same values as `run` gives for that dynamics, bit for bit, and
+        the same draws (`_draws`, 2 streams per HMC step: momenta, Metropolis-Hastings uniforms).  The caller's `x` is
+        not advanced in place.  `temperature` as in `run`, per chain included.  `eps`: None (the dynamics' own), a
+        scalar, or [B], one step size per chain -- chains never interact, so "HMC at three eps" is one call whose
+        columns are the runs at each eps.  `dynamics.alpha` and `dynamics.temperature` are left as they were.
+        ValueError for an L2HMC dynamics and NotImplementedError for one that runs layer by layer (a callable energy,
+        x_dim > 8): `run` takes both."""
+        dyn = self.dynamics
+        if not dyn.hmc:
+            raise ValueError("run_hmc: the dynamics is an L2HMC sampler (hmc=False): `run` runs it, in one launch per "
+                             "chunk where the one-launch kernel holds it")
+        if dyn.layered:
+            raise NotImplementedError(
+                "run_hmc: this hmc dynamics runs layer by layer (arbitrary energy function or x_dim > 8), which the "
+                "one-launch kernel does not hold: `run` takes it through the loop over `propose`")
+        run_steps = int(run_steps)
+        if run_steps < 0:
+            raise ValueError(f"run_steps={run_steps} must not be negative")
+        if x is None:
+            if self.batch_size is None:
+                raise ValueError("run_hmc: pass the start `x`, or give the sampler a batch_size to start from N(0, 1)")
+            x = np.random.randn(int(self.batch_size), dyn.x_dim)
+        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        B, D = x.shape
+        temps = None if temperature is None else self._temperatures(temperature, run_steps, B)
+        step = None if eps is None else self._step_sizes(eps, B)
+        if run_steps == 0:
+            out = {"px": np.empty((0, B), dtype=np.float32), "samples_out": x.clone()}
+            if keep_samples:
+                out["samples"] = np.empty((0, B, D), dtype=np.float32)
+        else:
+            plan = dyn._plan()
+            eps_chain = None
+            if step is not None and step.ndim == 0:
+                plan.eps = float(step)
+            elif step is not None:
+                eps_chain = _lib.as_dev(step, x.device)
+            out = self._run_launches(run_steps, x, keep_samples, temps, hmc_plan=plan, eps_chain=eps_chain)
+        px = out["px"]
+        out["mean_accept"] = float(px.mean(dtype=np.float64)) if px.size else float("nan")
         return out
 
     def generate_trajectories(self, temp=1., num_samples=500, num_steps=100, x=None):

@@ -236,3 +236,20 @@ __device__ __forceinline__ float accept_from_delta(T dh) {
 }
 
 }  // namespace l2hmc
+
+// Cycle stamps of the diagnostic build (-DL2HMC_STAMPS, tools/build_diag.sh): the wave's clock, fenced against the
+// scheduler on both sides, and `arr[slot] += now - t0`.  Nothing in the shipped library.
+#ifdef L2HMC_STAMPS
+#define L2HMC_CYCLES_NOW()                                                                    \
+  ({                                                                                          \
+    unsigned long long t_;                                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    t_;                                                                                       \
+  })
+#define L2HMC_CYCLES_ADD(arr, slot, t0) (arr)[slot] += L2HMC_CYCLES_NOW() - (t0)
+#else
+#define L2HMC_CYCLES_NOW() 0ull
+#define L2HMC_CYCLES_ADD(arr, slot, t0) do {} while (0)
+#endif

@@ -200,21 +200,6 @@ __global__ __launch_bounds__(256) void pack_heads_kernel(l2hmc_dense_net n, cons
   }
 }
 
-#ifdef L2HMC_STAMPS
-#define FT_NOW()                                                                              \
-  ({                                                                                          \
-    unsigned long long t_;                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-    t_;                                                                                       \
-  })
-#define FT_ADD(slot, t0) ft[slot] += FT_NOW() - (t0)
-#else
-#define FT_NOW() 0ull
-#define FT_ADD(slot, t0) do {} while (0)
-#endif
-
 // (struct FusedArgs: fused_args.h, shared with the sub-tile form in fused_traj4.hip)
 
 #ifdef L2HMC_STAMPS
@@ -262,7 +247,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 
   // diagnostic cycle shares: 0-2 gemm L1/L2/heads, 3-5 their epilogues, 6 barriers, 7 force, 8 mask pass, 9 total
   [[maybe_unused]] unsigned long long ft[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  [[maybe_unused]] const unsigned long long ft_start = FT_NOW();
+  [[maybe_unused]] const unsigned long long ft_start = L2HMC_CYCLES_NOW();
 #ifdef L2HMC_STAMPS
   unsigned long long rt0;
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt0)::"memory");
@@ -518,17 +503,17 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     {
       constexpr int KH = Cfg::KC1 / 2;
       f32x4 acc[NT1];
-      [[maybe_unused]] unsigned long long t0 = FT_NOW();
+      [[maybe_unused]] unsigned long long t0 = L2HMC_CYCLES_NOW();
       // inputs of the dense trunk: the LDS rows themselves, or their conv features
       const float* src1 = in1;
       const float* src2 = gs;
       int s1 = SX;
       if constexpr (CONV) {
         const float* cwn = cwl + (is_vnet ? 2 : 0) * Cfg::CW;
-        [[maybe_unused]] const unsigned long long tc0 = FT_NOW();
+        [[maybe_unused]] const unsigned long long tc0 = L2HMC_CYCLES_NOW();
         if (l1 == 0 || l1 == 1 || l1 == 3) conv_features(in1, cwn, fa);            // first input (conv_v*)
         if (l1 != 2) conv_features(gs, cwn + Cfg::CW, fb);                          // second input (conv_x*)
-        FT_ADD(8, tc0);                                                             // (slot 8: conv front-end; also inside slot 0)
+        L2HMC_CYCLES_ADD(ft, 8, tc0);               // (slot 8: conv front-end; also inside slot 0)
         src1 = fa;
         src2 = fb;
         s1 = SA;
@@ -595,8 +580,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         }
       }
       ring_prime<NT1, DP2, NTI1>(R2, wp2, zig, Cfg::KC2, to1);      // layer-2 weights start flowing under the epilogue + barrier
-      FT_ADD(0, t0);
-      t0 = FT_NOW();
+      L2HMC_CYCLES_ADD(ft, 0, t0);
+      t0 = L2HMC_CYCLES_NOW();
       [[maybe_unused]] unsigned gmask = 0;
 #pragma unroll
       for (int t = 0; t < NT1; ++t) {
@@ -618,12 +603,12 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         if constexpr (RW == 1) tp.gate[word] = gmask;
         else reinterpret_cast<unsigned short*>(tp.gate)[word * 2 + wsub] = (unsigned short)gmask;
       }
-      FT_ADD(3, t0);
+      L2HMC_CYCLES_ADD(ft, 3, t0);
     }
     {
-      [[maybe_unused]] const unsigned long long tb = FT_NOW();
+      [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
       __syncthreads();
-      FT_ADD(6, tb);
+      L2HMC_CYCLES_ADD(ft, 6, tb);
     }
     if constexpr (TAPE) tape_rows(tp.h1, h1);
     // ----- layer 2
@@ -632,7 +617,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 #pragma unroll
       for (int t = 0; t < NT1; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
       const float* a = h1 + r * SH + q * 4;
-      [[maybe_unused]] unsigned long long t0 = FT_NOW();
+      [[maybe_unused]] unsigned long long t0 = L2HMC_CYCLES_NOW();
       stream_layer<NT1, Cfg::KC2, DP2, NTI1>(
           R2, wp2, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acc, zig, to1);
       if (ACTOK && actv) {
@@ -640,8 +625,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       } else {
         ring_prime<3 * NTH, DPH, 3 * NTIH, TSH>(R3, wph, zig, Cfg::KC2, toh);
       }
-      FT_ADD(1, t0);
-      t0 = FT_NOW();
+      L2HMC_CYCLES_ADD(ft, 1, t0);
+      t0 = L2HMC_CYCLES_NOW();
       [[maybe_unused]] unsigned gmask = 0;
 #pragma unroll
       for (int t = 0; t < NT1; ++t) {
@@ -661,12 +646,12 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         if constexpr (RW == 1) tp.gate[word] = gmask;
         else reinterpret_cast<unsigned short*>(tp.gate)[word * 2 + wsub] = (unsigned short)gmask;
       }
-      FT_ADD(4, t0);
+      L2HMC_CYCLES_ADD(ft, 4, t0);
     }
     {
-      [[maybe_unused]] const unsigned long long tb = FT_NOW();
+      [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
       __syncthreads();
-      FT_ADD(6, tb);
+      L2HMC_CYCLES_ADD(ft, 6, tb);
     }
     if constexpr (TAPE) tape_rows(tp.h2, h2);
     // ----- heads + update
@@ -675,7 +660,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 #pragma unroll
       for (int t = 0; t < 3 * NTH; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
       const float* a = h2 + r * SH + q * 4;
-      [[maybe_unused]] unsigned long long t0 = FT_NOW();
+      [[maybe_unused]] unsigned long long t0 = L2HMC_CYCLES_NOW();
       if (ACTOK && actv) {
         if (wv < 4)
           stream_layer<3 * NTH, Cfg::KC2, DPH, 3, 1>(
@@ -684,8 +669,8 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         stream_layer<3 * NTH, Cfg::KC2, DPH, 3 * NTIH, TSH>(
             R3, wph, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acc, zig, toh);
       }
-      FT_ADD(2, t0);
-      t0 = FT_NOW();
+      L2HMC_CYCLES_ADD(ft, 2, t0);
+      t0 = L2HMC_CYCLES_NOW();
       float ld = 0.f;                       // this lane's share of row r's log-det
       const float* bhd = cn + 4 * H;
       const float* es = bhd + 3 * D;
@@ -812,12 +797,12 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         if (wsub == 0) ldx[wimg * 64 + lane] = ld;
       }
       }
-      FT_ADD(5, t0);
+      L2HMC_CYCLES_ADD(ft, 5, t0);
     }
     {
-      [[maybe_unused]] const unsigned long long tb = FT_NOW();
+      [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
       __syncthreads();
-      FT_ADD(6, tb);
+      L2HMC_CYCLES_ADD(ft, 6, tb);
     }
     if (ACTOK && actv) {
       // the chain of adds of the all-columns form over both waves' columns of the section; a kept column adds +-0
@@ -869,10 +854,10 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     for (int call = 0; call < 4; ++call) {
       const bool is_v = call == 0 || call == 3;
       if (call == 3) {
-        [[maybe_unused]] const unsigned long long tf = FT_NOW();
+        [[maybe_unused]] const unsigned long long tf = L2HMC_CYCLES_NOW();
         float unused[1];
         force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, unused);   // force at the new position
-        FT_ADD(7, tf);
+        L2HMC_CYCLES_ADD(ft, 7, tf);
       }
       // call 0: momentum half-kick (+ keep (.) x into gs)      call 1: position sub-update 1 (+ complement mask)
       // call 2: position sub-update 2                          call 3: second momentum half-kick (product kept)
@@ -966,7 +951,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   if (p.stamps && tid == 0) {
     unsigned long long rt1;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt1)::"memory");
-    ft[9] = FT_NOW() - ft_start;
+    ft[9] = L2HMC_CYCLES_NOW() - ft_start;
     for (int i = 0; i < 10; ++i) p.stamps[blockIdx.x * 12 + i] = ft[i];
     p.stamps[blockIdx.x * 12 + 10] = rt0;
     p.stamps[blockIdx.x * 12 + 11] = rt1;

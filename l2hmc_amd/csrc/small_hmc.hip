@@ -10,12 +10,12 @@
 // (small_mlp.hip), which the loop over `propose` runs for an hmc plan, gives a chain four lanes, 16 chains a wave of
 // 256-thread workgroups and sizes its LDS image for two networks that are not there.
 //
-// The arithmetic is that kernel's forward body with P.hmc, statement by statement (lf_update.h with S = T = Q = 0, the
-// same target instances: MD = 2 for x_dim <= 2, kMaxDim otherwise; AN for the analytic kinds), followed by
-// mix_accept_kernel(strict = 0) as sampler.py's tf_accept calls it, so a run gives the bits of the loop over
-// fill_normal, l2hmc_small_trajectory, fill_uniform and l2hmc_mix_accept.
-#include "small_mlp.h"
-#include "lf_update.h"
+// The arithmetic is small_step.h's: the trajectory small_traj_mfma_kernel runs for an hmc plan, here with NoNet in
+// place of both networks (S = T = Q = 0, which the compiler folds), on the same target instances (MD = 2 for
+// x_dim <= 2, kMaxDim otherwise; AN for the analytic kinds), followed by mix_accept_kernel(strict = 0) as sampler.py's
+// tf_accept calls it, so a run gives the bits of the loop over fill_normal, l2hmc_small_trajectory, fill_uniform and
+// l2hmc_mix_accept.
+#include "small_step.h"
 
 namespace l2hmc {
 
@@ -55,20 +55,17 @@ __global__ __launch_bounds__(kHmcThreads) void small_hmc_run_kernel(SmallHmcArgs
   if (r >= a.B) return;                           // chains never meet: nothing below is collective
   const float eps = a.eps_chain ? a.eps_chain[r] : a.eps;
   float inv_temp = TEMPERED ? 1.f : 1.f / a.target.temperature;      // (TEMPERED: set at the head of every step)
-  const TargetKind tk = a.tk;
 
   float x[MD], v[MD], g[MD], x_init[MD];
 #pragma unroll
   for (int d = 0; d < MD; ++d) x[d] = d < dim ? a.x_in[r * dim + d] : 0.f;
-  TargetRegs<MD> tregs;
-  const bool treg = TargetRegs<MD>::kFits && K <= TargetRegs<MD>::KM;       // uniform
-  if (treg && !AN) tregs.load(Lt, dim, K);
-  auto target = [&](const float (&xx)[MD], float* E, float (&gg)[MD]) {
-    float dummy;
-    if constexpr (AN) analytic_energy_grad<MD>(tk, dim, inv_temp, xx, E, gg);
-    else if (treg) tregs.eval(dim, K, tk.kind, inv_temp, xx, E, gg);
-    else energy_grad<MD>(Lt, dim, K, tk, inv_temp, xx, E ? E : &dummy, gg);
+  SmallTarget<MD, AN> tgt;
+  const TargetKind tk = a.tk;
+  tgt.load(Lt, dim, K);
+  auto target = [&](const float (&xx)[MD], float* E, float (&gg)[MD]) __attribute__((always_inline)) {
+    tgt.eval(Lt, dim, K, tk, inv_temp, xx, E, gg);
   };
+  auto no_time = [](int, float& tc, float& ts) __attribute__((always_inline)) { tc = ts = 0.f; };
 
   for (int sidx = 0; sidx < a.n_steps; ++sidx) {
     const uint64_t draw = a.draw0 + 2 * (uint64_t)sidx;
@@ -97,53 +94,17 @@ __global__ __launch_bounds__(kHmcThreads) void small_hmc_run_kernel(SmallHmcArgs
     }
 #pragma unroll
     for (int d = 0; d < MD; ++d) x_init[d] = x[d];
-    float E0, E1;
-    target(x, &E0, g);
-    float kin0 = 0.f;
-#pragma unroll
-    for (int d = 0; d < MD; ++d) kin0 += v[d] * v[d];
-    const float H0 = E0 + 0.5f * kin0;
-    float logdet = 0.f;
-    for (int it = 0; it < N; ++it) {
-      const float* m = Lm + it * dim;
-      for (int half = 0; half < 2; ++half) {
-        if (half == 1) {
-          for (int sub = 0; sub < 2; ++sub) {       // keep mask m, then 1 - m
-#pragma unroll
-            for (int d = 0; d < MD; ++d) {
-              if (d < dim) {
-                float s, omk;
-                x[d] = lf_drift<ExpFast>(x[d], v[d], keep_of(m[d], m[d], 0, sub), 0.f, 0.f, 0.f, eps, 0, s, omk);
-                logdet += omk * s;
-              }
-            }
-          }
-          target(x, nullptr, g);
-        }
-#pragma unroll
-        for (int d = 0; d < MD; ++d) {
-          if (d < dim) {
-            float s;
-            v[d] = lf_kick<ExpFast>(v[d], g[d], 0.f, 0.f, 0.f, eps, 0, s);
-            logdet += s;
-          }
-        }
-      }
-    }
-    target(x, &E1, g);
-    float kin1 = 0.f;
-#pragma unroll
-    for (int d = 0; d < MD; ++d) kin1 += v[d] * v[d];
-    const float H1 = E1 + 0.5f * kin1;
-    const float pacc = accept_from_delta(H0 - H1 + logdet);
+    const SmallTraj tj =
+        small_trajectory<ExpFast>(dim, N, 0, eps, Lm, x, v, g, no_time, NoNet<MD>{}, NoNet<MD>{}, target);
+    const float pacc = tj.p_accept();
     // mix_accept_kernel(strict = 0) with coin = 1 and the proposal in both slots (sampler.py: tf_accept)
     const float fm = 1.f, bm = 1.f - fm;
-    const float pm = fm * pacc + bm * pacc;
-    const bool acc = pm - philox_uniform_at(a.seed, draw + 1, r) >= 0.f;
+    const float pm = mix_dir(fm, bm, pacc, pacc);
+    const bool acc = mh_accept(pm, a.seed, draw + 1, r);
     if (a.px) a.px[(int64_t)sidx * a.B + r] = pm;
 #pragma unroll
     for (int d = 0; d < MD; ++d) {
-      const float xp = fm * x[d] + bm * x[d];
+      const float xp = mix_dir(fm, bm, x[d], x[d]);
       x[d] = acc ? xp : x_init[d];
       if (a.samples && d < dim) a.samples[((int64_t)sidx * a.B + r) * dim + d] = x[d];
     }
@@ -179,22 +140,12 @@ extern "C" int l2hmc_small_hmc_run(const l2hmc_small_plan* plan, const float* x_
                                    uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps,
                                    int64_t step_stride, int64_t chain_stride, const float* eps_chain, float* px,
                                    float* samples, l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(plan != nullptr, "small_hmc_run: plan is NULL");
-  L2HMC_REQUIRE(x_in != nullptr && x_next != nullptr, "small_hmc_run: x_in / x_next is NULL");
-  L2HMC_REQUIRE(B >= 0, "small_hmc_run: B < 0");
-  L2HMC_REQUIRE(n_steps > 0, "small_hmc_run: n_steps=%d must be positive", n_steps);
+  const char* who = "small_hmc_run";
+  if (int e = check_small_run_args(who, plan, x_in, x_next, B, draw0, n_steps, 2, step_stride, chain_stride)) return e;
   L2HMC_REQUIRE(plan->hmc, "small_hmc_run: the plan is an L2HMC sampler's (hmc == 0), which proposes in both "
                            "directions with its networks: use l2hmc_small_run");
-  L2HMC_REQUIRE(2 * (uint64_t)n_steps <= UINT64_MAX - draw0,
-                "small_hmc_run: draw0 + 2 * n_steps overflows 64 bits (draw0=%llu, n_steps=%d)",
-                (unsigned long long)draw0, n_steps);
-  L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0,
-                "small_hmc_run: negative stride (step_stride=%lld, chain_stride=%lld)", (long long)step_stride,
-                (long long)chain_stride);
+  if (int e = check_small_plan(plan, who, false)) return e;
   const int dim = plan->x_dim, N = plan->trajectory_length;
-  L2HMC_REQUIRE(dim == plan->target.dim, "small_hmc_run: x_dim=%d != target dim=%d", dim, plan->target.dim);
-  L2HMC_REQUIRE(N > 0 && plan->masks != nullptr, "small_hmc_run: bad trajectory_length / masks");
-  if (int e = check_target_args(&plan->target, "small_hmc_run")) return e;
   const size_t lds = sizeof(float) * ((size_t)target_view(dim, plan->target.K).size + (size_t)N * dim);
   L2HMC_REQUIRE(lds <= 64 * 1024, "small_hmc_run: trajectory_length=%d: target and masks take %zu B of LDS (max 65536)",
                 N, lds);

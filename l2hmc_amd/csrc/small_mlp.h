@@ -1,7 +1,9 @@
-// Device helpers shared by the toy-target integrator (small_mlp.hip), its training kernel (small_train.hip) and the
-// plain-HMC run (small_hmc.hip): LDS images of the MLP weights and the mixture target, one network evaluation by the
-// sixteen lanes of a chain, closed-form energy / gradient (from LDS, and from registers: TargetRegs), single elements
-// of the library's Philox streams.
+// Device and host helpers shared by the toy-target integrator (small_mlp.hip), its training kernel (small_train.hip)
+// and the plain-HMC run (small_hmc.hip): LDS images of the MLP weights and the mixture target, the ONE network
+// evaluation by the sixteen lanes of a chain (the training kernel's forward and reverse passes), closed-form energy /
+// gradient (from LDS, and from registers: TargetRegs), single elements of the library's Philox streams, and the host
+// checks of a plan, its networks and a run's arguments that every entry makes before any launch.  The stages of a
+// sampler step built from these: small_step.h.
 #pragma once
 #include "common.h"
 
@@ -57,32 +59,34 @@ __device__ void load_net(const l2hmc_dense_net& n, float* L, int dim) {
 
 // (S, T, Q) = net([a, b, t]) for the chain this lane belongs to.  `sub` = lane within the chain (0..15),
 // `hrow` = the chain's HP-float LDS row for the hidden-vector exchange.  Must be called by all threads of the
-// workgroup (it contains workgroup barriers).
+// workgroup (it contains workgroup barriers).  h1 / h2 [HP / 16]: this lane's hidden units after the relu, which the
+// training kernel's reverse pass differentiates through (its forward pass drops them).
 // MD: compile-time bound on x_dim (2 for the benchmark targets, kMaxDim otherwise); register arrays and the
 // unrolled loops are sized by it.
 template <int HP, int MD = L2HMC_MAX_SMALL_DIM>
 __device__ void net_eval(const float* L, int dim, int q_tanh, const float* a, const float* b, float tc, float ts,
-                         int sub, float* hrow, float* S, float* T, float* Q) {
+                         int sub, float* hrow, float* h1, float* h2, float* S, float* T, float* Q) {
   constexpr int kMaxDim = MD;
   constexpr int UPL = HP / kLPC;           // hidden units per lane: n = sub * UPL + j
   const SmallNetView v = small_net_view(HP, dim);
   const int n0 = sub * UPL;
-  float h[UPL];
 #pragma unroll
-  for (int j = 0; j < UPL; ++j) h[j] = L[v.b1 + n0 + j] + tc * L[v.wt + n0 + j] + ts * L[v.wt + HP + n0 + j];
+  for (int j = 0; j < UPL; ++j) h1[j] = L[v.b1 + n0 + j] + tc * L[v.wt + n0 + j] + ts * L[v.wt + HP + n0 + j];
 #pragma unroll
   for (int k = 0; k < kMaxDim; ++k) {
     if (k < dim) {
 #pragma unroll
       for (int j = 0; j < UPL; ++j)
-        h[j] += a[k] * L[v.w1 + k * HP + n0 + j] + b[k] * L[v.w1 + (dim + k) * HP + n0 + j];
+        h1[j] += a[k] * L[v.w1 + k * HP + n0 + j] + b[k] * L[v.w1 + (dim + k) * HP + n0 + j];
     }
   }
   __syncthreads();                          // previous readers of hrow are done
 #pragma unroll
-  for (int j = 0; j < UPL; ++j) hrow[n0 + j] = fmaxf(h[j], 0.f);
+  for (int j = 0; j < UPL; ++j) {
+    h1[j] = fmaxf(h1[j], 0.f);
+    hrow[n0 + j] = h1[j];
+  }
   __syncthreads();
-  float h2[UPL];
 #pragma unroll
   for (int j = 0; j < UPL; ++j) h2[j] = L[v.bh + n0 + j];
   // four input units per step: one 16-byte read of the hidden row (broadcast within the chain's 16 lanes) instead of
@@ -334,6 +338,49 @@ inline int check_target_args(const l2hmc_mog_target* t, const char* who) {
     L2HMC_REQUIRE(t->mu && t->prec && (kind == L2HMC_TARGET_GAUSSIAN || t->log_const), "%s: target has a NULL parameter pointer", who);
     L2HMC_REQUIRE(kind != L2HMC_TARGET_GAUSSIAN || t->K == 1, "%s: gaussian target needs K == 1", who);
   }
+  return L2HMC_OK;
+}
+
+// What every entry that takes a plan checks before any launch: the target, the plan's dimension against it, the masks;
+// need_nets (every plan but a plain-HMC one): a hidden width the kernels have an instance for.
+inline int check_small_plan(const l2hmc_small_plan* plan, const char* who, bool need_nets) {
+  L2HMC_REQUIRE(plan->x_dim == plan->target.dim, "%s: x_dim=%d != target dim=%d", who, plan->x_dim, plan->target.dim);
+  if (int e = check_target_args(&plan->target, who)) return e;
+  L2HMC_REQUIRE(plan->trajectory_length > 0 && plan->masks != nullptr, "%s: bad trajectory_length / masks", who);
+  L2HMC_REQUIRE(!need_nets || (plan->num_nodes > 0 && plan->num_nodes <= 64), "%s: num_nodes=%d unsupported (1..64)",
+                who, plan->num_nodes);
+  return L2HMC_OK;
+}
+
+// ... and of its two networks: the plan's shape, no NULL weight.  (Apart from check_small_plan: the training entries
+// return for an empty batch in between.)
+inline int check_small_nets(const l2hmc_small_plan* plan, const char* who) {
+  const int dim = plan->x_dim, H = plan->num_nodes;
+  const l2hmc_dense_net* nets[2] = {&plan->xnet, &plan->vnet};
+  for (const l2hmc_dense_net* n : nets) {
+    L2HMC_REQUIRE(n->D == dim && n->Ka == dim && n->Kb == dim && n->H == H,
+                  "%s: net shape (D=%d Ka=%d Kb=%d H=%d) != (x_dim=%d, num_nodes=%d)", who, n->D, n->Ka, n->Kb, n->H,
+                  dim, H);
+    L2HMC_REQUIRE(n->w1_t && n->wt && n->b1 && n->wh_t && n->bh && n->whd_t && n->bhd && n->coeff_s && n->coeff_q,
+                  "%s: net has NULL weight pointer", who);
+  }
+  return L2HMC_OK;
+}
+
+// What the run entries (l2hmc_small_run, _run_tempered, _hmc_run) check of their own arguments; a step draws from
+// `streams` Philox streams.  (Temperatures and step sizes live on the device and are not looked at.)
+inline int check_small_run_args(const char* who, const l2hmc_small_plan* plan, const float* x_in, const float* x_next,
+                                int64_t B, uint64_t draw0, int32_t n_steps, int streams, int64_t step_stride,
+                                int64_t chain_stride) {
+  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  L2HMC_REQUIRE(x_in != nullptr && x_next != nullptr, "%s: x_in / x_next is NULL", who);
+  L2HMC_REQUIRE(B >= 0, "%s: B < 0", who);
+  L2HMC_REQUIRE(n_steps > 0, "%s: n_steps=%d must be positive", who, n_steps);
+  L2HMC_REQUIRE((uint64_t)streams * (uint64_t)n_steps <= UINT64_MAX - draw0,
+                "%s: draw0 + %d * n_steps overflows 64 bits (draw0=%llu, n_steps=%d)", who, streams,
+                (unsigned long long)draw0, n_steps);
+  L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0, "%s: negative stride (step_stride=%lld, chain_stride=%lld)",
+                who, (long long)step_stride, (long long)chain_stride);
   return L2HMC_OK;
 }
 

@@ -68,18 +68,6 @@ struct SmallTrajArgs {
 #ifdef L2HMC_STAMPS
 extern unsigned long long* g_stamp_buf;      // stq_dense.hip (l2hmc_debug_set_stamps)
 extern int g_stamp_cls;
-#define ST_NOW()                                                                              \
-  ({                                                                                          \
-    unsigned long long t_;                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-    t_;                                                                                       \
-  })
-#define ST_ADD(slot, t0) st[slot] += ST_NOW() - (t0)
-#else
-#define ST_NOW() 0ull
-#define ST_ADD(slot, t0) do {} while (0)
 #endif
 
 // =====================================================================================================
@@ -355,7 +343,7 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
   using V = MfmaNet<HP, MD, KS_, KSH_>;
   constexpr int NT = V::NT, KS = V::KS, KSH = V::KSH, NTH = V::NTH, KS1 = V::KS1, K1 = V::K1;
   const int q = lane >> 4, r = lane & 15;
-  [[maybe_unused]] unsigned long long t0 = ST_NOW();
+  [[maybe_unused]] unsigned long long t0 = L2HMC_CYCLES_NOW();
   // ---- layer 1: h1[s] = relu(pre-activation of unit 4 s + q), the same ascending-k fma chain in both forms
   constexpr int K2 = L1M ? KSH : KS;        // k-steps of the hidden layer: unit 16 t + 4 q + e at step 4 t + e (L1M), 4 s + q (VALU)
   float h1[K2];
@@ -398,8 +386,8 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
       h1[s] = fmaxf(pre, 0.f);
     }
   }
-  ST_ADD(0, t0);
-  t0 = ST_NOW();
+  L2HMC_CYCLES_ADD(st, 0, t0);
+  t0 = L2HMC_CYCLES_NOW();
   // ---- layer 2
 #pragma unroll
   for (int to = 0; to < NT; ++to) acc[to] = f32x4s{0.f, 0.f, 0.f, 0.f};
@@ -416,8 +404,8 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
     else bias = L[V::bh + 16 * (s >> 2) + 4 * q + (s & 3)];
     h2[s] = fmaxf(acc[s >> 2][s & 3] + bias, 0.f);
   }
-  ST_ADD(1, t0);
-  t0 = ST_NOW();
+  L2HMC_CYCLES_ADD(st, 1, t0);
+  t0 = L2HMC_CYCLES_NOW();
   // ---- heads
   f32x4s hv[NTH];
 #pragma unroll
@@ -434,8 +422,8 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
     else bias = *reinterpret_cast<const f32x4s*>(L + V::bhd + 16 * th + 4 * q);
     hv[th] = c0 + c1 + bias;
   }
-  ST_ADD(2, t0);
-  t0 = ST_NOW();
+  L2HMC_CYCLES_ADD(st, 2, t0);
+  t0 = L2HMC_CYCLES_NOW();
   // output o = head * MD + d sits in register o % 4 of tile o / 16 on the lane with q = (o % 16) / 4 of this chain
   float out[3 * MD];
 #pragma unroll
@@ -454,7 +442,7 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
 #ifdef L2HMC_STAMPS
   asm volatile("" :: "v"(S[0]), "v"(T[0]), "v"(Q[0]));
 #endif
-  ST_ADD(3, t0);
+  L2HMC_CYCLES_ADD(st, 3, t0);
 }
 
 // RUN: the propose-mode body loops over a.n_steps sampler steps (l2hmc_small_run).  The single pass is the same code
@@ -523,7 +511,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   const TargetKind tk = target_kind(P.target);
   const int K = P.target.K;
   [[maybe_unused]] unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  [[maybe_unused]] const unsigned long long st_begin = ST_NOW();
+  [[maybe_unused]] const unsigned long long st_begin = L2HMC_CYCLES_NOW();
 
   float x[MD], v[MD], x_init[MD];
 #pragma unroll
@@ -532,7 +520,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   const bool treg = TargetRegs<MD>::kFits && K <= TargetRegs<MD>::KM;       // uniform
   if (treg && !AN) tregs.load(Lt, dim, K);
   auto target = [&](const float (&xx)[MD], float* E, float (&gg)[MD]) {
-    [[maybe_unused]] const unsigned long long tt = ST_NOW();
+    [[maybe_unused]] const unsigned long long tt = L2HMC_CYCLES_NOW();
     float dummy;
     // rough well / funnel: no parameter arrays, the scalars are kernel arguments -- register-resident at any MD
     if constexpr (AN) analytic_energy_grad<MD>(tk, dim, inv_temp, xx, E, gg);
@@ -541,7 +529,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
 #ifdef L2HMC_STAMPS
     asm volatile("" :: "v"(gg[0]));
 #endif
-    ST_ADD(4, tt);
+    L2HMC_CYCLES_ADD(st, 4, tt);
   };
   float g[MD], E0, E1, H0, H1, logdet;
   float S[MD], T[MD], Q[MD], bin[MD];
@@ -600,7 +588,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
               if constexpr (TW) net_eval_twin<HP, MD, KS_, KSH_>(Wx, dim, P.xnet.q_tanh, v, bin, tc, ts, lane, part, xch, ncall++ & 1, S, T, Q);
               else net_eval_mfma<HP, MD, KS_, KSH_, L1M>(Lx, Wx, dim, P.xnet.q_tanh, v, bin, tc, ts, lane, S, T, Q, st);
             }
-            [[maybe_unused]] const unsigned long long tu = ST_NOW();
+            [[maybe_unused]] const unsigned long long tu = L2HMC_CYCLES_NOW();
 #pragma unroll
             for (int d = 0; d < MD; ++d) {
               if (d < dim) {
@@ -612,7 +600,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
 #ifdef L2HMC_STAMPS
             asm volatile("" :: "v"(x[0]), "v"(logdet));
 #endif
-            ST_ADD(5, tu);
+            L2HMC_CYCLES_ADD(st, 5, tu);
           }
           target(x, nullptr, g);         // (the energy itself is needed only after the last step: below)
         }
@@ -620,7 +608,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
           if constexpr (TW) net_eval_twin<HP, MD, KS_, KSH_>(Wv, dim, P.vnet.q_tanh, x, g, tc, ts, lane, part, xch, ncall++ & 1, S, T, Q);
           else net_eval_mfma<HP, MD, KS_, KSH_, L1M>(Lv, Wv, dim, P.vnet.q_tanh, x, g, tc, ts, lane, S, T, Q, st);
         }
-        [[maybe_unused]] const unsigned long long tu2 = ST_NOW();
+        [[maybe_unused]] const unsigned long long tu2 = L2HMC_CYCLES_NOW();
 #pragma unroll
         for (int d = 0; d < MD; ++d) {
           if (d < dim) {
@@ -632,12 +620,12 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
 #ifdef L2HMC_STAMPS
         asm volatile("" :: "v"(v[0]), "v"(logdet));
 #endif
-        ST_ADD(5, tu2);
+        L2HMC_CYCLES_ADD(st, 5, tu2);
       }
     }
 #ifdef L2HMC_STAMPS
     if (a.stamps && lane == 0 && part == 0) {        // (totals so far: a run leaves those of all its steps)
-      st[6] = ST_NOW() - st_begin;
+      st[6] = L2HMC_CYCLES_NOW() - st_begin;
       for (int i = 0; i < 8; ++i) a.stamps[gw * 8 + i] = st[i];
     }
 #endif
@@ -800,7 +788,7 @@ extern "C" int l2hmc_mog_energy_grad(const l2hmc_mog_target* tgt, const float* x
   return L2HMC_OK;
 }
 
-static int small_launch(const l2hmc_small_plan* plan, SmallTrajArgs a, l2hmc_stream_t stream);
+static int small_launch(const char* who, const l2hmc_small_plan* plan, SmallTrajArgs a, l2hmc_stream_t stream);
 static int small_run_entry(const char* who, const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
                            uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride,
                            int64_t chain_stride, bool tempered, float* px, float* samples, l2hmc_stream_t stream);
@@ -817,7 +805,7 @@ extern "C" int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x,
   SmallTrajArgs a{};
   a.plan = *plan; a.x0 = x; a.rows = 2 * B;
   a.prop_B = B; a.seed = seed; a.draw0 = draw0; a.Lx = Lx; a.Lv = Lv; a.px = px; a.mh_out = x_out;
-  return small_launch(plan, a, stream);
+  return small_launch("small_propose", plan, a, stream);
 }
 
 extern "C" int l2hmc_small_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
@@ -840,27 +828,17 @@ extern "C" int l2hmc_small_run_tempered(const l2hmc_small_plan* plan, const floa
 static int small_run_entry(const char* who, const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
                            uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride,
                            int64_t chain_stride, bool tempered, float* px, float* samples, l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
-  L2HMC_REQUIRE(x_in != nullptr && x_next != nullptr, "%s: x_in / x_next is NULL", who);
-  L2HMC_REQUIRE(B >= 0, "%s: B < 0", who);
-  L2HMC_REQUIRE(n_steps > 0, "%s: n_steps=%d must be positive", who, n_steps);
+  if (int e = check_small_run_args(who, plan, x_in, x_next, B, draw0, n_steps, 4, step_stride, chain_stride)) return e;
   L2HMC_REQUIRE(!plan->hmc, "%s: the hmc sampler proposes with the forward trajectory only "
                             "(utils/sampler.py:30-32): use l2hmc_small_trajectory + l2hmc_mix_accept", who);
-  L2HMC_REQUIRE(4 * (uint64_t)n_steps <= UINT64_MAX - draw0,
-                "%s: draw0 + 4 * n_steps overflows 64 bits (draw0=%llu, n_steps=%d)", who,
-                (unsigned long long)draw0, n_steps);
-  if (tempered) {
-    L2HMC_REQUIRE(temps != nullptr, "%s: temps is NULL", who);
-    L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0, "%s: negative stride (step_stride=%lld, chain_stride=%lld)",
-                  who, (long long)step_stride, (long long)chain_stride);
-  }
+  L2HMC_REQUIRE(!tempered || temps != nullptr, "%s: temps is NULL", who);
   if (B == 0) return L2HMC_OK;
   SmallTrajArgs a{};
   a.plan = *plan; a.x0 = x_in; a.rows = 2 * B;
   a.prop_B = B; a.seed = seed; a.draw0 = draw0; a.px = px; a.mh_out = x_next;
   a.n_steps = n_steps; a.samples = samples;
   a.temps = temps; a.temp_step_stride = step_stride; a.temp_chain_stride = chain_stride;
-  return small_launch(plan, a, stream);
+  return small_launch(who, plan, a, stream);
 }
 
 extern "C" int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float* x0, const float* v0,
@@ -873,30 +851,18 @@ extern "C" int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float*
   SmallTrajArgs a{};
   a.plan = *plan; a.x0 = x0; a.v0 = v0; a.dir = dir; a.rows = rows;
   a.x_out = x_out; a.v_out = v_out; a.sumlogdet = sumlogdet; a.p_accept = p_accept;
-  return small_launch(plan, a, stream);
+  return small_launch("small_trajectory", plan, a, stream);
 }
 
-static int small_launch(const l2hmc_small_plan* plan, SmallTrajArgs a, l2hmc_stream_t stream) {
-  if (int e = check_target(&plan->target)) return e;
-  const int dim = plan->x_dim, H = plan->num_nodes, N = plan->trajectory_length;
-  L2HMC_REQUIRE(dim == plan->target.dim, "small_trajectory: x_dim=%d != target dim=%d", dim, plan->target.dim);
-  L2HMC_REQUIRE(N > 0 && plan->masks != nullptr, "small_trajectory: bad trajectory_length / masks");
+static int small_launch(const char* who, const l2hmc_small_plan* plan, SmallTrajArgs a, l2hmc_stream_t stream) {
+  if (int e = check_small_plan(plan, who, !plan->hmc)) return e;
+  if (!plan->hmc)
+    if (int e = check_small_nets(plan, who)) return e;
   L2HMC_REQUIRE(plan->first_layer_form >= 0 && plan->first_layer_form <= 3,
-                "small_trajectory: first_layer_form=%d (0 by batch size, 1 matrix pipe, 2 VALU, 3 two waves per group)",
+                "%s: first_layer_form=%d (0 by batch size, 1 matrix pipe, 2 VALU, 3 two waves per group)", who,
                 plan->first_layer_form);
+  const int dim = plan->x_dim, H = plan->num_nodes;
   const int64_t rows = a.rows;
-  if (!plan->hmc) {
-    L2HMC_REQUIRE(H > 0 && H <= 64, "small_trajectory: num_nodes=%d unsupported (1..64)", H);
-    const l2hmc_dense_net* nets[2] = {&plan->xnet, &plan->vnet};
-    for (const l2hmc_dense_net* n : nets) {
-      L2HMC_REQUIRE(n->D == dim && n->Ka == dim && n->Kb == dim && n->H == H,
-                    "small_trajectory: net shape (D=%d Ka=%d Kb=%d H=%d) != (x_dim=%d, num_nodes=%d)", n->D,
-                    n->Ka, n->Kb, n->H, dim, H);
-      L2HMC_REQUIRE(n->w1_t && n->wt && n->b1 && n->wh_t && n->bh && n->whd_t && n->bhd && n->coeff_s &&
-                        n->coeff_q,
-                    "small_trajectory: net has NULL weight pointer");
-    }
-  }
   const bool d2 = dim <= 2;          // the benchmark targets: x_dim 2 instance (chain state entirely in registers)
   const dim3 grid((unsigned)ceil_div(rows, (kSmallThreads / 64) * 16));     // 16 chains per wave
   hipStream_t st = (hipStream_t)stream;

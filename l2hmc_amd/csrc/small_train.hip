@@ -8,7 +8,9 @@
 //
 // A chain's loss term depends only on that chain's trajectory, so ONE launch does forward, loss and
 // the whole reverse pass for the sixteen chains of a workgroup, entirely on-chip:
-//  * forward as small_traj_kernel (sixteen lanes per chain, weights in LDS), keeping only each
+//  * forward with net_eval (small_mlp.h: sixteen lanes per chain, weights in LDS; the one copy, which the reverse
+//    pass calls again for the hidden units), the loop of small_step.h's small_trajectory spelled out here (through
+//    that function nine of the sixteen instances gained scratch or a register step), keeping only each
 //    network call's inputs and the state it updated in an LDS tape (3*dim floats per call);
 //  * reverse pass call by call: the network is RE-EVALUATED from the taped inputs (cheaper than
 //    taping 2*H activations per call), the sub-update and the three heads are differentiated in
@@ -198,76 +200,6 @@ __device__ __forceinline__ void acc_store(const SmallAcc<HP, MD, TH>& a, int H, 
   }
 }
 
-// network evaluation that also returns this lane's hidden units (post-relu)
-template <int HP, int MD>
-__device__ void net_eval_keep(const float* L, int dim, int q_tanh, const float* a, const float* b, float tc, float ts,
-                              int sub, float* hrow, float* h1, float* h2, float* S, float* T, float* Q) {
-  constexpr int kMaxDim = MD;
-  constexpr int UPL = HP / kLPC;
-  const SmallNetView v = small_net_view(HP, dim);
-  const int n0 = sub * UPL;
-#pragma unroll
-  for (int j = 0; j < UPL; ++j) h1[j] = L[v.b1 + n0 + j] + tc * L[v.wt + n0 + j] + ts * L[v.wt + HP + n0 + j];
-#pragma unroll
-  for (int k = 0; k < kMaxDim; ++k) {
-    if (k < dim) {
-#pragma unroll
-      for (int j = 0; j < UPL; ++j)
-        h1[j] += a[k] * L[v.w1 + k * HP + n0 + j] + b[k] * L[v.w1 + (dim + k) * HP + n0 + j];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < UPL; ++j) {
-    h1[j] = fmaxf(h1[j], 0.f);
-    hrow[n0 + j] = h1[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < UPL; ++j) h2[j] = L[v.bh + n0 + j];
-  // four input units per step: one 16-byte read of the hidden row (broadcast within the chain's 16 lanes) instead of
-  // four scalar ones -- the loop is LDS-issue-bound (one weight read per UPL multiply-adds); same summation order
-  using hvec4 = __attribute__((ext_vector_type(4))) float;
-#pragma unroll 4
-  for (int k = 0; k < HP; k += 4) {
-    const hvec4 hv = *reinterpret_cast<const hvec4*>(hrow + k);
-    const float* w = L + v.wh + k * HP + n0;
-#pragma unroll
-    for (int j = 0; j < UPL; ++j) {
-      h2[j] += hv[0] * w[j];
-      h2[j] += hv[1] * w[HP + j];
-      h2[j] += hv[2] * w[2 * HP + j];
-      h2[j] += hv[3] * w[3 * HP + j];
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < UPL; ++j) h2[j] = fmaxf(h2[j], 0.f);
-#pragma unroll
-  for (int d = 0; d < kMaxDim; ++d) {
-    if (d < dim) {
-      float ps = 0.f, pt = 0.f, pq = 0.f;
-      const float* ws = L + v.whd + (0 * dim + d) * HP + n0;
-      const float* wt = L + v.whd + (1 * dim + d) * HP + n0;
-      const float* wq = L + v.whd + (2 * dim + d) * HP + n0;
-#pragma unroll
-      for (int j = 0; j < UPL; ++j) {
-        ps += h2[j] * ws[j];
-        pt += h2[j] * wt[j];
-        pq += h2[j] * wq[j];
-      }
-      // the chain's sixteen lanes are one DPP row: four VALU steps each instead of four ds_bpermute round trips
-      static_assert(kLPC == 16, "row16_sum reduces over the 16 lanes of a chain");
-      ps = row16_sum(ps);
-      pt = row16_sum(pt);
-      pq = row16_sum(pq);
-      const float s = ps + L[v.bhd + d], t = pt + L[v.bhd + dim + d], q = pq + L[v.bhd + 2 * dim + d];
-      S[d] = tanhf(s) * L[v.es + d];
-      T[d] = t;
-      Q[d] = (q_tanh ? tanhf(q) : q) * L[v.eq + d];
-    }
-  }
-}
-
 // Hessian(energy)(x) . u for the mixture / Gaussian target (second derivative of distributions.py:151-158):
 //   H = sum_k r_k P_k - sum_k r_k g_k g_k^T + gbar gbar^T,   g_k = P_k (x - mu_k), r = softmax(V), gbar = sum r_k g_k
 // with P_k the symmetrised precision; everything divided by the temperature.
@@ -380,21 +312,6 @@ struct SmallTrainArgs {
   float* dx0; float* dv0; float* sumlogdet;       // outputs of the VJP instance, each may be NULL
 };
 
-#ifdef L2HMC_STAMPS
-#define ST_NOW()                                                                              \
-  ({                                                                                          \
-    unsigned long long t_;                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                \
-    __builtin_amdgcn_sched_barrier(0);                                                        \
-    t_;                                                                                       \
-  })
-#define ST_ADD(slot, t0) st_[slot] += ST_NOW() - (t0)
-#else
-#define ST_NOW() 0ull
-#define ST_ADD(slot, t0) do {} while (0)
-#endif
-
 // VJP = false: the reverse pass is seeded by the squared-jump-distance loss (l2hmc_small_train_step);
 // VJP = true: by the caller's cotangents of (x_N, v_N, sumlogdet, p) (l2hmc_small_vjp), and the gradient with
 // respect to the start state is written out.  Everything else is the same code.
@@ -405,7 +322,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   // diagnostic cycle shares (class 7): 0 prologue, 1 forward, 2 loss, 3 net re-evaluation, 4 sub-update + head deltas,
   // 5 hidden deltas (d2, d1, input gradients), 6 owner pass, 7 total
   [[maybe_unused]] unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  [[maybe_unused]] const unsigned long long st_begin = ST_NOW();
+  [[maybe_unused]] const unsigned long long st_begin = L2HMC_CYCLES_NOW();
   constexpr int kMaxDim = MD, kMisc = small_misc(MD);      // shadow the library-wide bound for this instance
   constexpr int UPL = HP / kLPC;
   extern __shared__ __attribute__((aligned(16))) float lds[];      // (every carve-out below is a multiple of 16 bytes)
@@ -464,8 +381,8 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   for (int d = 0; d < kMaxDim; ++d) kin0 += v[d] * v[d];
   const float H0 = E0 + 0.5f * kin0;
 
-  ST_ADD(0, st_begin);
-  [[maybe_unused]] unsigned long long st_t = ST_NOW();
+  L2HMC_CYCLES_ADD(st_, 0, st_begin);
+  [[maybe_unused]] unsigned long long st_t = L2HMC_CYCLES_NOW();
   // ------------------------------------------------------------------ forward, taping call inputs
   float logdet = 0.f;
   float S[kMaxDim], T[kMaxDim], Q[kMaxDim], bin[kMaxDim], h1[UPL], h2[UPL];
@@ -488,7 +405,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
               tp[2 * dim + d] = x[d];
             }
           }
-          net_eval<HP, MD>(Lx, dim, P.xnet.q_tanh, v, bin, tc, ts, lsub, hrow, S, T, Q);
+          net_eval<HP, MD>(Lx, dim, P.xnet.q_tanh, v, bin, tc, ts, lsub, hrow, h1, h2, S, T, Q);
 #pragma unroll
           for (int d = 0; d < kMaxDim; ++d) {
             if (d < dim) {
@@ -510,7 +427,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
             tp[2 * dim + d] = v[d];
           }
       }
-      net_eval<HP, MD>(Lv, dim, P.vnet.q_tanh, x, g, tc, ts, lsub, hrow, S, T, Q);
+      net_eval<HP, MD>(Lv, dim, P.vnet.q_tanh, x, g, tc, ts, lsub, hrow, h1, h2, S, T, Q);
 #pragma unroll
       for (int d = 0; d < kMaxDim; ++d) {
         if (d < dim) {
@@ -528,8 +445,8 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   const float H1 = E1 + 0.5f * kin1;
   const float p = accept_from_delta(H0 - H1 + logdet);
 
-  ST_ADD(1, st_t);
-  st_t = ST_NOW();
+  L2HMC_CYCLES_ADD(st_, 1, st_t);
+  st_t = L2HMC_CYCLES_NOW();
   float dx[kMaxDim], dv[kMaxDim], dD, dl;
   if constexpr (!VJP) {
     // ---------------------------------------------------------------- loss (mog_model.py:336-355)
@@ -583,7 +500,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   }
   float deps = 0.f;
 
-  ST_ADD(2, st_t);
+  L2HMC_CYCLES_ADD(st_, 2, st_t);
   // ------------------------------------------------------------------ reverse pass
   SmallAcc<HP, MD, TH> accX, accV;
   acc_zero(accX);
@@ -606,10 +523,10 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       bin[d] = d < dim ? tp[dim + d] : 0.f;
       st[d] = d < dim ? tp[2 * dim + d] : 0.f;
     }
-    st_t = ST_NOW();
-    net_eval_keep<HP, MD>(L, dim, q_tanh, ain, bin, tc, ts, lsub, hrow, h1, h2, S, T, Q);
-    ST_ADD(3, st_t);
-    st_t = ST_NOW();
+    st_t = L2HMC_CYCLES_NOW();
+    net_eval<HP, MD>(L, dim, q_tanh, ain, bin, tc, ts, lsub, hrow, h1, h2, S, T, Q);
+    L2HMC_CYCLES_ADD(st_, 3, st_t);
+    st_t = L2HMC_CYCLES_NOW();
     const SmallNetView nvw = small_net_view(HP, dim);
     // ---- sub-update backward -> head pre-activation gradients (replicated over the chain's lanes)
     float dS[kMaxDim], dT[kMaxDim], dQ[kMaxDim], dgd[kMaxDim], keep[kMaxDim];
@@ -663,8 +580,8 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       dSS[d] = dS[d] * S[d];
       dQQ[d] = dQ[d] * Q[d];
     }
-    ST_ADD(4, st_t);
-    st_t = ST_NOW();
+    L2HMC_CYCLES_ADD(st_, 4, st_t);
+    st_t = L2HMC_CYCLES_NOW();
     // ---- hidden deltas
     float d2[UPL], d1[UPL];
 #pragma unroll
@@ -733,11 +650,11 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
       rm[(2 * kMaxDim + 1) * SS] = live ? ts : 0.f;
     }
     __syncthreads();
-    ST_ADD(5, st_t);
-    st_t = ST_NOW();
+    L2HMC_CYCLES_ADD(st_, 5, st_t);
+    st_t = L2HMC_CYCLES_NOW();
     if (vcall) acc_add<HP, MD, TH>(accV, dim, Rh1, Rh2, Rd1, Rd2, Rm);
     else acc_add<HP, MD, TH>(accX, dim, Rh1, Rh2, Rd1, Rd2, Rm);
-    ST_ADD(6, st_t);
+    L2HMC_CYCLES_ADD(st_, 6, st_t);
     // ---- into the upstream gradients
     if (vcall) {
       float u[kMaxDim], hv[kMaxDim];
@@ -784,7 +701,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   }
 #ifdef L2HMC_STAMPS
   if (a.stamps && threadIdx.x == 0) {
-    st_[7] = ST_NOW() - st_begin;
+    st_[7] = L2HMC_CYCLES_NOW() - st_begin;
     for (int i = 0; i < 8; ++i) a.stamps[blockIdx.x * 8 + i] = st_[i];
   }
 #endif
@@ -825,22 +742,8 @@ extern "C" size_t l2hmc_small_train_ws_bytes(const l2hmc_small_plan* plan, int64
 static int small_train_check(const l2hmc_small_plan* plan, int64_t rows, const char* who) {
   L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
   L2HMC_REQUIRE(!plan->hmc, "%s: hmc plans have no trainable networks", who);
-  const int dim = plan->x_dim, H = plan->num_nodes, N = plan->trajectory_length;
-  L2HMC_REQUIRE(plan->target.dim == dim, "%s: x_dim=%d != target dim=%d", who, dim, plan->target.dim);
-  if (int rc = check_target_args(&plan->target, who)) return rc;
-  L2HMC_REQUIRE(N > 0 && plan->masks != nullptr && H > 0 && H <= 64, "%s: bad plan (num_nodes 1..64)", who);
+  if (int rc = check_small_plan(plan, who, true)) return rc;
   L2HMC_REQUIRE(rows >= 0, "%s: bad rows", who);
-  return L2HMC_OK;
-}
-
-static int small_train_check_nets(const l2hmc_small_plan* plan, const char* who) {
-  const int dim = plan->x_dim, H = plan->num_nodes;
-  const l2hmc_dense_net* nets[2] = {&plan->xnet, &plan->vnet};
-  for (const l2hmc_dense_net* n : nets) {
-    L2HMC_REQUIRE(n->D == dim && n->Ka == dim && n->Kb == dim && n->H == H, "%s: net shape mismatch", who);
-    L2HMC_REQUIRE(n->w1_t && n->wt && n->b1 && n->wh_t && n->bh && n->whd_t && n->bhd && n->coeff_s && n->coeff_q,
-                  "%s: net has NULL weight pointer", who);
-  }
   return L2HMC_OK;
 }
 
@@ -906,7 +809,7 @@ extern "C" int l2hmc_small_train_step(const l2hmc_small_plan* plan, const float*
   L2HMC_REQUIRE(scale > 0.f, "small_train_step: bad rows / scale");
   if (rows == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x0 && v0 && x_out && v_out && p_accept && terms && grads && ws, "small_train_step: NULL pointer");
-  if (int rc = small_train_check_nets(plan, who)) return rc;
+  if (int rc = check_small_nets(plan, who)) return rc;
   SmallTrainArgs a{*plan, x0, v0, dir, rows, scale, inv_count, x_out, v_out, p_accept, terms, static_cast<float*>(ws),
                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   return small_train_launch<false>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
@@ -920,7 +823,7 @@ extern "C" int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, co
   if (int rc = small_train_check(plan, rows, who)) return rc;
   if (rows == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x0 && v0 && grads && ws, "small_vjp: NULL pointer (x0, v0, grads and ws are required)");
-  if (int rc = small_train_check_nets(plan, who)) return rc;
+  if (int rc = check_small_nets(plan, who)) return rc;
   SmallTrainArgs a{*plan, x0, v0, dir, rows, 0.f, 0.f, x_out, v_out, p_accept, nullptr, static_cast<float*>(ws),
                    nullptr, g_x, g_v, g_logdet, g_p, dx0, dv0, sumlogdet};
   return small_train_launch<true>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);

@@ -2,11 +2,15 @@
 
     python tools/lf_update_bits.py build PARENT_TREE OUT_DIR      the parent's library -> OUT_DIR/libl2hmc_hip_parent.so
     python tools/lf_update_bits.py dump GROUP OUT.npz             one group of cases with the library L2HMC_LIB_PATH names
-    python tools/lf_update_bits.py run PARENT_TREE OUT_DIR        build (unless OUT_DIR already holds the library), then per
-                                                                  group: dump(parent), dump(this tree), compare
-    python tools/lf_update_bits.py time OUT.json                  ms per call of every timing case, one after another in
-                                                                  this process, library as for dump
-    python tools/lf_update_bits.py timing PARENT_TREE OUT_DIR     build, then time(parent), time(this tree) alternating,
+    python tools/lf_update_bits.py run PARENT_TREE OUT_DIR [GROUP]
+                                                                  build (unless OUT_DIR already holds the library), then per
+                                                                  group (or for GROUP alone): dump(parent), dump(this
+                                                                  tree), compare
+    python tools/lf_update_bits.py time OUT.json [ONLY]           ms per call of every timing case (or of those whose name
+                                                                  holds ONLY), one after another in this process,
+                                                                  library as for dump
+    python tools/lf_update_bits.py timing PARENT_TREE OUT_DIR [ONLY]
+                                                                  build, then time(parent), time(this tree) alternating,
                                                                   three rounds (one child process per library and
                                                                   round), and the table with the bound
 
@@ -193,19 +197,90 @@ def group_fused(la, out):
     _train_steps(GaugeTrainer(dyn, lr_init=1e-3), x, beta, out, "fused/train8x8")
 
 
-def _toy_dyn(la, dim, nodes, form, target="gmm", N=3, seed=42):
+def _toy_dyn(la, dim, nodes, form, target="gmm", N=3, seed=42, hmc=False, use_temperature=False):
     import numpy as np
     np.random.seed(seed)
     if target == "gmm":
         mus = [np.eye(dim)[0], np.eye(dim)[1]]
         fn = la.GMM(mus, [0.1 * np.eye(dim)] * 2, [0.5, 0.5]).get_energy_function()
+    elif target == "gmm3":          # K = 3: more components than TargetRegs holds, so energy_grad from LDS
+        mus = [np.eye(dim)[0], np.eye(dim)[1], -np.eye(dim)[0]]
+        fn = la.GMM(mus, [0.1 * np.eye(dim)] * 3, [0.5, 0.25, 0.25]).get_energy_function()
+    elif target == "funnel":
+        fn = la.GaussianFunnel(dim).get_energy_function()
     else:
         fn = la.RoughWell(dim, 0.1).get_energy_function()
-    dyn = la.Dynamics(dim, fn, trajectory_length=N, eps=0.1,
+    dyn = la.Dynamics(dim, fn, trajectory_length=N, eps=0.1, hmc=hmc, use_temperature=use_temperature,
                       net_factory=lambda d, scope, factor: la.network(d, scope, factor, num_nodes=nodes))
     dyn.first_layer_form = form
     assert not dyn.layered
     return dyn
+
+
+def _toy_more(la, out):
+    """the paths the cases below leave out: plain-HMC runs, tempered runs, the hmc plan, K = 3, the analytic kinds above
+    x_dim 2, training above x_dim 2 / 10 nodes.  3 leapfrog steps, 3 MCMC steps."""
+    import numpy as np
+    import torch
+    from l2hmc_amd.dynamics_sampler import DynamicsSampler
+    from l2hmc_amd.dynamics_trainer import DynamicsTrainer
+    from l2hmc_amd.sampler import propose
+    rng = np.random.default_rng(11)
+
+    def keep(name, run):
+        out[f"{name}/px"], out[f"{name}/samples"], out[f"{name}/x"] = run["px"], run["samples"], run["samples_out"]
+
+    # run_hmc at 70 chains: one full 64-thread workgroup and a part-full one
+    B = 70
+    sched = np.linspace(2.0, 1.0, 3)
+    for dim, target in ((2, "gmm"), (2, "gmm3"), (2, "rough"), (5, "funnel")):
+        smp = DynamicsSampler(_toy_dyn(la, dim, 10, 0, target, hmc=True, use_temperature=True))
+        x = _dev(rng.normal(0, 0.8, (B, dim)))
+        ladder = np.linspace(1.0, 3.0, B)[None, :]
+        keep(f"toy/run_hmc/{target}_d{dim}/plain", smp.run_hmc(3, x=x))
+        keep(f"toy/run_hmc/{target}_d{dim}/schedule", smp.run_hmc(3, x=x, temperature=sched))
+        keep(f"toy/run_hmc/{target}_d{dim}/ladder", smp.run_hmc(3, x=x, temperature=ladder))
+        keep(f"toy/run_hmc/{target}_d{dim}/eps_chain", smp.run_hmc(3, x=x, eps=np.linspace(0.05, 0.15, B)))
+    # run with a schedule and with a ladder, 40 chains
+    B = 40
+    ladder = np.linspace(1.0, 3.0, B)[None, :]
+    for dim, nodes in ((2, 10), (5, 64)):
+        for form in (1, 2, 3):
+            smp = DynamicsSampler(_toy_dyn(la, dim, nodes, form, use_temperature=True))
+            x = _dev(rng.normal(0, 0.8, (B, dim)))
+            keep(f"toy/run_tempered/d{dim}_n{nodes}_form{form}/schedule", smp.run(3, x=x, temperature=sched))
+            keep(f"toy/run_tempered/d{dim}_n{nodes}_form{form}/ladder", smp.run(3, x=x, temperature=ladder))
+    # the P.hmc path of small_traj_mfma_kernel
+    dyn = _toy_dyn(la, 2, 10, 0, hmc=True)
+    x, v = _dev(rng.normal(0, 0.8, (B, 2))), _dev(rng.standard_normal((B, 2)))
+    for tag, res in (("fwd", dyn.forward(x, init_v=v, log_jac=True)), ("bwd", dyn.backward(x, init_v=v, log_jac=True)),
+                     ("fwd_p", dyn.forward(x, init_v=v))):
+        for k, a in zip(("x", "v", "third"), res):
+            out[f"toy/hmc_plan/{tag}/{k}"] = a
+    Lx, _, px, outs = propose(x, dyn, do_mh_step=True)
+    out["toy/hmc_plan/propose/Lx"], out["toy/hmc_plan/propose/px"], out["toy/hmc_plan/propose/out"] = Lx, px, outs[0]
+    # run on the three-component mixture
+    keep("toy/run/gmm3_d2", DynamicsSampler(_toy_dyn(la, 2, 10, 0, "gmm3")).run(3, x=x))
+    # training: x_dim 5 / 64 nodes on the mixture (2 leapfrog steps: the tape fits the LDS), the AN instance on the rough well
+    for dim, nodes, target, N in ((5, 64, "gmm", 2), (2, 10, "rough", 3)):
+        name = f"toy/train/{target}_d{dim}_n{nodes}"
+        x = _dev(rng.normal(0, 0.8, (B, dim)))
+        tr = DynamicsTrainer(_toy_dyn(la, dim, nodes, 0, target, N=N), scale=0.1)
+        res = tr.train_step(x)
+        for k, a in zip(("loss", "x_out", "px"), res):
+            out[f"{name}/train_step/{k}"] = a
+        out[f"{name}/train_step/grads"] = tr.grads.clone()
+        dyn = _toy_dyn(la, dim, nodes, 0, target, N=N)
+        for t in dyn.variables:
+            t.requires_grad_()
+        xg, vg = x.clone().requires_grad_(), _dev(rng.standard_normal((B, dim))).requires_grad_()
+        for tag, fn in (("fwd", dyn.forward), ("bwd", dyn.backward)):
+            X, V, lj = fn(xg, init_v=vg, log_jac=True)
+            (X.sum() + 0.5 * (V * V).sum() + 0.25 * lj.sum()).backward()
+            for i, t in enumerate([xg, vg, *dyn.variables]):
+                if t.grad is not None:
+                    out[f"{name}/vjp/{tag}/grad{i}"] = t.grad.clone()
+                    t.grad = None
 
 
 def group_toy(la, out):
@@ -252,6 +327,7 @@ def group_toy(la, out):
             if t.grad is not None:
                 out[f"toy/vjp/{tag}/grad{i}"] = t.grad.clone()
                 t.grad = None
+    _toy_more(la, out)
 
 
 # ---- timing cases: name -> builder of a callable that runs one call --------------------------------------------
@@ -344,7 +420,8 @@ def dump(group, path):
     print(f"dump {group}: {len(arrays)} arrays with {_lib.LIB_PATH} -> {path}", flush=True)
 
 
-def time_calls(path):
+def time_calls(path, only=""):
+    """`only`: substring of the names of the cases to time (all when empty)."""
     import json
     import time
     import torch
@@ -352,6 +429,8 @@ def time_calls(path):
     from l2hmc_amd import _lib
     res = {}
     for name, build in time_cases(la).items():
+        if only not in name:
+            continue
         call = build()
         for _ in range(2):
             call()
@@ -374,7 +453,7 @@ def time_calls(path):
         json.dump(res, f)
 
 
-def timing(parent, outdir):
+def timing(parent, outdir, only=""):
     import json
     import statistics
     os.makedirs(outdir, exist_ok=True)
@@ -383,7 +462,7 @@ def timing(parent, outdir):
     for r in range(3):
         for who, lib in libs.items():
             path = os.path.join(outdir, f"time_{who}_{r}.json")
-            rc = subprocess.run(["timeout", "-k", "10", "400", sys.executable, os.path.abspath(__file__), "time", path],
+            rc = subprocess.run(["timeout", "-k", "10", "400", sys.executable, os.path.abspath(__file__), "time", path, only],
                                 env=dict(os.environ, L2HMC_LIB_PATH=lib)).returncode
             if rc != 0:
                 sys.exit(f"timing: round {r} ({who}) ended with status {rc}; nothing more is started")
@@ -414,11 +493,13 @@ def compare(a, b):
         return len(fa.files), len(bad), len(nonfinite)
 
 
-def run(parent, outdir):
+def run(parent, outdir, only=None):
     os.makedirs(outdir, exist_ok=True)
     libs = {"parent": build(parent, outdir), "new": os.path.join(HERE, "l2hmc_amd", "libl2hmc_hip.so")}
     total = [0, 0, 0]
     for group, (_, limit) in GROUPS.items():
+        if only and group != only:
+            continue
         for who, lib in libs.items():
             rc = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "dump", group,
                                  os.path.join(outdir, f"bits_{group}_{who}.npz")],
@@ -438,11 +519,11 @@ if __name__ == "__main__":
         build(*args)
     elif mode == "dump" and len(args) == 2:
         dump(*args)
-    elif mode == "run" and len(args) == 2:
+    elif mode == "run" and len(args) in (2, 3):
         sys.exit(run(*args))
-    elif mode == "time" and len(args) == 1:
+    elif mode == "time" and len(args) in (1, 2):
         time_calls(*args)
-    elif mode == "timing" and len(args) == 2:
+    elif mode == "timing" and len(args) in (2, 3):
         sys.exit(timing(*args))
     else:
         sys.exit(__doc__)

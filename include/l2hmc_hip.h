@@ -203,6 +203,9 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
 #define L2HMC_PLAN_FULL_L1 64        /* whole-step kernel with plan.heads set: a position sub-update forms XNet's first-layer
                                       * product with keep (.) x over all D columns instead of the D / 2 it keeps (same bits;
                                       * the active-column heads stay on; L2HMC_PLAN_ALL_COLUMNS switches off both).  A/B switch */
+#define L2HMC_PLAN_SINGLE_KICKS 128  /* whole-step kernel, 16-row GenericNet sampling form: the second momentum half-kick of a
+                                      * leapfrog step and the first of the next one stay two network calls instead of one
+                                      * pass over two time slices (same bits).  A/B switch */
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */
@@ -260,6 +263,11 @@ int l2hmc_gauge_step_plan(int64_t rows_all, int32_t cus, int64_t* rows_out, int3
 int l2hmc_gauge_leapfrog(const l2hmc_gauge_plan* plan, float beta, int32_t step, float* x, float* v,
                          const int32_t* dir, int64_t rows, float* logdet, void* ws, size_t ws_bytes,
                          l2hmc_stream_t stream);
+/* ... and the steps [step_begin, step_end) of a trajectory in one call (one launch where the plan has a
+ * whole-trajectory kernel): 0 <= step_begin < step_end <= num_steps. */
+int l2hmc_gauge_leapfrog_steps(const l2hmc_gauge_plan* plan, float beta, int32_t step_begin, int32_t step_end, float* x,
+                               float* v, const int32_t* dir, int64_t rows, float* logdet, void* ws, size_t ws_bytes,
+                               l2hmc_stream_t stream);
 
 /* Full trajectory of `rows` chain-direction pairs: x0, v0 -> x_out, v_out,
  * sumlogdet, accept probability (any of the last two may be NULL). */

@@ -18,6 +18,7 @@ c_float_p = C.c_void_p   # device pointers travel as integers
 MAX_MIX, MAX_SMALL_DIM, MAX_SMALL_NODES = 8, 8, 64
 PLAN_LAYERED, PLAN_CONV3D, PLAN_SELECTED_ONLY, PLAN_RECOMPUTE, PLAN_TILES16_ONLY, PLAN_ALL_COLUMNS = 1, 2, 4, 8, 16, 32
 PLAN_FULL_L1 = 64
+PLAN_SINGLE_KICKS = 128
 GRAD_BUCKET_REST = 6
 BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32)
 
@@ -100,6 +101,7 @@ _PROTOS = {
     "l2hmc_gauge_pack_heads_bytes": (_SZ, [C.POINTER(GaugePlan)]),
     "l2hmc_gauge_pack_heads": (C.c_int, [C.POINTER(GaugePlan), _P, _P]),
     "l2hmc_gauge_leapfrog": (C.c_int, [C.POINTER(GaugePlan), _F, _I32, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
+    "l2hmc_gauge_leapfrog_steps": (C.c_int, [C.POINTER(GaugePlan), _F, _I32, _I32, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
     "l2hmc_gauge_trajectory": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _P, _P, _I64, _P, _P, _P, _P, _P,
                                          _SZ, _P]),
     "l2hmc_gauge_transition_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64, _I32]),

@@ -49,6 +49,8 @@ struct FusedArgs {
   const int* heads_meta;                 // l2hmc_gauge_pack_heads image (step_split only), or NULL = all columns:
   const float* heads_img;                //   [N][2] eligibility, [N][2][D / 2] columns, [N][D] compact k; [N][2] packed heads sections
   const float* l1_img;                   // its [N][2] kept-column first-layer sections (needs heads_img), or NULL = full K
+  int single_kicks;                      // 16-row GenericNet sampling form: every momentum half-kick a network call of its own
+                                         // (L2HMC_PLAN_SINGLE_KICKS); 0 = step s's second and step s + 1's first as one pass
 };
 
 // the sub-tile form (fused_traj4.hip): GenericNet 8x8 plans, sampling only

@@ -23,6 +23,16 @@
 // buffered one k-chunk (16 k) ahead.  The A operand (16 rows of activations) is
 // shared by the 4 waves and read from LDS with conflict-free ds_read_b128
 // (row stride = K + 8 floats).
+//
+// Paired momentum half-kicks (GenericNet sampling instance, 8 waves on the 4-wave image): the second half-kick of
+// leapfrog step s and the first of step s + 1 are two VNet evaluations at the same (x, force) that differ only in the
+// time term of the first-layer epilogue.  Inside a launch they run as ONE pass: the first layer once, its epilogue
+// twice (step s's rows into h1, step s + 1's into h2), then in every image section the even wave walks layer 2 and
+// the heads for step s over all of the section's tiles in the reverse direction (as an odd call does) and the odd
+// wave does the same for step s + 1 forward -- every accumulator keeps its k order, so the bits do not change -- and
+// the odd wave applies its kick to the v' the even wave has written, behind a barrier.  Five barriers and three MFMA
+// phases of twice the length instead of seven and five; the next step's masks are loaded inside the pass.
+// L2HMC_PLAN_SINGLE_KICKS keeps one network call per half-kick (A/B).  DESIGN.md section 4, K1.
 #include "fused_step.h"
 #include "lf_update.h"
 #include <atomic>
@@ -428,7 +438,15 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   //   keep_v: VNet's whole first-layer product.  The second half-kick of step s and the first half-kick of
   //           step s+1 see the same (x, force); only the time term differs, and that is added in the epilogue.
   //   keep_x: XNet's product with its FIRST input (v), identical for the two position sub-updates of a step.
-  f32x4 keep_v[NT1], keep_x[NT1];
+  // keep_x lives from call 1 to call 2 of a step and keep_v from call 3 to the next step's call 0: never both, so
+  // the instance with the paired call (below), which needs the registers, keeps them in ONE set.
+  constexpr bool KEEP1 = !CONV && !TAPE && Cfg::NTH == 1 && RW == 2 && kFWaves == 8;
+  f32x4 keep_v[NT1];
+  [[maybe_unused]] f32x4 keep_x_own[KEEP1 ? 1 : NT1];
+  f32x4 (&keep_x)[NT1] = *[&]() {
+    if constexpr (KEEP1) return &keep_v;
+    else return &keep_x_own;
+  }();
   bool keep_v_valid = false;
   // Active-column heads (split step mode, l2hmc_gauge_pack_heads): a position sub-update moves only the columns whose
   // keep is 0 -- x' = keep x + (1 - keep) upd and the log-det term carry (1 - keep) -- so S / T / Q are formed for those
@@ -437,12 +455,15 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   // epilogue expressions; the log-det terms are staged at their columns and summed in today's grouping.
   constexpr bool ACTOK = !CONV && !TAPE && Cfg::NTH == 1 && RW == 2 && kFWaves == 8;
   int arow = 0;                        // mask row of this workgroup's direction at the current step
+  // Paired momentum half-kicks (8 waves on the 4-wave image, sampling only): call 3 of step s and call 0 of step s + 1
+  // run as ONE pass over two time slices (net_update's `pair`)
+  constexpr bool PAIROK = !CONV && !TAPE && Cfg::NTH == 1 && RW == 2 && kFWaves == 8;
 
   // l1: 0 = compute both halves; 1 = as 0 and store the raw product in keep_v; 2 = take keep_v, no GEMM;
   //     3 = compute, snapshot the first-input half into keep_x; 4 = start from keep_x, second half only.
   auto net_update = [&](const l2hmc_dense_net& net, const float* cn, const float* in1, int mode, int sub,
                         bool prep_next_mask, int l1, bool is_vnet, const float tcr, const float tsr,
-                        int callidx) {
+                        int callidx, bool pair, const float tcr2, const float tsr2) {
     const float* pk = net.packed;
     // layers 2 and 3 of a network are streamed in alternating directions on its consecutive calls (fused_common.h)
     const bool zig = (callidx & 1) != 0;
@@ -499,6 +520,14 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     constexpr int DP1 = L2HMC_DP1, DP2 = L2HMC_DP2, DPH = L2HMC_DPH;   // ring depths (fused_common.h): first-layer halves, layer 2, heads
     BRing<NT1, DP2> R2;
     BRing<3 * NTH, DPH> R3;
+    // paired call: a wave walks ALL tiles of its image section for one time slice (layer 2: NTI1, heads: 3 NTIH)
+#ifndef L2HMC_DP2P
+#define L2HMC_DP2P 2
+#define L2HMC_DPHP 3
+#endif
+    constexpr int DP2P = L2HMC_DP2P, DPHP = L2HMC_DPHP;
+    [[maybe_unused]] BRing<NTI1, DP2P> R2P;
+    [[maybe_unused]] BRing<3 * NTIH, DPHP> R3P;
     // ----- layer 1: two half-K streams (first input rows, then the second-input rows in gs)
     {
       constexpr int KH = Cfg::KC1 / 2;
@@ -574,9 +603,168 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
           stream_layer<NT1, KH, DP1, NTI1>(
               RB, wpb, [&](int kc) { return *reinterpret_cast<const f32x4*>(a2 + kc * 16); }, acc, false, to1);
         }
-        if (l1 == 1) {
+        if (l1 == 1 && !(PAIROK && pair)) {        // (a paired call spends the product at once, on both time terms)
 #pragma unroll
           for (int t = 0; t < NT1; ++t) keep_v[t] = acc[t];
+        }
+      }
+      if constexpr (PAIROK) {
+        if (pair) {
+          // ----- paired call (a path of its own from here on: the single calls' code below stays as it is).  The first
+          //       layer's product gets both steps' time terms: slice A (this step's second half-kick) into the h1 rows,
+          //       slice B (the next step's first half-kick) into the h2 rows, with the single calls' statement.
+          ring_prime<NTI1, DP2P, NTI1, 1>(R2P, wp2, wsub == 0, Cfg::KC2, 0);
+          L2HMC_CYCLES_ADD(ft, 0, t0);
+          t0 = L2HMC_CYCLES_NOW();
+#pragma unroll
+          for (int t = 0; t < NT1; ++t) {
+            const int c0 = (wave * NT1 + t) * 16 + q * 4;          // this lane: row r, columns c0 .. c0 + 3
+            const f32x4 b = *reinterpret_cast<const f32x4*>(cn + c0);
+            const f32x4 w0 = *reinterpret_cast<const f32x4*>(cn + H + c0);
+            const f32x4 w1 = *reinterpret_cast<const f32x4*>(cn + 2 * H + c0);
+            f32x4 hv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[t][e] + b[e] + (tcr * w0[e] + tsr * w1[e]), 0.f);
+            *reinterpret_cast<f32x4*>(h1 + r * SH + c0) = hv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[t][e] + b[e] + (tcr2 * w0[e] + tsr2 * w1[e]), 0.f);
+            *reinterpret_cast<f32x4*>(h2 + r * SH + c0) = hv;
+          }
+          L2HMC_CYCLES_ADD(ft, 3, t0);
+          {
+            [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
+            __syncthreads();
+            L2HMC_CYCLES_ADD(ft, 6, tb);
+          }
+          // The even wave of a section takes slice A (the reverse walk of an odd call), the odd wave slice B (forward
+          // walk), each over ALL tiles of the section: every accumulator sees the chunks and the direction it sees in
+          // the single calls.  Every barrier below is met by all waves.
+          const bool sliceb = wsub != 0;
+          float* hs = sliceb ? h2 : h1;
+          const float* a = hs + r * SH + q * 4;
+          {
+            f32x4 acc2[NTI1];
+#pragma unroll
+            for (int t = 0; t < NTI1; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            t0 = L2HMC_CYCLES_NOW();
+            stream_layer<NTI1, Cfg::KC2, DP2P, NTI1, 1>(
+                R2P, wp2, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acc2, !sliceb, 0);
+            ring_prime<3 * NTIH, DPHP, 3 * NTIH, 1>(R3P, wph, !sliceb, Cfg::KC2, 0);
+            L2HMC_CYCLES_ADD(ft, 1, t0);
+            {
+              [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
+              __syncthreads();                    // every wave has read its slice's rows: they take layer 2's output
+              L2HMC_CYCLES_ADD(ft, 6, tb);
+            }
+            t0 = L2HMC_CYCLES_NOW();
+#pragma unroll
+            for (int t = 0; t < NTI1; ++t) {
+              const int c0 = (wimg * NTI1 + t) * 16 + q * 4;
+              const f32x4 b = *reinterpret_cast<const f32x4*>(cn + 3 * H + c0);
+              f32x4 hv;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc2[t][e] + b[e], 0.f);
+              *reinterpret_cast<f32x4*>(hs + r * SH + c0) = hv;
+            }
+            L2HMC_CYCLES_ADD(ft, 4, t0);
+          }
+          {
+            [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
+            __syncthreads();
+            L2HMC_CYCLES_ADD(ft, 6, tb);
+          }
+          f32x4 acch[3 * NTIH];
+#pragma unroll
+          for (int t = 0; t < 3 * NTIH; ++t) acch[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+          t0 = L2HMC_CYCLES_NOW();
+          stream_layer<3 * NTIH, Cfg::KC2, DPHP, 3 * NTIH, 1>(
+              R3P, wph, [&](int kc) { return *reinterpret_cast<const f32x4*>(a + kc * 16); }, acch, !sliceb, 0);
+          L2HMC_CYCLES_ADD(ft, 2, t0);
+          t0 = L2HMC_CYCLES_NOW();
+          const float* bhd = cn + 4 * H;
+          const float* es = bhd + 3 * D;
+          const float* eq = es + D;
+          const int d = dirl;
+          f32x4 S[NTIH], Tt[NTIH], Q[NTIH];
+#pragma unroll
+          for (int t = 0; t < NTIH; ++t) {
+            const int c0 = wimg * (D / IMGW) + t * 16 + q * 4;      // row r, columns c0 .. c0 + 3
+            const f32x4 b_s = *reinterpret_cast<const f32x4*>(bhd + c0);
+            const f32x4 b_t = *reinterpret_cast<const f32x4*>(bhd + D + c0);
+            const f32x4 b_q = *reinterpret_cast<const f32x4*>(bhd + 2 * D + c0);
+            const f32x4 e_s = *reinterpret_cast<const f32x4*>(es + c0);
+            const f32x4 e_q = *reinterpret_cast<const f32x4*>(eq + c0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              float s_, t_, q_;
+              heads_stq(acch[0 * NTIH + t][e], acch[1 * NTIH + t][e], acch[2 * NTIH + t][e], b_s[e], b_t[e], b_q[e], e_s[e],
+                        e_q[e], net.q_tanh, s_, t_, q_);
+              S[t][e] = s_; Tt[t][e] = t_; Q[t][e] = q_;
+            }
+          }
+          // the slice's kick on its section's columns and row r's log-det share, one chain of adds per lane over both
+          // tiles, then the cross-lane steps: the order of the 4-wave forms
+          auto kick_slice = [&]() {
+            float ld = 0.f;
+#pragma unroll
+            for (int t = 0; t < NTIH; ++t) {
+              const int idx = r * SX + wimg * (D / IMGW) + t * 16 + q * 4;
+              const f32x4 g = *reinterpret_cast<const f32x4*>(gs + idx);
+              const f32x4 v = *reinterpret_cast<const f32x4*>(vs + idx);
+              f32x4 vn;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                float s;
+                vn[e] = lf_kick<ExpFast>(v[e], g[e], S[t][e], Tt[t][e], Q[t][e], eps, d, s);
+                ld += s;
+              }
+              *reinterpret_cast<f32x4*>(vs + idx) = vn;
+            }
+            ld += __shfl_xor(ld, 16, 64);
+            ld += __shfl_xor(ld, 32, 64);
+            if (q == 0) ldw[wimg * kFM + r] += ld;
+          };
+          if (!sliceb) kick_slice();
+          L2HMC_CYCLES_ADD(ft, 5, t0);
+          {
+            [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
+            __syncthreads();                      // slice A's v' and log-det sums are in place
+            L2HMC_CYCLES_ADD(ft, 6, tb);
+          }
+          t0 = L2HMC_CYCLES_NOW();
+          if (sliceb) {
+            kick_slice();
+            // the next net call is the next step's first position sub-update: its second input is keep (.) x, under the
+            // masks of that step (in skm / scp / sel since the barrier behind layer 1)
+            const bool l1n = ACTOK && SPLIT && p.l1_img && p.heads_img && __builtin_amdgcn_readfirstlane(sel[0] & sel[1]) != 0;
+#pragma unroll
+            for (int t = 0; t < NTIH; ++t) {
+              const int c0 = wimg * (D / IMGW) + t * 16 + q * 4;
+              const int idx = r * SX + c0;
+              const f32x4 mf = *reinterpret_cast<const f32x4*>(skm + c0);
+              const f32x4 mb = *reinterpret_cast<const f32x4*>(skm + D + c0);
+              const f32x4 x = *reinterpret_cast<const f32x4*>(xs + idx);
+              f32x4 kx;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) kx[e] = keep_of(mf[e], mb[e], d, 0) * x[e];
+              if (l1n) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                  if (keep_of(mf[e], mb[e], d, 0) != 0.f) stg[r * SX + scp[c0 + e]] = kx[e];
+                  else if (kx[e] != kx[e]) spz[r] = kx[e];
+                }
+              } else {
+                *reinterpret_cast<f32x4*>(gs + idx) = kx;
+              }
+            }
+          }
+          L2HMC_CYCLES_ADD(ft, 5, t0);
+          {
+            [[maybe_unused]] const unsigned long long tb = L2HMC_CYCLES_NOW();
+            __syncthreads();
+            L2HMC_CYCLES_ADD(ft, 6, tb);
+          }
+          return;
         }
       }
       ring_prime<NT1, DP2, NTI1>(R2, wp2, zig, Cfg::KC2, to1);      // layer-2 weights start flowing under the epilogue + barrier
@@ -830,11 +1018,17 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 
   // ---- leapfrog steps -----------------------------------------------------------
   const float two_pi = 6.28318530717958647692f;
-  for (int step = p.step_begin; step < p.step_end; ++step) {
-    const int sf = step, sb = p.num_steps - 1 - step;       // gauge_dynamics.py:453-457
+  // time encoding of this lane's row at a step (gauge_dynamics.py:453-457)
+  auto step_time = [&](int step, float& tc, float& ts) {
+    const int sf = step, sb = p.num_steps - 1 - step;
     const float af = two_pi * (float)sf / (float)p.num_steps, ab = two_pi * (float)sb / (float)p.num_steps;
     const float tcf = cosf(af), tsf = sinf(af), tcb = cosf(ab), tsb = sinf(ab);
-    const float tcr = dirl ? tcb : tcf, tsr = dirl ? tsb : tsf;      // time encoding of this lane's row
+    tc = dirl ? tcb : tcf;
+    ts = dirl ? tsb : tsf;
+  };
+  // masks, column lists and compact-k map of a step -> LDS (the caller puts a barrier in front of their readers)
+  auto load_step_masks = [&](int step) {
+    const int sf = step, sb = p.num_steps - 1 - step;
     for (int i = tid; i < D; i += kFThreads) {
       skm[i] = p.masks[(size_t)sf * D + i];
       skm[D + i] = p.masks[(size_t)sb * D + i];
@@ -846,26 +1040,45 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       if (p.l1_img)
         for (int i = tid; i < D; i += kFThreads) scp[i] = p.heads_meta[2 * p.num_steps + (p.num_steps + arow) * D + i];
     }
-    // (gs holds the force of the current x: from the prologue or the previous step's last kick)
-    __syncthreads();
+  };
+  const bool PAIR = PAIROK && !p.single_kicks;
+  bool paired_in = false;              // this step's first half-kick ran inside the previous step's paired call
+  for (int step = p.step_begin; step < p.step_end; ++step) {
+    float tcr, tsr, tcr2 = 0.f, tsr2 = 0.f;
+    step_time(step, tcr, tsr);
+    const bool pair_out = PAIR && step + 1 < p.step_end;
+    if (!paired_in) {
+      load_step_masks(step);
+      // (gs holds the force of the current x: from the prologue or the previous step's last kick)
+      __syncthreads();
+    }
     // the four network calls of a leapfrog step run through ONE copy of the code (runtime parameters,
     // wave-uniform branches): the kernel stays well inside the instruction cache
 #pragma nounroll
-    for (int call = 0; call < 4; ++call) {
+    for (int call = paired_in ? 1 : 0; call < 4; ++call) {
       const bool is_v = call == 0 || call == 3;
+      const bool pair = pair_out && call == 3;
       if (call == 3) {
         [[maybe_unused]] const unsigned long long tf = L2HMC_CYCLES_NOW();
         float unused[1];
         force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, unused);   // force at the new position
         L2HMC_CYCLES_ADD(ft, 7, tf);
+        // paired call: no call of this step reads a mask any more (call 3 uses none), so the next step's take their
+        // place now; the barrier behind the first layer stands between these writes and slice B's reads
+        if (pair) {
+          load_step_masks(step + 1);
+          step_time(step + 1, tcr2, tsr2);
+        }
       }
       // call 0: momentum half-kick (+ keep (.) x into gs)      call 1: position sub-update 1 (+ complement mask)
-      // call 2: position sub-update 2                          call 3: second momentum half-kick (product kept)
+      // call 2: position sub-update 2                          call 3: second momentum half-kick (product kept),
+      //                                                                paired with the next step's call 0 if there is one
       const int l1 = call == 0 ? (keep_v_valid ? 2 : 0) : call == 1 ? 3 : call == 2 ? 4 : 1;
       net_update(is_v ? p.vnet : p.xnet, is_v ? cv : cx, is_v ? xs : vs, is_v ? 1 : 2, call == 2 ? 1 : 0,
-                 call < 2, l1, is_v, tcr, tsr, 2 * step + (call == 0 || call == 1 ? 0 : 1));
+                 call < 2, l1, is_v, tcr, tsr, 2 * step + (call == 0 || call == 1 ? 0 : 1), pair, tcr2, tsr2);
     }
     keep_v_valid = true;
+    paired_in = pair_out;
   }
 
   // ---- epilogue: energies, accept probability, write back -------------------------
@@ -1030,6 +1243,7 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
   a.x0 = x0; a.v0 = v0; a.dir = dir; a.rows = rows; a.x_out = x_out; a.v_out = v_out;
   a.x_mod = x_mod; a.dir_split = dir_split;
   a.logdet = logdet; a.logdet_accumulate = logdet_accumulate; a.p_accept = p_accept;
+  a.single_kicks = (p->flags & L2HMC_PLAN_SINGLE_KICKS) != 0;
   if (tape) {
     L2HMC_REQUIRE(step_begin == 0, "fused trajectory: taping needs the whole trajectory");
     L2HMC_REQUIRE(!conv || (tape_x->feat && tape_v->feat), "fused trajectory: ConvNet3D taping needs the feature tape");
@@ -1180,6 +1394,7 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
     a.step_plq = plaqs ? plaqs + c0 : nullptr; a.step_chg = charges ? charges + c0 : nullptr;
     a.step_dq = dq ? dq + c0 : nullptr;
     a.step_sums = step_sums; a.step_part = part;
+    a.single_kicks = (p->flags & L2HMC_PLAN_SINGLE_KICKS) != 0;
 #ifdef L2HMC_STAMPS
     a.stamps = g_stamp_cls == 5 ? g_stamp_buf : nullptr;
     a.stagger = g_fused_stagger;

@@ -623,8 +623,15 @@ extern "C" int l2hmc_gauge_plan_fused(const l2hmc_gauge_plan* plan) {
 extern "C" int l2hmc_gauge_leapfrog(const l2hmc_gauge_plan* plan, float beta, int32_t step, float* x, float* v,
                                     const int32_t* dir, int64_t rows, float* logdet, void* ws, size_t ws_bytes,
                                     l2hmc_stream_t stream) {
+  return l2hmc_gauge_leapfrog_steps(plan, beta, step, step + 1, x, v, dir, rows, logdet, ws, ws_bytes, stream);
+}
+
+extern "C" int l2hmc_gauge_leapfrog_steps(const l2hmc_gauge_plan* plan, float beta, int32_t step_begin, int32_t step_end,
+                                          float* x, float* v, const int32_t* dir, int64_t rows, float* logdet, void* ws,
+                                          size_t ws_bytes, l2hmc_stream_t stream) {
   if (int e = check_plan(plan)) return e;
-  L2HMC_REQUIRE(rows >= 0 && step >= 0 && step < plan->num_steps, "gauge_leapfrog: bad rows/step");
+  L2HMC_REQUIRE(rows >= 0 && step_begin >= 0 && step_begin < step_end && step_end <= plan->num_steps,
+                "gauge_leapfrog: bad rows/step");
   if (rows == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x && v && ws, "gauge_leapfrog: NULL pointer");
   const GaugeWs w = carve_gauge_ws(plan, rows, ws);
@@ -634,13 +641,14 @@ extern "C" int l2hmc_gauge_leapfrog(const l2hmc_gauge_plan* plan, float beta, in
   }
   hipStream_t s = (hipStream_t)stream;
   if (use_hmc_kernel(plan))
-    return launch_hmc_trajectory(plan, beta, step, step + 1, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
+    return launch_hmc_trajectory(plan, beta, step_begin, step_end, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
   if (use_fused(plan))
-    return launch_fused_trajectory(plan, beta, step, step + 1, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
+    return launch_fused_trajectory(plan, beta, step_begin, step_end, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
   if (int e = prepare_ws(plan, rows, w, s)) return e;
-  if (int e = leapfrog_step(plan, beta, step, x, v, dir, rows, w, s, carry_possible(plan, x, v, w), false, false,
-                            dir ? -1 : rows))
-    return e;
+  for (int step = step_begin; step < step_end; ++step)
+    if (int e = leapfrog_step(plan, beta, step, x, v, dir, rows, w, s, carry_possible(plan, x, v, w), false, false,
+                              dir ? -1 : rows))
+      return e;
   if (logdet) {
     hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, s, w.ld_part,
                        gauge_ncb(plan), rows, logdet, 1);

@@ -39,6 +39,7 @@ class GaugeDynamics:
         self.tiles16_only = False        # True: whole-step kernel on its 16-row form for every batch (A/B, bit-identity test)
         self.all_columns = False         # True: layer-by-layer path forms S/T/Q for every column of a position sub-update
         self.full_l1 = False             # True: whole-step kernel forms XNet's first-layer x product over all D columns (A/B)
+        self.single_kicks = False        # True: whole-step kernel runs every momentum half-kick as a network call of its own (A/B)
         for key, val in kwargs.items():
             if key != 'eps':             # :73-75
                 setattr(self, key, val)
@@ -140,7 +141,8 @@ class GaugeDynamics:
                            | (_lib.PLAN_RECOMPUTE if self.recompute else 0)
                            | (_lib.PLAN_TILES16_ONLY if self.tiles16_only else 0)
                            | (_lib.PLAN_ALL_COLUMNS if self.all_columns else 0)
-                           | (_lib.PLAN_FULL_L1 if self.full_l1 else 0),
+                           | (_lib.PLAN_FULL_L1 if self.full_l1 else 0)
+                           | (_lib.PLAN_SINGLE_KICKS if self.single_kicks else 0),
                            masks=_lib.dev_ptr(self.mask, name="mask"))
         if not self.hmc:
             p.xnet = self.position_fn.pack()
@@ -248,15 +250,16 @@ class GaugeDynamics:
             return x_out, v_out, p, sld
         return x_out, v_out, p
 
-    def _lf(self, position, momentum, beta, step, backward):
+    def _lf(self, position, momentum, beta, step, backward, step_end=None):
+        """Leapfrog step `step` (or the steps [step, step_end) in one call) -> (x, v, log-det)."""
         x, v = self._x(position).clone(), self._x(momentum).clone()
         rows = x.shape[0]
         logdet = torch.zeros(rows, dtype=torch.float32, device=x.device)
         plan, L = self._plan(), _lib.lib()
         dirs = self._dir(rows, True) if backward else None
         ws, nb = self._ws.get(L.l2hmc_gauge_ws_bytes(C.byref(plan), rows), x.device)
-        _lib.call("l2hmc_gauge_leapfrog", C.byref(plan), float(beta), int(step), x, v, dirs, rows, logdet, ws, nb,
-                  device=self._device)
+        _lib.call("l2hmc_gauge_leapfrog_steps", C.byref(plan), float(beta), int(step),
+                  int(step + 1 if step_end is None else step_end), x, v, dirs, rows, logdet, ws, nb, device=self._device)
         return x, v, logdet
 
     def _forward_lf(self, position, momentum, beta, step):

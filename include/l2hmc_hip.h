@@ -341,6 +341,37 @@ int l2hmc_gauge_hmc_run(const l2hmc_gauge_plan* plan, const float* betas, const 
                         float* charges, float* charge_diff, float* step_sums, float* samples, void* ws,
                         size_t ws_bytes, l2hmc_stream_t stream);
 
+/* l2hmc_gauge_hmc_run with beta per step, per chain, or both, and a step size per chain: a scan over beta or over the
+ * step size -- the columns of a ladder are independent runs, chains never interact -- in ONE launch.  The contract of
+ * l2hmc_gauge_hmc_run in every respect (the draws (seed, 2*(draw0 + s)) and (seed, 2*(draw0 + s) + 1), the
+ * [n_steps][B] histories, samples, x_next that may alias x_in, step_sums with ALL ticket words 0 on entry and left at
+ * 0, the workspace only with step_sums, one launch, graph capture, draw0 + n_steps <= 2^63, B == 0 a no-op) but this:
+ * step s of chain c runs at beta betas[s * step_stride + c * chain_stride], and chain c integrates with step size
+ * eps_chain[c] (DEVICE pointer [B], or NULL: plan->eps for every chain).  Both directions of a chain, both of its
+ * momentum half-kicks, both position sub-updates and both ends of its Hamiltonian difference use the chain's pair.
+ * betas is a DEVICE pointer; a stride may be 0:
+ *   (step_stride, chain_stride) = (1, 0)  a schedule, betas [n_steps]  (what l2hmc_gauge_hmc_run takes)
+ *                                 (0, 1)  a ladder, betas [B]
+ *                                 (B, 1)  both, betas [n_steps][B]
+ *                                 (0, 0)  one value
+ * The kernel runs the step's own fp32 operations on per-chain values, so column c has the bits of l2hmc_gauge_hmc_run
+ * with the same B, x_in, seed and draw0 at that column's betas on a plan with eps = eps_chain[c].
+ * Only plans for which l2hmc_gauge_plan_fused() is 1 are served; there is no host loop behind this entry.
+ * Refused with L2HMC_ERR_ARG before any device call: NULL plan / betas / x_in / x_next, hmc = 0, a plan without the
+ * one-launch kernel (more than 1024 sites, L2HMC_PLAN_LAYERED), n_steps <= 0, B < 0, a negative stride,
+ * draw0 + n_steps beyond 2^63, step_sums without a workspace.  l2hmc_gauge_hmc_run_ladder_ws_bytes is
+ * l2hmc_gauge_hmc_run_ws_bytes for a served plan, and 0 with l2hmc_last_error set for a plan or arguments that the
+ * entry refuses.
+ * The VALUES of both arrays are on the device and are not checked (as in l2hmc_small_run_tempered and
+ * l2hmc_small_hmc_run): a beta that is negative or not finite is no beta, and a step size that is 0, negative or not
+ * finite is no step size.  Callers check: GaugeSampler.run_hmc does. */
+size_t l2hmc_gauge_hmc_run_ladder_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps);
+int l2hmc_gauge_hmc_run_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t step_stride,
+                               int64_t chain_stride, const float* eps_chain, const float* x_in, float* x_next,
+                               int64_t B, uint64_t seed, uint64_t draw0, int32_t n_steps, float* px, float* actions,
+                               float* plaqs, float* charges, float* charge_diff, float* step_sums, float* samples,
+                               void* ws, size_t ws_bytes, l2hmc_stream_t stream);
+
 /* Forward value of the training loss, per chain (gauge_model.py:766-795): terms[b] = std_loss + charge_loss;
  * the scalar loss is their mean over ALL chains of all ranks.  x, x_prop, z: [B][2*T*X]; px, pz: [B].
  * metric: 0 'l1', 1 'l2', 2 'cos', 3 'cos2', 4 'cos_diff' (:632-657).  Both auxiliary terms compare z with

@@ -1,7 +1,8 @@
 // Plain HMC on the 2D U(1) lattice in ONE launch, at a lattice size chosen at run time: the whole MCMC step
 // (l2hmc_gauge_mcmc_step, l2hmc_gauge_transition_draw) or a whole trajectory / single leapfrog step
 // (l2hmc_gauge_trajectory, l2hmc_gauge_leapfrog) of plans with hmc = 1 (gauge_dynamics.py:102-108: S = T = Q = 0), and
-// a whole RUN of MCMC steps in one launch (l2hmc_gauge_hmc_run: hmc_run_kernel loops over the one copy of the step).
+// a whole RUN of MCMC steps in one launch (l2hmc_gauge_hmc_run: hmc_run_kernel loops over the one copy of the step;
+// l2hmc_gauge_hmc_run_ladder: the same run with beta and the step size per chain).
 //
 // Without networks a leapfrog step is a few flops and ONE sin per plaquette, so the kernel is transcendental- and
 // latency-bound and its mapping is chosen for waves in flight, not for the matrix pipe:
@@ -24,6 +25,8 @@
 // sums and the wrap are fused_step.h's own code.  The per-row sums (action, kinetic energy, sum cos P, sum project P)
 // are grouped differently from fused_step.h's 16-lane form: a thread adds its SPT terms in ascending order, a
 // butterfly adds the threads of a wave, waves are added in ascending order.
+#include <type_traits>
+
 #include "fused_step.h"
 
 namespace l2hmc {
@@ -35,6 +38,9 @@ struct HmcGeom {
   int spt, tsh, threads, rows_wg;         // sites per thread, log2(threads per row), workgroup size, rows per workgroup
   size_t lds;
 };
+
+// floats per row that the ladder run of `spt` sites per thread keeps in LDS on top of HmcGeom::lds (HmcRowLds)
+constexpr int hmc_ladder_lds_floats(int spt) { return spt == 4 ? 2 : 0; }
 
 static bool hmc_geom(int T, int X, HmcGeom* g) {
   if (T <= 0 || X <= 0 || (int64_t)T * X > kHmcMaxSites) return false;
@@ -87,7 +93,7 @@ struct HmcLanes {
   float* xs;                                // [R][2][sites]: the x0 links of a row, then its x1 links
   float* vs;                                // [R][2][sites] (step epilogue only)
   float* sp;                                // [R][sites]  sin P
-  float* stp;                               // [8 R]       StepWg scratch
+  float* stp;                               // [8 R]       StepWg scratch (+ [R][2] beta, eps in the SPT 4 ladder run)
   float* red;                               // [R][4][2]   per-wave partial sums of a row
   float* fin;                               // [2][256]
   float* xrow;                              // the thread's row of xs
@@ -96,8 +102,10 @@ struct HmcLanes {
   int nr[SPT], nu[SPT], nl[SPT], nd[SPT];
 };
 
+// stp_extra: floats per row that the launch adds to the step scratch (hmc_ladder_lds_floats; 0 for every other launch)
 template <int SPT>
-__device__ __forceinline__ HmcLanes<SPT> hmc_lanes(const FusedArgs& p, int tsh, float* lds, int tid) {
+__device__ __forceinline__ HmcLanes<SPT> hmc_lanes(const FusedArgs& p, int tsh, float* lds, int tid,
+                                                   const int stp_extra = 0) {
   HmcLanes<SPT> g;
   g.T = p.T;
   g.X = p.X;
@@ -112,7 +120,7 @@ __device__ __forceinline__ HmcLanes<SPT> hmc_lanes(const FusedArgs& p, int tsh, 
   g.vs = g.xs + g.R * g.D;
   g.sp = g.vs + g.R * g.D;
   g.stp = g.sp + g.R * g.sites;
-  g.red = g.stp + 8 * g.R;
+  g.red = g.stp + (8 + stp_extra) * g.R;
   g.fin = g.red + 8 * g.R;
   g.xrow = g.xs + g.r * g.D;
   g.sprow = g.sp + g.r * g.sites;
@@ -151,17 +159,32 @@ __device__ __forceinline__ StepWg hmc_workgroup(const FusedArgs& p, const HmcLan
   return w;
 }
 
+// beta and the step size of a ROW, as the trajectory takes them.  HmcRowValues: two values (the step and trajectory
+// kernels and the uniform run pass p.beta and p.eps, uniform over the launch; the ladder run of SPT 1 and 2 the pair of
+// the row's chain, in two registers).  HmcRowLds: the pair in the row's LDS scratch, read where it is used, so that it
+// is live in no register across the trajectory (the ladder run of SPT 4, which has no register to spare).
+struct HmcRowValues {
+  float b, e;
+  __device__ __forceinline__ float beta() const { return b; }
+  __device__ __forceinline__ float eps() const { return e; }
+};
+struct HmcRowLds {
+  const float* be;                          // [beta, eps] of the row
+  __device__ __forceinline__ float beta() const { return be[0]; }
+  __device__ __forceinline__ float eps() const { return be[1]; }
+};
+
 // The trajectory of the thread's row from (x, v) in registers, direction d (0 forward, 1 backward), steps
-// [p.step_begin, p.step_end) at p.beta; returns the row's accept probability (0 unless want_p).  Every thread of the
-// workgroup calls it.  On return the row's x is also in its xs row (published ahead of the last sin P pass).
-template <int SPT>
-__device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLanes<SPT>& g, const int d,
+// [p.step_begin, p.step_end) at the ROW's beta with the row's step size (be; p.beta and p.eps are not read); returns
+// the row's accept probability (0 unless want_p).  Every thread of the workgroup calls it.  On return the row's x is
+// also in its xs row (published ahead of the last sin P pass).
+template <int SPT, class BE>
+__device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLanes<SPT>& g, const BE be, const int d,
                                                 const bool want_p, float (&x0)[SPT], float (&x1)[SPT],
                                                 float (&v0)[SPT], float (&v1)[SPT]) {
   const int sites = g.sites, D = g.D, tpc = g.tpc, fl = g.fl;
   float* xrow = g.xrow;
   float* sprow = g.sprow;
-  const float beta = p.beta, eps = p.eps;
   float sP[SPT];
 
   auto publish_x = [&]() {
@@ -194,6 +217,7 @@ __device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLan
   };
   // momentum half-kick (lf_update_v_kernel with S = T = Q = 0): force = beta dS/dx from sin P
   auto kick = [&]() {
+    const float beta = be.beta(), eps = be.eps();
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
       if (g.ok[j]) {
@@ -232,6 +256,7 @@ __device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLan
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
       const bool inv = (sub == 1) != (d != 0);
+      const float eps = be.eps();
 #pragma unroll
       for (int j = 0; j < SPT; ++j) {
         const float ka = inv ? 1.f - m0[j] : m0[j], kb = inv ? 1.f - m1[j] : m1[j];
@@ -249,7 +274,7 @@ __device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLan
   if (want_p) {
     float kin1 = kinetic();
     hmc_row_sum2(act1, kin1, g.tsh, g.r, fl, g.red);
-    pr = accept_prob(beta, act0, act1, 0.5f * kin0, 0.5f * kin1, 0.f);
+    pr = accept_prob(be.beta(), act0, act1, 0.5f * kin0, 0.5f * kin1, 0.f);
   }
   return pr;
 }
@@ -280,15 +305,17 @@ __device__ __forceinline__ void hmc_load_x(const FusedArgs& p, const HmcLanes<SP
 }
 
 // ONE MCMC step, the only copy (hmc_step_kernel runs it once, hmc_run_kernel once per step of its loop): the coin /
-// MH uniform / momentum draws of draw index p.step_draw, the trajectory at p.beta with its fp64 accept probability,
-// the mix of the directions with Metropolis-Hastings, the observables of the step's input, |dQ|, the wrap and the
-// step's sums.  In: x0 / x1 = the step's input x of the row's chain (every row, whatever its direction).  Out, in the
+// MH uniform / momentum draws of draw index p.step_draw, the trajectory at be's beta and eps with its fp64 accept
+// probability, the mix of the directions with Metropolis-Hastings, the observables of the step's input, |dQ|, the
+// wrap and the step's sums.
+// In: x0 / x1 = the step's input x of the row's chain (every row, whatever its direction).  Out, in the
 // threads of the chains' primary rows (r < w.cpw): x0 / x1 = the wrapped output, the very fp32 values that go to
 // p.step_x_next; the other rows' x0 / x1 are left over from their trajectory.  Every per-step pointer of p (step_px
 // ... step_dq, step_x_next, step_xprop / _vprop / _xout, step_sums, step_part) is that of THIS step.  p.x0 is not read.
-template <int SPT>
-__device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>& g, const StepWg& w, const int k,
-                                         const int64_t grow, const bool live, float (&x0)[SPT], float (&x1)[SPT]) {
+template <int SPT, class BE>
+__device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>& g, const StepWg& w, const BE be,
+                                         const int k, const int64_t grow, const bool live, float (&x0)[SPT],
+                                         float (&x1)[SPT]) {
   const int sites = g.sites, D = g.D, tpc = g.tpc, r = g.r, fl = g.fl, tid = w.tid, tsh = g.tsh;
   float* xs = g.xs;
   float* vs = g.vs;
@@ -326,7 +353,7 @@ __device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>
     xi1[j] = x1[j];
   }
 
-  const float pr = hmc_trajectory<SPT>(p, g, d, true, x0, x1, v0, v1);
+  const float pr = hmc_trajectory<SPT>(p, g, be, d, true, x0, x1, v0, v1);
 
   // ---- mix the directions, Metropolis-Hastings (gauge_dynamics.py:221-257, mask * a + (1 - mask) * b) ----
   // xs rows hold the final x already (published ahead of the last sin P pass); v rows and p join them
@@ -476,7 +503,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
     bool live;
     hmc_step_row<SPT>(p, g, w, k, grow, live);
     hmc_load_x<SPT>(p, g, grow, live, x0, x1);
-    hmc_step<SPT>(p, g, w, k, grow, live, x0, x1);
+    hmc_step<SPT>(p, g, w, HmcRowValues{p.beta, p.eps}, k, grow, live, x0, x1);
     return;
   }
   // ---- trajectory mode: x, v, sumlogdet (exactly 0), p of the live rows ----
@@ -494,7 +521,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
       v1[j] = vr[1];
     }
   }
-  const float pr = hmc_trajectory<SPT>(p, g, d, p.p_accept != nullptr, x0, x1, v0, v1);
+  const float pr = hmc_trajectory<SPT>(p, g, HmcRowValues{p.beta, p.eps}, d, p.p_accept != nullptr, x0, x1, v0, v1);
   if (live) {
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
@@ -530,15 +557,31 @@ struct HmcRunArgs {
   int64_t sample_stride;
 };
 
+// What the LADDER form of the run adds (l2hmc_gauge_hmc_run_ladder): beta and the step size get a chain axis.  Step s
+// of chain c runs at betas[s * step_stride + c * chain_stride] and chain c integrates with eps_chain[c] (NULL: the
+// plan's eps for every chain).  Only the ladder instances take this struct, so the uniform instances keep their
+// kernel arguments.
+struct HmcLadderArgs : HmcRunArgs {
+  int64_t step_stride, chain_stride;     // elements of betas between two steps / two chains; either may be 0
+  const float* eps_chain;                // [B], or NULL
+};
+
 // n_steps MCMC steps in ONE launch: chains never meet, so a workgroup walks its own chains through the whole run with
 // their state in registers.  Step s + 1 starts from the wrapped output of step s -- the fp32 values the step kernel
 // stores and its next launch reloads -- and forms everything else anew, so the run gives the bits of n_steps launches
 // of hmc_step_kernel.  Workgroups drift apart freely: the only thing that crosses them is a step's sums, and every
 // step has a ticket (step_sums[s][3]) and a slice of step_part of its own, so nobody waits for anybody.
-template <int SPT>
-__global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(const FusedArgs p, const HmcRunArgs ra, const int tsh) {
+// LADDER: beta and eps belong to the CHAIN (HmcLadderArgs).  Both rows of a chain of the paired layout read the same
+// pair, so both half-kicks, both position sub-updates and both ends of the Hamiltonian difference of a chain see one
+// beta and one eps; a row whose chain is beyond step_Bl reads neither array.  The step is the same copy run on per-row
+// values instead of uniform ones: the same fp32 operations in the same order, so a column of a ladder has the bits of
+// the uniform run at its (beta, eps).
+template <int SPT, bool LADDER>
+__global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(
+    const FusedArgs p, const typename std::conditional<LADDER, HmcLadderArgs, HmcRunArgs>::type ra, const int tsh) {
   extern __shared__ float lds[];
-  const HmcLanes<SPT> g = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x);
+  constexpr int kExtra = LADDER ? hmc_ladder_lds_floats(SPT) : 0;
+  const HmcLanes<SPT> g = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x, kExtra);
   const StepWg w = hmc_workgroup<SPT>(p, g);
   int k;
   int64_t grow;
@@ -551,7 +594,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(const FusedArgs
   q.step_xprop = q.step_vprop = q.step_xout = nullptr;       // a run has no use for apply_transition's own outputs
   q.step_sums_acc = 0;
   for (int s = 0; s < ra.n_steps; ++s) {
-    q.beta = ra.betas[s];
+    if constexpr (!LADDER) q.beta = ra.betas[s];
     q.step_draw = p.step_draw + (unsigned long long)s;
     q.step_x_next = ra.samples ? ra.samples + s * ra.sample_stride : nullptr;
     q.step_px = p.step_px ? p.step_px + s * ra.hist_stride : nullptr;
@@ -566,13 +609,14 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(const FusedArgs
     // VGPRs, half its workgroups per CU.  z is 0 (a draw index does not reach 2^63), which the compiler cannot know,
     // so the addresses are formed where they are used, as in the step kernel; the neighbour tables stay hoisted.
     // The host refuses a run whose draw indices reach 2^63 (HmcRunArgs).  The register counts depend on the compiler:
-    // 78 / 96 / 127 VGPRs (SPT 1 / 2 / 4), no scratch, with hipcc of ROCm 7.2.0 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0) at -O3.
+    // 78 / 96 / 127 VGPRs (SPT 1 / 2 / 4), no scratch, with hipcc of ROCm 7.2.0 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0) at -O3;
+    // the ladder instances 80 / 98 / 126 (profiles/hmc_run_ladder.txt).
     const int z = (int)(q.step_draw >> 63);
     HmcLanes<SPT> gs = g;
     if (SPT == 4) {
       // four sites per thread: the 20 registers of the neighbour tables would cost the second workgroup of a CU
       // (136 VGPRs with them hoisted, 127 without), so this instance forms them per step as well
-      gs = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x + z);
+      gs = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x + z, kExtra);
     } else {
       gs.fl = g.fl + z;
       gs.r = g.r + z;
@@ -581,7 +625,30 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(const FusedArgs
     }
     StepWg ws = w;
     ws.tid = w.tid + z;
-    hmc_step<SPT>(q, gs, ws, k + z, grow + z, live, x0, x1);
+    if constexpr (LADDER) {
+      // the pair of the row's chain, read where the step starts (two cached loads per row and step) so that neither is
+      // live across the step's epilogue; the chain's index is formed here like every other address of the step.  A dead
+      // row (x = v = 0) reads neither array.
+      const int64_t c = grow + z;
+      const float beta = live ? ra.betas[s * ra.step_stride + c * ra.chain_stride] : 0.f;
+      const float eps = live && ra.eps_chain ? ra.eps_chain[c] : p.eps;
+      if constexpr (kExtra != 0) {
+        // 127 VGPRs without the pair, 128 is what two workgroups per CU allow (130 with the pair in registers): the
+        // pair waits in the row's LDS scratch, 126 VGPRs.
+        // The step's first barrier (after the coins) comes ahead of the trajectory's first read, and the barriers of
+        // the step's epilogue come between the trajectory's last read and the next step's write.
+        float* rb = gs.stp + 8 * gs.R + 2 * gs.r;
+        if (gs.fl == 0) {
+          rb[0] = beta;
+          rb[1] = eps;
+        }
+        hmc_step<SPT>(q, gs, ws, HmcRowLds{rb}, k + z, c, live, x0, x1);
+      } else {
+        hmc_step<SPT>(q, gs, ws, HmcRowValues{beta, eps}, k + z, c, live, x0, x1);
+      }
+    } else {
+      hmc_step<SPT>(q, gs, ws, HmcRowValues{q.beta, q.eps}, k + z, grow + z, live, x0, x1);
+    }
     if (w.paired) {
       // the chain's new state is in its forward row's registers: hand it to the backward row through that row's
       // own (free) x row.  The next write there is the backward row's own publish of the same values.
@@ -619,17 +686,25 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(const FusedArgs
 }
 
 static int launch_hmc(const FusedArgs& a, const HmcGeom& g, int64_t nwg, hipStream_t stream,
-                      const HmcRunArgs* run = nullptr) {
+                      const HmcRunArgs* run = nullptr, const HmcLadderArgs* ladder = nullptr) {
   L2HMC_REQUIRE(nwg > 0 && nwg < (1ll << 31), "hmc step: too many rows");
   prof_before(kProfFused, stream);
   const dim3 grid((unsigned)nwg), block((unsigned)g.threads);
-  if (run) {
+  if (ladder) {
+    const size_t lds = g.lds + sizeof(float) * (size_t)(g.rows_wg * hmc_ladder_lds_floats(g.spt));
     if (g.spt == 1)
-      hipLaunchKernelGGL((hmc_run_kernel<1>), grid, block, g.lds, stream, a, *run, g.tsh);
+      hipLaunchKernelGGL((hmc_run_kernel<1, true>), grid, block, lds, stream, a, *ladder, g.tsh);
     else if (g.spt == 2)
-      hipLaunchKernelGGL((hmc_run_kernel<2>), grid, block, g.lds, stream, a, *run, g.tsh);
+      hipLaunchKernelGGL((hmc_run_kernel<2, true>), grid, block, lds, stream, a, *ladder, g.tsh);
     else
-      hipLaunchKernelGGL((hmc_run_kernel<4>), grid, block, g.lds, stream, a, *run, g.tsh);
+      hipLaunchKernelGGL((hmc_run_kernel<4, true>), grid, block, lds, stream, a, *ladder, g.tsh);
+  } else if (run) {
+    if (g.spt == 1)
+      hipLaunchKernelGGL((hmc_run_kernel<1, false>), grid, block, g.lds, stream, a, *run, g.tsh);
+    else if (g.spt == 2)
+      hipLaunchKernelGGL((hmc_run_kernel<2, false>), grid, block, g.lds, stream, a, *run, g.tsh);
+    else
+      hipLaunchKernelGGL((hmc_run_kernel<4, false>), grid, block, g.lds, stream, a, *run, g.tsh);
   } else if (g.spt == 1)
     hipLaunchKernelGGL((hmc_step_kernel<1>), grid, block, g.lds, stream, a, g.tsh);
   else if (g.spt == 2)
@@ -677,30 +752,59 @@ int launch_hmc_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, fl
 
 size_t hmc_run_part_bytes(int64_t B) { return align_up(sizeof(float) * 2 * (size_t)B, 256); }
 
+// the FusedArgs and HmcRunArgs of a run, uniform or ladder (the ladder form's own three fields are its launcher's)
+static int hmc_run_args(const l2hmc_gauge_plan* p, const float* betas, const float* x_in, float* x_next, int64_t B,
+                        uint64_t seed, uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
+                        float* charges, float* dq, float* step_sums, float* samples, float* part, HmcGeom* g,
+                        int64_t* nwg, FusedArgs* a, HmcRunArgs* r) {
+  L2HMC_REQUIRE(hmc_plan_supported(p) && hmc_geom(p->T, p->X, g), "hmc run: plan has no one-launch kernel");
+  L2HMC_REQUIRE(betas && x_in && x_next && B > 0 && n_steps > 0 && (!step_sums || part), "hmc run: bad arguments");
+  L2HMC_REQUIRE(draw0 <= (1ull << 63) - (uint64_t)n_steps, "hmc run: draw0 + n_steps exceeds 2^63");   // HmcRunArgs
+  const int cpw = both ? g->rows_wg / 2 : g->rows_wg;
+  *nwg = ceil_div(B, cpw);
+  const int64_t D = 2 * (int64_t)p->T * p->X;
+  a->T = p->T; a->X = p->X; a->num_steps = p->num_steps; a->step_begin = 0; a->step_end = p->num_steps;
+  a->eps = p->eps; a->masks = p->masks;
+  a->x0 = x_in; a->rows = *nwg * g->rows_wg;
+  a->step_x_next = x_next;
+  a->step_B = B; a->step_Bl = B; a->step_chain0 = 0;
+  a->step_seed = seed; a->step_draw = draw0; a->step_both = both;
+  a->step_px = px; a->step_act = actions; a->step_plq = plaqs; a->step_chg = charges; a->step_dq = dq;
+  a->step_sums = step_sums; a->step_part = part;     // part: hmc_run_part_bytes(B) per step (2 floats per workgroup)
+  r->n_steps = n_steps; r->betas = betas; r->hist_stride = B;
+  r->part_stride = (int64_t)(hmc_run_part_bytes(B) / sizeof(float));
+  r->samples = samples; r->sample_stride = B * D;
+  return L2HMC_OK;
+}
+
 int launch_hmc_run(const l2hmc_gauge_plan* p, const float* betas, const float* x_in, float* x_next, int64_t B,
                    uint64_t seed, uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
                    float* charges, float* dq, float* step_sums, float* samples, float* part, hipStream_t stream) {
   HmcGeom g;
-  L2HMC_REQUIRE(hmc_plan_supported(p) && hmc_geom(p->T, p->X, &g), "hmc run: plan has no one-launch kernel");
-  L2HMC_REQUIRE(betas && x_in && x_next && B > 0 && n_steps > 0 && (!step_sums || part), "hmc run: bad arguments");
-  L2HMC_REQUIRE(draw0 <= (1ull << 63) - (uint64_t)n_steps, "hmc run: draw0 + n_steps exceeds 2^63");   // HmcRunArgs
-  const int cpw = both ? g.rows_wg / 2 : g.rows_wg;
-  const int64_t nwg = ceil_div(B, cpw);
-  const int64_t D = 2 * (int64_t)p->T * p->X;
+  int64_t nwg;
   FusedArgs a{};
-  a.T = p->T; a.X = p->X; a.num_steps = p->num_steps; a.step_begin = 0; a.step_end = p->num_steps;
-  a.eps = p->eps; a.masks = p->masks;
-  a.x0 = x_in; a.rows = nwg * g.rows_wg;
-  a.step_x_next = x_next;
-  a.step_B = B; a.step_Bl = B; a.step_chain0 = 0;
-  a.step_seed = seed; a.step_draw = draw0; a.step_both = both;
-  a.step_px = px; a.step_act = actions; a.step_plq = plaqs; a.step_chg = charges; a.step_dq = dq;
-  a.step_sums = step_sums; a.step_part = part;       // part: hmc_run_part_bytes(B) per step (2 floats per workgroup)
   HmcRunArgs r{};
-  r.n_steps = n_steps; r.betas = betas; r.hist_stride = B;
-  r.part_stride = (int64_t)(hmc_run_part_bytes(B) / sizeof(float));
-  r.samples = samples; r.sample_stride = B * D;
+  if (int e = hmc_run_args(p, betas, x_in, x_next, B, seed, draw0, n_steps, both, px, actions, plaqs, charges, dq,
+                           step_sums, samples, part, &g, &nwg, &a, &r))
+    return e;
   return launch_hmc(a, g, nwg, stream, &r);
+}
+
+int launch_hmc_run_ladder(const l2hmc_gauge_plan* p, const float* betas, int64_t step_stride, int64_t chain_stride,
+                          const float* eps_chain, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                          uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
+                          float* charges, float* dq, float* step_sums, float* samples, float* part,
+                          hipStream_t stream) {
+  HmcGeom g;
+  int64_t nwg;
+  FusedArgs a{};
+  HmcLadderArgs r{};
+  L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0, "hmc run: negative stride");
+  if (int e = hmc_run_args(p, betas, x_in, x_next, B, seed, draw0, n_steps, both, px, actions, plaqs, charges, dq,
+                           step_sums, samples, part, &g, &nwg, &a, &r))
+    return e;
+  r.step_stride = step_stride; r.chain_stride = chain_stride; r.eps_chain = eps_chain;
+  return launch_hmc(a, g, nwg, stream, nullptr, &r);
 }
 
 }  // namespace l2hmc

@@ -269,3 +269,49 @@ extern "C" int l2hmc_gauge_hmc_run(const l2hmc_gauge_plan* plan, const float* be
   }
   return L2HMC_OK;
 }
+
+// ---- the same run with beta per step and chain and a step size per chain (hmc_run_kernel<SPT, true>).  Only plans
+// with the one-launch kernel: a ladder is there to fill ONE launch, so there is no host loop to fall back on.
+// Returns L2HMC_OK or sets the error; `who` words it for the entry and for its workspace query.
+static int hmc_run_ladder_check(const char* who, const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps) {
+  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  L2HMC_REQUIRE(plan->hmc, "%s: plan.hmc = 0 (a run is steps of plain HMC)", who);
+  L2HMC_REQUIRE(hmc_run_one_launch(plan),
+                "%s: the plan has no one-launch kernel (more than 1024 sites, or L2HMC_PLAN_LAYERED): "
+                "l2hmc_gauge_hmc_run runs it step by step, one beta at a time", who);
+  L2HMC_REQUIRE(n_steps > 0, "%s: n_steps = %d, expected at least 1", who, (int)n_steps);
+  L2HMC_REQUIRE(B >= 0, "%s: B < 0", who);
+  return L2HMC_OK;
+}
+
+extern "C" size_t l2hmc_gauge_hmc_run_ladder_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps) {
+  if (hmc_run_ladder_check("gauge_hmc_run_ladder_ws_bytes", plan, B, n_steps)) return 0;
+  return (size_t)n_steps * hmc_run_part_bytes(B > 0 ? B : 1);
+}
+
+extern "C" int l2hmc_gauge_hmc_run_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t step_stride,
+                                          int64_t chain_stride, const float* eps_chain, const float* x_in,
+                                          float* x_next, int64_t B, uint64_t seed, uint64_t draw0, int32_t n_steps,
+                                          float* px, float* actions, float* plaqs, float* charges, float* charge_diff,
+                                          float* step_sums, float* samples, void* ws, size_t ws_bytes,
+                                          l2hmc_stream_t stream) {
+  if (int e = hmc_run_ladder_check("gauge_hmc_run_ladder", plan, B, n_steps)) return e;
+  L2HMC_REQUIRE(betas != nullptr, "gauge_hmc_run_ladder: NULL betas");
+  L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0,
+                "gauge_hmc_run_ladder: negative stride (step_stride=%lld, chain_stride=%lld)", (long long)step_stride,
+                (long long)chain_stride);
+  // the run kernel relies on bit 63 of every draw index being 0 (hmc_step.hip: HmcRunArgs)
+  L2HMC_REQUIRE(draw0 <= (1ull << 63) - (uint64_t)n_steps, "gauge_hmc_run_ladder: draw0 + n_steps exceeds 2^63");
+  L2HMC_REQUIRE(x_in && x_next, "gauge_hmc_run_ladder: NULL x_in / x_next");
+  L2HMC_REQUIRE(!step_sums || ws, "gauge_hmc_run_ladder: step_sums needs the workspace");
+  if (B == 0) return L2HMC_OK;
+  const size_t need = l2hmc_gauge_hmc_run_ladder_ws_bytes(plan, B, n_steps);
+  if (step_sums && ws_bytes < need) {
+    set_error("gauge_hmc_run_ladder: workspace %zu < %zu bytes", ws_bytes, need);
+    return L2HMC_ERR_WORKSPACE;
+  }
+  const bool selected = (plan->flags & L2HMC_PLAN_SELECTED_ONLY) != 0;
+  return launch_hmc_run_ladder(plan, betas, step_stride, chain_stride, eps_chain, x_in, x_next, B, seed, draw0, n_steps,
+                               selected ? 0 : 1, px, actions, plaqs, charges, charge_diff, step_sums, samples,
+                               step_sums ? static_cast<float*>(ws) : nullptr, (hipStream_t)stream);
+}

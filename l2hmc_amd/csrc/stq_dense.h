@@ -172,6 +172,13 @@ size_t hmc_run_part_bytes(int64_t B);
 int launch_hmc_run(const l2hmc_gauge_plan* p, const float* betas, const float* x_in, float* x_next, int64_t B,
                    uint64_t seed, uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
                    float* charges, float* dq, float* step_sums, float* samples, float* part, hipStream_t stream);
+// the same run with beta per step and chain, betas[s * step_stride + c * chain_stride], and a step size per chain,
+// eps_chain[c] (NULL: the plan's) -- l2hmc_gauge_hmc_run_ladder
+int launch_hmc_run_ladder(const l2hmc_gauge_plan* p, const float* betas, int64_t step_stride, int64_t chain_stride,
+                          const float* eps_chain, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                          uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
+                          float* charges, float* dq, float* step_sums, float* samples, float* part,
+                          hipStream_t stream);
 // bytes of launch_fused_step's `hand` workspace for B chains (the hand-off of the split 16-row form)
 size_t fused_step_hand_bytes(int64_t B, int D);
 // whole-trajectory reverse pass (fused_train.hip); deltas_*: {dout, d2, d1} tapes, coef_parts: {dcs_x, dcq_x, dcs_v, dcq_v}

@@ -160,9 +160,10 @@ class DynamicsSampler:
             out["samples"] = samples
         return out
 
-    def _step_sizes(self, eps, B):
-        """`run_hmc`'s `eps` as a float32 array of shape [] or [B]; ValueError for any other shape and for an entry that
-        is not finite and > 0 in float32."""
+    @staticmethod
+    def _step_sizes(eps, B):
+        """`run_hmc`'s `eps` (this sampler's and GaugeSampler's) as a float32 array of shape [] or [B]; ValueError for
+        any other shape and for an entry that is not finite and > 0 in float32."""
         if isinstance(eps, torch.Tensor):
             eps = eps.detach().cpu().numpy()
         with np.errstate(over="ignore"):

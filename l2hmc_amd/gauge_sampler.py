@@ -10,6 +10,7 @@ import torch
 
 from . import _lib, ops
 from .dist import StepStats
+from .dynamics_sampler import DynamicsSampler
 from .lattice import u1_observables, u1_plaq_exact
 
 
@@ -141,21 +142,36 @@ class GaugeSampler:
 
     def _run_launches(self, run_steps, betas, x, keep_samples):
         """`run` for plain HMC through l2hmc_gauge_hmc_run: chunks of at most `steps_per_launch` MCMC steps, ONE launch
-        each, the chains' state in registers from step to step.  The same draws (consecutive draw indices from the
-        dynamics' counter), histories, sums and samples as the loop over `step`, bit for bit.  The chunks bound the
-        workspace and, with `keep_samples`, the device buffer of the samples (copied to the host chunk by chunk)."""
+        each (`_run_chunks`).  The same draws, histories, sums and samples as the loop over `step`, bit for bit."""
+        import ctypes as C
+        plan = self.dynamics._plan()
+        beta_dev = torch.tensor(betas, dtype=torch.float32, device=x.device)
+
+        def launch(s0, *tail):
+            _lib.call("l2hmc_gauge_hmc_run", C.byref(plan), beta_dev[s0:], *tail, device=self.dynamics._device)
+
+        out = self._run_chunks(run_steps, x, keep_samples, plan, _lib.lib().l2hmc_gauge_hmc_run_ws_bytes, launch)
+        out["plaq_exact"] = u1_plaq_exact(betas[-1])
+        return out
+
+    def _run_chunks(self, run_steps, x, keep_samples, plan, ws_bytes, launch):
+        """A run of plain-HMC steps in chunks of at most `steps_per_launch`, ONE launch each, the chains' state in
+        registers from step to step.  `launch(s0, x_in, x_next, B, seed, draw, n, px, actions, plaqs, charges,
+        charge_diff, step_sums, samples, ws, ws_nbytes)` runs steps [s0, s0 + n) through the caller's entry (the common
+        tail of l2hmc_gauge_hmc_run and l2hmc_gauge_hmc_run_ladder; the caller puts its plan and betas in front) and
+        `ws_bytes` is that entry's workspace query.  Consecutive draw indices from the dynamics' counter, as the loop
+        over `step` takes them.  The chunks bound the workspace and, with `keep_samples`, the device buffer of the
+        samples (copied to the host chunk by chunk).  Returns `run`'s dictionary without `plaq_exact`."""
         import ctypes as C
         dyn = self.dynamics
         B, D, dev = x.shape[0], x.shape[1], x.device
-        plan, L = dyn._plan(), _lib.lib()
         chunk = min(int(self.steps_per_launch), run_steps)
         names = ("px", "actions", "plaqs", "charges", "charge_diff")
         hist = {k: torch.empty(run_steps, B, dtype=torch.float32, device=dev) for k in names}
-        beta_dev = torch.tensor(betas, dtype=torch.float32, device=dev)
         if self._run_sums is None or self._run_sums.shape[0] < run_steps or self._run_sums.device != dev:
             self._run_sums = torch.zeros(run_steps, 4, dtype=torch.float32, device=dev)
         sums = self._run_sums
-        ws, nb = dyn._ws.get(L.l2hmc_gauge_hmc_run_ws_bytes(C.byref(plan), B, chunk), dev)
+        ws, nb = dyn._ws.get(ws_bytes(C.byref(plan), B, chunk), dev)
         samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
         samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
         # the steps' random streams come from the dynamics' own draw counter, as in `step`
@@ -164,8 +180,8 @@ class GaugeSampler:
         x_in = x
         for s0 in range(0, run_steps, chunk):
             n = min(chunk, run_steps - s0)
-            _lib.call("l2hmc_gauge_hmc_run", C.byref(plan), beta_dev[s0:], x_in, x_next, B, dyn._seed, draw0 + s0, n,
-                      *(hist[k][s0:] for k in names), sums[s0:], samples_dev, ws, nb, device=dyn._device)
+            launch(s0, x_in, x_next, B, dyn._seed, draw0 + s0, n, *(hist[k][s0:] for k in names), sums[s0:],
+                   samples_dev, ws, nb)
             _, dyn._draws = _lib.run_draw_index(2 * draw0, s0 + n)      # the counter moves with the completed steps
             x_in = x_next                                  # later chunks advance the state in place
             for i in range(s0, s0 + n):
@@ -173,11 +189,92 @@ class GaugeSampler:
             if keep_samples:
                 samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
         out = {k: v.cpu().numpy() for k, v in hist.items()}
-        out["plaq_exact"] = u1_plaq_exact(betas[-1])
         out["samples_out"] = x_next
         out["mean_accept"] = self.stats.mean_accept()
         if keep_samples:
             out["samples"] = samples
+        return out
+
+    @staticmethod
+    def _ladder_betas(beta, run_steps, B):
+        """`run_hmc`'s `beta` -> (float64 array as given, flat float32 array for the device, step_stride, chain_stride):
+        a scalar (0, 0), [run_steps] a schedule (1, 0), [1, B] a ladder (0, 1), [run_steps, B] both (B, 1) -- the
+        element strides of l2hmc_gauge_hmc_run_ladder.  ValueError for any other shape and for an entry that is negative
+        or not finite in float32."""
+        if isinstance(beta, torch.Tensor):
+            beta = beta.detach().cpu().numpy()
+        b = np.asarray(beta, dtype=np.float64)
+        with np.errstate(over="ignore"):
+            b32 = b.astype(np.float32)
+        if b.ndim == 0:
+            strides = (0, 0)
+        elif b.shape == (run_steps,):
+            strides = (1, 0)
+        elif b.shape == (1, B):
+            strides = (0, 1)
+        elif b.shape == (run_steps, B):
+            strides = (B, 1)
+        else:
+            raise ValueError(f"run_hmc: beta of shape {b.shape}: expected a scalar, [{run_steps}] (one per step), "
+                             f"[1, {B}] (one per chain) or [{run_steps}, {B}]")
+        if not (np.isfinite(b32) & (b32 >= 0)).all():
+            raise ValueError("run_hmc: every beta must be finite and not negative (in float32)")
+        return b, np.ascontiguousarray(b32).reshape(-1), strides[0], strides[1]
+
+    def run_hmc(self, run_steps, beta, x=None, eps=None, keep_samples=False):
+        """`run` for a plain-HMC dynamics (`hmc=True`) with a chain axis on beta and on the step size: a scan over
+        either, or a grid of both, in ONE launch per chunk of `steps_per_launch` steps (l2hmc_gauge_hmc_run_ladder).
+        `beta`: a scalar, [run_steps] (one per step), [1, B] (one per chain) or [run_steps, B].  `eps`: None (the
+        dynamics' own), a scalar, or [B].  Chains never interact, so column c of every history is the run of the whole
+        batch at that column's beta and eps -- `run` on a dynamics with that eps -- bit for bit.  Returns the dictionary
+        of `run`; `plaq_exact` is a float where beta has no chain axis and a [B] array (at the last step's beta)
+        where it has one.  Draws from the dynamics' counter as `run` does; the caller's `x`, `dynamics.eps` and the
+        dynamics' plan are left as they were.  ValueError for an L2HMC dynamics, a wrong shape, a beta that is negative
+        or not finite and an eps that is not finite and > 0; NotImplementedError for an hmc dynamics whose plan has no
+        one-launch kernel (more than 1024 sites, `fused = False`): `run` takes those, one beta at a time."""
+        import ctypes as C
+        dyn = self.dynamics
+        if not dyn.hmc:
+            raise ValueError("run_hmc: the dynamics is an L2HMC sampler (hmc=False): `run` runs it")
+        run_steps = int(run_steps)
+        if run_steps < 0:
+            raise ValueError(f"run_steps={run_steps} must not be negative")
+        if x is None:
+            x = np.random.randn(dyn.batch_size, dyn.x_dim)
+        x = _lib.as_dev(x, dyn._device)
+        if x.ndim != 2 or x.shape[1] != dyn.x_dim:
+            raise ValueError(f"run_hmc: x of shape {tuple(x.shape)}: expected [B, {dyn.x_dim}]")
+        B, D = x.shape
+        b64, b32, step_stride, chain_stride = self._ladder_betas(beta, run_steps, B)
+        step = None if eps is None else DynamicsSampler._step_sizes(eps, B)     # one rule for both samplers
+        if run_steps == 0:
+            out = {k: np.empty((0, B), dtype=np.float32) for k in ("px", "actions", "plaqs", "charges", "charge_diff")}
+            out["samples_out"] = x.clone()
+            out["mean_accept"] = self.stats.mean_accept()
+            if keep_samples:
+                out["samples"] = np.empty((0, B, D), dtype=np.float32)
+        else:
+            plan = dyn._plan()                             # a fresh struct: a scalar eps goes into it alone
+            if _lib.lib().l2hmc_gauge_plan_fused(C.byref(plan)) != 1:
+                raise NotImplementedError(
+                    "run_hmc: this hmc dynamics has no one-launch kernel (more than 1024 sites, or fused = False): "
+                    "`run` takes it through the loop over `step`, one beta at a time")
+            eps_chain = None
+            if step is not None and step.ndim == 0:
+                plan.eps = float(step)
+            elif step is not None:
+                eps_chain = _lib.as_dev(step, x.device)
+            beta_dev = _lib.as_dev(b32, x.device)          # goes over once; every chunk starts at its own row
+
+            def launch(s0, *tail):
+                _lib.call("l2hmc_gauge_hmc_run_ladder", C.byref(plan), beta_dev[s0 * step_stride:], step_stride,
+                          chain_stride, eps_chain, *tail, device=dyn._device)
+
+            out = self._run_chunks(run_steps, x, keep_samples, plan, _lib.lib().l2hmc_gauge_hmc_run_ladder_ws_bytes,
+                                   launch)
+        # the last step's beta (an empty run with an empty schedule has none)
+        last = b64 if b64.ndim == 0 else b64[-1] if b64.shape[0] else np.full(b64.shape[1:], np.nan)
+        out["plaq_exact"] = u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
         return out
 
     @staticmethod

@@ -372,6 +372,27 @@ int l2hmc_gauge_hmc_run_ladder(const l2hmc_gauge_plan* plan, const float* betas,
                                float* plaqs, float* charges, float* charge_diff, float* step_sums, float* samples,
                                void* ws, size_t ws_bytes, l2hmc_stream_t stream);
 
+/* ONE replica-exchange (parallel tempering) round between neighbouring rungs of a beta ladder, in place on
+ * x [B][2*T*X] (no plan: T, X as l2hmc_u1_plaq_sums takes them).  Columns [g * group, (g + 1) * group) form one
+ * replica group and column c runs at betas[c * chain_stride] (DEVICE pointer; the stride may be 0).  A round of
+ * parity 0 or 1 proposes, in every group, the disjoint pairs (a, b) = (g * group + j, g * group + j + 1) for
+ * j = parity, parity + 2, ... with j + 1 < group.  Per pair: S_a, S_b = sum over plaquettes of 1 - cos P of the two
+ * rows (fp32, ONE summation order, so S depends on nothing but the row);
+ *   p = min(1, exp((double)(beta_a - beta_b) * ((double)S_a - (double)S_b)))   (the exponential in fp64, NaN -> 0)
+ * which is exp(-beta_b S_a - beta_a S_b) / exp(-beta_a S_a - beta_b S_b); u = element a of the stream
+ * l2hmc_fill_uniform(B, seed, stream_index) writes; the pair is exchanged iff p > u (strict): the two rows of x and
+ * the two entries of replica trade places.  Outputs, each [B], each may be NULL: replica (int32 labels, exchanged in
+ * place), action[c] = S_c for the members of a pair (other chains' entries are left untouched), swap_p[a] = p at the
+ * LOWER chain of each pair and NaN elsewhere, swapped[a] = 1 / 0 at the lower chain and 0 elsewhere.
+ * Any lattice size is served (up to 2^29 sites).  One launch; a round without a pair (group 2 at parity 1) fills
+ * swap_p and swapped and launches nothing; B == 0 is a no-op without a device call.  Refused with L2HMC_ERR_ARG before
+ * any device call: T or X <= 0, B < 0, group < 2, B not a multiple of group, parity not 0 or 1, a negative stride,
+ * NULL x or betas with B > 0. */
+int l2hmc_gauge_replica_swap(int32_t T, int32_t X, float* x, int64_t B, int32_t group, int32_t parity,
+                             const float* betas, int64_t chain_stride, uint64_t seed, uint64_t stream_index,
+                             int32_t* replica, float* action, float* swap_p, uint8_t* swapped,
+                             l2hmc_stream_t stream);
+
 /* Forward value of the training loss, per chain (gauge_model.py:766-795): terms[b] = std_loss + charge_loss;
  * the scalar loss is their mean over ALL chains of all ranks.  x, x_prop, z: [B][2*T*X]; px, pz: [B].
  * metric: 0 'l1', 1 'l2', 2 'cos', 3 'cos2', 4 'cos_diff' (:632-657).  Both auxiliary terms compare z with
@@ -730,6 +751,7 @@ int l2hmc_fill_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, l2
  *   1 = first dense layer   2 = hidden dense layer   3 = heads (+update)
  *   4 = u1_action_force     5 = fused whole-trajectory kernel
  *   6 = ConvNet3D front-end 7 = toy-target trajectory kernel (l2hmc_small_*)
+ *   8 = replica-exchange round (l2hmc_gauge_replica_swap)
  * ------------------------------------------------------------------------ */
 int l2hmc_profile_begin(int32_t kernel_class);
 int l2hmc_profile_end(double* total_ms, int64_t* launches);

@@ -120,6 +120,7 @@ _PROTOS = {
     "l2hmc_gauge_hmc_run_ladder_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64, _I32]),
     "l2hmc_gauge_hmc_run_ladder": (C.c_int, [C.POINTER(GaugePlan), _P, _I64, _I64, _P, _P, _P, _I64, _U64, _U64, _I32,
                                              _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "l2hmc_gauge_replica_swap": (C.c_int, [_I32, _I32, _P, _I64, _I32, _I32, _P, _I64, _U64, _U64, _P, _P, _P, _P, _P]),
     "l2hmc_gauge_loss_terms": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P]),
     "l2hmc_gauge_train_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64]),
     "l2hmc_gauge_train_forward": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _SZ,

@@ -11,7 +11,7 @@ import torch
 from . import _lib, ops
 from .dist import StepStats
 from .dynamics_sampler import DynamicsSampler
-from .lattice import u1_observables, u1_plaq_exact
+from .lattice import replica_swap, u1_observables, u1_plaq_exact
 
 
 class GaugeSampler:
@@ -29,6 +29,9 @@ class GaugeSampler:
         # (1 = one launch per step through `step`, the cross-check)
         self.steps_per_launch = 256
         self._run_sums = None        # [steps][4] like _sums_ring: zeroed once, the kernel leaves the tickets at 0
+        # int32 [B] on the device, or None: the label of the configuration that sits in every column.  Every
+        # replica-exchange round (`swap_replicas`) exchanges it with the rows; `run_hmc_exchange` starts it anew
+        self.replica = None
 
     def update_beta(self, step):
         """gauge_model.py:1039-1046: linear annealing of 1/beta."""
@@ -154,9 +157,11 @@ class GaugeSampler:
         out["plaq_exact"] = u1_plaq_exact(betas[-1])
         return out
 
-    def _run_chunks(self, run_steps, x, keep_samples, plan, ws_bytes, launch):
+    def _run_chunks(self, run_steps, x, keep_samples, plan, ws_bytes, launch, cut_every=None, after=None):
         """A run of plain-HMC steps in chunks of at most `steps_per_launch`, ONE launch each, the chains' state in
-        registers from step to step.  `launch(s0, x_in, x_next, B, seed, draw, n, px, actions, plaqs, charges,
+        registers from step to step.  With `cut_every` = k no chunk spans a multiple of k steps, and `after(s, x)` is
+        called after every chunk with the steps completed so far and the state they left (it may change x in place and
+        take streams from the dynamics' counter: every chunk takes its draw index from the counter as it then stands).  `launch(s0, x_in, x_next, B, seed, draw, n, px, actions, plaqs, charges,
         charge_diff, step_sums, samples, ws, ws_nbytes)` runs steps [s0, s0 + n) through the caller's entry (the common
         tail of l2hmc_gauge_hmc_run and l2hmc_gauge_hmc_run_ladder; the caller puts its plan and betas in front) and
         `ws_bytes` is that entry's workspace query.  Consecutive draw indices from the dynamics' counter, as the loop
@@ -174,20 +179,27 @@ class GaugeSampler:
         ws, nb = dyn._ws.get(ws_bytes(C.byref(plan), B, chunk), dev)
         samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
         samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
-        # the steps' random streams come from the dynamics' own draw counter, as in `step`
-        draw0, _ = _lib.run_draw_index(dyn._draws, run_steps)
         x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
         x_in = x
-        for s0 in range(0, run_steps, chunk):
+        s0 = 0
+        while s0 < run_steps:
             n = min(chunk, run_steps - s0)
-            launch(s0, x_in, x_next, B, dyn._seed, draw0 + s0, n, *(hist[k][s0:] for k in names), sums[s0:],
+            if cut_every is not None:
+                n = min(n, cut_every - s0 % cut_every)
+            # the steps' random streams come from the dynamics' own draw counter, as in `step`: consecutive draw
+            # indices from chunk to chunk unless `after` took a stream in between (then the next even-aligned pair)
+            draw, draws_after = _lib.run_draw_index(dyn._draws, n)
+            launch(s0, x_in, x_next, B, dyn._seed, draw, n, *(hist[k][s0:] for k in names), sums[s0:],
                    samples_dev, ws, nb)
-            _, dyn._draws = _lib.run_draw_index(2 * draw0, s0 + n)      # the counter moves with the completed steps
+            dyn._draws = draws_after                       # the counter moves with the completed steps
             x_in = x_next                                  # later chunks advance the state in place
             for i in range(s0, s0 + n):
                 self.stats.push_sums(sums[i, :3])
             if keep_samples:
                 samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
+            s0 += n
+            if after is not None:
+                after(s0, x_next)
         out = {k: v.cpu().numpy() for k, v in hist.items()}
         out["samples_out"] = x_next
         out["mean_accept"] = self.stats.mean_accept()
@@ -231,7 +243,79 @@ class GaugeSampler:
         where it has one.  Draws from the dynamics' counter as `run` does; the caller's `x`, `dynamics.eps` and the
         dynamics' plan are left as they were.  ValueError for an L2HMC dynamics, a wrong shape, a beta that is negative
         or not finite and an eps that is not finite and > 0; NotImplementedError for an hmc dynamics whose plan has no
-        one-launch kernel (more than 1024 sites, `fused = False`): `run` takes those, one beta at a time."""
+        one-launch kernel (more than 1024 sites, `fused = False`): `run` takes those, one beta at a time.
+        `run_hmc_exchange` is this run with replica exchange between the columns of a ladder."""
+        return self.run_hmc_exchange(run_steps, beta, x, eps, keep_samples)
+
+    def swap_replicas(self, x, beta, replicas, parity):
+        """ONE replica-exchange round on device state x [B, x_dim], IN PLACE (l2hmc_gauge_replica_swap): columns
+        [g * replicas, (g + 1) * replicas) are one group, column c at beta[c] (`beta`: [B] or [1, B]); the round of
+        `parity` 0 / 1 proposes the pairs (j, j + 1), j = parity, parity + 2, ... of every group and exchanges two rows
+        with probability min(1, exp((beta_a - beta_b)(S_a - S_b))).  The uniforms are one stream of the dynamics'
+        counter, taken as `GaugeDynamics._uniform` takes it.  If the sampler keeps labels (`self.replica`, int32 [B]
+        on the device) the round exchanges them too.  Returns (swap_p [B], NaN off the lower chain of a pair;
+        swapped [B] bool; action [B], sum (1 - cos P) of the chains that were in a pair, NaN elsewhere) as tensors."""
+        dyn = self.dynamics
+        if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[1] != dyn.x_dim:
+            raise ValueError(f"swap_replicas: x: expected a device tensor [B, {dyn.x_dim}] (exchanged in place)")
+        B = x.shape[0]
+        G, _, _, parity = self._check_replicas(replicas, B, parity=parity, who="swap_replicas")
+        if isinstance(beta, torch.Tensor) and beta.is_cuda and beta.dtype == torch.float32 and beta.numel() == B:
+            beta_dev = beta.reshape(-1)                    # (a ladder that is on the device already stays there)
+        else:
+            b = np.asarray(beta.detach().cpu().numpy() if isinstance(beta, torch.Tensor) else beta, dtype=np.float64)
+            if b.shape not in ((B,), (1, B)):
+                raise ValueError(f"swap_replicas: beta of shape {b.shape}: expected [{B}] or [1, {B}]")
+            beta_dev = _lib.as_dev(b.reshape(-1).astype(np.float32), x.device)
+        return self._swap_round(x, beta_dev, 1, G, parity)
+
+    def _swap_round(self, x, beta_dev, chain_stride, G, parity):
+        dyn = self.dynamics
+        T, X = self.lattice.time_size, self.lattice.space_size
+        out = replica_swap(x, T, X, G, parity, beta_dev, dyn._seed, dyn._draws, chain_stride, self.replica)
+        dyn._draws += 1                                    # one stream, as GaugeDynamics._uniform
+        return out
+
+    @staticmethod
+    def _check_replicas(replicas, B, swap_every=1, first_parity=0, parity=0, who="run_hmc_exchange"):
+        try:
+            G, k, fp, par = int(replicas), int(swap_every), int(first_parity), int(parity)
+            whole = G == replicas and k == swap_every and fp == first_parity and par == parity
+        except (TypeError, ValueError):
+            whole = False
+        if not whole:
+            raise ValueError(f"{who}: replicas, swap_every and the parity must be whole numbers")
+        if G < 2:
+            raise ValueError(f"{who}: replicas={G}: a replica group has 2 rungs or more")
+        if B % G != 0:
+            raise ValueError(f"{who}: the {B} chains (of this rank) are no whole number of groups of replicas={G}")
+        if k < 1:
+            raise ValueError(f"{who}: swap_every={k} must be 1 or more")
+        if fp not in (0, 1) or par not in (0, 1):
+            raise ValueError(f"{who}: the parity of a round is 0 or 1")
+        return G, k, fp, par
+
+    def run_hmc_exchange(self, run_steps, beta, x=None, eps=None, keep_samples=False, replicas=None, swap_every=1,
+                         first_parity=0, replica0=None):
+        """`run_hmc` with replica exchange (parallel tempering) between the columns of a ladder.  `replicas=None`:
+        `run_hmc` itself, bit for bit (the other three arguments are then ignored).  `replicas=G`: columns
+        [g * G, (g + 1) * G) are one group of G rungs.  After every MCMC step s (counting from 1) with
+        s % swap_every == 0 -- the last step of the call included -- ONE round (`swap_replicas`) runs on the state that
+        step left, with parity (first_parity + s // swap_every - 1) % 2 and the betas step s ran with.  beta and eps
+        belong to the COLUMN: configurations move, rungs stay.  A launch of the run kernel never spans a round and never
+        exceeds `steps_per_launch` steps; the run is the loop `run_hmc(swap_every, ...)`, `swap_replicas(...)`, bit
+        for bit.  `samples[s]` is what step s wrote, before any round; `samples_out` the state after the last round.
+        Added to `run_hmc`'s dictionary (n_r = run_steps // swap_every rounds):
+          swap_p [n_r, B] float32   p at the lower chain of every proposed pair, NaN elsewhere
+          swapped [n_r, B] bool
+          replica [n_r, B] int32    the label of the configuration that sits in column c after the round; labels start
+                                    as arange(B), or as `replica0` (the last row of an earlier call: a run continues
+                                    with first_parity = (first_parity + n_r) % 2 of that call)
+          swap_rate [G - 1]         the mean of `swapped` over rounds and groups for each neighbouring pair of rungs (a
+                                    pair is proposed in every other round)
+        Nothing is exchanged between ranks: a group lives on one rank.  ValueError, on top of `run_hmc`'s, for
+        replicas < 2, a batch that is no multiple of it, swap_every < 1, first_parity not 0 or 1, and a replica0 that
+        is not int32 [B]."""
         import ctypes as C
         dyn = self.dynamics
         if not dyn.hmc:
@@ -247,6 +331,17 @@ class GaugeSampler:
         B, D = x.shape
         b64, b32, step_stride, chain_stride = self._ladder_betas(beta, run_steps, B)
         step = None if eps is None else DynamicsSampler._step_sizes(eps, B)     # one rule for both samplers
+        rounds = None
+        if replicas is not None:
+            G, k, parity0, _ = self._check_replicas(replicas, B, swap_every, first_parity)
+            if replica0 is None:
+                labels = np.arange(B, dtype=np.int32)
+            else:
+                labels = replica0.detach().cpu().numpy() if isinstance(replica0, torch.Tensor) else np.asarray(replica0)
+                if labels.dtype != np.int32 or labels.shape != (B,):
+                    raise ValueError(f"run_hmc_exchange: replica0 of dtype {labels.dtype} and shape {labels.shape}: "
+                                     f"expected int32 [{B}]")
+            rounds = {"swap_p": [], "swapped": [], "replica": []}
         if run_steps == 0:
             out = {k: np.empty((0, B), dtype=np.float32) for k in ("px", "actions", "plaqs", "charges", "charge_diff")}
             out["samples_out"] = x.clone()
@@ -270,8 +365,28 @@ class GaugeSampler:
                 _lib.call("l2hmc_gauge_hmc_run_ladder", C.byref(plan), beta_dev[s0 * step_stride:], step_stride,
                           chain_stride, eps_chain, *tail, device=dyn._device)
 
+            cut, after = None, None
+            if rounds is not None:
+                self.replica = _lib.as_dev(labels, x.device, torch.int32)
+                cut = k
+
+                def after(s, x_now):
+                    if s % k == 0:
+                        # the betas step s ran with: row s - 1 of a schedule, the only row otherwise
+                        p, sw, _ = self._swap_round(x_now, beta_dev[(s - 1) * step_stride:], chain_stride, G,
+                                                    (parity0 + s // k - 1) % 2)
+                        rounds["swap_p"].append(p)
+                        rounds["swapped"].append(sw)
+                        rounds["replica"].append(self.replica.clone())
+
             out = self._run_chunks(run_steps, x, keep_samples, plan, _lib.lib().l2hmc_gauge_hmc_run_ladder_ws_bytes,
-                                   launch)
+                                   launch, cut, after)
+        if rounds is not None:
+            for name, dtype in (("swap_p", np.float32), ("swapped", np.bool_), ("replica", np.int32)):
+                out[name] = (torch.stack(rounds[name]).cpu().numpy() if rounds[name]
+                             else np.empty((0, B), dtype=dtype))
+            sw = out["swapped"].reshape(-1, B // G, G)[:, :, :G - 1]
+            out["swap_rate"] = sw.mean(axis=(0, 1)) if sw.shape[0] else np.full(G - 1, np.nan)
         # the last step's beta (an empty run with an empty schedule has none)
         last = b64 if b64.ndim == 0 else b64[-1] if b64.shape[0] else np.full(b64.shape[1:], np.nan)
         out["plaq_exact"] = u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)

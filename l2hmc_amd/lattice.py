@@ -15,6 +15,29 @@ def u1_plaq_exact(beta):
     return i1(beta) / i0(beta)
 
 
+def replica_swap(x, T, X, group, parity, betas, seed, stream_index, chain_stride=1, replica=None):
+    """One replica-exchange round of parity 0 / 1 between neighbouring columns of every group of `group` columns of
+    x [B, 2*T*X], IN PLACE (l2hmc_gauge_replica_swap): column c at betas[c * chain_stride], the uniforms are elements
+    of ops.fill_uniform(B, seed, stream_index), `replica` (int32 [B], or None) is exchanged with the rows
+    -> (swap_p [B] fp32, NaN off the lower chain of a pair; swapped [B] bool; action [B] fp32 with sum (1 - cos P) of
+    every chain that was in a pair, NaN for the chains that sat the round out)."""
+    px, pb = _lib.dev_ptr(x, name="x"), _lib.dev_ptr(betas, name="betas")
+    pr = _lib.dev_ptr(replica, torch.int32, "replica")
+    if x.dim() != 2 or x.shape[1] != 2 * T * X:
+        raise ValueError(f"x: expected [B, {2 * T * X}], got {tuple(x.shape)}")
+    B = x.shape[0]
+    if replica is not None and tuple(replica.shape) != (B,):
+        raise ValueError(f"replica: expected [{B}], got {tuple(replica.shape)}")
+    if betas.numel() < (B - 1) * int(chain_stride) + 1 and B > 0:
+        raise ValueError(f"betas: {betas.numel()} values do not reach column {B - 1} at chain_stride {chain_stride}")
+    swap_p = torch.empty(B, dtype=torch.float32, device=x.device)
+    swapped = torch.empty(B, dtype=torch.uint8, device=x.device)
+    action = torch.full((B,), float("nan"), dtype=torch.float32, device=x.device)
+    _lib.call("l2hmc_gauge_replica_swap", int(T), int(X), px, B, int(group), int(parity), pb, int(chain_stride),
+              int(seed), int(stream_index), pr, action, swap_p, swapped, device=x.device)
+    return swap_p, swapped.view(torch.bool), action
+
+
 def _x2d(x, D):
     x = _lib.as_dev(x)
     return x.reshape(-1, D)

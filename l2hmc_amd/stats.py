@@ -259,3 +259,34 @@ def calc_observables_stats(actions, plaqs, charges, therm_frac=10):
     probs = {int(v): float(c) / counts.sum() for v, c in zip(vals, counts)}
     return ((actions.mean(axis=0), sem(actions)), (plaqs.mean(axis=0), sem(plaqs)),
             (charges.mean(axis=0), sem(charges)), (suscept.mean(axis=0), sem(suscept)), probs)
+
+
+def replica_round_trips(replica, replicas):
+    """Round trips of the configurations of a replica-exchange run through the ladder.  `replica`: [n_r, B] label
+    history (`GaugeSampler.run_hmc_exchange`'s: the label of the configuration that sits in column c after each
+    round; every row is a permutation of 0 .. B-1 that keeps a label inside its group of `replicas` columns).  The rung
+    of a label at round t is (the column it sits in) % replicas.  A round trip is lowest rung -> highest rung -> lowest
+    rung; only what the history shows counts, so a trip starts at the first row that has the label on the lowest rung
+    (stack the starting labels on top of the history to count from the start).
+    Returns (trips [B] int64, completed round trips per label; per_group [B // replicas] int64, their sums)."""
+    rep = np.asarray(replica)
+    G = int(replicas)
+    if rep.ndim != 2 or G < 2 or rep.shape[1] % G != 0:
+        raise ValueError(f"replica_round_trips: a [rounds, B] history with B a multiple of replicas={replicas} expected, "
+                         f"got shape {rep.shape}")
+    n_r, B = rep.shape
+    cols = np.arange(B)
+    trips = np.zeros(B, dtype=np.int64)
+    phase = np.zeros(B, dtype=np.int8)          # per label: 0 not seen at the bottom yet, 1 on its way up, 2 on its way down
+    for t in range(n_r):
+        row = rep[t].astype(np.int64)
+        if not np.array_equal(np.sort(row.reshape(-1, G), axis=1), cols.reshape(-1, G)):
+            raise ValueError(f"replica_round_trips: row {t} is no permutation of the labels within every group")
+        rung = np.empty(B, dtype=np.int64)
+        rung[row] = cols % G                    # rung[label] = where the label sits
+        bottom, top = rung == 0, rung == G - 1
+        done = bottom & (phase == 2)
+        trips += done
+        phase[bottom] = 1
+        phase[top & (phase == 1)] = 2
+    return trips, trips.reshape(-1, G).sum(axis=1)

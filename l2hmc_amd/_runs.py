@@ -1,0 +1,98 @@
+"""What the "many MCMC steps in one launch" runs of GaugeSampler and DynamicsSampler share, host code only: the rule for
+a value with an optional step axis and chain axis, the step-size rule, the empty run, and the ONE loop over chunks."""
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def _float32(value):
+    """tensor / array / list / scalar -> (float64 array as given, the float32 array the device takes)."""
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu().numpy()
+    v = np.asarray(value, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        return v, v.astype(np.float32)
+
+
+def chain_axis(value, run_steps, B, *, who, name, positive):
+    """A per-run value (beta, temperature) -> (float64 array as given, flat contiguous float32 array for the device,
+    (step_stride, chain_stride)): step s of chain c reads flat[s * step_stride + c * chain_stride], the element strides
+    of l2hmc_gauge_hmc_run_ladder, l2hmc_small_run_tempered and l2hmc_small_hmc_run.  ValueError for a shape that is
+    not in the table and for an entry that, in float32, is not finite or is negative (`positive`: or is 0)."""
+    v, v32 = _float32(value)
+    # one value, a schedule, both, a ladder over the chains (last: [1, B] of a run of 1 step is read as a ladder)
+    strides = {(): (0, 0), (run_steps,): (1, 0), (run_steps, B): (B, 1), (1, B): (0, 1)}
+    if v.shape not in strides:
+        raise ValueError(f"{who}: {name} of shape {v.shape}: expected a scalar, [{run_steps}] (one per step), "
+                         f"[1, {B}] (one per chain) or [{run_steps}, {B}]")
+    if not (np.isfinite(v32) & ((v32 > 0) if positive else (v32 >= 0))).all():
+        raise ValueError(f"{who}: every {name} must be finite and {'> 0' if positive else 'not negative'} (in float32)")
+    return v, np.ascontiguousarray(v32).reshape(-1), strides[v.shape]
+
+
+def step_sizes(eps, B, who="run_hmc"):
+    """`run_hmc`'s `eps` as a float32 array [] or [B]; ValueError for another shape or an entry not > 0 in float32."""
+    _, e = _float32(eps)
+    if e.shape not in ((), (B,)):
+        raise ValueError(f"{who}: eps of shape {e.shape}: expected a scalar or [{B}] (one per chain)")
+    if not (np.isfinite(e) & (e > 0)).all():
+        raise ValueError(f"{who}: every eps must be finite and > 0 (in float32)")
+    return e
+
+
+def plan_with_step_sizes(dyn, step, device):
+    """(a fresh plan struct of `dyn`, eps_chain) for `step` = None or what `step_sizes` returned: a scalar goes into
+    `plan.eps` of this struct alone (the dynamics' own plan and eps stay), a [B] array goes to the device."""
+    plan, eps_chain = dyn._plan(), None
+    if step is not None and step.ndim == 0:
+        plan.eps = float(step)
+    elif step is not None:
+        eps_chain = _lib.as_dev(step, device)
+    return plan, eps_chain
+
+
+def empty_run(names, x, keep_samples):
+    """The dictionary of a run of 0 steps from `x` [B, D]: empty histories, a copy of the start as the final state."""
+    out = {k: np.empty((0, x.shape[0]), dtype=np.float32) for k in names}
+    out["samples_out"] = x.clone()
+    if keep_samples:
+        out["samples"] = np.empty((0, *x.shape), dtype=np.float32)
+    return out
+
+
+def chunk_length(run_steps, steps_per_launch):
+    """The most steps one launch of a run takes: what a caller sizes its workspace by."""
+    return min(int(steps_per_launch), run_steps)
+
+
+def run_chunks(run_steps, x, steps_per_launch, keep_samples, launch, cut_every=None, after=None):
+    """`run_steps` > 0 steps from `x` [B, D] in chunks of at most `steps_per_launch`.  `launch(s0, n, x_in, x_next,
+    samples_dev)` runs steps [s0, s0 + n) through the caller's entry: state from `x_in` to `x_next`, the n samples (if
+    kept) to the head of `samples_dev`.  With `cut_every` = k no chunk spans a multiple of k steps.  `after(s, x_next)`
+    is called after every chunk with the steps completed so far and the state they left, which it may change in place.
+    Returns {"samples_out": the final state, "samples": host array [run_steps, B, D] (if kept)}; histories are the
+    caller's.  Allocated once per run: `x_next`, and with `keep_samples` a device buffer ONE chunk long and the host
+    array.  Per chunk: the launch and, with `keep_samples`, the one device-to-host copy -- nothing else allocates or
+    synchronises.  A chunk's draw index is the caller's, read in `launch`: `after` may take streams in between."""
+    B, D = x.shape
+    chunk = chunk_length(run_steps, steps_per_launch)
+    samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=x.device) if keep_samples else None
+    x_next = torch.empty_like(x)                           # the first chunk leaves the caller's x alone
+    out = {"samples_out": x_next}
+    if keep_samples:
+        out["samples"] = np.empty((run_steps, B, D), dtype=np.float32)
+    x_in = x
+    s0 = 0
+    while s0 < run_steps:
+        n = min(chunk, run_steps - s0)
+        if cut_every is not None:
+            n = min(n, cut_every - s0 % cut_every)
+        launch(s0, n, x_in, x_next, samples_dev)           # raises if the entry fails: nothing below has happened
+        x_in = x_next                                      # later chunks advance the state in place
+        if keep_samples:
+            out["samples"][s0:s0 + n] = samples_dev[:n].cpu().numpy()
+        s0 += n
+        if after is not None:
+            after(s0, x_next)
+    return out

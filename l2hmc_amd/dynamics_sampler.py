@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _runs
 from .sampler import propose
 
 
@@ -39,22 +39,31 @@ class DynamicsSampler:
         return int(self.steps_per_launch) > 1 and not dyn.hmc and not dyn.layered
 
     def _temperatures(self, temperature, run_steps, B):
-        """`run`'s `temperature` as a float32 array of shape [] (the whole run), [run_steps] (a schedule), [1, B] (a
-        ladder over the chains) or [run_steps, B] (both); ValueError for any other shape, for an entry that is not
-        finite and > 0 in float32, and for a dynamics that would ignore it."""
+        """`run`'s `temperature` by `_runs.chain_axis` -> (flat float32 array, step_stride, chain_stride)."""
         if not self.dynamics.use_temperature:
             raise ValueError("run: temperature= on a Dynamics built with use_temperature=False, which ignores "
                              "temperatures (Dynamics._temp): build it with use_temperature=True")
-        if isinstance(temperature, torch.Tensor):
-            temperature = temperature.detach().cpu().numpy()
-        with np.errstate(over="ignore"):
-            t = np.asarray(temperature, dtype=np.float64).astype(np.float32)
-        if t.shape not in ((), (run_steps,), (1, B), (run_steps, B)):
-            raise ValueError(f"run: temperature of shape {t.shape}: expected a scalar, [{run_steps}] (one per step), "
-                             f"[1, {B}] (one per chain) or [{run_steps}, {B}]")
-        if not (np.isfinite(t) & (t > 0)).all():
-            raise ValueError("run: every temperature must be finite and > 0 (in float32)")
-        return t
+        _, flat, strides = _runs.chain_axis(temperature, run_steps, B, who="run", name="temperature", positive=True)
+        return (flat, *strides)
+
+    def _start(self, who, run_steps, x, temperature):
+        """What `run` and `run_hmc` (`who`) check alike -> (run_steps, start on the device, `_temperatures` or None)."""
+        dyn, run_steps = self.dynamics, int(run_steps)
+        if run_steps < 0:
+            raise ValueError(f"run_steps={run_steps} must not be negative")
+        if x is None:
+            if self.batch_size is None:
+                raise ValueError(f"{who}: pass the start `x`, or give the sampler a batch_size to start from N(0, 1)")
+            x = np.random.randn(int(self.batch_size), dyn.x_dim)
+        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        temps = None if temperature is None else self._temperatures(temperature, run_steps, x.shape[0])
+        return run_steps, x, temps
+
+    @staticmethod
+    def _finish(out):
+        px = out["px"]
+        out["mean_accept"] = float(px.mean(dtype=np.float64)) if px.size else float("nan")
+        return out
 
     def run(self, run_steps, x=None, keep_samples=True, temperature=None):
         """`run_steps` MCMC steps (utils/sampler.py:28-59 with the Metropolis-Hastings step) from `x` [B, x_dim], or
@@ -66,44 +75,34 @@ class DynamicsSampler:
         (a schedule: step s at temperature[s]), [1, B] (a ladder: chain c at temperature[0, c]) or [run_steps, B]
         (both).  Chains never interact, so the columns of a ladder are independent runs at their own temperatures.
         `dynamics.temperature` is left as it was.  Temperatures per chain need the one-launch path."""
-        dyn = self.dynamics
-        run_steps = int(run_steps)
-        if run_steps < 0:
-            raise ValueError(f"run_steps={run_steps} must not be negative")
-        if x is None:
-            if self.batch_size is None:
-                raise ValueError("run: pass the start `x`, or give the sampler a batch_size to start from N(0, 1)")
-            x = np.random.randn(int(self.batch_size), dyn.x_dim)
-        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
-        B, D = x.shape
-        temps = None if temperature is None else self._temperatures(temperature, run_steps, B)
-        if temps is not None and temps.ndim == 2 and not self._one_launch():
+        run_steps, x, temps = self._start("run", run_steps, x, temperature)
+        if temps is not None and temps[2] and not self._one_launch():
             raise NotImplementedError(
                 "run: temperatures per chain need the one-launch path (an L2HMC dynamics the one-launch kernel holds: "
                 "not hmc, not layer by layer, and steps_per_launch > 1); the loop over `propose` has one "
                 "`dynamics.temperature` for all chains")
         if run_steps == 0:
-            out = {"px": np.empty((0, B), dtype=np.float32), "samples_out": x.clone()}
-            if keep_samples:
-                out["samples"] = np.empty((0, B, D), dtype=np.float32)
-        elif self._one_launch():
-            out = self._run_launches(run_steps, x, keep_samples, temps)
-        else:
+            out = _runs.empty_run(("px",), x, keep_samples)
+        elif not self._one_launch():
             out = self._run_loop(run_steps, x, keep_samples, temps)
-        px = out["px"]
-        out["mean_accept"] = float(px.mean(dtype=np.float64)) if px.size else float("nan")
-        return out
+        else:
+            plan = self.dynamics._plan()
+            entry, middle = "l2hmc_small_run", lambda s0: ()
+            if temps is not None:
+                entry, middle = "l2hmc_small_run_tempered", self._temps_from(temps, x.device)
+            out = self._run_launches(run_steps, x, keep_samples, plan, entry, middle, streams=4)
+        return self._finish(out)
 
     def _run_loop(self, run_steps, x, keep_samples, temps=None):
-        """One `propose` per step: any dynamics.  `temps` ([] or [run_steps]) is set on `dynamics.temperature` step by
-        step, and what was there is put back."""
+        """One `propose` per step: any dynamics.  `temps` (one value or a schedule, as `_temperatures` returns it) is
+        set on `dynamics.temperature` step by step, and what was there is put back."""
         dyn = self.dynamics
         px_hist, samples = [], []
         saved = dyn.temperature
         try:
             for s in range(run_steps):
                 if temps is not None:
-                    dyn.temperature = float(temps[s] if temps.ndim else temps)
+                    dyn.temperature = float(temps[0][s * temps[1]])
                 _, _, px, (x,) = propose(x, dyn, do_mh_step=True)
                 px_hist.append(px)
                 if keep_samples:
@@ -115,64 +114,33 @@ class DynamicsSampler:
             out["samples"] = torch.stack(samples).cpu().numpy()
         return out
 
-    def _run_launches(self, run_steps, x, keep_samples, temps=None, hmc_plan=None, eps_chain=None):
-        """Chunks of at most `steps_per_launch` steps through l2hmc_small_run, ONE launch each (l2hmc_small_run_tempered
-        with `temps`: the array goes to the device once and every chunk starts at its own row).  The same draws (four
-        consecutive streams per step from the dynamics' counter), accept probabilities and samples as `_run_loop`, bit
-        for bit.  With `keep_samples` the device buffer of the samples is one chunk long and is copied to the host
-        chunk by chunk.  `hmc_plan` (`run_hmc`): the chunks go through l2hmc_small_hmc_run with that plan and
-        `eps_chain` ([B] on the device, or None), two streams per step."""
-        dyn = self.dynamics
-        B, D, dev = x.shape[0], x.shape[1], x.device
-        plan = hmc_plan if hmc_plan is not None else dyn._plan()
-        streams = 4 if hmc_plan is None else 2             # per step
-        chunk = min(int(self.steps_per_launch), run_steps)
-        px = torch.empty(run_steps, B, dtype=torch.float32, device=dev)
-        samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
-        samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
-        x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
-        x_in = x
-        step_stride = chain_stride = 0
-        if temps is not None:
-            # element strides of (step, chain): (0, 0) one value, (1, 0) a schedule, (0, 1) a ladder, (B, 1) both
-            step_stride, chain_stride = ((0, 0) if temps.ndim == 0 else (1, 0) if temps.ndim == 1 else
-                                         (0, 1) if temps.shape[0] == 1 else (B, 1))
-            temps_dev = _lib.as_dev(np.ascontiguousarray(temps).reshape(-1), dev)
-        for s0 in range(0, run_steps, chunk):
-            n = min(chunk, run_steps - s0)
-            if hmc_plan is not None:
-                _lib.call("l2hmc_small_hmc_run", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
-                          None if temps is None else temps_dev[s0 * step_stride:], step_stride, chain_stride,
-                          eps_chain, px[s0:], samples_dev, device=dyn._device)
-            elif temps is None:
-                _lib.call("l2hmc_small_run", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n, px[s0:],
-                          samples_dev, device=dyn._device)
-            else:
-                _lib.call("l2hmc_small_run_tempered", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
-                          temps_dev[s0 * step_stride:], step_stride, chain_stride, px[s0:], samples_dev,
-                          device=dyn._device)
-            dyn._draws += streams * n                      # the counter moves with the completed steps
-            x_in = x_next                                  # later chunks advance the state in place
-            if keep_samples:
-                samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
-        out = {"px": px.cpu().numpy(), "samples_out": x_next}
-        if keep_samples:
-            out["samples"] = samples
-        return out
-
     @staticmethod
-    def _step_sizes(eps, B):
-        """`run_hmc`'s `eps` (this sampler's and GaugeSampler's) as a float32 array of shape [] or [B]; ValueError for
-        any other shape and for an entry that is not finite and > 0 in float32."""
-        if isinstance(eps, torch.Tensor):
-            eps = eps.detach().cpu().numpy()
-        with np.errstate(over="ignore"):
-            e = np.asarray(eps, dtype=np.float64).astype(np.float32)
-        if e.shape not in ((), (B,)):
-            raise ValueError(f"run_hmc: eps of shape {e.shape}: expected a scalar or [{B}] (one per chain)")
-        if not (np.isfinite(e) & (e > 0)).all():
-            raise ValueError("run_hmc: every eps must be finite and > 0 (in float32)")
-        return e
+    def _temps_from(temps, dev):
+        """s0 -> (the temperatures from step s0 on, step_stride, chain_stride) as the tempered entries take them: the
+        array goes to the device once and every chunk starts at its own row.  `temps` None: (NULL, 0, 0)."""
+        if temps is None:
+            return lambda s0: (None, 0, 0)
+        flat, step_stride, chain_stride = temps
+        temps_dev = _lib.as_dev(flat, dev)
+        return lambda s0: (temps_dev[s0 * step_stride:], step_stride, chain_stride)
+
+    def _run_launches(self, run_steps, x, keep_samples, plan, entry, middle, streams):
+        """ONE launch of `entry` per chunk (`_runs.run_chunks`), `streams` per step: the same values as `_run_loop`, bit
+        for bit.  `middle(s0)`: what the entry takes between n_steps and px for a chunk from step s0 on."""
+        dyn = self.dynamics
+        B = x.shape[0]
+        px = torch.empty(run_steps, B, dtype=torch.float32, device=x.device)
+
+        def launch(s0, n, x_in, x_next, samples_dev):
+            # the chunk's first stream is the counter as it stands at this launch, and the counter moves only after
+            # the entry returned: a failed launch leaves it where it was
+            _lib.call(entry, C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n, *middle(s0), px[s0:],
+                      samples_dev, device=dyn._device)
+            dyn._draws += streams * n
+
+        out = _runs.run_chunks(run_steps, x, self.steps_per_launch, keep_samples, launch)
+        out["px"] = px.cpu().numpy()
+        return out
 
     def run_hmc(self, run_steps, x=None, keep_samples=True, temperature=None, eps=None):
         """`run` for a plain-HMC dynamics (`hmc=True`) on a packed toy target, `steps_per_launch` steps per launch
@@ -191,32 +159,14 @@ class DynamicsSampler:
             raise NotImplementedError(
                 "run_hmc: this hmc dynamics runs layer by layer (arbitrary energy function or x_dim > 8), which the "
                 "one-launch kernel does not hold: `run` takes it through the loop over `propose`")
-        run_steps = int(run_steps)
-        if run_steps < 0:
-            raise ValueError(f"run_steps={run_steps} must not be negative")
-        if x is None:
-            if self.batch_size is None:
-                raise ValueError("run_hmc: pass the start `x`, or give the sampler a batch_size to start from N(0, 1)")
-            x = np.random.randn(int(self.batch_size), dyn.x_dim)
-        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
-        B, D = x.shape
-        temps = None if temperature is None else self._temperatures(temperature, run_steps, B)
-        step = None if eps is None else self._step_sizes(eps, B)
+        run_steps, x, temps = self._start("run_hmc", run_steps, x, temperature)
+        step = None if eps is None else _runs.step_sizes(eps, x.shape[0])
         if run_steps == 0:
-            out = {"px": np.empty((0, B), dtype=np.float32), "samples_out": x.clone()}
-            if keep_samples:
-                out["samples"] = np.empty((0, B, D), dtype=np.float32)
-        else:
-            plan = dyn._plan()
-            eps_chain = None
-            if step is not None and step.ndim == 0:
-                plan.eps = float(step)
-            elif step is not None:
-                eps_chain = _lib.as_dev(step, x.device)
-            out = self._run_launches(run_steps, x, keep_samples, temps, hmc_plan=plan, eps_chain=eps_chain)
-        px = out["px"]
-        out["mean_accept"] = float(px.mean(dtype=np.float64)) if px.size else float("nan")
-        return out
+            return self._finish(_runs.empty_run(("px",), x, keep_samples))
+        plan, eps_chain = _runs.plan_with_step_sizes(dyn, step, x.device)
+        temps_from = self._temps_from(temps, x.device)
+        return self._finish(self._run_launches(run_steps, x, keep_samples, plan, "l2hmc_small_hmc_run",
+                                               lambda s0: (*temps_from(s0), eps_chain), streams=2))
 
     def generate_trajectories(self, temp=1., num_samples=500, num_steps=100, x=None):
         """mog_model.py:394-421 -> (trajectories [num_steps, num_samples, x_dim], px [num_steps, num_samples]).  As in

@@ -5,12 +5,13 @@ The reference runs one `sess.run` per MCMC step, copying the whole sample batch 
 `feed_dict` and wrapping it with `np.mod(., 2*pi)` on the host (:1371-1388).  Here the chain state never
 leaves HBM: transition -> wrap -> per-step observables are all library calls on device buffers, and the
 per-step scalars of all ranks are combined by one small asynchronous all-reduce (l2hmc_amd/dist.py)."""
+import ctypes as C
+
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, _runs, ops
 from .dist import StepStats
-from .dynamics_sampler import DynamicsSampler
 from .lattice import replica_swap, u1_observables, u1_plaq_exact
 
 
@@ -49,7 +50,6 @@ class GaugeSampler:
         (l2hmc_gauge_mcmc_step: draws + trajectories + mix/accept + observables + wrap).  With
         `dynamics.both_directions = False` the plan carries L2HMC_PLAN_SELECTED_ONLY: each chain is integrated
         only in the direction its coin picks -- same random streams, same chains, half the work."""
-        import ctypes as C
         dyn = self.dynamics
         x_next = torch.empty_like(x)                       # written by the step (out of place: no copy of x)
         B = x.shape[0]
@@ -110,8 +110,7 @@ class GaugeSampler:
         """:1304-1460 without the file/plot side effects.  Starts from N(0,1) samples like the reference
         (:1354) unless `x` is given.  Returns per-step histories as NumPy arrays [steps, B].  `beta`: a float, or a
         sequence of `run_steps` values (one per step; `plaq_exact` is then taken at the last).  Plain HMC on a plan
-        with the one-launch kernel runs `steps_per_launch` steps per launch (`_run_launches`): the same values."""
-        import ctypes as C
+        with the one-launch kernel runs `steps_per_launch` steps per launch (`_run_chunks`): the same values."""
         dyn = self.dynamics
         if x is None:
             x = _lib.as_dev(np.random.randn(dyn.batch_size, dyn.x_dim), dyn._device)
@@ -123,7 +122,12 @@ class GaugeSampler:
             raise ValueError(f"beta: expected a float or {run_steps} values, got {len(betas)}")
         if (run_steps > 0 and dyn.hmc and int(self.steps_per_launch) > 1
                 and _lib.lib().l2hmc_gauge_plan_fused(C.byref(dyn._plan())) == 1):
-            return self._run_launches(run_steps, betas, x, keep_samples)
+            # l2hmc_gauge_hmc_run: the same draws, histories, sums and samples as the loop below, bit for bit
+            beta_dev = torch.tensor(betas, dtype=torch.float32, device=x.device)
+            out = self._run_chunks(run_steps, x, keep_samples, dyn._plan(), "l2hmc_gauge_hmc_run",
+                                   lambda s0: (beta_dev[s0:],))
+            out["plaq_exact"] = u1_plaq_exact(betas[-1])
+            return out
         hist = {k: [] for k in ("px", "actions", "plaqs", "charges", "charge_diff")}
         samples = []
         for i in range(run_steps):
@@ -143,95 +147,43 @@ class GaugeSampler:
             out["samples"] = torch.stack(samples).cpu().numpy()
         return out
 
-    def _run_launches(self, run_steps, betas, x, keep_samples):
-        """`run` for plain HMC through l2hmc_gauge_hmc_run: chunks of at most `steps_per_launch` MCMC steps, ONE launch
-        each (`_run_chunks`).  The same draws, histories, sums and samples as the loop over `step`, bit for bit."""
-        import ctypes as C
-        plan = self.dynamics._plan()
-        beta_dev = torch.tensor(betas, dtype=torch.float32, device=x.device)
+    HISTORIES = ("px", "actions", "plaqs", "charges", "charge_diff")
 
-        def launch(s0, *tail):
-            _lib.call("l2hmc_gauge_hmc_run", C.byref(plan), beta_dev[s0:], *tail, device=self.dynamics._device)
-
-        out = self._run_chunks(run_steps, x, keep_samples, plan, _lib.lib().l2hmc_gauge_hmc_run_ws_bytes, launch)
-        out["plaq_exact"] = u1_plaq_exact(betas[-1])
-        return out
-
-    def _run_chunks(self, run_steps, x, keep_samples, plan, ws_bytes, launch, cut_every=None, after=None):
-        """A run of plain-HMC steps in chunks of at most `steps_per_launch`, ONE launch each, the chains' state in
-        registers from step to step.  With `cut_every` = k no chunk spans a multiple of k steps, and `after(s, x)` is
-        called after every chunk with the steps completed so far and the state they left (it may change x in place and
-        take streams from the dynamics' counter: every chunk takes its draw index from the counter as it then stands).  `launch(s0, x_in, x_next, B, seed, draw, n, px, actions, plaqs, charges,
-        charge_diff, step_sums, samples, ws, ws_nbytes)` runs steps [s0, s0 + n) through the caller's entry (the common
-        tail of l2hmc_gauge_hmc_run and l2hmc_gauge_hmc_run_ladder; the caller puts its plan and betas in front) and
-        `ws_bytes` is that entry's workspace query.  Consecutive draw indices from the dynamics' counter, as the loop
-        over `step` takes them.  The chunks bound the workspace and, with `keep_samples`, the device buffer of the
-        samples (copied to the host chunk by chunk).  Returns `run`'s dictionary without `plaq_exact`."""
-        import ctypes as C
+    def _run_chunks(self, run_steps, x, keep_samples, plan, entry, front, cut_every=None, after=None):
+        """Plain-HMC steps through `_runs.run_chunks` (`cut_every`, `after`: see there), ONE launch of `entry` per
+        chunk: l2hmc_gauge_hmc_run or l2hmc_gauge_hmc_run_ladder; `front(s0)` is what it takes between the plan and x_in
+        for a chunk from step s0 on.  Histories, `_run_sums`, workspace: once per run.  `run`'s dictionary less
+        `plaq_exact`."""
         dyn = self.dynamics
-        B, D, dev = x.shape[0], x.shape[1], x.device
-        chunk = min(int(self.steps_per_launch), run_steps)
-        names = ("px", "actions", "plaqs", "charges", "charge_diff")
-        hist = {k: torch.empty(run_steps, B, dtype=torch.float32, device=dev) for k in names}
+        B, dev = x.shape[0], x.device
+        hist = {k: torch.empty(run_steps, B, dtype=torch.float32, device=dev) for k in self.HISTORIES}
         if self._run_sums is None or self._run_sums.shape[0] < run_steps or self._run_sums.device != dev:
             self._run_sums = torch.zeros(run_steps, 4, dtype=torch.float32, device=dev)
         sums = self._run_sums
-        ws, nb = dyn._ws.get(ws_bytes(C.byref(plan), B, chunk), dev)
-        samples_dev = torch.empty(chunk, B, D, dtype=torch.float32, device=dev) if keep_samples else None
-        samples = np.empty((run_steps, B, D), dtype=np.float32) if keep_samples else None
-        x_next = torch.empty_like(x)                       # the first chunk leaves the caller's x alone
-        x_in = x
-        s0 = 0
-        while s0 < run_steps:
-            n = min(chunk, run_steps - s0)
-            if cut_every is not None:
-                n = min(n, cut_every - s0 % cut_every)
-            # the steps' random streams come from the dynamics' own draw counter, as in `step`: consecutive draw
-            # indices from chunk to chunk unless `after` took a stream in between (then the next even-aligned pair)
+        chunk = _runs.chunk_length(run_steps, self.steps_per_launch)
+        ws, nb = dyn._ws.get(getattr(_lib.lib(), entry + "_ws_bytes")(C.byref(plan), B, chunk), dev)
+
+        def launch(s0, n, x_in, x_next, samples_dev):
+            # the draw index comes from the dynamics' counter as it stands when the chunk is launched: consecutive from
+            # chunk to chunk unless `after` took a stream in between (then the next even-aligned pair).  The counter
+            # moves only after the entry returned: a failed launch leaves it where it was
             draw, draws_after = _lib.run_draw_index(dyn._draws, n)
-            launch(s0, x_in, x_next, B, dyn._seed, draw, n, *(hist[k][s0:] for k in names), sums[s0:],
-                   samples_dev, ws, nb)
-            dyn._draws = draws_after                       # the counter moves with the completed steps
-            x_in = x_next                                  # later chunks advance the state in place
+            _lib.call(entry, C.byref(plan), *front(s0), x_in, x_next, B, dyn._seed, draw, n,
+                      *(hist[k][s0:] for k in self.HISTORIES), sums[s0:], samples_dev, ws, nb, device=dyn._device)
+            dyn._draws = draws_after
             for i in range(s0, s0 + n):
                 self.stats.push_sums(sums[i, :3])
-            if keep_samples:
-                samples[s0:s0 + n] = samples_dev[:n].cpu().numpy()
-            s0 += n
-            if after is not None:
-                after(s0, x_next)
-        out = {k: v.cpu().numpy() for k, v in hist.items()}
-        out["samples_out"] = x_next
+
+        out = _runs.run_chunks(run_steps, x, self.steps_per_launch, keep_samples, launch, cut_every, after)
+        out.update((k, v.cpu().numpy()) for k, v in hist.items())
         out["mean_accept"] = self.stats.mean_accept()
-        if keep_samples:
-            out["samples"] = samples
         return out
 
     @staticmethod
     def _ladder_betas(beta, run_steps, B):
-        """`run_hmc`'s `beta` -> (float64 array as given, flat float32 array for the device, step_stride, chain_stride):
-        a scalar (0, 0), [run_steps] a schedule (1, 0), [1, B] a ladder (0, 1), [run_steps, B] both (B, 1) -- the
-        element strides of l2hmc_gauge_hmc_run_ladder.  ValueError for any other shape and for an entry that is negative
-        or not finite in float32."""
-        if isinstance(beta, torch.Tensor):
-            beta = beta.detach().cpu().numpy()
-        b = np.asarray(beta, dtype=np.float64)
-        with np.errstate(over="ignore"):
-            b32 = b.astype(np.float32)
-        if b.ndim == 0:
-            strides = (0, 0)
-        elif b.shape == (run_steps,):
-            strides = (1, 0)
-        elif b.shape == (1, B):
-            strides = (0, 1)
-        elif b.shape == (run_steps, B):
-            strides = (B, 1)
-        else:
-            raise ValueError(f"run_hmc: beta of shape {b.shape}: expected a scalar, [{run_steps}] (one per step), "
-                             f"[1, {B}] (one per chain) or [{run_steps}, {B}]")
-        if not (np.isfinite(b32) & (b32 >= 0)).all():
-            raise ValueError("run_hmc: every beta must be finite and not negative (in float32)")
-        return b, np.ascontiguousarray(b32).reshape(-1), strides[0], strides[1]
+        """`run_hmc`'s `beta` by `_runs.chain_axis` -> (float64 as given, flat float32, step_stride, chain_stride)."""
+        b, flat, strides = _runs.chain_axis(beta, run_steps, B, who="run_hmc", name="beta", positive=False)
+        return b, flat, strides[0], strides[1]
 
     def run_hmc(self, run_steps, beta, x=None, eps=None, keep_samples=False):
         """`run` for a plain-HMC dynamics (`hmc=True`) with a chain axis on beta and on the step size: a scan over
@@ -245,7 +197,45 @@ class GaugeSampler:
         or not finite and an eps that is not finite and > 0; NotImplementedError for an hmc dynamics whose plan has no
         one-launch kernel (more than 1024 sites, `fused = False`): `run` takes those, one beta at a time.
         `run_hmc_exchange` is this run with replica exchange between the columns of a ladder."""
-        return self.run_hmc_exchange(run_steps, beta, x, eps, keep_samples)
+        return self._ladder_run(*self._run_hmc_args(run_steps, beta, x, eps), keep_samples)
+
+    def _run_hmc_args(self, run_steps, beta, x, eps):
+        """What `run_hmc` refuses -> (run_steps, start on the device, `_ladder_betas`, `_runs.step_sizes` or None)."""
+        dyn = self.dynamics
+        if not dyn.hmc:
+            raise ValueError("run_hmc: the dynamics is an L2HMC sampler (hmc=False): `run` runs it")
+        run_steps = int(run_steps)
+        if run_steps < 0:
+            raise ValueError(f"run_steps={run_steps} must not be negative")
+        if x is None:
+            x = np.random.randn(dyn.batch_size, dyn.x_dim)
+        x = _lib.as_dev(x, dyn._device)
+        if x.ndim != 2 or x.shape[1] != dyn.x_dim:
+            raise ValueError(f"run_hmc: x of shape {tuple(x.shape)}: expected [B, {dyn.x_dim}]")
+        betas = self._ladder_betas(beta, run_steps, x.shape[0])
+        return run_steps, x, betas, None if eps is None else _runs.step_sizes(eps, x.shape[0])
+
+    def _ladder_run(self, run_steps, x, betas, step, keep_samples, exchange=None):
+        """What `run_hmc` means, on checked arguments.  `exchange(beta_dev)`, called once when a run of 1 step or more
+        is about to start (its betas are on the device), returns the `cut_every` and `after` of `_run_chunks`."""
+        b64, b32, step_stride, chain_stride = betas
+        if run_steps == 0:
+            out = _runs.empty_run(self.HISTORIES, x, keep_samples)
+            out["mean_accept"] = self.stats.mean_accept()
+        else:
+            plan, eps_chain = _runs.plan_with_step_sizes(self.dynamics, step, x.device)
+            if _lib.lib().l2hmc_gauge_plan_fused(C.byref(plan)) != 1:
+                raise NotImplementedError(
+                    "run_hmc: this hmc dynamics has no one-launch kernel (more than 1024 sites, or fused = False): "
+                    "`run` takes it through the loop over `step`, one beta at a time")
+            beta_dev = _lib.as_dev(b32, x.device)          # goes over once; every chunk starts at its own row
+            out = self._run_chunks(run_steps, x, keep_samples, plan, "l2hmc_gauge_hmc_run_ladder",
+                                   lambda s0: (beta_dev[s0 * step_stride:], step_stride, chain_stride, eps_chain),
+                                   *(exchange(beta_dev) if exchange else ()))
+        # the last step's beta (an empty run with an empty schedule has none)
+        last = b64 if b64.ndim == 0 else b64[-1] if b64.shape[0] else np.full(b64.shape[1:], np.nan)
+        out["plaq_exact"] = u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
+        return out
 
     def swap_replicas(self, x, beta, replicas, parity):
         """ONE replica-exchange round on device state x [B, x_dim], IN PLACE (l2hmc_gauge_replica_swap): columns
@@ -316,80 +306,41 @@ class GaugeSampler:
         Nothing is exchanged between ranks: a group lives on one rank.  ValueError, on top of `run_hmc`'s, for
         replicas < 2, a batch that is no multiple of it, swap_every < 1, first_parity not 0 or 1, and a replica0 that
         is not int32 [B]."""
-        import ctypes as C
-        dyn = self.dynamics
-        if not dyn.hmc:
-            raise ValueError("run_hmc: the dynamics is an L2HMC sampler (hmc=False): `run` runs it")
-        run_steps = int(run_steps)
-        if run_steps < 0:
-            raise ValueError(f"run_steps={run_steps} must not be negative")
-        if x is None:
-            x = np.random.randn(dyn.batch_size, dyn.x_dim)
-        x = _lib.as_dev(x, dyn._device)
-        if x.ndim != 2 or x.shape[1] != dyn.x_dim:
-            raise ValueError(f"run_hmc: x of shape {tuple(x.shape)}: expected [B, {dyn.x_dim}]")
-        B, D = x.shape
-        b64, b32, step_stride, chain_stride = self._ladder_betas(beta, run_steps, B)
-        step = None if eps is None else DynamicsSampler._step_sizes(eps, B)     # one rule for both samplers
-        rounds = None
-        if replicas is not None:
-            G, k, parity0, _ = self._check_replicas(replicas, B, swap_every, first_parity)
-            if replica0 is None:
-                labels = np.arange(B, dtype=np.int32)
-            else:
-                labels = replica0.detach().cpu().numpy() if isinstance(replica0, torch.Tensor) else np.asarray(replica0)
-                if labels.dtype != np.int32 or labels.shape != (B,):
-                    raise ValueError(f"run_hmc_exchange: replica0 of dtype {labels.dtype} and shape {labels.shape}: "
-                                     f"expected int32 [{B}]")
-            rounds = {"swap_p": [], "swapped": [], "replica": []}
-        if run_steps == 0:
-            out = {k: np.empty((0, B), dtype=np.float32) for k in ("px", "actions", "plaqs", "charges", "charge_diff")}
-            out["samples_out"] = x.clone()
-            out["mean_accept"] = self.stats.mean_accept()
-            if keep_samples:
-                out["samples"] = np.empty((0, B, D), dtype=np.float32)
+        run_steps, x, betas, step = self._run_hmc_args(run_steps, beta, x, eps)
+        if replicas is None:
+            return self._ladder_run(run_steps, x, betas, step, keep_samples)
+        B = x.shape[0]
+        G, k, parity0, _ = self._check_replicas(replicas, B, swap_every, first_parity)
+        if replica0 is None:
+            labels = np.arange(B, dtype=np.int32)
         else:
-            plan = dyn._plan()                             # a fresh struct: a scalar eps goes into it alone
-            if _lib.lib().l2hmc_gauge_plan_fused(C.byref(plan)) != 1:
-                raise NotImplementedError(
-                    "run_hmc: this hmc dynamics has no one-launch kernel (more than 1024 sites, or fused = False): "
-                    "`run` takes it through the loop over `step`, one beta at a time")
-            eps_chain = None
-            if step is not None and step.ndim == 0:
-                plan.eps = float(step)
-            elif step is not None:
-                eps_chain = _lib.as_dev(step, x.device)
-            beta_dev = _lib.as_dev(b32, x.device)          # goes over once; every chunk starts at its own row
+            labels = replica0.detach().cpu().numpy() if isinstance(replica0, torch.Tensor) else np.asarray(replica0)
+            if labels.dtype != np.int32 or labels.shape != (B,):
+                raise ValueError(f"run_hmc_exchange: replica0 of dtype {labels.dtype} and shape {labels.shape}: "
+                                 f"expected int32 [{B}]")
+        # the exchange layer over `_ladder_run`: chunks cut at the multiples of k steps, one round after each of them
+        step_stride, chain_stride = betas[2:]
+        rounds = {"swap_p": [], "swapped": [], "replica": []}
 
-            def launch(s0, *tail):
-                _lib.call("l2hmc_gauge_hmc_run_ladder", C.byref(plan), beta_dev[s0 * step_stride:], step_stride,
-                          chain_stride, eps_chain, *tail, device=dyn._device)
+        def exchange(beta_dev):
+            self.replica = _lib.as_dev(labels, x.device, torch.int32)
 
-            cut, after = None, None
-            if rounds is not None:
-                self.replica = _lib.as_dev(labels, x.device, torch.int32)
-                cut = k
+            def after(s, x_now):
+                if s % k == 0:
+                    # the betas step s ran with: row s - 1 of a schedule, the only row otherwise.  The round takes one
+                    # stream of the dynamics' counter; the next chunk reads the counter when it is launched
+                    p, sw, _ = self._swap_round(x_now, beta_dev[(s - 1) * step_stride:], chain_stride, G,
+                                                (parity0 + s // k - 1) % 2)
+                    rounds["swap_p"].append(p)
+                    rounds["swapped"].append(sw)
+                    rounds["replica"].append(self.replica.clone())
+            return k, after
 
-                def after(s, x_now):
-                    if s % k == 0:
-                        # the betas step s ran with: row s - 1 of a schedule, the only row otherwise
-                        p, sw, _ = self._swap_round(x_now, beta_dev[(s - 1) * step_stride:], chain_stride, G,
-                                                    (parity0 + s // k - 1) % 2)
-                        rounds["swap_p"].append(p)
-                        rounds["swapped"].append(sw)
-                        rounds["replica"].append(self.replica.clone())
-
-            out = self._run_chunks(run_steps, x, keep_samples, plan, _lib.lib().l2hmc_gauge_hmc_run_ladder_ws_bytes,
-                                   launch, cut, after)
-        if rounds is not None:
-            for name, dtype in (("swap_p", np.float32), ("swapped", np.bool_), ("replica", np.int32)):
-                out[name] = (torch.stack(rounds[name]).cpu().numpy() if rounds[name]
-                             else np.empty((0, B), dtype=dtype))
-            sw = out["swapped"].reshape(-1, B // G, G)[:, :, :G - 1]
-            out["swap_rate"] = sw.mean(axis=(0, 1)) if sw.shape[0] else np.full(G - 1, np.nan)
-        # the last step's beta (an empty run with an empty schedule has none)
-        last = b64 if b64.ndim == 0 else b64[-1] if b64.shape[0] else np.full(b64.shape[1:], np.nan)
-        out["plaq_exact"] = u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
+        out = self._ladder_run(run_steps, x, betas, step, keep_samples, exchange)
+        for name, dtype in (("swap_p", np.float32), ("swapped", np.bool_), ("replica", np.int32)):
+            out[name] = (torch.stack(rounds[name]).cpu().numpy() if rounds[name] else np.empty((0, B), dtype=dtype))
+        sw = out["swapped"].reshape(-1, B // G, G)[:, :, :G - 1]
+        out["swap_rate"] = sw.mean(axis=(0, 1)) if sw.shape[0] else np.full(G - 1, np.nan)
         return out
 
     @staticmethod

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.run_cases import assert_same_run, count_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -49,11 +50,8 @@ def _plan_fused(dyn):
 
 def _assert_same_run(a, b, sa, sb, what):
     assert set(a) == set(b), what
-    for k in HIST + ("samples",):
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
-        assert np.array_equal(a[k], b[k]), (what, k, float(np.abs(a[k] - b[k]).max()))
-    assert torch.equal(a["samples_out"], b["samples_out"]), what
-    assert a["mean_accept"] == b["mean_accept"] and a["plaq_exact"] == b["plaq_exact"], what
+    assert_same_run(a, b, HIST + ("samples",), what)
+    assert a["plaq_exact"] == b["plaq_exact"], what
     assert torch.equal(sa.stats.total, sb.stats.total), (what, sa.stats.total, sb.stats.total)
     assert sa.dynamics._draws == sb.dynamics._draws, what
 
@@ -108,24 +106,14 @@ def test_run_with_one_beta_per_step_equals_steps_at_those_betas(la):
 
 
 # ----------------------------------------------------------------- 2. launches
-def _count(cls, run):
-    from l2hmc_amd import _lib
-    Lh = _lib.lib()
-    _lib.check(Lh.l2hmc_profile_begin(cls))
-    run()
-    ms, n = C.c_double(), C.c_int64()
-    _lib.check(Lh.l2hmc_profile_end(C.byref(ms), C.byref(n)))
-    return int(n.value)
-
-
 @pytest.mark.parametrize("T,X,B", [(8, 8, 64), (32, 32, 4)])
 def test_run_is_one_launch_per_chunk(la, T, X, B):
     x = _x0(T, X, B)
     for spl in (8, 3, 1):
         smp = _sampler(la, T, X, B, spl=spl)
         smp.run(8, 2.0, x)                                           # warm-up
-        assert _count(5, lambda: smp.run(8, 2.0, x)) == math.ceil(8 / spl)
-        assert _count(4, lambda: smp.run(8, 2.0, x)) == 0
+        assert count_launches(5, lambda: smp.run(8, 2.0, x)) == math.ceil(8 / spl)
+        assert count_launches(4, lambda: smp.run(8, 2.0, x)) == 0
 
 
 # ----------------------------------------------------------------- 3. the C entry on its own

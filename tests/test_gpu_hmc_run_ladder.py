@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.run_cases import assert_same_run, count_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -77,11 +78,7 @@ def _assert_columns(a, u, cols, what):
 
 
 def _assert_same_run(a, b, sa, sb, what):
-    for k in HIST + ("samples",):
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
-        assert np.array_equal(a[k], b[k]), (what, k)
-    assert torch.equal(a["samples_out"], b["samples_out"]), what
-    assert a["mean_accept"] == b["mean_accept"], what
+    assert_same_run(a, b, HIST + ("samples",), what)
     assert torch.equal(sa.stats.total, sb.stats.total), (what, sa.stats.total, sb.stats.total)
     assert sa.dynamics._draws == sb.dynamics._draws, what
 
@@ -188,16 +185,6 @@ def test_chunks_with_a_shorter_last_one_equal_one_chunk(la, T, X, B, both):
 
 
 # ----------------------------------------------------------------- 5. launches
-def _count(cls, run):
-    from l2hmc_amd import _lib
-    Lh = _lib.lib()
-    _lib.check(Lh.l2hmc_profile_begin(cls))
-    run()
-    ms, n = C.c_double(), C.c_int64()
-    _lib.check(Lh.l2hmc_profile_end(C.byref(ms), C.byref(n)))
-    return int(n.value)
-
-
 @pytest.mark.parametrize("T,X,B", [(8, 8, 64), (32, 32, 4)])
 def test_run_hmc_is_one_launch_per_chunk(la, T, X, B):
     x = _x0(T, X, B)
@@ -206,8 +193,8 @@ def test_run_hmc_is_one_launch_per_chunk(la, T, X, B):
     for spl in (8, 3, 1):
         smp = _sampler(la, T, X, B, spl=spl)
         smp.run_hmc(8, beta, x, eps=eps)                             # warm-up
-        assert _count(5, lambda: smp.run_hmc(8, beta, x, eps=eps)) == math.ceil(8 / spl)
-        assert _count(4, lambda: smp.run_hmc(8, beta, x, eps=eps)) == 0
+        assert count_launches(5, lambda: smp.run_hmc(8, beta, x, eps=eps)) == math.ceil(8 / spl)
+        assert count_launches(4, lambda: smp.run_hmc(8, beta, x, eps=eps)) == 0
 
 
 # ----------------------------------------------------------------- 6. the C entry on its own

@@ -11,6 +11,7 @@ import torch
 
 from oracle import lattice as olat
 from tests import helpers as H
+from tests.run_cases import count_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -239,16 +240,6 @@ def test_hmc_kernel_matches_layered_path_with_fractional_masks(la):
 
 
 # ----------------------------------------------------------------- 4. one launch
-def _count(cls, run):
-    from l2hmc_amd import _lib
-    Lh = _lib.lib()
-    _lib.check(Lh.l2hmc_profile_begin(cls))
-    run()
-    ms, n = C.c_double(), C.c_int64()
-    _lib.check(Lh.l2hmc_profile_end(C.byref(ms), C.byref(n)))
-    return int(n.value)
-
-
 @pytest.mark.parametrize("T,X", [(8, 8), (6, 6), (32, 32)])
 def test_hmc_step_is_one_launch(la, T, X):
     N, B = 10, 64
@@ -258,10 +249,10 @@ def test_hmc_step_is_one_launch(la, T, X):
     sn, so = la.GaugeSampler(new), la.GaugeSampler(old)
     sn.step(x, 2.0)
     so.step(x, 2.0)
-    assert _count(5, lambda: sn.step(x, 2.0)) == 1
-    assert _count(4, lambda: sn.step(x, 2.0)) == 0
-    assert _count(5, lambda: so.step(x, 2.0)) == 0
-    assert _count(4, lambda: so.step(x, 2.0)) > 2 * N
+    assert count_launches(5, lambda: sn.step(x, 2.0)) == 1
+    assert count_launches(4, lambda: sn.step(x, 2.0)) == 0
+    assert count_launches(5, lambda: so.step(x, 2.0)) == 0
+    assert count_launches(4, lambda: so.step(x, 2.0)) > 2 * N
 
 
 # ----------------------------------------------------------------- 5. determinism and capture

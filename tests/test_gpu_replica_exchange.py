@@ -12,7 +12,6 @@ Measured on the MI355X (max |z| over rungs, checkpoints and test functions; `_re
   round);  0.3 s per case.
   round replaced by the torch restatement of a defect (4x4 / 8x8):  exponent sign flipped 234 / 142, always accept
   208 / 121."""
-import ctypes as C
 import math
 import time
 
@@ -22,6 +21,7 @@ import torch
 
 from tests import helpers as H
 from tests import replica_ref as R
+from tests.run_cases import count_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -185,16 +185,6 @@ def test_labels_are_permutations_and_the_rate_is_the_mean(la, T, X, B, G):
 
 
 # ----------------------------------------------------------------- 5. launches
-def _count(cls, run):
-    from l2hmc_amd import _lib
-    Lh = _lib.lib()
-    _lib.check(Lh.l2hmc_profile_begin(cls))
-    run()
-    ms, n = C.c_double(), C.c_int64()
-    _lib.check(Lh.l2hmc_profile_end(C.byref(ms), C.byref(n)))
-    return int(n.value)
-
-
 @pytest.mark.parametrize("T,X,B", [(8, 8, 72), (32, 32, 4)])
 def test_one_run_launch_per_chunk_and_one_swap_launch_per_round_with_a_pair(la, T, X, B):
     """No launch of the run kernel spans a round or exceeds steps_per_launch: between two rounds (k steps, and the
@@ -209,12 +199,12 @@ def test_one_run_launch_per_chunk_and_one_swap_launch_per_round_with_a_pair(la, 
                 run = lambda: smp.run_hmc_exchange(n, beta, x, replicas=G, swap_every=k, first_parity=1)
                 run()                                                # warm-up
                 want = (n // k) * math.ceil(k / spl) + math.ceil((n % k) / spl)
-                assert _count(5, run) == want, (G, k, spl)
+                assert count_launches(5, run) == want, (G, k, spl)
                 # parities 1, 0, 1, ...: with two rungs only the rounds of parity 0 have a pair
                 parities = [(1 + r) % 2 for r in range(n // k)]
-                assert _count(8, run) == sum(1 for p in parities if G > 2 or p == 0), (G, k, spl)
-                assert _count(4, run) == 0
-                assert _count(8, lambda: smp.run_hmc(n, beta, x)) == 0
+                assert count_launches(8, run) == sum(1 for p in parities if G > 2 or p == 0), (G, k, spl)
+                assert count_launches(4, run) == 0
+                assert count_launches(8, lambda: smp.run_hmc(n, beta, x)) == 0
 
 
 # ----------------------------------------------------------------- 6. the target stays invariant

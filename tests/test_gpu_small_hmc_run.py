@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.run_cases import assert_same_run, count_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -97,11 +98,7 @@ def _loop(la, kind, B, steps=STEPS, eps=0.1, temperature=None, schedule=None):
 
 def _assert_same_run(a, b, what):
     assert set(a) == set(b) == {"px", "samples", "samples_out", "mean_accept"}, what
-    for k in ("px", "samples"):
-        assert a[k].dtype == b[k].dtype == np.float32 and a[k].shape == b[k].shape, (what, k)
-        assert np.array_equal(a[k], b[k]), (what, k, float(np.abs(a[k] - b[k]).max()))
-    assert torch.equal(a["samples_out"], b["samples_out"]), what
-    assert a["mean_accept"] == b["mean_accept"], what
+    assert_same_run(a, b, ("px", "samples"), what)
 
 
 def _run_hmc(la, kind, B, steps=STEPS, spl=256, dyn_eps=0.1, dyn_temperature=None, **kw):
@@ -150,22 +147,12 @@ def test_run_in_chunks_with_a_shorter_last_one(la):
     assert draws == 4 + 2 * 7
 
 
-def _count(cls, run):
-    from l2hmc_amd import _lib
-    Lh = _lib.lib()
-    _lib.check(Lh.l2hmc_profile_begin(cls))
-    run()
-    ms, n = C.c_double(), C.c_int64()
-    _lib.check(Lh.l2hmc_profile_end(C.byref(ms), C.byref(n)))
-    return int(n.value)
-
-
 def test_run_hmc_is_one_launch_per_chunk(la):
     x = _x0(64, 2)
     for spl in (8, 3):
         smp = _sampler(la, "mog", spl)
         smp.run_hmc(8, x)                                            # warm-up
-        assert _count(7, lambda: smp.run_hmc(8, x)) == math.ceil(8 / spl)
+        assert count_launches(7, lambda: smp.run_hmc(8, x)) == math.ceil(8 / spl)
 
 
 # ----------------------------------------------------------------- 3. the C entry on its own

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.run_cases import assert_same_run, count_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -70,11 +71,7 @@ def _x0(B, dim):
 
 def _assert_same_run(a, b, sa, sb, what):
     assert set(a) == set(b) == {"px", "samples", "samples_out", "mean_accept"}, what
-    for k in ("px", "samples"):
-        assert a[k].dtype == b[k].dtype == np.float32 and a[k].shape == b[k].shape, (what, k)
-        assert np.array_equal(a[k], b[k]), (what, k, float(np.abs(a[k] - b[k]).max()))
-    assert torch.equal(a["samples_out"], b["samples_out"]), what
-    assert a["mean_accept"] == b["mean_accept"], what
+    assert_same_run(a, b, ("px", "samples"), what)
     assert sa.dynamics._draws == sb.dynamics._draws, what
 
 
@@ -163,22 +160,12 @@ def test_c_entry_equals_chained_proposes_and_its_outputs_are_optional(la, kind, 
 
 
 # ----------------------------------------------------------------- 4. launches
-def _count(cls, run):
-    from l2hmc_amd import _lib
-    Lh = _lib.lib()
-    _lib.check(Lh.l2hmc_profile_begin(cls))
-    run()
-    ms, n = C.c_double(), C.c_int64()
-    _lib.check(Lh.l2hmc_profile_end(C.byref(ms), C.byref(n)))
-    return int(n.value)
-
-
 def test_run_is_one_launch_per_chunk(la):
     x = _x0(64, 2)
     for spl in (8, 3, 1):
         smp = _sampler(la, "mog", 0, spl)
         smp.run(8, x)                                                # warm-up
-        assert _count(7, lambda: smp.run(8, x)) == (math.ceil(8 / spl) if spl > 1 else 8)
+        assert count_launches(7, lambda: smp.run(8, x)) == (math.ceil(8 / spl) if spl > 1 else 8)
 
 
 # ----------------------------------------------------------------- 5. dynamics the kernel does not hold

@@ -2,13 +2,12 @@
 binding, its workspace query, the argument checks that must fail before any device call, and the draw counter of a
 run.  No GPU: the plans and arguments carry any non-NULL address where a pointer is checked."""
 import ctypes as C
-import re
 
 import pytest
 
 from l2hmc_amd import _lib
+from tests.run_cases import PTR, header_text
 
-PTR = 16          # any non-NULL address: host checks only
 _P, _I32, _I64, _SZ, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_uint64
 
 
@@ -32,8 +31,7 @@ def test_header_declares_and_binding_matches():
     # plan, betas, x_in, x_next, B, seed, draw0, n_steps, five histories, step_sums, samples, ws, ws_bytes, stream
     assert _lib._PROTOS["l2hmc_gauge_hmc_run"] == (
         C.c_int, [C.POINTER(_lib.GaugePlan), _P, _P, _P, _I64, _U64, _U64, _I32] + [_P] * 5 + [_P, _P, _P, _SZ, _P])
-    with open(_lib.HEADER_PATH) as f:
-        text = re.sub(r"\s+", " ", f.read())
+    text = header_text(comments=True)
     assert ("int l2hmc_gauge_hmc_run(const l2hmc_gauge_plan* plan, const float* betas, const float* x_in, "
             "float* x_next, int64_t B, uint64_t seed, uint64_t draw0, int32_t n_steps, float* px, float* actions, "
             "float* plaqs, float* charges, float* charge_diff, float* step_sums, float* samples, void* ws, "

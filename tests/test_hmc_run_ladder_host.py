@@ -5,7 +5,6 @@ any non-NULL address where a pointer is checked, and the sampler runs on stub dy
 plan."""
 import ctypes as C
 import inspect
-import re
 import types
 
 import numpy as np
@@ -13,8 +12,8 @@ import pytest
 import torch
 
 from l2hmc_amd import _lib
+from tests.run_cases import PTR, header_text
 
-PTR = 16          # any non-NULL address: host checks only
 _P, _I32, _I64, _SZ, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_uint64
 
 
@@ -43,8 +42,7 @@ def test_header_declares_and_binding_matches():
     assert _lib._PROTOS["l2hmc_gauge_hmc_run_ladder"] == (
         C.c_int, [C.POINTER(_lib.GaugePlan), _P, _I64, _I64, _P, _P, _P, _I64, _U64, _U64, _I32] + [_P] * 5
         + [_P, _P, _P, _SZ, _P])
-    with open(_lib.HEADER_PATH) as f:
-        text = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S))
+    text = header_text()
     assert ("size_t l2hmc_gauge_hmc_run_ladder_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps);"
             in text)
     assert ("int l2hmc_gauge_hmc_run_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t step_stride, "

@@ -13,7 +13,6 @@ for the correct rule, > 8 for each defect (Z_PASS / Z_DEFECT of tests/test_gpu_i
 mean swap rate of the proposed pairs 0.34 / 0.60 / 0.40.  About 2 s per ladder."""
 import ctypes as C
 import inspect
-import re
 import types
 
 import numpy as np
@@ -22,8 +21,8 @@ import torch
 
 from l2hmc_amd import _lib, stats
 from tests import replica_ref as R
+from tests.run_cases import PTR, header_text
 
-PTR = 16          # any non-NULL address: host checks only
 _P, _I32, _I64, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
 Z_PASS, Z_DEFECT = 5.0, 8.0
 
@@ -44,8 +43,7 @@ def test_header_declares_and_binding_matches():
     # T, X, x, B, group, parity, betas, chain_stride, seed, stream_index, replica, action, swap_p, swapped, stream
     assert _lib._PROTOS["l2hmc_gauge_replica_swap"] == (
         C.c_int, [_I32, _I32, _P, _I64, _I32, _I32, _P, _I64, _U64, _U64, _P, _P, _P, _P, _P])
-    with open(_lib.HEADER_PATH) as f:
-        text = re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S))
+    text = header_text()
     assert ("int l2hmc_gauge_replica_swap(int32_t T, int32_t X, float* x, int64_t B, int32_t group, int32_t parity, "
             "const float* betas, int64_t chain_stride, uint64_t seed, uint64_t stream_index, int32_t* replica, "
             "float* action, float* swap_p, uint8_t* swapped, l2hmc_stream_t stream);") in text

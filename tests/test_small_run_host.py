@@ -3,7 +3,6 @@ the argument checks that must fail before any device call, the tunnelling rate o
 `DynamicsSampler` picks.  No GPU: plans and arguments carry any non-NULL address where a pointer is checked, and the
 sampler runs on a stub dynamics with `propose` replaced."""
 import ctypes as C
-import re
 import types
 
 import numpy as np
@@ -11,8 +10,8 @@ import pytest
 import torch
 
 from l2hmc_amd import _lib
+from tests.run_cases import PTR, header_text
 
-PTR = 16          # any non-NULL address: host checks only
 _P, _I32, _I64, _U64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
 
 
@@ -42,8 +41,7 @@ def test_header_declares_and_binding_matches():
     # plan, x_in, x_next, B, seed, draw0, n_steps, px, samples, stream
     assert _lib._PROTOS["l2hmc_small_run"] == (
         C.c_int, [C.POINTER(_lib.SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _P, _P])
-    with open(_lib.HEADER_PATH) as f:
-        text = re.sub(r"\s+", " ", f.read())
+    text = header_text(comments=True)
     assert ("int l2hmc_small_run(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B, "
             "uint64_t seed, uint64_t draw0, int32_t n_steps, float* px, float* samples, "
             "l2hmc_stream_t stream);") in text

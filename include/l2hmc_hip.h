@@ -642,6 +642,57 @@ int l2hmc_small_hmc_run(const l2hmc_small_plan* plan, const float* x_in, float* 
                         uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride, int64_t chain_stride,
                         const float* eps_chain, float* px, float* samples, l2hmc_stream_t stream);
 
+/* ONE replica-exchange (parallel tempering) round between neighbouring rungs of a temperature ladder on a packed toy
+ * target, in place on x [B][x_dim].  Any plan with a packed target is served, an L2HMC sampler's included: of the plan
+ * only x_dim and target are read.  Columns [g * group, (g + 1) * group) form one replica group and column c is at
+ * temperature temps[c * chain_stride] (DEVICE pointer; the stride may be 0; the values are not checked, as in
+ * l2hmc_small_run_tempered).  A round of parity 0 or 1 proposes, in every group, the disjoint pairs
+ * (a, b) = (g * group + j, g * group + j + 1) for j = parity, parity + 2, ... with j + 1 < group, the rule of
+ * l2hmc_gauge_replica_swap.  Per pair: U_a, U_b = the target's energy at temperature 1 of the two rows (fp32, the
+ * arithmetic of l2hmc_mog_energy_grad: U depends on nothing but the row and the target), it = 1.f / temperature as
+ * every step forms it;
+ *   p = min(1, exp(((double)it_a - (double)it_b) * ((double)U_a - (double)U_b)))   (the exponential in fp64, NaN -> 0)
+ * which is exp(-U_b / T_a - U_a / T_b) / exp(-U_a / T_a - U_b / T_b); u = element a of the stream
+ * l2hmc_fill_uniform(B, seed, stream_index) writes; the pair is exchanged iff p > u (strict): the two rows of x and
+ * the two entries of replica trade places, temperatures stay with the column.  Outputs, each [B], each may be NULL:
+ * replica (int32 labels, exchanged in place), energy[c] = U_c for the members of a pair (other chains' entries are
+ * left untouched), swap_p[a] = p at the LOWER chain of each pair and NaN elsewhere, swapped[a] = 1 / 0 at the lower
+ * chain and 0 elsewhere (the chains that sit the round out included).
+ * One thread per chain, a group inside one wave (hence group <= 64).  One launch (profile class 8); a round without a
+ * pair (group 2 at parity 1) fills swap_p and swapped and launches nothing; B == 0 is a no-op.  Refused with
+ * L2HMC_ERR_ARG before any device call: NULL plan, B < 0, group < 2 or > 64, B not a multiple of group, parity not 0
+ * or 1, a negative stride, x_dim != target.dim and what every entry refuses of a target, NULL x or temps with B > 0. */
+int l2hmc_small_replica_swap(const l2hmc_small_plan* plan, float* x, int64_t B, int32_t group, int32_t parity,
+                             const float* temps, int64_t chain_stride, uint64_t seed, uint64_t stream_index,
+                             int32_t* replica, float* energy, float* swap_p, uint8_t* swapped,
+                             l2hmc_stream_t stream);
+
+/* l2hmc_small_hmc_run with replica exchange between the columns of a temperature ladder INSIDE the launch: its contract
+ * (momenta and Metropolis-Hastings uniforms per step, px, samples, x_next that may alias x_in, temps with its strides,
+ * eps_chain, no workspace, graph capture, the same bits on every run, B == 0 a no-op) with these differences.
+ * After step s of the launch one round of l2hmc_small_replica_swap (group, the rule and the arithmetic above) runs iff
+ * (swap_phase + s + 1) % swap_every == 0, on the state the step left and at the temperatures the step ran with
+ * (temps[s * step_stride + c * chain_stride]); the j-th round of the launch has parity (first_parity + j) % 2.
+ * Streams are taken in the order of the loop a caller would write: a step takes two (momenta, uniforms), a round the
+ * next one -- a round without a pair takes its stream as well, so the accounting does not depend on the group size.
+ * The launch consumes streams draw0 .. draw0 + 2 n_steps + rounds - 1, rounds = (swap_phase + n_steps) / swap_every.
+ * samples[s] and px[s] are step s's own outputs, taken BEFORE its round; the round shows in the next step's input and
+ * in x_next.  replica [B] (int32 labels, or NULL) is read on entry and written on exit.  swap_p, swapped and
+ * replica_hist (the labels after each round) are [rounds][B]; each may be NULL.
+ * ONE launch (profile class 7) of the run kernel: a workgroup (one wave) holds (64 / group) * group chains, so a group
+ * never straddles a wave and a round is a handful of cross-lane reads between two steps.  Bit for bit the loop
+ * l2hmc_small_hmc_run (up to the next round), l2hmc_small_replica_swap: both call one device function on the fp32
+ * state the run would store and reload.
+ * Refused with L2HMC_ERR_ARG before any device call: everything l2hmc_small_hmc_run refuses, NULL temps, group < 2 or
+ * > 64, B not a multiple of group, swap_every < 1, swap_phase outside [0, swap_every), first_parity not 0 or 1,
+ * draw0 + 2 n_steps + rounds beyond 2^64 - 1. */
+int l2hmc_small_hmc_run_exchange(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                                 uint64_t seed, uint64_t draw0, int32_t n_steps,
+                                 const float* temps, int64_t step_stride, int64_t chain_stride, const float* eps_chain,
+                                 int32_t group, int32_t swap_every, int32_t swap_phase, int32_t first_parity,
+                                 int32_t* replica, float* px, float* samples,
+                                 float* swap_p, uint8_t* swapped, int32_t* replica_hist, l2hmc_stream_t stream);
+
 /* One training evaluation on the toy targets (mog_model.py:324-363): `rows` = 2B stacked chains (B started at
  * x, B at z ~ N(0,1); sampler.py:28-55 picks a direction per chain, passed in `dir`), each integrated in its
  * direction; per chain v = |x0 - x_N|^2 * p + 1e-4, term = scale / v - v / scale, loss = inv_count * sum of all
@@ -751,7 +802,8 @@ int l2hmc_fill_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, l2
  *   1 = first dense layer   2 = hidden dense layer   3 = heads (+update)
  *   4 = u1_action_force     5 = fused whole-trajectory kernel
  *   6 = ConvNet3D front-end 7 = toy-target trajectory kernel (l2hmc_small_*)
- *   8 = replica-exchange round (l2hmc_gauge_replica_swap)
+ *   8 = replica-exchange round on its own (l2hmc_gauge_replica_swap, l2hmc_small_replica_swap; the rounds inside
+ *       l2hmc_small_hmc_run_exchange are part of its class-7 launch)
  * ------------------------------------------------------------------------ */
 int l2hmc_profile_begin(int32_t kernel_class);
 int l2hmc_profile_end(double* total_ms, int64_t* launches);

@@ -52,6 +52,61 @@ def plan_with_step_sizes(dyn, step, device):
     return plan, eps_chain
 
 
+def check_replicas(replicas, B, swap_every=1, first_parity=0, parity=0, who="run_hmc_exchange", most=None):
+    """The replica-exchange arguments of both samplers -> (G, swap_every, first_parity, parity) as ints; ValueError
+    otherwise.  `most`: the largest group the entry behind `who` takes (the toy targets keep a group in one wave)."""
+    try:
+        G, k, fp, par = int(replicas), int(swap_every), int(first_parity), int(parity)
+        whole = G == replicas and k == swap_every and fp == first_parity and par == parity
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError(f"{who}: replicas, swap_every and the parity must be whole numbers")
+    if G < 2:
+        raise ValueError(f"{who}: replicas={G}: a replica group has 2 rungs or more")
+    if most is not None and G > most:
+        raise ValueError(f"{who}: replicas={G}: a replica group has {most} rungs at the most (it sits in one wave)")
+    if B % G != 0:
+        raise ValueError(f"{who}: the {B} chains (of this rank) are no whole number of groups of replicas={G}")
+    if k < 1:
+        raise ValueError(f"{who}: swap_every={k} must be 1 or more")
+    if fp not in (0, 1) or par not in (0, 1):
+        raise ValueError(f"{who}: the parity of a round is 0 or 1")
+    return G, k, fp, par
+
+
+def replica_labels(replica0, B, who="run_hmc_exchange"):
+    """The labels an exchange run starts with, int32 [B] on the host: arange(B), or `replica0` (ValueError unless it
+    is int32 [B])."""
+    if replica0 is None:
+        return np.arange(B, dtype=np.int32)
+    labels = replica0.detach().cpu().numpy() if isinstance(replica0, torch.Tensor) else np.asarray(replica0)
+    if labels.dtype != np.int32 or labels.shape != (B,):
+        raise ValueError(f"{who}: replica0 of dtype {labels.dtype} and shape {labels.shape}: expected int32 [{B}]")
+    return labels
+
+
+def exchange_histories(out, rounds, B, G):
+    """Adds what an exchange run returns on top of its run's dictionary `out`: swap_p [n_r, B] float32, swapped bool,
+    replica int32 -- from `rounds`, per name a list of [B] device tensors or one [n_r, B] device tensor -- and
+    swap_rate [G - 1], the mean of `swapped` over rounds and groups for each neighbouring pair of rungs."""
+    counts = None
+    for name, dtype in (("swap_p", np.float32), ("swapped", np.bool_), ("replica", np.int32)):
+        r = rounds[name]
+        if isinstance(r, list):
+            r = torch.stack(r) if r else None
+        if r is not None and name == "swapped":
+            # (uint8 from the run kernel: the same bytes.)  The exchanges are counted where the history lives: a run
+            # with a round after every step has as many rows as steps, and the host would walk them all for G - 1 numbers
+            r = r.view(torch.bool) if r.dtype == torch.uint8 else r
+            counts = r.reshape(-1, B // G, G)[:, :, :G - 1].sum(dim=(0, 1), dtype=torch.int64).cpu().numpy()
+        out[name] = np.empty((0, B), dtype=dtype) if r is None else r.cpu().numpy().astype(dtype, copy=False)
+    n_r = out["swapped"].shape[0]
+    # the mean of `swapped` over rounds and groups, as NumPy forms it: the exact count over the number of entries
+    out["swap_rate"] = counts / np.float64(n_r * (B // G)) if n_r else np.full(G - 1, np.nan)
+    return out
+
+
 def empty_run(names, x, keep_samples):
     """The dictionary of a run of 0 steps from `x` [B, D]: empty histories, a copy of the start as the final state."""
     out = {k: np.empty((0, x.shape[0]), dtype=np.float32) for k in names}

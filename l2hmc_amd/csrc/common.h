@@ -235,6 +235,15 @@ __device__ __forceinline__ float accept_from_delta(T dh) {
   return isfinite(pr) ? pr : 0.f;
 }
 
+// The replica-exchange rounds' min(1, exp(dh)) with accept_from_delta's NaN rule (NaN -> 0), the exponential taken in
+// fp64 and rounded ONCE: accept_from_delta rounds the exponent to fp32 ahead of expf, |dh| 2^-24 relative in p, which
+// is tens of ulps at the p << 1 a far pair of rungs proposes with.
+__device__ __forceinline__ float swap_accept_prob(double dh) {
+  if (dh != dh) return 0.f;
+  const float pr = (float)exp(dh < 0.0 ? dh : 0.0);
+  return isfinite(pr) ? pr : 0.f;
+}
+
 }  // namespace l2hmc
 
 // Cycle stamps of the diagnostic build (-DL2HMC_STAMPS, tools/build_diag.sh): the wave's clock, fenced against the

@@ -22,15 +22,7 @@ namespace l2hmc {
 
 constexpr int kSwapThreads = 256;
 
-// min(1, exp(dh)) with accept_from_delta's NaN rule (NaN -> 0), the exponential taken in fp64 and rounded ONCE:
-// accept_from_delta rounds the exponent to fp32 ahead of expf, |dh| 2^-24 relative in p, which is tens of ulps at the
-// p << 1 a far pair of rungs proposes with.
-__device__ __forceinline__ float swap_accept_prob(double dh) {
-  if (dh != dh) return 0.f;
-  const float pr = (float)exp(dh < 0.0 ? dh : 0.0);
-  return isfinite(pr) ? pr : 0.f;
-}
-
+// p: swap_accept_prob (common.h), shared with the toy targets' round (small_swap.h).
 // npg: pairs of a group in this round (> 0).  tsh: log2(TPP).  vec: rows are 16-byte aligned and D % 4 == 0.
 __global__ __launch_bounds__(kSwapThreads) void replica_swap_kernel(
     float* __restrict__ x, const int T, const int X, const int64_t npairs, const int group, const int parity,

@@ -14,7 +14,12 @@ step, per chain, or both, where `dynamics.temperature` is one value for the laun
 
 `run_hmc` is the plain-HMC baseline in one launch per chunk (l2hmc_small_hmc_run, a kernel of its own: one thread per
 chain): the values of `run` on an `hmc=True` dynamics, bit for bit, and beyond them a temperature and a step size per
-chain, so that "HMC at three eps" is one call."""
+chain, so that "HMC at three eps" is one call.
+
+`run_hmc_exchange` is `run_hmc` on a temperature ladder with replica exchange (parallel tempering) between the rungs,
+the rounds inside the launch (l2hmc_small_hmc_run_exchange: a replica group sits in one wave); `swap_replicas` is one
+round on its own (l2hmc_small_replica_swap) and `run_exchange` the host composition of `run(temperature=)` and that
+round for an L2HMC dynamics."""
 import ctypes as C
 
 import numpy as np
@@ -33,6 +38,8 @@ class DynamicsSampler:
         self.batch_size = batch_size
         # MCMC steps per launch of l2hmc_small_run (1 = one launch per step through `propose`, the cross-check)
         self.steps_per_launch = 256
+        # int32 [B] labels on the device while an exchange run is followed (`run_hmc_exchange`, `run_exchange`)
+        self.replica = None
 
     def _one_launch(self):
         dyn = self.dynamics
@@ -124,9 +131,10 @@ class DynamicsSampler:
         temps_dev = _lib.as_dev(flat, dev)
         return lambda s0: (temps_dev[s0 * step_stride:], step_stride, chain_stride)
 
-    def _run_launches(self, run_steps, x, keep_samples, plan, entry, middle, streams):
-        """ONE launch of `entry` per chunk (`_runs.run_chunks`), `streams` per step: the same values as `_run_loop`, bit
-        for bit.  `middle(s0)`: what the entry takes between n_steps and px for a chunk from step s0 on."""
+    def _run_launches(self, run_steps, x, keep_samples, plan, entry, middle, streams, cut_every=None, after=None):
+        """ONE launch of `entry` per chunk (`_runs.run_chunks`, which takes `cut_every` and `after`), `streams` per
+        step: the same values as `_run_loop`, bit for bit.  `middle(s0)`: what the entry takes between n_steps and px
+        for a chunk from step s0 on."""
         dyn = self.dynamics
         B = x.shape[0]
         px = torch.empty(run_steps, B, dtype=torch.float32, device=x.device)
@@ -138,9 +146,20 @@ class DynamicsSampler:
                       samples_dev, device=dyn._device)
             dyn._draws += streams * n
 
-        out = _runs.run_chunks(run_steps, x, self.steps_per_launch, keep_samples, launch)
+        out = _runs.run_chunks(run_steps, x, self.steps_per_launch, keep_samples, launch, cut_every, after)
         out["px"] = px.cpu().numpy()
         return out
+
+    def _check_hmc(self, who):
+        """What `run_hmc` and `run_hmc_exchange` (`who`) refuse of the dynamics."""
+        dyn = self.dynamics
+        if not dyn.hmc:
+            raise ValueError(f"{who}: the dynamics is an L2HMC sampler (hmc=False): `run` runs it, in one launch per "
+                             "chunk where the one-launch kernel holds it")
+        if dyn.layered:
+            raise NotImplementedError(
+                f"{who}: this hmc dynamics runs layer by layer (arbitrary energy function or x_dim > 8), which the "
+                "one-launch kernel does not hold: `run` takes it through the loop over `propose`")
 
     def run_hmc(self, run_steps, x=None, keep_samples=True, temperature=None, eps=None):
         """`run` for a plain-HMC dynamics (`hmc=True`) on a packed toy target, `steps_per_launch` steps per launch
@@ -152,13 +171,7 @@ class DynamicsSampler:
         ValueError for an L2HMC dynamics and NotImplementedError for one that runs layer by layer (a callable energy,
         x_dim > 8): `run` takes both."""
         dyn = self.dynamics
-        if not dyn.hmc:
-            raise ValueError("run_hmc: the dynamics is an L2HMC sampler (hmc=False): `run` runs it, in one launch per "
-                             "chunk where the one-launch kernel holds it")
-        if dyn.layered:
-            raise NotImplementedError(
-                "run_hmc: this hmc dynamics runs layer by layer (arbitrary energy function or x_dim > 8), which the "
-                "one-launch kernel does not hold: `run` takes it through the loop over `propose`")
+        self._check_hmc("run_hmc")
         run_steps, x, temps = self._start("run_hmc", run_steps, x, temperature)
         step = None if eps is None else _runs.step_sizes(eps, x.shape[0])
         if run_steps == 0:
@@ -167,6 +180,166 @@ class DynamicsSampler:
         temps_from = self._temps_from(temps, x.device)
         return self._finish(self._run_launches(run_steps, x, keep_samples, plan, "l2hmc_small_hmc_run",
                                                lambda s0: (*temps_from(s0), eps_chain), streams=2))
+
+    # ------------------------------------------------------------------------------------------ replica exchange
+    MAX_REPLICAS = 64                # a replica group sits in one wave (l2hmc_small_replica_swap)
+
+    def _exchange_args(self, who, run_steps, x, temperature, replicas, swap_every, first_parity, replica0):
+        """What the two exchange runs (`who`) check alike, before any launch -> (run_steps, start on the device,
+        `_temperatures`, G, swap_every, first_parity, starting labels on the host)."""
+        if temperature is None:
+            raise ValueError(f"{who}: replicas={replicas} without temperature=: the rungs of a replica group are the "
+                             "columns of a temperature ladder")
+        run_steps, x, temps = self._start(who, run_steps, x, temperature)
+        B = x.shape[0]
+        G, k, fp, _ = _runs.check_replicas(replicas, B, swap_every, first_parity, who=who, most=self.MAX_REPLICAS)
+        return run_steps, x, temps, G, k, fp, _runs.replica_labels(replica0, B, who)
+
+    def run_hmc_exchange(self, run_steps, x=None, keep_samples=True, temperature=None, eps=None, replicas=None,
+                         swap_every=1, first_parity=0, replica0=None):
+        """`run_hmc` with replica exchange (parallel tempering) between the columns of a temperature ladder, the rounds
+        INSIDE the launch (l2hmc_small_hmc_run_exchange): still one launch per chunk of `steps_per_launch` steps, with
+        an exchange after every step if asked.  `replicas=None`: `run_hmc` itself, bit for bit (the other three
+        arguments are then ignored).  `replicas=G` (2..64): columns [g * G, (g + 1) * G) are one group of G rungs and
+        `temperature` is required, in any shape `run_hmc` takes (a scalar makes every exchange certain).  After every
+        MCMC step s (counting from 1) with s % swap_every == 0 -- the last step of the call included -- ONE round runs
+        on the state that step left, with parity (first_parity + s // swap_every - 1) % 2 and the temperatures step s
+        ran with: the pairs (j, j + 1), j = parity, parity + 2, ... of every group trade places with probability
+        min(1, exp((1 / T_a - 1 / T_b)(U_a - U_b))), U the target's energy at temperature 1.  Temperature and eps
+        belong to the COLUMN: states move, rungs stay.  The run is the loop `run_hmc(swap_every, ...)`,
+        `swap_replicas(...)`, bit for bit, and takes the same draws (2 streams per step, 1 per round).  `samples[s]` is
+        what step s wrote, before any round; `samples_out` the state after the last round.  Added to `run_hmc`'s
+        dictionary, named and shaped as `GaugeSampler.run_hmc_exchange`'s (n_r = run_steps // swap_every rounds):
+          swap_p [n_r, B] float32   p at the lower chain of every proposed pair, NaN elsewhere
+          swapped [n_r, B] bool
+          replica [n_r, B] int32    the label of the state that sits in column c after the round; labels start as
+                                    arange(B), or as `replica0` (the last row of an earlier call: a run continues with
+                                    first_parity = (first_parity + n_r) % 2 of that call)
+          swap_rate [G - 1]         the mean of `swapped` over rounds and groups for each neighbouring pair of rungs
+        `self.replica` keeps the labels on the device; `stats.replica_round_trips` reads `replica`.  ValueError, on top
+        of `run_hmc`'s, for replicas outside 2..64, a batch that is no multiple of it, swap_every < 1, first_parity
+        not 0 or 1, a replica0 that is not int32 [B], and replicas without a temperature."""
+        if replicas is None:
+            return self.run_hmc(run_steps, x, keep_samples, temperature, eps)
+        who, dyn = "run_hmc_exchange", self.dynamics
+        self._check_hmc(who)
+        run_steps, x, temps, G, k, parity0, labels = self._exchange_args(who, run_steps, x, temperature, replicas,
+                                                                         swap_every, first_parity, replica0)
+        B = x.shape[0]
+        step = None if eps is None else _runs.step_sizes(eps, B, who)
+        if run_steps == 0:
+            out = _runs.empty_run(("px",), x, keep_samples)
+            return self._finish(_runs.exchange_histories(out, dict(swap_p=None, swapped=None, replica=None), B, G))
+        plan, eps_chain = _runs.plan_with_step_sizes(dyn, step, x.device)
+        temps_from = self._temps_from(temps, x.device)
+        n_r = run_steps // k
+        self.replica = _lib.as_dev(labels, x.device, torch.int32)
+        rounds = {"swap_p": torch.empty(n_r, B, dtype=torch.float32, device=x.device),
+                  "swapped": torch.empty(n_r, B, dtype=torch.uint8, device=x.device),
+                  "replica": torch.empty(n_r, B, dtype=torch.int32, device=x.device)}
+        px = torch.empty(run_steps, B, dtype=torch.float32, device=x.device)
+
+        def launch(s0, n, x_in, x_next, samples_dev):
+            # a chunk may end inside a swap period: it passes where in the period it starts and its first round's
+            # parity, and moves the counter by its steps' streams and its rounds'
+            r0, n_rounds = s0 // k, (s0 % k + n) // k
+            hist = [rounds[name][r0:] if n_rounds else None for name in ("swap_p", "swapped", "replica")]
+            _lib.call("l2hmc_small_hmc_run_exchange", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
+                      *temps_from(s0), eps_chain, G, k, s0 % k, (parity0 + r0) % 2, self.replica, px[s0:], samples_dev,
+                      *hist, device=dyn._device)
+            dyn._draws += 2 * n + n_rounds
+
+        out = _runs.run_chunks(run_steps, x, self.steps_per_launch, keep_samples, launch)
+        out["px"] = px.cpu().numpy()
+        return self._finish(_runs.exchange_histories(out, rounds, B, G))
+
+    def swap_replicas(self, x, temperature, replicas, parity):
+        """ONE replica-exchange round on device state x [B, x_dim], IN PLACE (l2hmc_small_replica_swap), for a
+        plain-HMC and an L2HMC dynamics on a packed target alike: columns [g * replicas, (g + 1) * replicas) are one
+        group, column c at temperature[c] (`temperature`: a scalar, [B] or [1, B]); the round of `parity` 0 / 1
+        proposes the pairs (j, j + 1), j = parity, parity + 2, ... of every group and exchanges two rows with
+        probability min(1, exp((1 / T_a - 1 / T_b)(U_a - U_b))), U the target's energy at temperature 1.  The uniforms
+        are one stream of the dynamics' counter (`_draws`, then + 1).  If the sampler keeps labels (`self.replica`,
+        int32 [B] on the device) the round exchanges them too.  Returns (swap_p [B], NaN off the lower chain of a pair;
+        swapped [B] bool; energy [B], U of the chains that were in a pair, NaN elsewhere) as tensors."""
+        dyn = self.dynamics
+        if dyn.layered:
+            raise NotImplementedError("swap_replicas: this dynamics runs layer by layer (arbitrary energy function or "
+                                      "x_dim > 8): the round needs a packed target")
+        if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[1] != dyn.x_dim:
+            raise ValueError(f"swap_replicas: x: expected a device tensor [B, {dyn.x_dim}] (exchanged in place)")
+        B = x.shape[0]
+        G, _, _, parity = _runs.check_replicas(replicas, B, parity=parity, who="swap_replicas", most=self.MAX_REPLICAS)
+        replica = getattr(self, "replica", None)
+        if replica is not None and tuple(replica.shape) != (B,):
+            raise ValueError(f"swap_replicas: the sampler's labels are {tuple(replica.shape)}: expected [{B}] (or None)")
+        if (isinstance(temperature, torch.Tensor) and temperature.is_cuda and temperature.dtype == torch.float32
+                and temperature.numel() == B):
+            temps_dev, stride = temperature.reshape(-1), 1       # (a ladder that is on the device already stays there)
+        else:
+            _, t = _runs._float32(temperature)
+            if t.shape not in ((), (B,), (1, B)):
+                raise ValueError(f"swap_replicas: temperature of shape {t.shape}: expected a scalar, [{B}] or [1, {B}]")
+            if not (np.isfinite(t) & (t > 0)).all():
+                raise ValueError("swap_replicas: every temperature must be finite and > 0 (in float32)")
+            temps_dev, stride = _lib.as_dev(np.ascontiguousarray(t).reshape(-1), x.device), int(t.ndim > 0)
+        return self._swap_round(x, temps_dev, stride, G, parity)
+
+    def _swap_round(self, x, temps_dev, chain_stride, G, parity):
+        dyn = self.dynamics
+        B = x.shape[0]
+        plan = dyn._plan()
+        swap_p = torch.empty(B, dtype=torch.float32, device=x.device)
+        swapped = torch.empty(B, dtype=torch.uint8, device=x.device)
+        energy = torch.full((B,), float("nan"), dtype=torch.float32, device=x.device)
+        _lib.call("l2hmc_small_replica_swap", C.byref(plan), x, B, G, parity, temps_dev, chain_stride, dyn._seed,
+                  dyn._draws, getattr(self, "replica", None), energy, swap_p, swapped, device=dyn._device)
+        dyn._draws += 1
+        return swap_p, swapped.view(torch.bool), energy
+
+    def run_exchange(self, run_steps, x=None, keep_samples=True, temperature=None, replicas=None, swap_every=1,
+                     first_parity=0, replica0=None):
+        """`run(..., temperature=)` of an L2HMC dynamics with replica exchange between the columns of the ladder: the
+        run cut at the multiples of `swap_every` steps (one launch of l2hmc_small_run_tempered per piece of at most
+        `steps_per_launch` steps) with `swap_replicas` after each cut -- the loop `run(swap_every, temperature=)`,
+        `swap_replicas(...)`, bit for bit, with its draws (4 streams per step, 1 per round).  Arguments and the added
+        entries of the dictionary as `run_hmc_exchange`; `replicas=None` is `run` itself.  The rounds are launches of
+        their own here: the L2HMC kernel gives a chain four lanes and a wave eight chains, so a group of rungs does not
+        sit in a wave as it does in the plain-HMC kernel.  ValueError for a plain-HMC dynamics (`run_hmc_exchange`
+        runs it); NotImplementedError where `run` has no one-launch path (layer by layer, steps_per_launch = 1)."""
+        if replicas is None:
+            return self.run(run_steps, x, keep_samples, temperature)
+        who, dyn = "run_exchange", self.dynamics
+        if dyn.hmc:
+            raise ValueError(f"{who}: the dynamics is a plain-HMC sampler (hmc=True): `run_hmc_exchange` runs it, with "
+                             "the rounds inside the launch")
+        if not self._one_launch():
+            raise NotImplementedError(
+                f"{who}: temperatures per chain need the one-launch path (an L2HMC dynamics the one-launch kernel "
+                "holds: not layer by layer, and steps_per_launch > 1)")
+        run_steps, x, temps, G, k, parity0, labels = self._exchange_args(who, run_steps, x, temperature, replicas,
+                                                                         swap_every, first_parity, replica0)
+        B = x.shape[0]
+        rounds = {"swap_p": [], "swapped": [], "replica": []}
+        if run_steps == 0:
+            out = _runs.empty_run(("px",), x, keep_samples)
+            return self._finish(_runs.exchange_histories(out, rounds, B, G))
+        self.replica = _lib.as_dev(labels, x.device, torch.int32)
+        temps_from = self._temps_from(temps, x.device)
+
+        def after(s, x_now):
+            if s % k == 0:
+                # the temperatures step s ran with: row s - 1 of a schedule, the only row otherwise.  The round takes
+                # one stream of the dynamics' counter; the next chunk reads the counter when it is launched
+                t, _, chain_stride = temps_from(s - 1)
+                p, sw, _ = self._swap_round(x_now, t, chain_stride, G, (parity0 + s // k - 1) % 2)
+                rounds["swap_p"].append(p)
+                rounds["swapped"].append(sw)
+                rounds["replica"].append(self.replica.clone())
+
+        out = self._run_launches(run_steps, x, keep_samples, dyn._plan(), "l2hmc_small_run_tempered", temps_from,
+                                 streams=4, cut_every=k, after=after)
+        return self._finish(_runs.exchange_histories(out, rounds, B, G))
 
     def generate_trajectories(self, temp=1., num_samples=500, num_steps=100, x=None):
         """mog_model.py:394-421 -> (trajectories [num_steps, num_samples, x_dim], px [num_steps, num_samples]).  As in

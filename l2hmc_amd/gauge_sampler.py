@@ -268,22 +268,7 @@ class GaugeSampler:
 
     @staticmethod
     def _check_replicas(replicas, B, swap_every=1, first_parity=0, parity=0, who="run_hmc_exchange"):
-        try:
-            G, k, fp, par = int(replicas), int(swap_every), int(first_parity), int(parity)
-            whole = G == replicas and k == swap_every and fp == first_parity and par == parity
-        except (TypeError, ValueError):
-            whole = False
-        if not whole:
-            raise ValueError(f"{who}: replicas, swap_every and the parity must be whole numbers")
-        if G < 2:
-            raise ValueError(f"{who}: replicas={G}: a replica group has 2 rungs or more")
-        if B % G != 0:
-            raise ValueError(f"{who}: the {B} chains (of this rank) are no whole number of groups of replicas={G}")
-        if k < 1:
-            raise ValueError(f"{who}: swap_every={k} must be 1 or more")
-        if fp not in (0, 1) or par not in (0, 1):
-            raise ValueError(f"{who}: the parity of a round is 0 or 1")
-        return G, k, fp, par
+        return _runs.check_replicas(replicas, B, swap_every, first_parity, parity, who)
 
     def run_hmc_exchange(self, run_steps, beta, x=None, eps=None, keep_samples=False, replicas=None, swap_every=1,
                          first_parity=0, replica0=None):
@@ -311,13 +296,7 @@ class GaugeSampler:
             return self._ladder_run(run_steps, x, betas, step, keep_samples)
         B = x.shape[0]
         G, k, parity0, _ = self._check_replicas(replicas, B, swap_every, first_parity)
-        if replica0 is None:
-            labels = np.arange(B, dtype=np.int32)
-        else:
-            labels = replica0.detach().cpu().numpy() if isinstance(replica0, torch.Tensor) else np.asarray(replica0)
-            if labels.dtype != np.int32 or labels.shape != (B,):
-                raise ValueError(f"run_hmc_exchange: replica0 of dtype {labels.dtype} and shape {labels.shape}: "
-                                 f"expected int32 [{B}]")
+        labels = _runs.replica_labels(replica0, B)
         # the exchange layer over `_ladder_run`: chunks cut at the multiples of k steps, one round after each of them
         step_stride, chain_stride = betas[2:]
         rounds = {"swap_p": [], "swapped": [], "replica": []}
@@ -337,11 +316,7 @@ class GaugeSampler:
             return k, after
 
         out = self._ladder_run(run_steps, x, betas, step, keep_samples, exchange)
-        for name, dtype in (("swap_p", np.float32), ("swapped", np.bool_), ("replica", np.int32)):
-            out[name] = (torch.stack(rounds[name]).cpu().numpy() if rounds[name] else np.empty((0, B), dtype=dtype))
-        sw = out["swapped"].reshape(-1, B // G, G)[:, :, :G - 1]
-        out["swap_rate"] = sw.mean(axis=(0, 1)) if sw.shape[0] else np.full(G - 1, np.nan)
-        return out
+        return _runs.exchange_histories(out, rounds, B, G)
 
     @staticmethod
     def run_dicts(out, beta):

@@ -393,6 +393,47 @@ int l2hmc_gauge_replica_swap(int32_t T, int32_t X, float* x, int64_t B, int32_t 
                              int32_t* replica, float* action, float* swap_p, uint8_t* swapped,
                              l2hmc_stream_t stream);
 
+/* l2hmc_gauge_hmc_run_ladder with the replica-exchange rounds of l2hmc_gauge_replica_swap INSIDE the launch: the loop
+ * "run k steps, one round, run k steps, ..." of the two entries on one draw counter, bit for bit, in ONE launch.
+ * The contract of l2hmc_gauge_hmc_run_ladder in every respect (optional outputs, x_next may alias x_in, step_sums with
+ * ALL ticket words 0 on entry and left at 0, the workspace only with step_sums, graph capture, B == 0 a no-op), and
+ * the round semantics of l2hmc_small_hmc_run_exchange: columns [g * group, (g + 1) * group) are one replica group; a
+ * round runs after step s (0 <= s < n_steps) iff (swap_phase + s + 1) % swap_every == 0, on the wrapped state that step
+ * left and at the betas it ran with; the j-th round of the call has parity (first_parity + j) % 2;
+ * rounds = (swap_phase + n_steps) / swap_every.  swap_p (float), swapped (uint8) and replica_hist (int32), each
+ * [rounds][B] and each may be NULL, receive per round what l2hmc_gauge_replica_swap writes to swap_p and swapped and
+ * the labels after the round; replica (int32 [B], or NULL: the labels start as the column index) is read on entry and
+ * written on exit.  samples[s] and row s of the histories are what step s wrote, BEFORE its round; x_next is the state
+ * after the last round.  A round without a pair (group 2 at parity 1) fills its rows and takes its stream.
+ * Streams: a step with draw index d takes (seed, 2 d) and (seed, 2 d + 1); a round after it takes the uniforms of
+ * (seed, 2 d + 2), and the step after a round has draw index d + 2 (stream 2 d + 3 is skipped): what a caller gets who
+ * keeps ONE counter of streams, gives a step the next even-aligned pair and a round the next stream.  So step s draws
+ * with index draw0 + s + (rounds of this call before step s), and draw0 + n_steps + rounds must not exceed 2^63.
+ * Served (l2hmc_gauge_hmc_run_exchange_served = 1) iff a workgroup of at most 1024 threads holds whole replica groups:
+ * the plan takes l2hmc_gauge_hmc_run_ladder (hmc = 1, not layered, at most 1024 sites), its lattice has at most 512
+ * sites (the instance of four sites per thread does not fit the registers of such a workgroup), and with
+ *   tpc  = threads per row: the least power of two >= ceil(sites / spt), spt = 1 up to 256 sites and 2 up to 512,
+ *   rpc  = rows per chain: 1 with L2HMC_PLAN_SELECTED_ONLY, else 2,
+ *   cpw0 = chains per workgroup of the ladder run = (tpc == 256 ? 512 : 256) / tpc / rpc,
+ * lcm(group, cpw0) * rpc * tpc <= 1024 (and the workgroup's LDS fits the 64 KiB a launch gets, which only a one-site
+ * lattice with 768 rows or more can exceed).  E.g. 8x8: groups of 2, 3, 4, 6, 8 rungs (selected-only also 12 and 16); 16x16
+ * and 16x32: 2 (selected-only also 4).  Every pair of rungs then meets inside one workgroup: no workgroup waits for
+ * another.  The query is host logic only (no device call); it returns 0 with l2hmc_last_error set for a (plan, group)
+ * that is not served, and l2hmc_gauge_replica_swap between launches of l2hmc_gauge_hmc_run_ladder takes those.
+ * Refused with L2HMC_ERR_ARG before any device call: everything l2hmc_gauge_hmc_run_ladder refuses, NULL betas,
+ * group < 2, B not a multiple of group, swap_every < 1, swap_phase outside [0, swap_every), first_parity not 0 or 1,
+ * a (plan, group) that is not served, draw0 + n_steps + rounds beyond 2^63.  l2hmc_gauge_hmc_run_exchange_ws_bytes is
+ * l2hmc_gauge_hmc_run_ladder_ws_bytes. */
+int l2hmc_gauge_hmc_run_exchange_served(const l2hmc_gauge_plan* plan, int32_t group);
+size_t l2hmc_gauge_hmc_run_exchange_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps);
+int l2hmc_gauge_hmc_run_exchange(const l2hmc_gauge_plan* plan, const float* betas, int64_t step_stride,
+                                 int64_t chain_stride, const float* eps_chain, const float* x_in, float* x_next,
+                                 int64_t B, uint64_t seed, uint64_t draw0, int32_t n_steps, int32_t group,
+                                 int32_t swap_every, int32_t swap_phase, int32_t first_parity, int32_t* replica,
+                                 float* px, float* actions, float* plaqs, float* charges, float* charge_diff,
+                                 float* step_sums, float* samples, float* swap_p, uint8_t* swapped,
+                                 int32_t* replica_hist, void* ws, size_t ws_bytes, l2hmc_stream_t stream);
+
 /* Forward value of the training loss, per chain (gauge_model.py:766-795): terms[b] = std_loss + charge_loss;
  * the scalar loss is their mean over ALL chains of all ranks.  x, x_prop, z: [B][2*T*X]; px, pz: [B].
  * metric: 0 'l1', 1 'l2', 2 'cos', 3 'cos2', 4 'cos_diff' (:632-657).  Both auxiliary terms compare z with
@@ -803,7 +844,8 @@ int l2hmc_fill_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, l2
  *   4 = u1_action_force     5 = fused whole-trajectory kernel
  *   6 = ConvNet3D front-end 7 = toy-target trajectory kernel (l2hmc_small_*)
  *   8 = replica-exchange round on its own (l2hmc_gauge_replica_swap, l2hmc_small_replica_swap; the rounds inside
- *       l2hmc_small_hmc_run_exchange are part of its class-7 launch)
+ *       l2hmc_small_hmc_run_exchange are part of its class-7 launch, those inside l2hmc_gauge_hmc_run_exchange of
+ *       its class-5 launch)
  * ------------------------------------------------------------------------ */
 int l2hmc_profile_begin(int32_t kernel_class);
 int l2hmc_profile_end(double* total_ms, int64_t* launches);

@@ -120,6 +120,11 @@ _PROTOS = {
     "l2hmc_gauge_hmc_run_ladder_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64, _I32]),
     "l2hmc_gauge_hmc_run_ladder": (C.c_int, [C.POINTER(GaugePlan), _P, _I64, _I64, _P, _P, _P, _I64, _U64, _U64, _I32,
                                              _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "l2hmc_gauge_hmc_run_exchange_served": (C.c_int, [C.POINTER(GaugePlan), _I32]),
+    "l2hmc_gauge_hmc_run_exchange_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64, _I32]),
+    "l2hmc_gauge_hmc_run_exchange": (C.c_int, [C.POINTER(GaugePlan), _P, _I64, _I64, _P, _P, _P, _I64, _U64, _U64, _I32,
+                                               _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               _SZ, _P]),
     "l2hmc_gauge_replica_swap": (C.c_int, [_I32, _I32, _P, _I64, _I32, _I32, _P, _I64, _U64, _U64, _P, _P, _P, _P, _P]),
     "l2hmc_gauge_loss_terms": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P]),
     "l2hmc_gauge_train_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64]),
@@ -269,6 +274,18 @@ def run_draw_index(draws, n_steps):
     what `n_steps` calls of step_draw_index hand out.  Returns (draw0, new_draws)."""
     d, _ = step_draw_index(draws)
     return d, 2 * (d + int(n_steps) - 1) + 2
+
+
+def exchange_run_draw_index(draws, n_steps, swap_every, swap_phase):
+    """The draws of `n_steps` native steps with the replica-exchange rounds between them in ONE launch
+    (l2hmc_gauge_hmc_run_exchange): what the loop `step_draw_index` per step, `draws += 1` per round hands out, a round
+    following step s (from 0) iff (swap_phase + s + 1) % swap_every == 0.  A step at draw index d leaves the counter at
+    2 d + 2 and a round after it at 2 d + 3, so a step after a round has index d + 2.  Returns (draw0, rounds of the
+    launch, new_draws)."""
+    n, k, ph = int(n_steps), int(swap_every), int(swap_phase)
+    d0, _ = step_draw_index(draws)
+    d_last = d0 + n - 1 + (ph + n - 1) // k                 # the rounds ahead of the last step
+    return d0, (ph + n) // k, 2 * d_last + (3 if (ph + n) % k == 0 else 2)
 
 
 def as_dev(a, device=None, dtype=torch.float32):

@@ -2,7 +2,8 @@
 // (l2hmc_gauge_mcmc_step, l2hmc_gauge_transition_draw) or a whole trajectory / single leapfrog step
 // (l2hmc_gauge_trajectory, l2hmc_gauge_leapfrog) of plans with hmc = 1 (gauge_dynamics.py:102-108: S = T = Q = 0), and
 // a whole RUN of MCMC steps in one launch (l2hmc_gauge_hmc_run: hmc_run_kernel loops over the one copy of the step;
-// l2hmc_gauge_hmc_run_ladder: the same run with beta and the step size per chain).
+// l2hmc_gauge_hmc_run_ladder: the same run with beta and the step size per chain; l2hmc_gauge_hmc_run_exchange: the
+// ladder run with the replica-exchange rounds inside the launch, hmc_run_exchange_kernel, a workgroup per replica group).
 //
 // Without networks a leapfrog step is a few flops and ONE sin per plaquette, so the kernel is transcendental- and
 // latency-bound and its mapping is chosen for waves in flight, not for the matrix pipe:
@@ -27,7 +28,7 @@
 // butterfly adds the threads of a wave, waves are added in ascending order.
 #include <type_traits>
 
-#include "fused_step.h"
+#include "gauge_swap.h"
 
 namespace l2hmc {
 
@@ -312,10 +313,13 @@ __device__ __forceinline__ void hmc_load_x(const FusedArgs& p, const HmcLanes<SP
 // threads of the chains' primary rows (r < w.cpw): x0 / x1 = the wrapped output, the very fp32 values that go to
 // p.step_x_next; the other rows' x0 / x1 are left over from their trajectory.  Every per-step pointer of p (step_px
 // ... step_dq, step_x_next, step_xprop / _vprop / _xout, step_sums, step_part) is that of THIS step.  p.x0 is not read.
+// ngrp, npart: the workgroup fills ngrp slots of the step's npart partial sums (fused_step.h: step_sums), one per
+// w.cpw / ngrp of its chains: 1 and the grid size everywhere but in hmc_run_exchange_kernel, whose workgroup holds the
+// chains of ngrp workgroups of the ladder run and leaves the partial sums those would.
 template <int SPT, class BE>
 __device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>& g, const StepWg& w, const BE be,
                                          const int k, const int64_t grow, const bool live, float (&x0)[SPT],
-                                         float (&x1)[SPT]) {
+                                         float (&x1)[SPT], const int ngrp, const int npart) {
   const int sites = g.sites, D = g.D, tpc = g.tpc, r = g.r, fl = g.fl, tid = w.tid, tsh = g.tsh;
   float* xs = g.xs;
   float* vs = g.vs;
@@ -488,7 +492,7 @@ __device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>
       }
     }
   }
-  step_sums<kHmcMaxThreads, 256>(p, w, 1, (int64_t)blockIdx.x, (int)gridDim.x, (int)gridDim.x, g.fin);
+  step_sums<kHmcMaxThreads, 256>(p, w, ngrp, (int64_t)blockIdx.x * ngrp, npart, (int)gridDim.x, g.fin);
 }
 
 template <int SPT>
@@ -503,7 +507,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
     bool live;
     hmc_step_row<SPT>(p, g, w, k, grow, live);
     hmc_load_x<SPT>(p, g, grow, live, x0, x1);
-    hmc_step<SPT>(p, g, w, HmcRowValues{p.beta, p.eps}, k, grow, live, x0, x1);
+    hmc_step<SPT>(p, g, w, HmcRowValues{p.beta, p.eps}, k, grow, live, x0, x1, 1, (int)gridDim.x);
     return;
   }
   // ---- trajectory mode: x, v, sumlogdet (exactly 0), p of the live rows ----
@@ -642,12 +646,12 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(
           rb[0] = beta;
           rb[1] = eps;
         }
-        hmc_step<SPT>(q, gs, ws, HmcRowLds{rb}, k + z, c, live, x0, x1);
+        hmc_step<SPT>(q, gs, ws, HmcRowLds{rb}, k + z, c, live, x0, x1, 1, (int)gridDim.x);
       } else {
-        hmc_step<SPT>(q, gs, ws, HmcRowValues{beta, eps}, k + z, c, live, x0, x1);
+        hmc_step<SPT>(q, gs, ws, HmcRowValues{beta, eps}, k + z, c, live, x0, x1, 1, (int)gridDim.x);
       }
     } else {
-      hmc_step<SPT>(q, gs, ws, HmcRowValues{q.beta, q.eps}, k + z, grow + z, live, x0, x1);
+      hmc_step<SPT>(q, gs, ws, HmcRowValues{q.beta, q.eps}, k + z, grow + z, live, x0, x1, 1, (int)gridDim.x);
     }
     if (w.paired) {
       // the chain's new state is in its forward row's registers: hand it to the backward row through that row's
@@ -806,5 +810,309 @@ int launch_hmc_run_ladder(const l2hmc_gauge_plan* p, const float* betas, int64_t
   r.step_stride = step_stride; r.chain_stride = chain_stride; r.eps_chain = eps_chain;
   return launch_hmc(a, g, nwg, stream, nullptr, &r);
 }
+
+// ---- the ladder run with the replica-exchange rounds INSIDE the launch (l2hmc_gauge_hmc_run_exchange) ----
+// A round is the one stage in which chains meet.  hmc_run_kernel's workgroups are sized by the lattice, so a pair of
+// rungs may sit in two of them and a round between its steps would need a grid-wide wait.  This instance sizes the
+// workgroup by the REPLICA GROUP instead: cpw = lcm(group, cpw0) chains (cpw0: the chains of a ladder-run workgroup),
+// i.e. a whole number of groups and a whole number of the ladder run's workgroups, with the same row layout (forward
+// rows [0, cpw), backward rows [cpw, 2 cpw)).  Every pair then sits in ONE workgroup and meets at __syncthreads():
+// nothing crosses workgroups, nobody spins, no co-residency is assumed.  A (lattice, group) whose workgroup would exceed
+// 1024 threads is not served (hmc_exchange_geom); l2hmc_gauge_replica_swap between launches takes it.
+//   * The step is hmc_step, the one copy; the workgroup leaves the partial sums of the ngrp = cpw / cpw0 ladder-run
+//     workgroups it stands for, so step_sums come out bit for bit.
+//   * The round (after step s iff (swap_phase + s + 1) % swap_every == 0) acts on the wrapped state in the primary
+//     rows' registers at the betas step s ran with: the rows publish x to their LDS planes, form S in the order of
+//     replica_swap_kernel (gauge_swap.h), decide with gauge_swap.h's rule, and on accept the two chains' threads take
+//     each other's x from the planes.  Labels travel in a register per chain thread and through LDS.
+//   * Every barrier of the round is reached by every thread of the workgroup: backward rows, dead rows, lanes beyond
+//     the lattice and chains that sit a round out go through them; the round's only conditions around a barrier are
+//     uniform over the grid (the round's schedule, tsh).
+//   * Streams: a step at draw index d takes 2 d and 2 d + 1, a round after it 2 d + 2, and the next step is d + 2
+//     (2 d + 3 is skipped) -- the loop `run_hmc(k)`, `swap_replicas` on one counter.  A pairless round (group 2 at parity
+//     1) takes its stream too.  PRECONDITION (host): step_draw + n_steps + rounds <= 2^63, HmcRunArgs' bit-63 rule.
+//   * Registers (hipcc of ROCm 7.2.0 at -O3, profiles/hmc_run_exchange.txt): 99 / 118 VGPRs at SPT 1 / 2, no scratch,
+//     under the 128 that sixteen waves per CU leave.  SPT 4 (513 .. 1024 sites) takes 128 VGPRs AND scratch -- its
+//     ladder form already sits at 126 --, so it is not shipped: those lattices are not served.  To read its resources,
+//     compile this file with -DL2HMC_HMC_EXCHANGE_SPT4 (an explicit instantiation at the end of the file, nothing else).
+constexpr int kHmcExchangeThreads = 1024;
+constexpr int kHmcExchangeSpt = 2;        // the largest SPT with an instance that is launched
+
+struct HmcExchangeArgs : HmcLadderArgs {
+  int group, swap_every, swap_phase, first_parity;
+  int ngrp, npart;                       // step_sums: slots per workgroup, and the ladder run's grid size
+  int32_t* replica;                      // [B] labels, read on entry and written on exit, or NULL (labels start as the column)
+  float* swap_p;                         // [rounds][B] or NULL
+  uint8_t* swapped;                      // [rounds][B] or NULL
+  int32_t* replica_hist;                 // [rounds][B] or NULL
+};
+
+template <int SPT>
+__global__ __launch_bounds__(kHmcExchangeThreads) void hmc_run_exchange_kernel(const FusedArgs p,
+                                                                               const HmcExchangeArgs ra,
+                                                                               const int tsh) {
+  extern __shared__ float lds[];
+  const HmcLanes<SPT> g = hmc_lanes<SPT>(p, tsh, lds, (int)threadIdx.x);
+  const StepWg w = hmc_workgroup<SPT>(p, g);
+  int k;
+  int64_t grow;
+  bool live;
+  hmc_step_row<SPT>(p, g, w, k, grow, live);
+  float x0[SPT], x1[SPT];
+  hmc_load_x<SPT>(p, g, grow, live, x0, x1);
+  const bool primary = g.r < w.cpw;
+  float* sS = g.fin + 2 * 256;                                       // [R] S of the workgroup's chains
+  int32_t* sLab = reinterpret_cast<int32_t*>(sS + g.R);              // [R] their labels
+  int32_t label = primary && live ? (ra.replica ? ra.replica[grow] : (int32_t)grow) : 0;
+  FusedArgs q = p;
+  q.step_xprop = q.step_vprop = q.step_xout = nullptr;
+  q.step_sums_acc = 0;
+  unsigned long long draw = p.step_draw;
+  int jr = 0;                                                        // rounds of this launch so far
+  for (int s = 0; s < ra.n_steps; ++s) {
+    q.step_draw = draw;
+    q.step_x_next = ra.samples ? ra.samples + s * ra.sample_stride : nullptr;
+    q.step_px = p.step_px ? p.step_px + s * ra.hist_stride : nullptr;
+    q.step_act = p.step_act ? p.step_act + s * ra.hist_stride : nullptr;
+    q.step_plq = p.step_plq ? p.step_plq + s * ra.hist_stride : nullptr;
+    q.step_chg = p.step_chg ? p.step_chg + s * ra.hist_stride : nullptr;
+    q.step_dq = p.step_dq ? p.step_dq + s * ra.hist_stride : nullptr;
+    q.step_sums = p.step_sums ? p.step_sums + 4 * (int64_t)s : nullptr;
+    q.step_part = p.step_part ? p.step_part + s * ra.part_stride : nullptr;
+    // z is 0: the addresses of the step are formed where they are used (hmc_run_kernel's step loop)
+    const int z = (int)(q.step_draw >> 63);
+    HmcLanes<SPT> gs = g;
+    gs.fl = g.fl + z;
+    gs.r = g.r + z;
+    gs.xrow = g.xs + gs.r * g.D;
+    gs.sprow = g.sp + gs.r * g.sites;
+    StepWg ws = w;
+    ws.tid = w.tid + z;
+    const int kz = k + z;
+    const int64_t c = grow + z;
+    const float* bs = ra.betas + s * ra.step_stride;
+    {
+      // the pair of the row's chain, as the ladder run reads it; a dead row (x = v = 0) reads neither array
+      const float beta = live ? bs[c * ra.chain_stride] : 0.f;
+      const float eps = live && ra.eps_chain ? ra.eps_chain[c] : p.eps;
+      hmc_step<SPT>(q, gs, ws, HmcRowValues{beta, eps}, kz, c, live, x0, x1, ra.ngrp, ra.npart);
+    }
+    const bool round = (ra.swap_phase + s + 1) % ra.swap_every == 0;  // uniform over the grid
+    if (round) {
+      const int parity = (ra.first_parity + jr) & 1;
+      // the primary rows' planes are free: the step's last reads of them lie behind its last barrier
+      if (primary) {
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+          if (gs.ok[j]) {
+            gs.xrow[gs.fl + j * gs.tpc] = x0[j];
+            gs.xrow[gs.sites + gs.fl + j * gs.tpc] = x1[j];
+          }
+        if (gs.fl == 0) sLab[kz] = label;
+      }
+      __syncthreads();
+      // S of the row: the thread's plaquettes in ascending order, wave_sum, the waves in ascending order
+      float a = 0.f;
+      if (primary) {
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+          if (gs.ok[j]) a += gauge_swap_term(x0[j], x1[j], gs.xrow[gs.nr[j]], gs.xrow[gs.sites + gs.nu[j]]);
+      }
+      if (tsh < 6) {
+        a = gauge_swap_subwave_sum(a, tsh);
+      } else {
+        a = wave_sum(a);
+        if (tsh > 6) {
+          if ((gs.fl & (kWave - 1)) == 0) gs.red[(gs.r * 4 + (gs.fl >> 6)) * 2] = a;
+          __syncthreads();
+          a = gauge_swap_add_waves(gs.red + gs.r * 8, 2, 0, 1 << (tsh - 6));
+        }
+      }
+      if (primary && gs.fl == 0) sS[kz] = a;
+      __syncthreads();
+      // cbase is a multiple of cpw and cpw of the group: the slot gives the rung, and a pair has both chains here and,
+      // as B is a multiple of the group, both live or both dead
+      const int jg = kz % ra.group;
+      const bool lower = gauge_swap_lower(jg, ra.group, parity), upper = gauge_swap_upper(jg, parity);
+      if (primary && live) {
+        bool acc = false;
+        float pp = 0.f;
+        if (lower || upper) {
+          const int ka = upper ? kz - 1 : kz;                         // the pair's lower chain
+          const int64_t ca = w.cbase + ka;
+          acc = gauge_swap_decide(bs[ca * ra.chain_stride], bs[(ca + 1) * ra.chain_stride], sS[ka], sS[ka + 1],
+                                  p.step_seed, (uint64_t)(p.step_chain0 + ca), 2 * draw + 2, &pp);
+        }
+        if (acc) {
+          const int ko = upper ? kz - 1 : kz + 1;
+          const float* xo = gs.xs + ko * gs.D;
+#pragma unroll
+          for (int j = 0; j < SPT; ++j)
+            if (gs.ok[j]) {
+              x0[j] = xo[gs.fl + j * gs.tpc];
+              x1[j] = xo[gs.sites + gs.fl + j * gs.tpc];
+            }
+          label = sLab[ko];
+        }
+        if (gs.fl == 0) {
+          const int64_t row = (int64_t)jr * p.step_B;
+          gauge_swap_outputs(ra.swap_p ? ra.swap_p + row : nullptr, ra.swapped ? ra.swapped + row : nullptr, c, lower,
+                             pp, acc);
+          if (ra.replica_hist) ra.replica_hist[row + c] = label;
+        }
+      }
+      ++jr;
+      // the next write to a primary row's planes, sS or sLab lies behind the barrier below (paired layout) or behind
+      // the next step's first barrier
+    }
+    draw += round ? 2ull : 1ull;
+    if (w.paired) {
+      if (primary) {
+        float* xb = gs.xs + (kz + w.cpw) * gs.D;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+          if (gs.ok[j]) {
+            xb[gs.fl + j * gs.tpc] = x0[j];
+            xb[gs.sites + gs.fl + j * gs.tpc] = x1[j];
+          }
+      }
+      __syncthreads();
+      if (!primary) {
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+          x0[j] = x1[j] = 0.f;
+          if (gs.ok[j]) {
+            x0[j] = gs.xrow[gs.fl + j * gs.tpc];
+            x1[j] = gs.xrow[gs.sites + gs.fl + j * gs.tpc];
+          }
+        }
+      }
+    }
+  }
+  if (primary && live) {
+    if (p.step_x_next) {
+#pragma unroll
+      for (int j = 0; j < SPT; ++j)
+        if (g.ok[j]) {
+          float* xn = p.step_x_next + grow * g.D + 2 * (g.fl + j * g.tpc);
+          xn[0] = x0[j];
+          xn[1] = x1[j];
+        }
+    }
+    if (ra.replica && g.fl == 0) ra.replica[grow] = label;
+  }
+}
+
+struct HmcExchangeGeom {
+  HmcGeom g;
+  int cpw0, cpw, threads;                // chains of a ladder-run workgroup, of this one, and its size
+  size_t lds;
+};
+
+// what a launch gets of dynamic LDS without an opt-in: a shape that needs more is not served (none does but a one-site
+// lattice with 768 rows or more per workgroup), so the launch needs no function attribute
+constexpr size_t kHmcExchangeLds = 64 * 1024;
+
+// The workgroup of the exchange run for (lattice, both, group), or false with `why` worded: the served rule.
+static bool hmc_exchange_geom(int T, int X, int both, int group, HmcExchangeGeom* e, char* why, size_t nwhy) {
+  if (T <= 0 || X <= 0) {
+    snprintf(why, nwhy, "bad lattice T=%d X=%d", T, X);
+    return false;
+  }
+  if (!hmc_geom(T, X, &e->g)) {
+    snprintf(why, nwhy, "the %dx%d lattice has no one-launch kernel (more than %d sites)", T, X, kHmcMaxSites);
+    return false;
+  }
+  const int rpc = both ? 2 : 1, tpc = 1 << e->g.tsh;
+  e->cpw0 = e->g.rows_wg / rpc;
+  int64_t a = group, b = e->cpw0;
+  while (b) {
+    const int64_t t = a % b;
+    a = b;
+    b = t;
+  }
+  const int64_t cpw = (int64_t)group / a * e->cpw0;                  // lcm(group, cpw0)
+  if (cpw * rpc * tpc > kHmcExchangeThreads) {
+    snprintf(why, nwhy, "a %dx%d lattice takes %d threads per row and %d row(s) per chain, and a workgroup that holds "
+             "whole groups of %d rungs and whole ladder-run workgroups of %d chains has lcm = %lld chains: %lld threads, "
+             "more than %d", T, X, tpc, rpc, group, e->cpw0, (long long)cpw, (long long)(cpw * rpc * tpc),
+             kHmcExchangeThreads);
+    return false;
+  }
+  if (e->g.spt > kHmcExchangeSpt) {
+    snprintf(why, nwhy, "the %dx%d lattice takes %d sites per thread, and that instance of the exchange run does not "
+             "fit 128 registers without scratch", T, X, e->g.spt);
+    return false;
+  }
+  e->cpw = (int)cpw;
+  e->threads = e->cpw * rpc * tpc;
+  const int R = e->cpw * rpc;
+  // hmc_geom's carve-up for R rows, and sS, sLab [R] behind the sum tree
+  e->lds = sizeof(float) * ((size_t)R * (5 * (size_t)T * X + 8 + 8 + 2) + 2 * 256);
+  if (e->lds > kHmcExchangeLds) {
+    snprintf(why, nwhy, "the %d rows of a %dx%d lattice that such a workgroup holds take %zu B of LDS, more than the %zu "
+             "a launch gets", R, T, X, e->lds, kHmcExchangeLds);
+    return false;
+  }
+  return true;
+}
+
+int hmc_exchange_served(const l2hmc_gauge_plan* p, int group, char* why, size_t nwhy) {
+  HmcExchangeGeom e;
+  if (!p->hmc || p->num_steps <= 0) {
+    snprintf(why, nwhy, "plan.hmc = 0 (a run is steps of plain HMC)");
+    return 0;
+  }
+  if (p->flags & L2HMC_PLAN_LAYERED) {
+    snprintf(why, nwhy, "the plan is L2HMC_PLAN_LAYERED: it has no one-launch kernel");
+    return 0;
+  }
+  if (group < 2) {
+    snprintf(why, nwhy, "group = %d: a replica group has 2 rungs or more", group);
+    return 0;
+  }
+  return hmc_exchange_geom(p->T, p->X, (p->flags & L2HMC_PLAN_SELECTED_ONLY) ? 0 : 1, group, &e, why, nwhy) ? 1 : 0;
+}
+
+int launch_hmc_run_exchange(const l2hmc_gauge_plan* p, const float* betas, int64_t step_stride, int64_t chain_stride,
+                            const float* eps_chain, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                            uint64_t draw0, int n_steps, int both, int group, int swap_every, int swap_phase,
+                            int first_parity, int32_t* replica, float* px, float* actions, float* plaqs,
+                            float* charges, float* dq, float* step_sums, float* samples, float* swap_p,
+                            uint8_t* swapped, int32_t* replica_hist, float* part, hipStream_t stream) {
+  HmcGeom g;
+  int64_t nwg0;
+  FusedArgs a{};
+  HmcExchangeArgs r{};
+  HmcExchangeGeom e;
+  char why[384];
+  L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0, "hmc run exchange: negative stride");
+  L2HMC_REQUIRE(hmc_exchange_geom(p->T, p->X, both, group, &e, why, sizeof(why)), "hmc run exchange: not served: %s",
+                why);
+  if (int err = hmc_run_args(p, betas, x_in, x_next, B, seed, draw0, n_steps, both, px, actions, plaqs, charges, dq,
+                             step_sums, samples, part, &g, &nwg0, &a, &r))
+    return err;
+  const int64_t nwg = ceil_div(B, e.cpw);
+  L2HMC_REQUIRE(nwg0 < (1ll << 31) && nwg > 0, "hmc run exchange: too many rows");
+  a.rows = nwg * (int64_t)(e.threads >> e.g.tsh);
+  r.step_stride = step_stride; r.chain_stride = chain_stride; r.eps_chain = eps_chain;
+  r.group = group; r.swap_every = swap_every; r.swap_phase = swap_phase; r.first_parity = first_parity;
+  r.ngrp = e.cpw / e.cpw0; r.npart = (int)nwg0;
+  r.replica = replica; r.swap_p = swap_p; r.swapped = swapped; r.replica_hist = replica_hist;
+  prof_before(kProfFused, stream);
+  const dim3 grid((unsigned)nwg), block((unsigned)e.threads);
+  if (e.g.spt == 1)
+    hipLaunchKernelGGL((hmc_run_exchange_kernel<1>), grid, block, e.lds, stream, a, r, e.g.tsh);
+  else
+    hipLaunchKernelGGL((hmc_run_exchange_kernel<2>), grid, block, e.lds, stream, a, r, e.g.tsh);
+  prof_after(kProfFused, stream);
+  L2HMC_CHECK_LAUNCH("hmc_run_exchange");
+  return L2HMC_OK;
+}
+
+#ifdef L2HMC_HMC_EXCHANGE_SPT4
+// diagnostic only: the instance that is not shipped, compiled so that the compiler reports its registers and scratch
+template __global__ void hmc_run_exchange_kernel<4>(const FusedArgs, const HmcExchangeArgs, const int);
+#endif
 
 }  // namespace l2hmc

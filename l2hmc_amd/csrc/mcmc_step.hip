@@ -315,3 +315,65 @@ extern "C" int l2hmc_gauge_hmc_run_ladder(const l2hmc_gauge_plan* plan, const fl
                                selected ? 0 : 1, px, actions, plaqs, charges, charge_diff, step_sums, samples,
                                step_sums ? static_cast<float*>(ws) : nullptr, (hipStream_t)stream);
 }
+
+// ---- the ladder run with the replica-exchange rounds inside the launch (hmc_run_exchange_kernel, hmc_step.hip)
+extern "C" int l2hmc_gauge_hmc_run_exchange_served(const l2hmc_gauge_plan* plan, int32_t group) {
+  if (!plan) {
+    set_error("gauge_hmc_run_exchange_served: plan is NULL");
+    return 0;
+  }
+  char why[384];
+  if (hmc_exchange_served(plan, group, why, sizeof(why))) return 1;
+  set_error("gauge_hmc_run_exchange_served: not served: %s (l2hmc_gauge_replica_swap between launches of "
+            "l2hmc_gauge_hmc_run_ladder takes it)", why);
+  return 0;
+}
+
+extern "C" size_t l2hmc_gauge_hmc_run_exchange_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B, int32_t n_steps) {
+  if (hmc_run_ladder_check("gauge_hmc_run_exchange_ws_bytes", plan, B, n_steps)) return 0;
+  return (size_t)n_steps * hmc_run_part_bytes(B > 0 ? B : 1);
+}
+
+extern "C" int l2hmc_gauge_hmc_run_exchange(const l2hmc_gauge_plan* plan, const float* betas, int64_t step_stride,
+                                            int64_t chain_stride, const float* eps_chain, const float* x_in,
+                                            float* x_next, int64_t B, uint64_t seed, uint64_t draw0, int32_t n_steps,
+                                            int32_t group, int32_t swap_every, int32_t swap_phase,
+                                            int32_t first_parity, int32_t* replica, float* px, float* actions,
+                                            float* plaqs, float* charges, float* charge_diff, float* step_sums,
+                                            float* samples, float* swap_p, uint8_t* swapped, int32_t* replica_hist,
+                                            void* ws, size_t ws_bytes, l2hmc_stream_t stream) {
+  const char* who = "gauge_hmc_run_exchange";
+  if (int e = hmc_run_ladder_check(who, plan, B, n_steps)) return e;
+  L2HMC_REQUIRE(betas != nullptr, "%s: NULL betas (a replica group is a ladder of betas)", who);
+  L2HMC_REQUIRE(step_stride >= 0 && chain_stride >= 0, "%s: negative stride (step_stride=%lld, chain_stride=%lld)", who,
+                (long long)step_stride, (long long)chain_stride);
+  L2HMC_REQUIRE(group >= 2, "%s: group = %d: a replica group has 2 rungs or more", who, group);
+  L2HMC_REQUIRE(B % group == 0, "%s: B = %lld is not a multiple of group = %d", who, (long long)B, group);
+  L2HMC_REQUIRE(swap_every >= 1, "%s: swap_every = %d must be 1 or more", who, swap_every);
+  L2HMC_REQUIRE(swap_phase >= 0 && swap_phase < swap_every, "%s: swap_phase = %d is not in [0, swap_every = %d)", who,
+                swap_phase, swap_every);
+  L2HMC_REQUIRE(first_parity == 0 || first_parity == 1, "%s: first_parity = %d is not 0 or 1", who, first_parity);
+  char why[384];
+  L2HMC_REQUIRE(hmc_exchange_served(plan, group, why, sizeof(why)),
+                "%s: not served: %s (l2hmc_gauge_replica_swap between launches of l2hmc_gauge_hmc_run_ladder takes it)",
+                who, why);
+  // a round after step s iff (swap_phase + s + 1) % swap_every == 0; a step or a round moves the draw index by one,
+  // and the run kernel relies on bit 63 of every draw index being 0 (hmc_step.hip: HmcRunArgs)
+  const uint64_t rounds = ((uint64_t)swap_phase + (uint64_t)n_steps) / (uint64_t)swap_every;
+  L2HMC_REQUIRE(draw0 <= (1ull << 63) - (uint64_t)n_steps - rounds,
+                "%s: draw0 + n_steps + rounds exceeds 2^63 (draw0=%llu, n_steps=%d, rounds=%llu)", who,
+                (unsigned long long)draw0, n_steps, (unsigned long long)rounds);
+  L2HMC_REQUIRE(x_in && x_next, "%s: NULL x_in / x_next", who);
+  L2HMC_REQUIRE(!step_sums || ws, "%s: step_sums needs the workspace", who);
+  if (B == 0) return L2HMC_OK;
+  const size_t need = l2hmc_gauge_hmc_run_exchange_ws_bytes(plan, B, n_steps);
+  if (step_sums && ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    return L2HMC_ERR_WORKSPACE;
+  }
+  const bool selected = (plan->flags & L2HMC_PLAN_SELECTED_ONLY) != 0;
+  return launch_hmc_run_exchange(plan, betas, step_stride, chain_stride, eps_chain, x_in, x_next, B, seed, draw0,
+                                 n_steps, selected ? 0 : 1, group, swap_every, swap_phase, first_parity, replica, px,
+                                 actions, plaqs, charges, charge_diff, step_sums, samples, swap_p, swapped,
+                                 replica_hist, step_sums ? static_cast<float*>(ws) : nullptr, (hipStream_t)stream);
+}

@@ -5,7 +5,8 @@
 //   p = min(1, exp((beta_a - beta_b) (S_a - S_b))),   S = sum_p (1 - cos P_p)      (accept iff p > u, strict: quirk Q5)
 //
 // This is the one stage of a ladder run in which chains meet, so it is a launch of its own: the run kernel's workgroups
-// never wait for each other (hmc_step.hip), and a pair may sit in two of them.
+// never wait for each other (hmc_step.hip), and a pair may sit in two of them.  (Where a whole replica group fits one
+// workgroup of 1024 threads, hmc_run_exchange_kernel runs the same round inside the run launch: gauge_swap.h.)
 //
 // Mapping, chosen for small rows (a pair of 8 x 8 rows is 256 floats): a PAIR is walked by TPP = 64, 128 or 256
 // threads -- one wave up to 64 sites, two up to 128, four beyond -- and a workgroup of 256 threads holds 256 / TPP
@@ -16,13 +17,14 @@
 // but the row (and T, X).  Every thread of the pair then forms p and u itself, and on accept the pair's threads
 // exchange the rows element by element (16 bytes per access where the rows allow it).  The barrier between the sums
 // and the exchange is also what orders every read of a row ahead of every write to it.
-#include "fused_step.h"
+#include "gauge_swap.h"
 
 namespace l2hmc {
 
 constexpr int kSwapThreads = 256;
 
-// p: swap_accept_prob (common.h), shared with the toy targets' round (small_swap.h).
+// S, the decision and the outputs' conventions are gauge_swap.h's, shared with the round inside the run launch
+// (hmc_run_exchange_kernel, hmc_step.hip); p is swap_accept_prob (common.h), shared with the toy targets' round too.
 // npg: pairs of a group in this round (> 0).  tsh: log2(TPP).  vec: rows are 16-byte aligned and D % 4 == 0.
 __global__ __launch_bounds__(kSwapThreads) void replica_swap_kernel(
     float* __restrict__ x, const int T, const int X, const int64_t npairs, const int group, const int parity,
@@ -46,14 +48,8 @@ __global__ __launch_bounds__(kSwapThreads) void replica_swap_kernel(
     for (int s = fl; s < sites; s += tpp) {
       const int i = s / X, jx = s - i * X;
       const int er = 2 * (i * X + (jx + 1 == X ? 0 : jx + 1)), eu = 2 * ((i + 1 == T ? 0 : i + 1) * X + jx) + 1;
-      // gauge_model.py:676-679: x0[i,j] - x1[i,j] - x0[i,j+1] + x1[i+1,j]
-      const float Pa = xa[2 * s] - xa[2 * s + 1] - xa[er] + xa[eu];
-      const float Pb = xb[2 * s] - xb[2 * s + 1] - xb[er] + xb[eu];
-      float sn, cs;
-      fast_sincos(Pa, &sn, &cs);
-      sa += 1.f - cs;
-      fast_sincos(Pb, &sn, &cs);
-      sb += 1.f - cs;
+      sa += gauge_swap_term(xa[2 * s], xa[2 * s + 1], xa[er], xa[eu]);
+      sb += gauge_swap_term(xb[2 * s], xb[2 * s + 1], xb[er], xb[eu]);
     }
   }
   sa = wave_sum(sa);
@@ -65,40 +61,21 @@ __global__ __launch_bounds__(kSwapThreads) void replica_swap_kernel(
   __syncthreads();                       // the sums are published; every plaquette read of the round is behind us
   if (!live) return;
   const int w0 = (slot << tsh) >> 6, nw = tpp >> 6;
-  sa = 0.f;
-  sb = 0.f;
-  for (int w = 0; w < nw; ++w) {
-    sa += red[w0 + w][0];
-    sb += red[w0 + w][1];
-  }
-  const float beta_a = betas[a * chain_stride], beta_b = betas[b * chain_stride];
-  // exp(-beta_b S_a - beta_a S_b) / exp(-beta_a S_a - beta_b S_b)
-  const float p = swap_accept_prob((double)(beta_a - beta_b) * ((double)sa - (double)sb));
-  const float u = philox_u01(seed, (uint64_t)a, stream_index);          // element a of l2hmc_fill_uniform's stream
-  const bool acc = p > u;
+  sa = gauge_swap_add_waves(&red[0][0], 2, w0, nw);
+  sb = gauge_swap_add_waves(&red[0][1], 2, w0, nw);
+  float p;
+  const bool acc = gauge_swap_decide(betas[a * chain_stride], betas[b * chain_stride], sa, sb, seed, (uint64_t)a,
+                                     stream_index, &p);
   if (fl == 0) {
-    const float nan = __int_as_float(0x7fc00000);
     if (action) {
       action[a] = sa;
       action[b] = sb;
     }
-    if (swap_p) {
-      swap_p[a] = p;
-      swap_p[b] = nan;
-    }
-    if (swapped) {
-      swapped[a] = acc ? 1 : 0;
-      swapped[b] = 0;
-    }
+    gauge_swap_outputs(swap_p, swapped, a, true, p, acc);
+    gauge_swap_outputs(swap_p, swapped, b, false, p, acc);
     // the chains of the group that sit the round out: its first at parity 1, its last where one is left over
-    if (q == 0 && parity == 1) {
-      if (swap_p) swap_p[a - 1] = nan;
-      if (swapped) swapped[a - 1] = 0;
-    }
-    if (q == npg - 1 && j + 2 < group) {
-      if (swap_p) swap_p[b + 1] = nan;
-      if (swapped) swapped[b + 1] = 0;
-    }
+    if (q == 0 && parity == 1) gauge_swap_outputs(swap_p, swapped, a - 1, false, p, acc);
+    if (q == npg - 1 && j + 2 < group) gauge_swap_outputs(swap_p, swapped, b + 1, false, p, acc);
     if (acc && replica) {
       const int32_t t = replica[a];
       replica[a] = replica[b];

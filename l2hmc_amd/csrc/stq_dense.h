@@ -179,6 +179,15 @@ int launch_hmc_run_ladder(const l2hmc_gauge_plan* p, const float* betas, int64_t
                           uint64_t draw0, int n_steps, int both, float* px, float* actions, float* plaqs,
                           float* charges, float* dq, float* step_sums, float* samples, float* part,
                           hipStream_t stream);
+// the ladder run with the replica-exchange rounds inside the launch (l2hmc_gauge_hmc_run_exchange); hmc_exchange_served:
+// 1, or 0 with the rule that fails worded in `why` (host logic only)
+int hmc_exchange_served(const l2hmc_gauge_plan* p, int group, char* why, size_t nwhy);
+int launch_hmc_run_exchange(const l2hmc_gauge_plan* p, const float* betas, int64_t step_stride, int64_t chain_stride,
+                            const float* eps_chain, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                            uint64_t draw0, int n_steps, int both, int group, int swap_every, int swap_phase,
+                            int first_parity, int32_t* replica, float* px, float* actions, float* plaqs,
+                            float* charges, float* dq, float* step_sums, float* samples, float* swap_p,
+                            uint8_t* swapped, int32_t* replica_hist, float* part, hipStream_t stream);
 // bytes of launch_fused_step's `hand` workspace for B chains (the hand-off of the split 16-row form)
 size_t fused_step_hand_bytes(int64_t B, int D);
 // whole-trajectory reverse pass (fused_train.hip); deltas_*: {dout, d2, d1} tapes, coef_parts: {dcs_x, dcq_x, dcs_v, dcq_v}

@@ -33,6 +33,9 @@ class GaugeSampler:
         # int32 [B] on the device, or None: the label of the configuration that sits in every column.  Every
         # replica-exchange round (`swap_replicas`) exchanges it with the rows; `run_hmc_exchange` starts it anew
         self.replica = None
+        # `run_hmc_exchange`: False = one launch per round between the launches of the run (every lattice and group);
+        # True = the rounds inside the run's launches (l2hmc_gauge_hmc_run_exchange), where `exchange_in_launch` says so
+        self.in_launch = False
 
     def update_beta(self, step):
         """gauge_model.py:1039-1046: linear annealing of 1/beta."""
@@ -149,11 +152,14 @@ class GaugeSampler:
 
     HISTORIES = ("px", "actions", "plaqs", "charges", "charge_diff")
 
-    def _run_chunks(self, run_steps, x, keep_samples, plan, entry, front, cut_every=None, after=None):
+    def _run_chunks(self, run_steps, x, keep_samples, plan, entry, front, cut_every=None, after=None, rounds=None):
         """Plain-HMC steps through `_runs.run_chunks` (`cut_every`, `after`: see there), ONE launch of `entry` per
         chunk: l2hmc_gauge_hmc_run or l2hmc_gauge_hmc_run_ladder; `front(s0)` is what it takes between the plan and x_in
         for a chunk from step s0 on.  Histories, `_run_sums`, workspace: once per run.  `run`'s dictionary less
-        `plaq_exact`."""
+        `plaq_exact`.  `rounds` = (G, k, parity0, swap_p, swapped, replica_hist): the entry is
+        l2hmc_gauge_hmc_run_exchange, whose chunks are not cut at the rounds -- a round follows every k-th step of the
+        run inside the launch, the chunk from step s0 on starts at phase s0 % k and fills the round histories
+        ([run_steps // k, B] device tensors) from row s0 // k on; the labels are `self.replica`."""
         dyn = self.dynamics
         B, dev = x.shape[0], x.device
         hist = {k: torch.empty(run_steps, B, dtype=torch.float32, device=dev) for k in self.HISTORIES}
@@ -167,9 +173,16 @@ class GaugeSampler:
             # the draw index comes from the dynamics' counter as it stands when the chunk is launched: consecutive from
             # chunk to chunk unless `after` took a stream in between (then the next even-aligned pair).  The counter
             # moves only after the entry returned: a failed launch leaves it where it was
-            draw, draws_after = _lib.run_draw_index(dyn._draws, n)
-            _lib.call(entry, C.byref(plan), *front(s0), x_in, x_next, B, dyn._seed, draw, n,
-                      *(hist[k][s0:] for k in self.HISTORIES), sums[s0:], samples_dev, ws, nb, device=dyn._device)
+            if rounds is None:
+                (draw, draws_after), mid, tail = _lib.run_draw_index(dyn._draws, n), (), ()
+            else:
+                G, k, parity0, *round_hist = rounds
+                draw, _, draws_after = _lib.exchange_run_draw_index(dyn._draws, n, k, s0 % k)
+                mid = (G, k, s0 % k, (parity0 + s0 // k) % 2, self.replica)
+                tail = tuple(h[s0 // k:] for h in round_hist)
+            _lib.call(entry, C.byref(plan), *front(s0), x_in, x_next, B, dyn._seed, draw, n, *mid,
+                      *(hist[k][s0:] for k in self.HISTORIES), sums[s0:], samples_dev, *tail, ws, nb,
+                      device=dyn._device)
             dyn._draws = draws_after
             for i in range(s0, s0 + n):
                 self.stats.push_sums(sums[i, :3])
@@ -215,9 +228,10 @@ class GaugeSampler:
         betas = self._ladder_betas(beta, run_steps, x.shape[0])
         return run_steps, x, betas, None if eps is None else _runs.step_sizes(eps, x.shape[0])
 
-    def _ladder_run(self, run_steps, x, betas, step, keep_samples, exchange=None):
+    def _ladder_run(self, run_steps, x, betas, step, keep_samples, exchange=None, in_launch=False):
         """What `run_hmc` means, on checked arguments.  `exchange(beta_dev)`, called once when a run of 1 step or more
-        is about to start (its betas are on the device), returns the `cut_every` and `after` of `_run_chunks`."""
+        is about to start (its betas are on the device), returns the `cut_every` and `after` of `_run_chunks`, or with
+        `in_launch` its `rounds`."""
         b64, b32, step_stride, chain_stride = betas
         if run_steps == 0:
             out = _runs.empty_run(self.HISTORIES, x, keep_samples)
@@ -229,9 +243,13 @@ class GaugeSampler:
                     "run_hmc: this hmc dynamics has no one-launch kernel (more than 1024 sites, or fused = False): "
                     "`run` takes it through the loop over `step`, one beta at a time")
             beta_dev = _lib.as_dev(b32, x.device)          # goes over once; every chunk starts at its own row
-            out = self._run_chunks(run_steps, x, keep_samples, plan, "l2hmc_gauge_hmc_run_ladder",
-                                   lambda s0: (beta_dev[s0 * step_stride:], step_stride, chain_stride, eps_chain),
-                                   *(exchange(beta_dev) if exchange else ()))
+            front = lambda s0: (beta_dev[s0 * step_stride:], step_stride, chain_stride, eps_chain)
+            if in_launch:
+                out = self._run_chunks(run_steps, x, keep_samples, plan, "l2hmc_gauge_hmc_run_exchange", front,
+                                       rounds=exchange(beta_dev))
+            else:
+                out = self._run_chunks(run_steps, x, keep_samples, plan, "l2hmc_gauge_hmc_run_ladder", front,
+                                       *(exchange(beta_dev) if exchange else ()))
         # the last step's beta (an empty run with an empty schedule has none)
         last = b64 if b64.ndim == 0 else b64[-1] if b64.shape[0] else np.full(b64.shape[1:], np.nan)
         out["plaq_exact"] = u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
@@ -270,6 +288,17 @@ class GaugeSampler:
     def _check_replicas(replicas, B, swap_every=1, first_parity=0, parity=0, who="run_hmc_exchange"):
         return _runs.check_replicas(replicas, B, swap_every, first_parity, parity, who)
 
+    def exchange_in_launch(self, replicas):
+        """Whether `run_hmc_exchange(..., replicas=replicas)` with `self.in_launch = True` is served for this dynamics
+        (l2hmc_gauge_hmc_run_exchange_served): a workgroup of at most 1024 threads has to hold whole groups."""
+        try:
+            G = int(replicas)
+        except (TypeError, ValueError):
+            return False
+        if G != replicas or not self.dynamics.hmc:
+            return False
+        return _lib.lib().l2hmc_gauge_hmc_run_exchange_served(C.byref(self.dynamics._plan()), G) == 1
+
     def run_hmc_exchange(self, run_steps, beta, x=None, eps=None, keep_samples=False, replicas=None, swap_every=1,
                          first_parity=0, replica0=None):
         """`run_hmc` with replica exchange (parallel tempering) between the columns of a ladder.  `replicas=None`:
@@ -288,6 +317,12 @@ class GaugeSampler:
                                     with first_parity = (first_parity + n_r) % 2 of that call)
           swap_rate [G - 1]         the mean of `swapped` over rounds and groups for each neighbouring pair of rungs (a
                                     pair is proposed in every other round)
+        With `self.in_launch = True` (an attribute of the sampler, like `steps_per_launch`; the signature is what it was)
+        the rounds run INSIDE the launches of the run (l2hmc_gauge_hmc_run_exchange) -- chunks of
+        `steps_per_launch` steps that are not cut at the rounds, no launch per round, the same dictionary and the same
+        `self.replica`, bit for bit.  Served where a workgroup of at most 1024 threads holds whole groups
+        (`exchange_in_launch(replicas)`: e.g. up to 8 rungs at 8x8, 2 at 16x16, none at 32x32); NotImplementedError
+        elsewhere.  The default stays the round between launches, which serves every lattice and group.
         Nothing is exchanged between ranks: a group lives on one rank.  ValueError, on top of `run_hmc`'s, for
         replicas < 2, a batch that is no multiple of it, swap_every < 1, first_parity not 0 or 1, and a replica0 that
         is not int32 [B]."""
@@ -297,6 +332,8 @@ class GaugeSampler:
         B = x.shape[0]
         G, k, parity0, _ = self._check_replicas(replicas, B, swap_every, first_parity)
         labels = _runs.replica_labels(replica0, B)
+        if self.in_launch:
+            return self._exchange_in_launch(run_steps, x, betas, step, keep_samples, G, k, parity0, labels)
         # the exchange layer over `_ladder_run`: chunks cut at the multiples of k steps, one round after each of them
         step_stride, chain_stride = betas[2:]
         rounds = {"swap_p": [], "swapped": [], "replica": []}
@@ -317,6 +354,26 @@ class GaugeSampler:
 
         out = self._ladder_run(run_steps, x, betas, step, keep_samples, exchange)
         return _runs.exchange_histories(out, rounds, B, G)
+
+    def _exchange_in_launch(self, run_steps, x, betas, step, keep_samples, G, k, parity0, labels):
+        """`run_hmc_exchange` with the rounds inside the run's launches, on checked arguments."""
+        L, B, dev = _lib.lib(), x.shape[0], x.device
+        if L.l2hmc_gauge_hmc_run_exchange_served(C.byref(self.dynamics._plan()), G) != 1:
+            raise NotImplementedError(
+                "run_hmc_exchange with in_launch = True: " + L.l2hmc_last_error().decode() + ".  The rule: lcm(replicas, "
+                "chains per workgroup of the ladder run) x rows per chain x threads per row must not exceed 1024, on a "
+                "lattice of at most 512 sites whose plan has the one-launch kernel (`exchange_in_launch(replicas)`); "
+                "in_launch = False takes every lattice and group")
+        n_r = run_steps // k
+        hist = (torch.empty(n_r, B, dtype=torch.float32, device=dev), torch.empty(n_r, B, dtype=torch.uint8, device=dev),
+                torch.empty(n_r, B, dtype=torch.int32, device=dev))
+
+        def exchange(beta_dev):
+            self.replica = _lib.as_dev(labels, dev, torch.int32)     # stays on the device from chunk to chunk
+            return (G, k, parity0, *hist)
+
+        out = self._ladder_run(run_steps, x, betas, step, keep_samples, exchange, in_launch=True)
+        return _runs.exchange_histories(out, dict(zip(("swap_p", "swapped", "replica"), hist)), B, G)
 
     @staticmethod
     def run_dicts(out, beta):

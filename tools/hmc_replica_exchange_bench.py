@@ -8,7 +8,12 @@ method of tools/hmc_run_ladder_bench.py, 8 rungs (chain c at betas[c % 8], beta 
                     parity between two synchronisations) and the kernel alone (l2hmc_profile class 8).
     python tools/hmc_replica_exchange_bench.py > table.txt
     python tools/hmc_replica_exchange_bench.py --stats      (the sampling figures below instead of the timings)
-profiles/hmc_replica_exchange.txt is made of both, and of (a) on the parent commit.
+    python tools/hmc_replica_exchange_bench.py --in-launch      (the rounds inside the run's launches)
+profiles/hmc_replica_exchange.txt is made of all three, and of (a) on the parent commit.
+
+--in-launch times, per row and swap_every, the round between launches (b) next to the round inside the launch
+(`run_hmc_exchange` on a sampler with `in_launch = True`, l2hmc_gauge_hmc_run_exchange), alternating with (a), at 8x8 with 8 rungs and
+at 16x16 with 2 (the most that shape is served with); a fifth field of --shape is the row's number of rungs.
 
 A window is `steps` MCMC steps between two device synchronisations on the host clock, `steps` a multiple of 256 chosen
 per row so that a window of (a) lasts about `--window` seconds, after a warm-up window of the same length; the variants
@@ -34,7 +39,8 @@ ap.add_argument("--label", default="this tree")
 ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                 help="root of the (built) tree whose l2hmc_amd is measured")
 ap.add_argument("--plain-only", action="store_true")
-ap.add_argument("--shape", action="append", metavar="T,X,CHAINS,LF",
+ap.add_argument("--in-launch", action="store_true", help="(b) between launches against the rounds in the launch")
+ap.add_argument("--shape", action="append", metavar="T,X,CHAINS,LF[,RUNGS]",
                 help="time this row instead of the two of profiles/hmc_run.txt (may be given more than once)")
 ap.add_argument("--rounds", type=int, default=2000, help="calls of swap_replicas per window of (c)")
 ap.add_argument("--stats", action="store_true")
@@ -49,10 +55,13 @@ import torch  # noqa: E402
 sys.path.insert(0, ROOT)
 from l2hmc_amd import GaugeDynamics, GaugeLattice, GaugeSampler, _lib, stats  # noqa: E402
 
+RUNGS, EPS = 8, 0.1
 SHAPES = [(8, 8, 2048, 10), (32, 32, 2048, 25)]          # T, X, chains, LF steps: rows of profiles/hmc_run.txt
+if args.in_launch:
+    SHAPES = [(8, 8, 2048, 10, 8), (16, 16, 2048, 15, 2)]
 if args.shape:
     SHAPES = [tuple(int(v) for v in s.split(",")) for s in args.shape]
-RUNGS, EPS = 8, 0.1
+SHAPES = [(s + (RUNGS,))[:5] for s in SHAPES]            # the rungs of a row: 8 unless it says otherwise
 BETAS = np.linspace(1.0, 4.5, RUNGS)
 SWAP_EVERY = (1, 4, 16)
 
@@ -67,10 +76,13 @@ def sampler(T, X, B, N, both, seed=None):
 class Run:
     """`run_hmc` of the ladder (swap_every None) or `run_hmc_exchange` with a round every `swap_every` steps"""
 
-    def __init__(self, T, X, B, N, both, swap_every=None):
+    def __init__(self, T, X, B, N, both, swap_every=None, rungs=RUNGS, in_launch=False):
         self.smp, _ = sampler(T, X, B, N, both)
         self.x = torch.rand(B, 2 * T * X, device="cuda") * (2 * np.pi)
-        self.beta, self.k, self.done = BETAS[np.arange(B) % RUNGS][None, :], swap_every, 0
+        self.beta = np.linspace(BETAS[0], BETAS[-1], rungs)[np.arange(B) % rungs][None, :]
+        self.k, self.done, self.rungs = swap_every, 0, rungs
+        if in_launch:                                                # (set only where asked for: other trees have none)
+            self.smp.in_launch = True
 
     def window(self, steps):
         torch.cuda.synchronize()
@@ -78,7 +90,7 @@ class Run:
         if self.k is None:
             self.x = self.smp.run_hmc(steps, self.beta, self.x)["samples_out"]
         else:
-            out = self.smp.run_hmc_exchange(steps, self.beta, self.x, replicas=RUNGS, swap_every=self.k,
+            out = self.smp.run_hmc_exchange(steps, self.beta, self.x, replicas=self.rungs, swap_every=self.k,
                                             first_parity=self.done % 2)
             self.x, self.done = out["samples_out"], self.done + steps // self.k
         torch.cuda.synchronize()
@@ -115,17 +127,21 @@ med = statistics.median
 def timings():
     fmt = lambda v: f"{med(v):7.4f} ({min(v):.4f} .. {max(v):.4f})"
     fmu = lambda v: f"{med(v):6.2f} ({min(v):.2f} .. {max(v):.2f})"
-    print(f"# device {torch.cuda.get_device_name(0)}; {args.label}; GaugeDynamics(hmc=True), eps {EPS}, {RUNGS} rungs of "
+    print(f"# device {torch.cuda.get_device_name(0)}; {args.label}; GaugeDynamics(hmc=True), eps {EPS}, rungs of "
           f"beta {BETAS[0]} .. {BETAS[-1]}, 256 steps per launch; ms per MCMC step: median (min .. max) of {args.reps} "
           f"alternating windows of about {args.window} s of (a)")
-    cols = ["(a) no exchange"] + ([] if args.plain_only else [f"(b) swap_every = {k}" for k in SWAP_EVERY])
-    print(f"# {'lattice':>7} {'chains':>6} {'LF':>3} {'mode':>9} {'steps':>6} | " + " | ".join(f"{c:>26}" for c in cols)
-          + ("" if args.plain_only else " | " + " ".join(f"(b {k})/(a)" for k in SWAP_EVERY)))
-    for T, X, B, N in SHAPES:
+    # (b): the round between launches; (c), with --in-launch: the rounds inside the run's launches
+    kinds = [("b", False), ("c", True)] if args.in_launch else [("b", False)]
+    variants = [] if args.plain_only else [(f"({n}) swap_every = {k}", k, inl) for k in SWAP_EVERY for n, inl in kinds]
+    cols = ["(a) no exchange"] + [v[0] for v in variants]
+    print(f"# {'lattice':>7} {'chains':>6} {'LF':>3} {'rungs':>5} {'mode':>9} {'steps':>6} | "
+          + " | ".join(f"{c:>26}" for c in cols)
+          + ("" if args.plain_only else " | " + " ".join(f"({n} {k})/(a)" for k in SWAP_EVERY for n, _ in kinds)))
+    for T, X, B, N, G in SHAPES:
         for both in (True, False):
-            var = {cols[0]: Run(T, X, B, N, both)}
-            for c, k in zip(cols[1:], SWAP_EVERY):
-                var[c] = Run(T, X, B, N, both, k)
+            var = {cols[0]: Run(T, X, B, N, both, rungs=G)}
+            for c, k, inl in variants:
+                var[c] = Run(T, X, B, N, both, k, G, inl)
             var[cols[0]].window(256)                                   # first touch, and the step count
             dt = var[cols[0]].window(256)
             steps = max(2, round(args.window / (dt * 1e-3) / 256)) * 256
@@ -137,15 +153,15 @@ def timings():
                     times[c].append(var[c].window(steps))
             a = med(times[cols[0]])
             ratios = "" if args.plain_only else " | " + " ".join(f"{med(times[c]) / a:9.3f}" for c in cols[1:])
-            print(f"  {T:>3}x{X:<3} {B:6d} {N:3d} {'both' if both else 'selected':>9} {steps:6d} | "
+            print(f"  {T:>3}x{X:<3} {B:6d} {N:3d} {G:5d} {'both' if both else 'selected':>9} {steps:6d} | "
                   + " | ".join(f"{fmt(times[c]):>26}" for c in cols) + ratios, flush=True)
             del var
-    if args.plain_only:
+    if args.plain_only or args.in_launch:
         return
     print(f"# (c) one round alone (swap_replicas, {RUNGS} rungs): us per round, median (min .. max) of {args.reps} windows "
           f"of {args.rounds} calls of alternating parity; the kernel alone over 200 calls (l2hmc_profile class 8)")
     print(f"# {'lattice':>7} {'chains':>6} | {'the call, host clock':>26} | {'the kernel':>26}")
-    for T, X, B, N in SHAPES:
+    for T, X, B, N, _ in SHAPES:
         host, dev = round_alone(T, X, B, N, args.reps, args.rounds)
         print(f"  {T:>3}x{X:<3} {B:6d} | {fmu(host):>26} | {fmu(dev):>26}", flush=True)
 

@@ -63,14 +63,17 @@ def _glorot_uniform(rng, shape, dtype):
 
 
 def conv3d_flat_size(L, num_filters):
-    """Spatial extent after conv/pool x2 (conv_net.py:247-262): ceil(ceil(L/2)/2)^2 * 1 * 2F."""
-    l2 = -(-(-(-L // 2)) // 2)
-    return l2 * l2 * 2 * num_filters
+    """Spatial extent after conv/pool x2 (conv_net.py:247-262): ceil(ceil(T/2)/2) * ceil(ceil(X/2)/2) * 1 * 2F.
+    `L` is the extent of a square lattice or a (T, X) pair."""
+    T, X = (L, L) if np.ndim(L) == 0 else L
+    t2, x2 = (-(-(-(-int(n) // 2)) // 2) for n in (T, X))
+    return t2 * x2 * 2 * num_filters
 
 
 def init_conv3d_net(rng, L, x_dim, num_hidden, num_filters, factor,
                     head_factor=0.001, bias_std=0.0, coeff_std=0.0, dtype=np.float64):
-    """conv_net.py:57-207 (filter_sizes [(3,3,2),(2,2,2)], gauge_dynamics.py:121-143)."""
+    """conv_net.py:57-207 (filter_sizes [(3,3,2),(2,2,2)], gauge_dynamics.py:121-143).  `L`: the extent of a square
+    lattice or a (T, X) pair; it only sets the first dense layer's fan-in, the draws keep their order."""
     F = num_filters
     p = {}
     for s in ('x', 'v'):

@@ -32,13 +32,14 @@ def gauge_weights(T, X, seed=106, regime="stress", hidden_mult=4):
     return xp, vp
 
 
-def conv_weights(T, X, seed=106, regime="stress"):
-    """ConvNet3D as gauge_dynamics.py:121-143 builds it: F = space_size, H = 2 * x_dim."""
+def conv_weights(T, X, seed=106, regime="stress", F=None):
+    """ConvNet3D as gauge_dynamics.py:121-143 builds it: F = space_size (unless given), H = 2 * x_dim."""
     rng = np.random.default_rng(seed)
     D = 2 * T * X
+    F = X if F is None else F
     kw = REGIMES[regime]
-    xp = nets.init_conv3d_net(rng, T, D, 2 * D, X, 2., **kw)
-    vp = nets.init_conv3d_net(rng, T, D, 2 * D, X, 1., **kw)
+    xp = nets.init_conv3d_net(rng, (T, X), D, 2 * D, F, 2., **kw)
+    vp = nets.init_conv3d_net(rng, (T, X), D, 2 * D, F, 1., **kw)
     return xp, vp
 
 

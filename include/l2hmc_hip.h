@@ -317,6 +317,31 @@ int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta, const flo
                              float* charge_diff, float* step_sums, void* ws, size_t ws_bytes,
                              l2hmc_stream_t stream);
 
+/* l2hmc_gauge_mcmc_step_ex with a beta per chain: the rungs of a ladder -- a scan of the trained sampler over beta, or
+ * the states a replica exchange (l2hmc_gauge_replica_swap) runs between -- in ONE step.  The contract of
+ * l2hmc_gauge_mcmc_step_ex in every respect (the draws (seed, 2*draw) and (seed, 2*draw + 1) and their element layout,
+ * the optional outputs, x_next that may alias x_in, step_sums with the ticket 0 on entry and left at 0, the workspace
+ * of l2hmc_gauge_mcmc_step_ws_bytes, one launch per part of the batch on plans with a whole-step kernel, no allocation
+ * and no synchronisation -- so graph capture --, B == 0 a no-op) but this: chain c runs at betas[c * chain_stride].
+ * betas is a DEVICE pointer; chain_stride is 1 (betas [B]) or 0 (one value).  Both directions of a chain, the forces of
+ * both momentum half-kicks of every leapfrog step and both ends of its Hamiltonian difference use the chain's value;
+ * the networks never see beta.
+ * The kernels run the step's own fp32 operations on the per-chain value, so chain c has the bits of
+ * l2hmc_gauge_mcmc_step_ex with the same B, x_in, seed and draw at beta = betas[c * chain_stride], and step_sums is
+ * the fixed-order sum of what the chains return.  Every L2HMC plan is served: plans with a whole-step kernel by an
+ * instance of it that reads the chain's beta (the uniform step's kernels are left as they are), the others layer by
+ * layer with the rows' betas.
+ * Refused with L2HMC_ERR_ARG before any device call: NULL plan / betas / x_in / x_next, B < 0, a chain_stride other
+ * than 0 or 1, hmc = 1 (l2hmc_gauge_hmc_run_ladder runs plain HMC with a beta per chain).  A workspace that is NULL or
+ * too small: L2HMC_ERR_WORKSPACE.  On plans without a whole-step kernel the plan is then checked as
+ * l2hmc_gauge_transition checks it (shapes, widths, NULL masks or weights: L2HMC_ERR_ARG), also before any device call.
+ * The VALUES of betas are on the device and are not checked (as in l2hmc_gauge_hmc_run_ladder): a beta that is
+ * negative or not finite is no beta.  Callers check: GaugeSampler.step and GaugeSampler.run do. */
+int l2hmc_gauge_mcmc_step_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t chain_stride,
+                                 const float* x_in, float* x_next, int64_t B, uint64_t seed, uint64_t draw,
+                                 float* px, float* actions, float* plaqs, float* charges, float* charge_diff,
+                                 float* step_sums, void* ws, size_t ws_bytes, l2hmc_stream_t stream);
+
 /* A RUN of n_steps consecutive MCMC steps of a plain-HMC plan (plan.hmc = 1; hmc = 0 is an error), with the results
  * of n_steps calls of l2hmc_gauge_mcmc_step_ex, bit for bit.  Step s (0 <= s < n_steps) draws with index draw0 + s
  * (Philox streams (seed, 2*(draw0 + s)) and (seed, 2*(draw0 + s) + 1), the element layout of the step), runs at

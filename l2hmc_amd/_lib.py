@@ -114,6 +114,8 @@ _PROTOS = {
                                         _SZ, _P]),
     "l2hmc_gauge_mcmc_step_ex": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _P, _I64, _U64, _U64, _P, _P, _P, _P, _P, _P, _P,
                                            _SZ, _P]),
+    "l2hmc_gauge_mcmc_step_ladder": (C.c_int, [C.POINTER(GaugePlan), _P, _I64, _P, _P, _I64, _U64, _U64, _P, _P, _P, _P, _P,
+                                               _P, _P, _SZ, _P]),
     "l2hmc_gauge_hmc_run_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64, _I32]),
     "l2hmc_gauge_hmc_run": (C.c_int, [C.POINTER(GaugePlan), _P, _P, _P, _I64, _U64, _U64, _I32, _P, _P, _P, _P, _P, _P,
                                       _P, _P, _SZ, _P]),

@@ -15,6 +15,18 @@ def _float32(value):
         return v, v.astype(np.float32)
 
 
+def ndim(value):
+    """Axes of a per-run value as it is given (tensor / array / list / scalar): 0 one value, 1 one per step (`step`: one
+    per chain), 2 a chain axis."""
+    return value.ndim if isinstance(value, torch.Tensor) else np.ndim(value)
+
+
+def last_step(v):
+    """The last step's entry of a `chain_axis` value (float64, as given): a 0-d array or a [B] array; NaN where an
+    empty run has an empty schedule."""
+    return v if v.ndim == 0 else v[-1] if v.shape[0] else np.full(v.shape[1:], np.nan)
+
+
 def chain_axis(value, run_steps, B, *, who, name, positive):
     """A per-run value (beta, temperature) -> (float64 array as given, flat contiguous float32 array for the device,
     (step_stride, chain_stride)): step s of chain c reads flat[s * step_stride + c * chain_stride], the element strides

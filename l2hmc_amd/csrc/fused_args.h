@@ -51,6 +51,12 @@ struct FusedArgs {
   const float* l1_img;                   // its [N][2] kept-column first-layer sections (needs heads_img), or NULL = full K
   int single_kicks;                      // 16-row GenericNet sampling form: every momentum half-kick a network call of its own
                                          // (L2HMC_PLAN_SINGLE_KICKS); 0 = step s's second and step s + 1's first as one pass
+  // A ladder of beta in step mode (l2hmc_gauge_mcmc_step_ladder; the LADDER instances of the kernels, launched iff
+  // step_betas is set): chain c of the launch runs at step_betas[c * step_beta_stride] -- a DEVICE pointer, moved to
+  // the launch's first chain like the other per-chain pointers; element stride 0 or 1.  NULL: `beta` for every chain.
+  // (Last in the struct: the uniform instances read what they read before, at the offsets they read it from.)
+  const float* step_betas;
+  int64_t step_beta_stride;
 };
 
 // the sub-tile form (fused_traj4.hip): GenericNet 8x8 plans, sampling only

@@ -30,9 +30,11 @@ struct StepWg {
   float* su;          // [ROWS] MH uniform
   float* spx;         // [ROWS] accept probability per row
   float* sobs;        // [ROWS][4] sum cos P (in), sum project P (in), sum project P (out), p
+  float* sbeta;       // [ROWS] LADDER instances: beta of the chain every row belongs to (stage_chains)
 };
 
-// stp: [8 * ROWS] floats of LDS.  split: only the 16-row GenericNet sampling instance has that layout.
+// stp: [8 * ROWS] floats of LDS (coin, u, p_row, obs [4], beta).  split: only the 16-row GenericNet sampling instance
+// has that layout.
 template <int ROWS>
 __device__ __forceinline__ StepWg step_workgroup(const FusedArgs& p, float* stp, bool split) {
   StepWg w;
@@ -49,6 +51,7 @@ __device__ __forceinline__ StepWg step_workgroup(const FusedArgs& p, float* stp,
   w.su = stp + ROWS;
   w.spx = stp + 2 * ROWS;
   w.sobs = stp + 3 * ROWS;
+  w.sbeta = stp + 7 * ROWS;
   return w;
 }
 
@@ -60,9 +63,13 @@ __device__ __forceinline__ float philox_u01(uint64_t seed, uint64_t elem, uint64
   return (float)(c[elem & 3] >> 8) * (1.0f / 16777216.0f);
 }
 
-// ---- stage chain state: x rows -> xs, v rows -> vs, the rows' directions -> sdir [ROWS] -------------------------
+// ---- stage chain state: x rows -> xs, v rows -> vs, the rows' directions -> sdir [ROWS], their betas -> w.sbeta ---
 // Step mode draws the coin and the MH uniform of every chain and the momenta of its rows; trajectory mode reads x0 / v0.
-template <int ROWS, int THREADS, int D, int SX>
+// LADDER (step mode with FusedArgs::step_betas, an instance of its own so that the uniform step stays the code it
+// was): the beta of a row is that of the row's CHAIN -- both directions of a chain (paired layout: rows r and
+// r + ROWS / 2; split layout: the same row of the pair's two workgroups) run at one value.  A dead row (chain >=
+// step_Bl) reads nothing and takes FusedArgs::beta.
+template <int ROWS, int THREADS, int D, int SX, bool LADDER = false>
 __device__ __forceinline__ void stage_chains(const FusedArgs& p, const StepWg& w, float* xs, float* vs, int* sdir) {
   const int tid = w.tid;
   if (w.stepm) {
@@ -110,6 +117,10 @@ __device__ __forceinline__ void stage_chains(const FusedArgs& p, const StepWg& w
     if (w.stepm) d = w.split ? w.sdw : w.paired ? (tid >= ROWS / 2 ? 1 : 0) : (w.scoin[tid] > 0.5f ? 0 : 1);
     else if (tid < w.nrow) d = p.dir ? p.dir[w.row0 + tid] : (p.dir_split > 0 && w.row0 + tid >= p.dir_split) ? 1 : 0;
     sdir[tid] = d;
+    if constexpr (LADDER) {
+      const int64_t chain = w.cbase + (w.paired && tid >= ROWS / 2 ? tid - ROWS / 2 : tid);
+      w.sbeta[tid] = chain < p.step_Bl ? p.step_betas[chain * p.step_beta_stride] : p.beta;
+    }
   }
 }
 
@@ -138,12 +149,13 @@ struct ChainLanes {
   int fc0, fl;           // chain (of pass 0), lane-in-chain; fl = kIdleLane for a thread without a chain
   int T, X, xsh;         // sites = 64 and X divides it: shifts instead of run-time divisions
   float beta;
+  const float* sbeta;    // LADDER instances: StepWg::sbeta, beta per row (LDS), read where it is used
 };
 
 constexpr int kIdleLane = 1 << 20;
 
 template <int ROWS, int TPC, int NCH>
-__device__ __forceinline__ ChainLanes chain_lanes(const FusedArgs& p, int tid) {
+__device__ __forceinline__ ChainLanes chain_lanes(const FusedArgs& p, const StepWg& w, int tid) {
   ChainLanes c;
   const bool own = tid < ROWS / NCH * TPC;
   c.fc0 = own ? tid / TPC : 0;
@@ -152,6 +164,7 @@ __device__ __forceinline__ ChainLanes chain_lanes(const FusedArgs& p, int tid) {
   c.X = p.X;
   c.xsh = 31 - __clz(p.X);
   c.beta = p.beta;
+  c.sbeta = w.sbeta;
   return c;
 }
 
@@ -164,7 +177,7 @@ __device__ __forceinline__ float chain_sum(float v) {
 
 // force (beta * dS/dx) of the x rows into gs; act[h] = the action of chain ROWS / NCH * h + fc0 (all TPC lanes of the
 // chain).  One barrier between the sin P pass and the force pass for all NCH chains, one behind the force pass.
-template <int ROWS, int TPC, int NCH, int D, int SX, int SP>
+template <int ROWS, int TPC, int NCH, int D, int SX, int SP, bool LADDER = false>
 __device__ __forceinline__ void force_pass(const ChainLanes& c, const float* xs, float* sp, float* gs, float (&act)[NCH]) {
   constexpr int sites = D / 2;
   const int T = c.T, X = c.X, xsh = c.xsh;
@@ -190,12 +203,13 @@ __device__ __forceinline__ void force_pass(const ChainLanes& c, const float* xs,
     const int fc = ROWS / NCH * h + c.fc0;
     float* gc = gs + fc * SX;
     const float* spc = sp + fc * SP;
+    const float beta = LADDER ? c.sbeta[fc] : c.beta;
     for (int s = c.fl; s < sites; s += TPC) {
       const int i = s >> xsh, j = s & (X - 1);            // X is a power of two (T * X = 64)
       const int jm = (j == 0) ? X - 1 : j - 1, im = (i == 0) ? T - 1 : i - 1;
       const float sP = spc[s];
-      gc[2 * s] = c.beta * (sP - spc[i * X + jm]);
-      gc[2 * s + 1] = c.beta * (-sP + spc[im * X + j]);
+      gc[2 * s] = beta * (sP - spc[i * X + jm]);
+      gc[2 * s + 1] = beta * (-sP + spc[im * X + j]);
     }
   }
   __syncthreads();
@@ -248,7 +262,7 @@ __device__ __forceinline__ float accept_prob(float beta, float act0, float act1,
 }
 
 // step mode: the accept probability of every row -> spx (the caller's barrier follows)
-template <int ROWS, int NCH, int NLD>
+template <int ROWS, int NCH, int NLD, bool LADDER = false>
 __device__ __forceinline__ void step_accept_probs(const ChainLanes& c, const float* ldw, const float (&act0)[NCH],
                                                   const float (&act1)[NCH], const float (&kin0)[NCH],
                                                   const float (&kin1)[NCH], float* spx) {
@@ -256,7 +270,8 @@ __device__ __forceinline__ void step_accept_probs(const ChainLanes& c, const flo
 #pragma unroll
     for (int h = 0; h < NCH; ++h) {
       const int fc = ROWS / NCH * h + c.fc0;
-      spx[fc] = accept_prob(c.beta, act0[h], act1[h], kin0[h], kin1[h], sum_logdet<ROWS, NLD>(ldw, fc));
+      const float beta = LADDER ? c.sbeta[fc] : c.beta;
+      spx[fc] = accept_prob(beta, act0[h], act1[h], kin0[h], kin1[h], sum_logdet<ROWS, NLD>(ldw, fc));
     }
   }
 }

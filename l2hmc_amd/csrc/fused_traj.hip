@@ -218,7 +218,8 @@ extern "C" void l2hmc_debug_set_stagger(int cycles) { g_fused_stagger = cycles; 
 #endif
 
 // TAPE: training instantiation (GenericNet plans) that also writes the per-call tape of train.hip
-template <int D, int H, int KA, bool CONV, bool TAPE = false>
+// LADDER: step mode with a beta per chain (FusedArgs::step_betas), an instance of its own next to the sampling one
+template <int D, int H, int KA, bool CONV, bool TAPE = false, bool LADDER = false>
 __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_traj_fused_kernel(FusedArgs p) {
   using Cfg = FusedCfg<D, H, KA, CONV>;
   constexpr int kFWaves = Cfg::WAVES, kFThreads = Cfg::THREADS, kTPC = Cfg::TPC;   // this instance's geometry
@@ -241,7 +242,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
                                            // [IMGW][64] the lane sums an even wave hands to its odd partner
   float* ldx = ldw + IMGW * kFM;
   int* sdir = reinterpret_cast<int*>(ldw + kFWaves * kFM + (RW > 1 ? IMGW * 64 : 0));   // [16]
-  float* stp = reinterpret_cast<float*>(sdir + kFM);  // step mode: coin[16] u[16] p_row[16] obs[16][4]
+  float* stp = reinterpret_cast<float*>(sdir + kFM);  // step mode: coin[16] u[16] p_row[16] obs[16][4] beta[16]
   // ConvNet3D front-end state (CONV only; zero-sized otherwise)
   float* fa = stp + 8 * kFM;                          // [16][SA] features of the first input
   float* fb = fa + kFM * SA;                          // [16][SA] features of the second input
@@ -284,7 +285,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   const bool STEPM = wg.stepm;
   const int sdw = wg.sdw;                                               // (SPLIT) this workgroup's direction
   float* spx = wg.spx;                                                  // [16] accept probability per row
-  stage_chains<kFM, kFThreads, D, SX>(p, wg, xs, vs, sdir);
+  stage_chains<kFM, kFThreads, D, SX, LADDER>(p, wg, xs, vs, sdir);
   load_consts<kFThreads, D, H>(p.xnet, cx, tid);
   load_consts<kFThreads, D, H>(p.vnet, cv, tid);
   if constexpr (CONV) {
@@ -313,9 +314,9 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   const int dirl = sdir[r];           // direction of the row this lane owns in a C fragment (fused_common.h)
 
   // ---- chain-local passes (fused_step.h): kTPC consecutive threads per chain, one chain per thread group
-  const ChainLanes cl = chain_lanes<kFM, kTPC, 1>(p, tid);
+  const ChainLanes cl = chain_lanes<kFM, kTPC, 1>(p, wg, tid);
   float act0[1], kin0[1];
-  force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
+  force_pass<kFM, kTPC, 1, D, SX, SP, LADDER>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
   kinetic_pass<kFM, kTPC, 1, D, SX>(cl, vs, kin0);
 
   // ---- one network evaluation + fused sub-update ------------------------------
@@ -1061,7 +1062,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
       if (call == 3) {
         [[maybe_unused]] const unsigned long long tf = L2HMC_CYCLES_NOW();
         float unused[1];
-        force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, unused);   // force at the new position
+        force_pass<kFM, kTPC, 1, D, SX, SP, LADDER>(cl, xs, sp, gs, unused);   // force at the new position
         L2HMC_CYCLES_ADD(ft, 7, tf);
         // paired call: no call of this step reads a mask any more (call 3 uses none), so the next step's take their
         // place now; the barrier behind the first layer stands between these writes and slice B's reads
@@ -1083,10 +1084,10 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
 
   // ---- epilogue: energies, accept probability, write back -------------------------
   float act1[1], kin1[1];
-  force_pass<kFM, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, act1);
+  force_pass<kFM, kTPC, 1, D, SX, SP, LADDER>(cl, xs, sp, gs, act1);
   kinetic_pass<kFM, kTPC, 1, D, SX>(cl, vs, kin1);
   if (STEPM) {
-    step_accept_probs<kFM, 1, IMGW>(cl, ldw, act0, act1, kin0, kin1, spx);
+    step_accept_probs<kFM, 1, IMGW, LADDER>(cl, ldw, act0, act1, kin0, kin1, spx);
     __syncthreads();
     // forward / backward rows of chain k (x, v: row stride SX) and their accept probabilities
     const float* xfr = xs;
@@ -1345,7 +1346,7 @@ size_t fused_step_hand_bytes(int64_t B, int D) {
 int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, float* x_next, int64_t B,
                       uint64_t seed, uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges,
                       float* dq, float* step_sums, float* part, void* hand, hipStream_t stream, float* x_prop,
-                      float* v_prop, float* x_out) {
+                      float* v_prop, float* x_out, const float* betas, int64_t chain_stride) {
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
   using CfgG = FusedCfg<128, 512, 128, false>;
   using CfgC = FusedCfg<128, 256, 64, true>;
@@ -1356,6 +1357,12 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(sizeof(float) * CfgG::LDS_FLOATS)) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused_kernel<128, 256, 64, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(sizeof(float) * CfgC::LDS_FLOATS)) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused_kernel<128, 512, 128, false, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(sizeof(float) * CfgG::LDS_FLOATS)) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused_kernel<128, 256, 64, true, false, true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(sizeof(float) * CfgC::LDS_FLOATS)) != hipSuccess) {
       set_error("fused step: cannot reserve %zu B of LDS", lds);
@@ -1390,6 +1397,7 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
     a.step_xout = x_out ? x_out + c0 * D : nullptr;
     a.step_B = B; a.step_Bl = nb; a.step_chain0 = c0; a.step_sums_acc = accumulate;
     a.step_seed = seed; a.step_draw = draw; a.step_both = both;
+    a.step_betas = betas ? betas + c0 * chain_stride : nullptr; a.step_beta_stride = chain_stride;   // (a ladder)
     a.step_px = px ? px + c0 : nullptr; a.step_act = actions ? actions + c0 : nullptr;
     a.step_plq = plaqs ? plaqs + c0 : nullptr; a.step_chg = charges ? charges + c0 : nullptr;
     a.step_dq = dq ? dq + c0 : nullptr;
@@ -1433,8 +1441,14 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
     }
     const unsigned nwg = (unsigned)(a.rows / kFM);
     prof_before(kProfFused, stream);
-    if (conv)
+    if (conv && a.step_betas)
+      hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 256, 64, true, false, true>), dim3(nwg), dim3(CfgC::THREADS), lds,
+                         stream, a);
+    else if (conv)
       hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 256, 64, true>), dim3(nwg), dim3(CfgC::THREADS), lds, stream, a);
+    else if (a.step_betas)
+      hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 512, 128, false, false, true>), dim3(nwg), dim3(CfgG::THREADS), lds,
+                         stream, a);
     else
       hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 512, 128, false>), dim3(nwg), dim3(CfgG::THREADS), lds, stream, a);
     prof_after(kProfFused, stream);

@@ -116,6 +116,8 @@ __device__ __forceinline__ void stream_layer2(BRing<NT, DEPTH>& R, const float* 
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// LADDER: step mode with a beta per chain (FusedArgs::step_betas), an instance of its own
+template <bool LADDER>
 __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
   constexpr int ROWS = kR32, SX = kSX, SH = kSH, SP = kSP, D = kD, H = kH, NT1 = kNT1, NTH = kNTH;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
   float* ldw = skm + 2 * D;                // [image waves][32] log-det partial sums per image wave
   float* ldx = ldw + kIW32 * ROWS;         // [image waves][2 row groups][64] lane sums an even wave hands to its odd partner
   int* sdir = reinterpret_cast<int*>(ldx + kIW32 * kG32 * 64);   // [32]
-  float* stp = reinterpret_cast<float*>(sdir + ROWS);      // step mode: coin[32] u[32] p_row[32] obs[32][4]
+  float* stp = reinterpret_cast<float*>(sdir + ROWS);      // step mode: coin[32] u[32] p_row[32] obs[32][4] beta[32]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -139,7 +141,7 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
 
   // ---- stage chain state and constants (fused_step.h) ----
   const StepWg wg = step_workgroup<ROWS>(p, stp, /*split=*/false);
-  stage_chains<ROWS, kT32, D, SX>(p, wg, xs, vs, sdir);
+  stage_chains<ROWS, kT32, D, SX, LADDER>(p, wg, xs, vs, sdir);
   load_consts<kT32, D, H>(p.xnet, cx, tid);
   load_consts<kT32, D, H>(p.vnet, cv, tid);
   if (tid < kIW32 * ROWS) ldw[tid] = 0.f;
@@ -150,9 +152,9 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
 
   // ---- chain-local passes (fused_step.h): 16 consecutive threads per chain on the first 256 threads, two chains
   //      per thread group (chain = 16 h + tid / 16)
-  const ChainLanes cl = chain_lanes<ROWS, kTPC, kG32>(p, tid);
+  const ChainLanes cl = chain_lanes<ROWS, kTPC, kG32>(p, wg, tid);
   float act0[kG32], kin0[kG32];
-  force_pass<ROWS, kTPC, kG32, D, SX, SP>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
+  force_pass<ROWS, kTPC, kG32, D, SX, SP, LADDER>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
   kinetic_pass<ROWS, kTPC, kG32, D, SX>(cl, vs, kin0);
 
   // recurring first-layer products kept in registers (fused_traj.hip: keep_v, keep_x)
@@ -379,7 +381,7 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
       const bool is_v = call == 0 || call == 3;
       if (call == 3) {
         float unused[kG32];
-        force_pass<ROWS, kTPC, kG32, D, SX, SP>(cl, xs, sp, gs, unused);   // force at the new position
+        force_pass<ROWS, kTPC, kG32, D, SX, SP, LADDER>(cl, xs, sp, gs, unused);   // force at the new position
       }
       const int l1 = call == 0 ? (keep_v_valid ? 2 : 0) : call == 1 ? 3 : call == 2 ? 4 : 1;
       net_update(is_v ? p.vnet : p.xnet, is_v ? cv : cx, is_v ? xs : vs, is_v ? 1 : 2, call == 2 ? 1 : 0, call < 2, l1,
@@ -390,10 +392,10 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
 
   // ---- epilogue: energies, accept probability, write back (fused_step.h) ----
   float act1[kG32], kin1[kG32];
-  force_pass<ROWS, kTPC, kG32, D, SX, SP>(cl, xs, sp, gs, act1);
+  force_pass<ROWS, kTPC, kG32, D, SX, SP, LADDER>(cl, xs, sp, gs, act1);
   kinetic_pass<ROWS, kTPC, kG32, D, SX>(cl, vs, kin1);
   if (wg.stepm) {
-    step_accept_probs<ROWS, kG32, kIW32>(cl, ldw, act0, act1, kin0, kin1, wg.spx);
+    step_accept_probs<ROWS, kG32, kIW32, LADDER>(cl, ldw, act0, act1, kin0, kin1, wg.spx);
     __syncthreads();
     // both directions: rows [0, 16) forward, [16, 32) backward of the same chains
     float* gin = gs;                                    // x_in -> gs rows, x_out -> hh rows (both free now)
@@ -421,7 +423,9 @@ int launch_fused32(const FusedArgs& a, hipStream_t stream) {
   static DeviceOnce once;
   const size_t lds = sizeof(float) * kLds32;
   if (once.pending()) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused32_kernel),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused32_kernel<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused32_kernel<true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
       set_error("fused 32-row kernel: cannot reserve %zu B of LDS", lds);
       return L2HMC_ERR_HIP;
@@ -430,7 +434,10 @@ int launch_fused32(const FusedArgs& a, hipStream_t stream) {
   }
   const dim3 grid((unsigned)ceil_div(a.rows, kR32));
   prof_before(kProfFused, stream);
-  hipLaunchKernelGGL(gauge_traj_fused32_kernel, grid, dim3(kT32), lds, stream, a);
+  if (a.step_betas)
+    hipLaunchKernelGGL(gauge_traj_fused32_kernel<true>, grid, dim3(kT32), lds, stream, a);
+  else
+    hipLaunchKernelGGL(gauge_traj_fused32_kernel<false>, grid, dim3(kT32), lds, stream, a);
   prof_after(kProfFused, stream);
   L2HMC_CHECK_LAUNCH("gauge_traj_fused32");
   return L2HMC_OK;

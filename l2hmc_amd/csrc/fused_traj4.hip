@@ -138,7 +138,8 @@ struct F4Cfg {
                                     (2 * kThreads4 > ROWS * kSX4 ? 2 * kThreads4 - ROWS * kSX4 : 0);   // final-sum scratch fits vs
 };
 
-template <int ROWS>
+// LADDER: step mode with a beta per chain (FusedArgs::step_betas), an instance of its own
+template <int ROWS, bool LADDER = false>
 __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs p) {
   using Cfg = F4Cfg<ROWS>;
   constexpr int RG = Cfg::RG, kTPC = Cfg::TPC, SX = kSX4, SH = kSH4, SP = Cfg::SP, D = kD, H = kH;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
   float* skm = sp + ROWS * SP;             // [2][D] masks of this step: forward row, backward row
   float* ldw = skm + 2 * D;                // [waves][ROWS] log-det partial sums per wave
   int* sdir = reinterpret_cast<int*>(ldw + kWaves4 * ROWS);   // [ROWS]
-  float* stp = reinterpret_cast<float*>(sdir + ROWS);        // step mode: coin[R] u[R] p_row[R] obs[R][4]
+  float* stp = reinterpret_cast<float*>(sdir + ROWS);        // step mode: coin[R] u[R] p_row[R] obs[R][4] beta[R]
   float* sst = stp + 8 * ROWS;             // [waves][ROWS][32] per-element log-det terms of a call (ordered sum)
 
   const int tid = threadIdx.x;
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
 
   // ---- stage chain state and constants (fused_step.h) ----
   const StepWg wg = step_workgroup<ROWS>(p, stp, /*split=*/false);
-  stage_chains<ROWS, kThreads4, D, SX>(p, wg, xs, vs, sdir);
+  stage_chains<ROWS, kThreads4, D, SX, LADDER>(p, wg, xs, vs, sdir);
   load_consts<kThreads4, D, H>(p.xnet, cx, tid);
   load_consts<kThreads4, D, H>(p.vnet, cv, tid);
   if (tid < kWaves4 * ROWS) ldw[tid] = 0.f;
@@ -178,9 +179,9 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
 
   // ---- chain-local passes (fused_step.h): 16 threads per chain as in the 16-row form, one chain per thread group;
   //      the threads beyond 16 ROWS idle
-  const ChainLanes cl = chain_lanes<ROWS, kTPC, 1>(p, tid);
+  const ChainLanes cl = chain_lanes<ROWS, kTPC, 1>(p, wg, tid);
   float act0[1], kin0[1];
-  force_pass<ROWS, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
+  force_pass<ROWS, kTPC, 1, D, SX, SP, LADDER>(cl, xs, sp, gs, act0);     // also leaves the force of x0 in gs
   kinetic_pass<ROWS, kTPC, 1, D, SX>(cl, vs, kin0);
 
   f32x4 keep_v[RG][2], keep_x[RG][2];
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
       const bool is_v = call == 0 || call == 3;
       if (call == 3) {
         float unused[1];
-        force_pass<ROWS, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, unused);   // force at the new position
+        force_pass<ROWS, kTPC, 1, D, SX, SP, LADDER>(cl, xs, sp, gs, unused);   // force at the new position
       }
       const int l1 = call == 0 ? (keep_v_valid ? 2 : 0) : call == 1 ? 3 : call == 2 ? 4 : 1;
       net_update(is_v ? p.vnet : p.xnet, is_v ? cv : cx, is_v ? xs : vs, is_v ? 1 : 2, call == 2 ? 1 : 0, call < 2, l1,
@@ -366,10 +367,10 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
 
   // ---- epilogue: energies, accept probability, write back (fused_step.h) ----
   float act1[1], kin1[1];
-  force_pass<ROWS, kTPC, 1, D, SX, SP>(cl, xs, sp, gs, act1);
+  force_pass<ROWS, kTPC, 1, D, SX, SP, LADDER>(cl, xs, sp, gs, act1);
   kinetic_pass<ROWS, kTPC, 1, D, SX>(cl, vs, kin1);
   if (wg.stepm) {
-    step_accept_probs<ROWS, 1, kWaves4>(cl, ldw, act0, act1, kin0, kin1, wg.spx);
+    step_accept_probs<ROWS, 1, kWaves4, LADDER>(cl, ldw, act0, act1, kin0, kin1, wg.spx);
     __syncthreads();
     // both directions: rows [0, ROWS / 2) forward, [ROWS / 2, ROWS) backward of the same chains
     float* gin = gs;                                    // x_in -> gs rows, x_out -> h1 rows (both free now)
@@ -418,6 +419,12 @@ int launch_fused4(const FusedArgs& a, int rows_per_wg, hipStream_t stream) {
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused4_kernel<8>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused4_kernel<12>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds12) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused4_kernel<4, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused4_kernel<8, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused4_kernel<12, true>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds12) != hipSuccess) {
       set_error("fused sub-tile kernel: cannot reserve %zu B of LDS", lds12);
       return L2HMC_ERR_HIP;
@@ -428,7 +435,14 @@ int launch_fused4(const FusedArgs& a, int rows_per_wg, hipStream_t stream) {
                 rows_per_wg);
   const dim3 grid((unsigned)ceil_div(a.rows, rows_per_wg));
   prof_before(kProfFused, stream);
-  if (rows_per_wg == 4)
+  if (a.step_betas) {                                  // a ladder of beta: the LADDER instances
+    if (rows_per_wg == 4)
+      hipLaunchKernelGGL((gauge_traj_fused4_kernel<4, true>), grid, dim3(kThreads4), lds4, stream, a);
+    else if (rows_per_wg == 8)
+      hipLaunchKernelGGL((gauge_traj_fused4_kernel<8, true>), grid, dim3(kThreads4), lds8, stream, a);
+    else
+      hipLaunchKernelGGL((gauge_traj_fused4_kernel<12, true>), grid, dim3(kThreads4), lds12, stream, a);
+  } else if (rows_per_wg == 4)
     hipLaunchKernelGGL((gauge_traj_fused4_kernel<4>), grid, dim3(kThreads4), lds4, stream, a);
   else if (rows_per_wg == 8)
     hipLaunchKernelGGL((gauge_traj_fused4_kernel<8>), grid, dim3(kThreads4), lds8, stream, a);

@@ -157,6 +157,7 @@ __device__ __forceinline__ StepWg hmc_workgroup(const FusedArgs& p, const HmcLan
   w.su = g.stp + R;
   w.spx = g.stp + 2 * R;
   w.sobs = g.stp + 3 * R;
+  w.sbeta = nullptr;                      // (unused: hmc_step takes the row's beta as an argument)
   return w;
 }
 

@@ -85,7 +85,7 @@ __global__ void accept_prob_kernel(const float* __restrict__ h_old, const float*
 // that p carries no cancellation error beyond the inputs' own rounding.
 __global__ void accept_from_parts_kernel(const float* __restrict__ act0, const float* __restrict__ kin0,
                                          const float* __restrict__ act1, const float* __restrict__ kin1,
-                                         const float* __restrict__ ld_part, int ncb, float beta,
+                                         const float* __restrict__ ld_part, int ncb, RowBeta beta,
                                          int64_t n, float* __restrict__ sumlogdet,
                                          float* __restrict__ p) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,7 +95,7 @@ __global__ void accept_from_parts_kernel(const float* __restrict__ act0, const f
   const float s = (float)sd;
   if (sumlogdet) sumlogdet[i] = s;
   if (p) {
-    const double dh = (double)beta * ((double)act0[i] - (double)act1[i]) +
+    const double dh = (double)beta.at(i) * ((double)act0[i] - (double)act1[i]) +
                       ((double)kin0[i] - (double)kin1[i]) + sd;
     p[i] = accept_from_delta(dh);
   }
@@ -345,7 +345,7 @@ static bool carry_possible(const l2hmc_gauge_plan* p, const float* x, const floa
 // one augmented leapfrog step in place; log-det goes to w.ld_part (+=)
 // use_prev: the previous step of this launch kept VNet's first-layer product and the force of the current x;
 // keep_last: keep them for the next step
-static int leapfrog_step(const l2hmc_gauge_plan* p, float beta, int step, float* x, float* v,
+static int leapfrog_step(const l2hmc_gauge_plan* p, RowBeta beta, int step, float* x, float* v,
                          const int* dir, int64_t rows, const GaugeWs& w, hipStream_t stream, bool carry = false,
                          bool use_prev = false, bool keep_last = false, int64_t dir_split = -1) {
   const int D = 2 * p->T * p->X;
@@ -424,10 +424,14 @@ static int prepare_ws(const l2hmc_gauge_plan* p, int64_t rows, const GaugeWs& w,
 // x, v: [rows][D] integrated in place over all num_steps; optional sumlogdet / p
 // dir_split: rows [0, dir_split) are known to run forward and [dir_split, rows) backward (-1: directions are whatever
 // `dir` says per row; then every heads launch forms all columns)
-static int trajectory_inplace(const l2hmc_gauge_plan* p, float beta, float* x, float* v, const int* dir,
+// beta: one value, or the rows' own (RowBeta) on the layer-by-layer path -- the whole-trajectory kernels keep the scalar
+static int trajectory_inplace(const l2hmc_gauge_plan* p, RowBeta rbeta, float* x, float* v, const int* dir,
                               int64_t rows, float* sumlogdet, float* p_accept, const GaugeWs& w,
                               hipStream_t stream, int64_t dir_split = -1) {
   const int D = 2 * p->T * p->X;
+  L2HMC_REQUIRE(!rbeta.betas || !(use_hmc_kernel(p) || use_fused(p)),
+                "gauge trajectory: a beta per row runs layer by layer (the whole-trajectory kernels take one value)");
+  const float beta = rbeta.beta;        // (of the whole-trajectory kernels)
   if (use_hmc_kernel(p))
     return launch_hmc_trajectory(p, beta, 0, p->num_steps, x, v, dir, rows, x, v, sumlogdet, 0, p_accept, stream);
   if (use_fused(p))
@@ -435,7 +439,7 @@ static int trajectory_inplace(const l2hmc_gauge_plan* p, float beta, float* x, f
                                    stream);
   if (int e = prepare_ws(p, rows, w, stream)) return e;
   if (p_accept) {
-    if (int e = launch_u1_action_force(x, rows, p->T, p->X, beta, w.act0, nullptr, nullptr, nullptr, stream))
+    if (int e = launch_u1_action_force(x, rows, p->T, p->X, rbeta, w.act0, nullptr, nullptr, nullptr, stream))
       return e;
     if (int e = l2hmc_kinetic_energy(v, rows, D, w.kin0, stream)) return e;
   }
@@ -444,17 +448,17 @@ static int trajectory_inplace(const l2hmc_gauge_plan* p, float beta, float* x, f
   //  tails overlap the other half's matrix work -- half-size kernels lose more than the overlap returns: cfg 4
   //  9.75 -> 10.18 ms, cfg 3 layered 2.58 -> 2.63 ms)
   for (int step = 0; step < p->num_steps; ++step)
-    if (int e = leapfrog_step(p, beta, step, x, v, dir, rows, w, stream, carry, carry && step > 0,
+    if (int e = leapfrog_step(p, rbeta, step, x, v, dir, rows, w, stream, carry, carry && step > 0,
                               carry && step + 1 < p->num_steps, dir ? dir_split : rows))
       return e;
   if (p_accept) {
-    if (int e = launch_u1_action_force(x, rows, p->T, p->X, beta, w.act1, nullptr, nullptr, nullptr, stream))
+    if (int e = launch_u1_action_force(x, rows, p->T, p->X, rbeta, w.act1, nullptr, nullptr, nullptr, stream))
       return e;
     if (int e = l2hmc_kinetic_energy(v, rows, D, w.kin1, stream)) return e;
   }
   if (p_accept || sumlogdet) {
     hipLaunchKernelGGL(accept_from_parts_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, stream,
-                       w.act0, w.kin0, w.act1, w.kin1, w.ld_part, gauge_ncb(p), beta, rows, sumlogdet,
+                       w.act0, w.kin0, w.act1, w.kin1, w.ld_part, gauge_ncb(p), rbeta, rows, sumlogdet,
                        p_accept);
     L2HMC_CHECK_LAUNCH("accept_from_parts");
   }
@@ -702,14 +706,27 @@ extern "C" int l2hmc_gauge_transition(const l2hmc_gauge_plan* plan, float beta, 
   if (B == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x && v0_f && v0_b && coin && u && x_prop && v_prop && p_accept && x_out && ws,
                 "gauge_transition: NULL pointer");
+  return gauge_transition_rows("gauge_transition", plan, beta, x, v0_f, v0_b, coin, u, B, both_directions, x_prop,
+                               v_prop, p_accept, x_out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int l2hmc::gauge_check_plan(const l2hmc_gauge_plan* plan) { return check_plan(plan); }
+
+// The transition on checked pointers and B > 0; the plan is checked here, ahead of every device call.  beta: one value,
+// or the rows' own with mod = B -- the stacked [forward; backward] rows B + c and c of chain c run at one value
+// (l2hmc_gauge_mcmc_step_ladder on plans without a whole-step kernel).
+int l2hmc::gauge_transition_rows(const char* who, const l2hmc_gauge_plan* plan, RowBeta beta, const float* x,
+                                 const float* v0_f, const float* v0_b, const float* coin, const float* u, int64_t B,
+                                 int both_directions, float* x_prop, float* v_prop, float* p_accept, float* x_out,
+                                 void* ws, size_t ws_bytes, hipStream_t s) {
+  if (int e = check_plan(plan)) return e;
   const int D = 2 * plan->T * plan->X;
   const int64_t R = both_directions ? 2 * B : B;
   const size_t need = l2hmc_gauge_transition_ws_bytes(plan, B, both_directions);
   if (ws_bytes < need) {
-    set_error("gauge_transition: workspace %zu < %zu bytes", ws_bytes, need);
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
     return L2HMC_ERR_WORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
   char* base = static_cast<char*>(ws);
   const size_t xv = align_up(sizeof(float) * (size_t)R * D, 256);
   float* Xw = reinterpret_cast<float*>(base);

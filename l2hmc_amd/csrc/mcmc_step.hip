@@ -93,17 +93,17 @@ extern "C" int l2hmc_gauge_mcmc_step(const l2hmc_gauge_plan* plan, float beta, f
                                   ws, ws_bytes, stream);
 }
 
-extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta, const float* x_in, float* x_next,
-                                        int64_t B, uint64_t seed, uint64_t draw, float* px, float* actions,
-                                        float* plaqs, float* charges, float* charge_diff, float* step_sums, void* ws,
-                                        size_t ws_bytes, l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(plan != nullptr && B >= 0, "gauge_mcmc_step: bad arguments");
-  if (B == 0) return L2HMC_OK;
-  L2HMC_REQUIRE(x_in && x_next && ws, "gauge_mcmc_step: NULL pointer");
+// The step of l2hmc_gauge_mcmc_step_ex (`who` = its name in messages) on checked pointers and B > 0.  betas: NULL, or
+// the ladder of l2hmc_gauge_mcmc_step_ladder (DEVICE; chain c at betas[c * chain_stride]; `beta` is then not read by a
+// live chain).
+static int mcmc_step_impl(const char* who, const l2hmc_gauge_plan* plan, float beta, const float* betas,
+                          int64_t chain_stride, const float* x_in, float* x_next, int64_t B, uint64_t seed,
+                          uint64_t draw, float* px, float* actions, float* plaqs, float* charges, float* charge_diff,
+                          float* step_sums, void* ws, size_t ws_bytes, l2hmc_stream_t stream) {
   const float* x = x_in;
   const size_t need = l2hmc_gauge_mcmc_step_ws_bytes(plan, B);
   if (ws_bytes < need) {
-    set_error("gauge_mcmc_step: workspace %zu < %zu bytes", ws_bytes, need);
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need);
     return L2HMC_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -126,8 +126,11 @@ extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta
   if (fused) {
     // ONE launch: the whole-trajectory kernel draws, integrates, mixes, accepts, measures and wraps (fused_traj.hip)
     return launch_fused_step(plan, beta, x, x_next, B, seed, draw, selected ? 0 : 1, px, actions, plaqs, charges,
-                             charge_diff, step_sums, Xw /* 2 * workgroups floats of scratch */, rest, s);
+                             charge_diff, step_sums, Xw /* 2 * workgroups floats of scratch */, rest, s, nullptr, nullptr,
+                             nullptr, betas, chain_stride);
   }
+  // the layer-by-layer path: the plan's checks (the transition's own) come ahead of its first launch, the draws
+  if (int e = gauge_check_plan(plan)) return e;
   // momenta of both directions, coin | u  (tf.random_normal :269, tf.random_uniform :223,:246)
   const int64_t nblk = (((int64_t)2 * B * D + 3) >> 2) + ((2 * B + 3) >> 2);
   hipLaunchKernelGGL(step_draws_kernel, dim3((unsigned)hmin(ceil_div(nblk, 256), 4096)), dim3(256), 0, s, Vw,
@@ -141,11 +144,12 @@ extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta
   float* x_out = reinterpret_cast<float*>(rest + 2 * bd);
   rest += 3 * bd;
   rest_bytes -= 3 * bd;
-  L2HMC_REQUIRE(!step_sums || (px && charge_diff), "gauge_mcmc_step: step_sums needs px and charge_diff on this path");
+  L2HMC_REQUIRE(!step_sums || (px && charge_diff), "%s: step_sums needs px and charge_diff on this path", who);
   float* pp = px ? px : Xw;        // Xw / Pw of the head are free here: the transition carves its own copies
-  if (int e = l2hmc_gauge_transition(plan, beta, x, Vw, Vw + (size_t)B * D, cu, cu + B, B, selected ? 0 : 1, x_prop,
-                                     v_prop, pp,
-                                     x_out, rest, rest_bytes, stream))
+  // (a ladder: rows B + c and c of the stacked [forward; backward] trajectories are chain c)
+  const RowBeta rbeta = betas ? RowBeta(betas, B, chain_stride) : RowBeta(beta);
+  if (int e = gauge_transition_rows(who, plan, rbeta, x, Vw, Vw + (size_t)B * D, cu, cu + B, B, selected ? 0 : 1, x_prop,
+                                    v_prop, pp, x_out, rest, rest_bytes, s))
     return e;
   float* q_in = Pw;
   float* q_out = Pw + B;
@@ -159,6 +163,38 @@ extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta
     L2HMC_CHECK_LAUNCH("step_sums");
   }
   return l2hmc_wrap_angle(x_out, (int64_t)B * D, x_next, stream);
+}
+
+extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta, const float* x_in, float* x_next,
+                                        int64_t B, uint64_t seed, uint64_t draw, float* px, float* actions,
+                                        float* plaqs, float* charges, float* charge_diff, float* step_sums, void* ws,
+                                        size_t ws_bytes, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(plan != nullptr && B >= 0, "gauge_mcmc_step: bad arguments");
+  if (B == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x_in && x_next && ws, "gauge_mcmc_step: NULL pointer");
+  return mcmc_step_impl("gauge_mcmc_step", plan, beta, nullptr, 0, x_in, x_next, B, seed, draw, px, actions, plaqs,
+                        charges, charge_diff, step_sums, ws, ws_bytes, stream);
+}
+
+// ---- the same step with a beta per chain: the whole-step kernels' LADDER instances, or the layer-by-layer path with
+// the rows' betas (RowBeta) -- every L2HMC plan
+extern "C" int l2hmc_gauge_mcmc_step_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t chain_stride,
+                                            const float* x_in, float* x_next, int64_t B, uint64_t seed, uint64_t draw,
+                                            float* px, float* actions, float* plaqs, float* charges,
+                                            float* charge_diff, float* step_sums, void* ws, size_t ws_bytes,
+                                            l2hmc_stream_t stream) {
+  const char* who = "gauge_mcmc_step_ladder";
+  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  L2HMC_REQUIRE(!plan->hmc, "%s: plan.hmc = 1: l2hmc_gauge_hmc_run_ladder runs plain HMC with a beta per chain", who);
+  L2HMC_REQUIRE(betas != nullptr, "%s: NULL betas", who);
+  L2HMC_REQUIRE(chain_stride == 0 || chain_stride == 1, "%s: chain_stride = %lld is not 0 or 1", who,
+                (long long)chain_stride);
+  L2HMC_REQUIRE(x_in && x_next, "%s: NULL x_in / x_next", who);
+  L2HMC_REQUIRE(B >= 0, "%s: B < 0", who);
+  if (B == 0) return L2HMC_OK;
+  if (!ws) ws_bytes = 0;
+  return mcmc_step_impl(who, plan, 0.f, betas, chain_stride, x_in, x_next, B, seed, draw, px, actions, plaqs, charges,
+                        charge_diff, step_sums, ws, ws_bytes, stream);
 }
 
 extern "C" int l2hmc_gauge_transition_draw(const l2hmc_gauge_plan* plan, float beta, const float* x, int64_t B,

@@ -154,7 +154,8 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
 int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, float* x_next, int64_t B,
                       uint64_t seed, uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges,
                       float* dq, float* step_sums, float* part, void* hand, hipStream_t stream,
-                      float* x_prop = nullptr, float* v_prop = nullptr, float* x_out = nullptr);
+                      float* x_prop = nullptr, float* v_prop = nullptr, float* x_out = nullptr,
+                      const float* betas = nullptr, int64_t chain_stride = 0);   // DEVICE betas: chain c at betas[c * chain_stride]
 // plain HMC (plan->hmc) in one launch at any lattice of up to 1024 sites (hmc_step.hip): the counterparts of
 // fused_plan_supported, launch_fused_trajectory and launch_fused_step (part: 2 floats per chain of scratch)
 int hmc_plan_supported(const l2hmc_gauge_plan* p);
@@ -218,7 +219,26 @@ struct TrunkBwdArgs {
 int trunk_bwd_supported(const l2hmc_dense_net* n);
 int launch_trunk_bwd_pack(const l2hmc_dense_net* n, float* pack, hipStream_t stream);
 int launch_trunk_bwd(TrunkBwdArgs& a, hipStream_t stream);
-int launch_u1_action_force(const float* x, int64_t rows, int T, int X, float beta, float* action,
+// beta of a row on the layer-by-layer path: one scalar for the launch (what a float converts to), or with `betas` (a
+// DEVICE pointer) row r at betas[(r % mod) * stride] -- mod = B covers the stacked [forward; backward] rows of a
+// transition.  The ladder of l2hmc_gauge_mcmc_step_ladder; the public entries pass the scalar.
+struct RowBeta {
+  float beta;
+  const float* betas;
+  int64_t mod, stride;
+  RowBeta(float b) : beta(b), betas(nullptr), mod(1), stride(0) {}
+  RowBeta(const float* bs, int64_t m, int64_t st) : beta(0.f), betas(bs), mod(m), stride(st) {}
+  __device__ __forceinline__ float at(int64_t r) const { return betas ? betas[(r % mod) * stride] : beta; }
+};
+int launch_u1_action_force(const float* x, int64_t rows, int T, int X, RowBeta beta, float* action,
                            float* force, float* avg_plaq, float* top_charge, hipStream_t stream);
+// l2hmc_gauge_transition with the beta of every row (leapfrog.hip): the plan is checked as every public entry of the
+// layer-by-layer path checks it (gauge_check_plan: L2HMC_ERR_ARG before any device call), pointers and B > 0 are the
+// caller's; `who` words the workspace message
+int gauge_check_plan(const l2hmc_gauge_plan* plan);
+int gauge_transition_rows(const char* who, const l2hmc_gauge_plan* plan, RowBeta beta, const float* x,
+                          const float* v0_f, const float* v0_b, const float* coin, const float* u, int64_t B,
+                          int both_directions, float* x_prop, float* v_prop, float* p_accept, float* x_out, void* ws,
+                          size_t ws_bytes, hipStream_t stream);
 
 }  // namespace l2hmc

@@ -12,6 +12,7 @@
 //
 // HBM-bound: 8*D + 4..12 bytes per chain (read x, write force + scalars).
 #include "common.h"
+#include "stq_dense.h"      // RowBeta
 
 namespace l2hmc {
 
@@ -22,7 +23,7 @@ constexpr float kPi = 3.14159265358979323846f;
 // One workgroup handles `cpw` consecutive chains (cpw*sites <= 256 threads busy)
 // or, for sites >= 256, one chain with several sites per thread.
 __global__ __launch_bounds__(kLatThreads) void u1_action_force_kernel(
-    const float* __restrict__ x, int64_t rows, int T, int X, float beta, int cpw,
+    const float* __restrict__ x, int64_t rows, int T, int X, RowBeta beta, int cpw,
     float* __restrict__ action, float* __restrict__ force, float* __restrict__ avg_plaq,
     float* __restrict__ top_charge) {
   extern __shared__ float lds[];
@@ -116,6 +117,9 @@ __global__ __launch_bounds__(kLatThreads) void u1_action_force_kernel(
 
   if (force) {
     float2* dst = reinterpret_cast<float2*>(force + row0 * D);
+    // the launch's beta, read once: with a beta per row (RowBeta) that of the workgroup's first chain, and only the
+    // further chains of a workgroup (cpw > 1) look theirs up inside the loop
+    const float b0 = beta.at(row0);
     for (int s = tid; s < work; s += kLatThreads) {
       const int c = one_chain ? 0 : s / sites;
       const int site = s - c * sites;
@@ -124,9 +128,10 @@ __global__ __launch_bounds__(kLatThreads) void u1_action_force_kernel(
       const int jm = (j == 0) ? X - 1 : j - 1;
       const int im = (i == 0) ? T - 1 : i - 1;
       const float sP = spc[site];
+      const float b = (beta.betas && c > 0) ? beta.at(row0 + c) : b0;
       float2 g;
-      g.x = beta * (sP - spc[i * X + jm]);       // d/dx0[i,j]
-      g.y = beta * (-sP + spc[im * X + j]);      // d/dx1[i,j]
+      g.x = b * (sP - spc[i * X + jm]);          // d/dx0[i,j]
+      g.y = b * (-sP + spc[im * X + j]);         // d/dx1[i,j]
       dst[s] = g;
     }
   }
@@ -143,7 +148,7 @@ __global__ __launch_bounds__(kLatThreads) void u1_action_force_kernel(
 //   dS/dx1[i,j] = beta (-sin P[i,j] + sin P[i-1,j])   (lattice.py:285-362, gauge_dynamics.py:592-609)
 template <bool SCALARS, int THREADS>
 __global__ __launch_bounds__(THREADS) void u1_pair_kernel(
-    const float* __restrict__ x, int64_t rows, int T, int X, float beta, int cpw,
+    const float* __restrict__ x, int64_t rows, int T, int X, RowBeta beta, int cpw,
     float* __restrict__ action, float* __restrict__ force, float* __restrict__ avg_plaq,
     float* __restrict__ top_charge) {
   __shared__ float2 x1s[THREADS];            // (x1[i,j], x1[i,j+1])
@@ -214,11 +219,12 @@ __global__ __launch_bounds__(THREADS) void u1_pair_kernel(
   }
   if (force && live) {
     const float2 dn = sps[n_down];
+    const float b = beta.at(row);
     float4 g;
-    g.x = beta * (sA - sps[n_left].y);
-    g.y = beta * (-sA + dn.x);
-    g.z = beta * (sB - sA);
-    g.w = beta * (-sB + dn.y);
+    g.x = b * (sA - sps[n_left].y);
+    g.y = b * (-sA + dn.x);
+    g.z = b * (sB - sA);
+    g.w = b * (-sB + dn.y);
     reinterpret_cast<float4*>(force)[row * lpc + l] = g;
   }
 }
@@ -305,7 +311,7 @@ __global__ __launch_bounds__(256) void u1_force_hvp_kernel(const float* __restri
   }
 }
 
-int launch_u1_action_force(const float* x, int64_t rows, int T, int X, float beta, float* action,
+int launch_u1_action_force(const float* x, int64_t rows, int T, int X, RowBeta beta, float* action,
                            float* force, float* avg_plaq, float* top_charge, hipStream_t stream) {
   const int sites = T * X;
   // pair kernel: even X, sites / 2 lanes per chain dividing the workgroup (256 threads; 512 for 1024 sites), rows

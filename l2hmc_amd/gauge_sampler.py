@@ -52,7 +52,32 @@ class GaugeSampler:
         (gauge_model.py:256-266) and dQ compares input and output (:718-725).  Runs as ONE library call
         (l2hmc_gauge_mcmc_step: draws + trajectories + mix/accept + observables + wrap).  With
         `dynamics.both_directions = False` the plan carries L2HMC_PLAN_SELECTED_ONLY: each chain is integrated
-        only in the direction its coin picks -- same random streams, same chains, half the work."""
+        only in the direction its coin picks -- same random streams, same chains, half the work.
+        `beta`: a float, or for an L2HMC dynamics one value per chain -- [B] or [1, B] as a list / array (checked:
+        finite and not negative in float32), or a float32 tensor of B elements on x's device, which is used as it is
+        (l2hmc_gauge_mcmc_step_ladder: chain c has the bits of the step of the whole batch at beta[c])."""
+        return self._step(x, beta, self._chain_betas(beta, x.shape[0], x.device))
+
+    def _chain_betas(self, beta, B, device):
+        """`step`'s beta -> None for one value, or the float32 [B] device tensor of a beta per chain.  ValueError
+        before any draw for another shape, a bad value, and a plain-HMC dynamics (`run_hmc` runs its ladders)."""
+        if _runs.ndim(beta) == 0:
+            return None
+        if self.dynamics.hmc:
+            raise ValueError("step: a beta per chain on a plain-HMC dynamics (hmc=True): `run_hmc` runs it")
+        if (isinstance(beta, torch.Tensor) and beta.device == device and beta.device.type != "cpu"
+                and beta.dtype == torch.float32 and tuple(beta.shape) in ((B,), (1, B))):
+            return beta.reshape(-1)                        # (a ladder that is on the device already stays there)
+        b, b32 = _runs._float32(beta)
+        if b.shape not in ((B,), (1, B)):
+            raise ValueError(f"step: beta of shape {b.shape}: expected a float, [{B}] or [1, {B}] (one per chain)")
+        if not (np.isfinite(b32) & (b32 >= 0)).all():
+            raise ValueError("step: every beta must be finite and not negative (in float32)")
+        return _lib.as_dev(np.ascontiguousarray(b32).reshape(-1), device)
+
+    def _step(self, x, beta, beta_dev=None):
+        """`step` on checked arguments: at the float `beta`, or with `beta_dev` (float32 [B] on the device, may be a
+        view) at a beta per chain."""
         dyn = self.dynamics
         x_next = torch.empty_like(x)                       # written by the step (out of place: no copy of x)
         B = x.shape[0]
@@ -65,7 +90,9 @@ class GaugeSampler:
         # the step's random streams come from the dynamics' own draw counter (saved / restored with the state):
         # a sampler never replays noise the dynamics, a trainer or another sampler on the same dynamics used
         draw, dyn._draws = _lib.step_draw_index(dyn._draws)
-        _lib.call("l2hmc_gauge_mcmc_step_ex", C.byref(plan), float(beta), x, x_next, B, dyn._seed, draw, outs["px"],
+        entry, front = (("l2hmc_gauge_mcmc_step_ex", (float(beta),)) if beta_dev is None else
+                        ("l2hmc_gauge_mcmc_step_ladder", (beta_dev, 1)))
+        _lib.call(entry, C.byref(plan), *front, x, x_next, B, dyn._seed, draw, outs["px"],
                   outs["action"], outs["avg_plaq"], outs["top_charge"], outs["dq"], sums, ws, nb, device=dyn._device)
         self.stats.push_sums(sums[:3])
         return x_next, outs["px"], outs, outs["dq"]
@@ -113,13 +140,20 @@ class GaugeSampler:
         """:1304-1460 without the file/plot side effects.  Starts from N(0,1) samples like the reference
         (:1354) unless `x` is given.  Returns per-step histories as NumPy arrays [steps, B].  `beta`: a float, or a
         sequence of `run_steps` values (one per step; `plaq_exact` is then taken at the last).  Plain HMC on a plan
-        with the one-launch kernel runs `steps_per_launch` steps per launch (`_run_chunks`): the same values."""
+        with the one-launch kernel runs `steps_per_launch` steps per launch (`_run_chunks`): the same values.
+        For an L2HMC dynamics `beta` may also have a chain axis, [1, B] (one per chain) or [run_steps, B]
+        (`_runs.chain_axis`): a scan of the trained sampler over beta in ONE run (l2hmc_gauge_mcmc_step_ladder per
+        step).  Chains never interact, so column c of every history is `run` of the whole batch at that column's betas,
+        bit for bit; `plaq_exact` is then a [B] array at the last step's betas.  ValueError for such a beta of another
+        shape, with an entry that is negative or not finite, and on a plain-HMC dynamics (`run_hmc` runs those)."""
         dyn = self.dynamics
+        if _runs.ndim(beta) > 1:
+            return self._exchange_run(*self._run_ladder_args("run", run_steps, beta, x), keep_samples)
         if x is None:
             x = _lib.as_dev(np.random.randn(dyn.batch_size, dyn.x_dim), dyn._device)
         else:
             x = _lib.as_dev(x, dyn._device)
-        per_step = (beta.ndim if isinstance(beta, torch.Tensor) else np.ndim(beta)) > 0
+        per_step = _runs.ndim(beta) > 0
         betas = [float(b) for b in beta] if per_step else [beta] * run_steps
         if len(betas) != run_steps:
             raise ValueError(f"beta: expected a float or {run_steps} values, got {len(betas)}")
@@ -131,10 +165,18 @@ class GaugeSampler:
                                    lambda s0: (beta_dev[s0:],))
             out["plaq_exact"] = u1_plaq_exact(betas[-1])
             return out
+        out = self._run_steps(run_steps, x, keep_samples, lambda i, x_now: self.step(x_now, betas[i]))
+        out["plaq_exact"] = u1_plaq_exact(betas[-1] if per_step else beta)
+        return out
+
+    def _run_steps(self, run_steps, x, keep_samples, step, after=None):
+        """The loop over `step(i, x) -> (x_next, px, obs, dq)`, a launch per step: `run`'s dictionary less
+        `plaq_exact`.  `after(s, x)`, called behind step s (from 1) once its sample is kept, returns the state the
+        next step starts from."""
         hist = {k: [] for k in ("px", "actions", "plaqs", "charges", "charge_diff")}
         samples = []
         for i in range(run_steps):
-            x, px, obs, dq = self.step(x, betas[i])
+            x, px, obs, dq = step(i, x)
             hist["px"].append(px)
             hist["actions"].append(obs["action"])
             hist["plaqs"].append(obs["avg_plaq"])
@@ -142,8 +184,9 @@ class GaugeSampler:
             hist["charge_diff"].append(dq)
             if keep_samples:
                 samples.append(x)
+            if after is not None:
+                x = after(i + 1, x)
         out = {k: torch.stack(v).cpu().numpy() for k, v in hist.items()}
-        out["plaq_exact"] = u1_plaq_exact(betas[-1] if per_step else beta)
         out["samples_out"] = x
         out["mean_accept"] = self.stats.mean_accept()
         if keep_samples:
@@ -151,6 +194,105 @@ class GaugeSampler:
         return out
 
     HISTORIES = ("px", "actions", "plaqs", "charges", "charge_diff")
+
+    def _run_ladder_args(self, who, run_steps, beta, x):
+        """What `run` with a chain axis on beta and `run_exchange` refuse, before any draw or plan -> (run_steps,
+        start on the device, (`_runs.chain_axis` of beta))."""
+        dyn = self.dynamics
+        if dyn.hmc:
+            raise ValueError(f"{who}: the dynamics is plain HMC (hmc=True): "
+                             f"`{'run_hmc_exchange' if who == 'run_exchange' else 'run_hmc'}` runs its ladders")
+        run_steps = int(run_steps)
+        if run_steps < 0:
+            raise ValueError(f"run_steps={run_steps} must not be negative")
+        shape = (dyn.batch_size, dyn.x_dim) if x is None else tuple(x.shape)
+        if len(shape) != 2 or shape[1] != dyn.x_dim:
+            raise ValueError(f"{who}: x of shape {shape}: expected [B, {dyn.x_dim}]")
+        betas = _runs.chain_axis(beta, run_steps, shape[0], who=who, name="beta", positive=False)
+        x = _lib.as_dev(np.random.randn(*shape) if x is None else x, dyn._device)
+        return run_steps, x, betas
+
+    def _exchange_run(self, run_steps, x, betas, keep_samples, after=None):
+        """`run` at the betas of `_runs.chain_axis` on checked arguments, a launch per step.  The array goes to the
+        device once and every step takes its row view (or, without a chain axis, its float).  `after(s, x, beta_row)`
+        is called behind step s (from 1) with the state it left and the device view of the betas it ran with ([B], or
+        [1] without a chain axis), and returns the state the next step starts from."""
+        b64, b32, (step_stride, chain_stride) = betas
+        B = x.shape[0]
+        if run_steps == 0:
+            out = _runs.empty_run(self.HISTORIES, x, keep_samples)
+            out["mean_accept"] = self.stats.mean_accept()
+        else:
+            beta_dev = _lib.as_dev(b32, x.device)
+
+            def row(i):
+                return beta_dev[i * step_stride:i * step_stride + (B if chain_stride else 1)]
+
+            def step(i, x_now):
+                if chain_stride:
+                    return self._step(x_now, None, row(i))
+                return self._step(x_now, float(b32[i * step_stride]))
+
+            out = self._run_steps(run_steps, x, keep_samples, step,
+                                  None if after is None else lambda s, x_now: after(s, x_now, row(s - 1)))
+        out["plaq_exact"] = self._plaq_exact_last(b64)
+        return out
+
+    @staticmethod
+    def _plaq_exact_last(b64):
+        """`plaq_exact` at the last step's beta: a float, or a [B] array where beta has a chain axis."""
+        last = _runs.last_step(b64)
+        return u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
+
+    def run_exchange(self, run_steps, beta, x=None, keep_samples=False, replicas=None, swap_every=1, first_parity=0,
+                     replica0=None):
+        """`run` of an L2HMC dynamics with replica exchange (parallel tempering) between the columns of a ladder: the
+        trained sampler, tempered.  `beta` as `run` takes it -- usually [1, B], G rungs repeated B / G times.
+        `replicas=None`: `run` itself, bit for bit (the other three arguments are then ignored).  `replicas=G`: columns
+        [g * G, (g + 1) * G) are one group of G rungs.  After every MCMC step s (counting from 1) with
+        s % swap_every == 0 -- the last step of the call included -- ONE round (`swap_replicas`) runs on the state that
+        step left, with parity (first_parity + s // swap_every - 1) % 2 and the betas step s ran with.  Beta belongs to
+        the COLUMN: configurations move, rungs stay.  The run is the loop `run(swap_every, ...)`,
+        `swap_replicas(...)`, bit for bit, on the dynamics' one draw counter: a step takes the next even-aligned pair
+        of streams, a round the next stream.  Every L2HMC step is a launch of its own anyway, so the rounds are launches
+        of their own between them (l2hmc_gauge_replica_swap) -- there is no in-launch form here, and `in_launch` is not
+        read.  `samples[s]` is what step s wrote, before any round; `samples_out` the state after the last round.
+        Added to `run`'s dictionary, as in `run_hmc_exchange` (n_r = run_steps // swap_every rounds): swap_p [n_r, B]
+        float32 (p at the lower chain of every proposed pair, NaN elsewhere), swapped [n_r, B] bool, replica [n_r, B]
+        int32 (the label of the configuration in column c after the round; labels start as arange(B) or as `replica0`,
+        the last row of an earlier call, which continues with first_parity = (first_parity + n_r) % 2 of that call;
+        `self.replica` holds them on the device) and swap_rate [G - 1].  Nothing is exchanged between ranks.
+        ValueError, before any draw or plan: a plain-HMC dynamics (`run_hmc_exchange` runs those), what `run` refuses,
+        replicas < 2, a batch that is no multiple of it, swap_every < 1, first_parity not 0 or 1, a replica0 that is
+        not int32 [B]."""
+        if replicas is None and _runs.ndim(beta) <= 1:
+            if self.dynamics.hmc:
+                raise ValueError("run_exchange: the dynamics is plain HMC (hmc=True): `run_hmc_exchange` runs its "
+                                 "ladders")
+            return self.run(run_steps, beta, x, keep_samples)
+        run_steps, x, betas = self._run_ladder_args("run_exchange", run_steps, beta, x)
+        if replicas is None:
+            return self._exchange_run(run_steps, x, betas, keep_samples)
+        B = x.shape[0]
+        G, k, parity0, _ = _runs.check_replicas(replicas, B, swap_every, first_parity, who="run_exchange")
+        labels = _runs.replica_labels(replica0, B, who="run_exchange")
+        rounds = {"swap_p": [], "swapped": [], "replica": []}
+        if run_steps > 0:
+            self.replica = _lib.as_dev(labels, x.device, torch.int32)
+        chain_stride = betas[2][1]
+
+        def after(s, x_now, beta_row):
+            if s % k == 0:
+                if keep_samples:
+                    x_now = x_now.clone()                  # (the round is in place: the step's output stays the sample)
+                p, sw, _ = self._swap_round(x_now, beta_row, chain_stride, G, (parity0 + s // k - 1) % 2)
+                rounds["swap_p"].append(p)
+                rounds["swapped"].append(sw)
+                rounds["replica"].append(self.replica.clone())
+            return x_now
+
+        out = self._exchange_run(run_steps, x, betas, keep_samples, after)
+        return _runs.exchange_histories(out, rounds, B, G)
 
     def _run_chunks(self, run_steps, x, keep_samples, plan, entry, front, cut_every=None, after=None, rounds=None):
         """Plain-HMC steps through `_runs.run_chunks` (`cut_every`, `after`: see there), ONE launch of `entry` per
@@ -250,9 +392,7 @@ class GaugeSampler:
             else:
                 out = self._run_chunks(run_steps, x, keep_samples, plan, "l2hmc_gauge_hmc_run_ladder", front,
                                        *(exchange(beta_dev) if exchange else ()))
-        # the last step's beta (an empty run with an empty schedule has none)
-        last = b64 if b64.ndim == 0 else b64[-1] if b64.shape[0] else np.full(b64.shape[1:], np.nan)
-        out["plaq_exact"] = u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
+        out["plaq_exact"] = self._plaq_exact_last(b64)
         return out
 
     def swap_replicas(self, x, beta, replicas, parity):

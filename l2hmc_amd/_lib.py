@@ -278,6 +278,12 @@ def run_draw_index(draws, n_steps):
     return d, 2 * (d + int(n_steps) - 1) + 2
 
 
+def exchange_rounds(n_steps, swap_every, swap_phase):
+    """The rounds inside `n_steps` steps that start `swap_phase` steps into a period of `swap_every`: one after every
+    step that completes a period."""
+    return (int(swap_phase) + int(n_steps)) // int(swap_every)
+
+
 def exchange_run_draw_index(draws, n_steps, swap_every, swap_phase):
     """The draws of `n_steps` native steps with the replica-exchange rounds between them in ONE launch
     (l2hmc_gauge_hmc_run_exchange): what the loop `step_draw_index` per step, `draws += 1` per round hands out, a round
@@ -287,7 +293,7 @@ def exchange_run_draw_index(draws, n_steps, swap_every, swap_phase):
     n, k, ph = int(n_steps), int(swap_every), int(swap_phase)
     d0, _ = step_draw_index(draws)
     d_last = d0 + n - 1 + (ph + n - 1) // k                 # the rounds ahead of the last step
-    return d0, (ph + n) // k, 2 * d_last + (3 if (ph + n) % k == 0 else 2)
+    return d0, exchange_rounds(n, k, ph), 2 * d_last + (3 if (ph + n) % k == 0 else 2)
 
 
 def as_dev(a, device=None, dtype=torch.float32):

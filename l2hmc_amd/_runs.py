@@ -1,5 +1,6 @@
 """What the "many MCMC steps in one launch" runs of GaugeSampler and DynamicsSampler share, host code only: the rule for
-a value with an optional step axis and chain axis, the step-size rule, the empty run, and the ONE loop over chunks."""
+a value with an optional step axis and chain axis, the rule for one value per chain, the step-size rule, the ONE
+replica-exchange schedule (`Exchange`), the empty run, and the ONE loop over chunks."""
 import numpy as np
 import torch
 
@@ -41,6 +42,31 @@ def chain_axis(value, run_steps, B, *, who, name, positive):
     if not (np.isfinite(v32) & ((v32 > 0) if positive else (v32 >= 0))).all():
         raise ValueError(f"{who}: every {name} must be finite and {'> 0' if positive else 'not negative'} (in float32)")
     return v, np.ascontiguousarray(v32).reshape(-1), strides[v.shape]
+
+
+def rows_from(flat_dev, strides):
+    """s0 -> (the values from step s0's row on, step_stride, chain_stride) as the ladder entries and the rounds take
+    them.  `flat_dev`: `chain_axis`' flat array on the device, where it goes once per run; every chunk starts at its own
+    row, and the row step s (from 1) ran with is the one from s - 1 on."""
+    step_stride, chain_stride = strides
+    return lambda s0: (flat_dev[s0 * step_stride:], step_stride, chain_stride)
+
+
+def per_chain(value, B, device, *, who, name, scalar=None, sign=None, hint=""):
+    """One value per chain (`step`'s and `swap_replicas`' beta or temperature) -> (float32 device tensor, chain_stride):
+    [B] or [1, B] -> ([B], 1); one value -> ([1], 0) where `scalar` (the word the message has for it) is given.  A
+    float32 tensor [B] or [1, B] on `device` (not the CPU) stays there, unchecked.  ValueError for another shape, and
+    with `sign` ("not negative" or "> 0") for an entry that, in float32, is not finite or not that."""
+    if (isinstance(value, torch.Tensor) and value.device == device and device.type != "cpu"
+            and value.dtype == torch.float32 and tuple(value.shape) in ((B,), (1, B))):
+        return value.reshape(-1), 1                        # (a ladder that is on the device already stays there)
+    v, v32 = _float32(value)
+    if v.shape not in ((B,), (1, B)) and (scalar is None or v.ndim):
+        raise ValueError(f"{who}: {name} of shape {v.shape}: expected {scalar + ', ' if scalar else ''}[{B}] or "
+                         f"[1, {B}]{hint}")
+    if sign is not None and not (np.isfinite(v32) & ((v32 > 0) if sign == "> 0" else (v32 >= 0))).all():
+        raise ValueError(f"{who}: every {name} must be finite and {sign} (in float32)")
+    return _lib.as_dev(np.ascontiguousarray(v32).reshape(-1), device), int(v.ndim > 0)
 
 
 def step_sizes(eps, B, who="run_hmc"):
@@ -117,6 +143,67 @@ def exchange_histories(out, rounds, B, G):
     # the mean of `swapped` over rounds and groups, as NumPy forms it: the exact count over the number of entries
     out["swap_rate"] = counts / np.float64(n_r * (B // G)) if n_r else np.full(G - 1, np.nan)
     return out
+
+
+class Exchange:
+    """The replica-exchange schedule of ONE run, for both samplers: groups of `G` columns, a round after every step s
+    (from 1) with s % k == 0, of parity (parity0 + s // k - 1) % 2, on the values step s ran with; the labels start as
+    `labels` (int32 [B] on the host).  The only place that knows which steps a round follows, how the rounds' results
+    are collected and how they complete the run's dictionary.  A sampler hands it what differs: its `_swap_round` for
+    rounds between the launches, its entry's arguments (`chunk`) for rounds inside them."""
+    NAMES = ("swap_p", "swapped", "replica")
+
+    def __init__(self, G, k, parity0, labels, B):
+        self.G, self.k, self.parity0, self.labels, self.B = G, k, parity0, labels, B
+        self.rounds = {name: [] for name in self.NAMES}    # per round a [B] device tensor; `in_launch`: [n_r, B] each
+        self.replica = None
+
+    def start(self, device):
+        """A run of 1 step or more starts: the labels on the device, which the sampler keeps as its `replica`."""
+        self.replica = _lib.as_dev(self.labels, device, torch.int32)
+        return self.replica
+
+    def parity_after(self, s):
+        """The parity of the round that follows step s (from 1), or None where none does."""
+        return (self.parity0 + s // self.k - 1) % 2 if s % self.k == 0 else None
+
+    def between(self, swap_round, rows, clone=False):
+        """Rounds as launches of their own: the `after(s, x)` of `run_chunks` (with `cut_every` = k) or of a loop over
+        steps; it returns the state the next step starts from.  `swap_round(x, values, chain_stride, G, parity)` is the
+        sampler's round, in place, taking one stream of its counter; `rows`: `rows_from`.  `clone`: the round gets a
+        copy of x, where x itself is kept as the step's sample."""
+        def after(s, x_now):
+            parity = self.parity_after(s)
+            if parity is not None:
+                x_now = x_now.clone() if clone else x_now
+                values, _, chain_stride = rows(s - 1)
+                p, swapped, _ = swap_round(x_now, values, chain_stride, self.G, parity)
+                for name, r in zip(self.NAMES, (p, swapped, self.replica.clone())):
+                    self.rounds[name].append(r)
+            return x_now
+        return after
+
+    def in_launch(self, run_steps, device):
+        """Rounds inside the launches of a run of `run_steps` steps: the three device histories, allocated once."""
+        self.rounds = {name: torch.empty(run_steps // self.k, self.B, dtype=dtype, device=device)
+                       for name, dtype in zip(self.NAMES, (torch.float32, torch.uint8, torch.int32))}
+
+    def place(self, s0, n):
+        """Steps [s0, s0 + n) in the schedule -> (steps into the period at s0, parity of the chunk's first round, its
+        row in the histories, rounds in the chunk)."""
+        phase, row = s0 % self.k, s0 // self.k
+        return phase, (self.parity0 + row) % 2, row, _lib.exchange_rounds(n, self.k, phase)
+
+    def chunk(self, s0, n):
+        """What an exchange entry takes for steps [s0, s0 + n) -> ((group, swap_every, swap_phase, first_parity), the
+        chunk's slices of the three histories -- NULL for a chunk without a round --, rounds in the chunk)."""
+        phase, parity, row, n_rounds = self.place(s0, n)
+        hist = tuple(self.rounds[name][row:] if n_rounds else None for name in self.NAMES)
+        return (self.G, self.k, phase, parity), hist, n_rounds
+
+    def finish(self, out):
+        """The run's dictionary `out` with the rounds' histories and swap_rate added (`exchange_histories`)."""
+        return exchange_histories(out, self.rounds, self.B, self.G)
 
 
 def empty_run(names, x, keep_samples):

@@ -127,9 +127,7 @@ class DynamicsSampler:
         array goes to the device once and every chunk starts at its own row.  `temps` None: (NULL, 0, 0)."""
         if temps is None:
             return lambda s0: (None, 0, 0)
-        flat, step_stride, chain_stride = temps
-        temps_dev = _lib.as_dev(flat, dev)
-        return lambda s0: (temps_dev[s0 * step_stride:], step_stride, chain_stride)
+        return _runs.rows_from(_lib.as_dev(temps[0], dev), temps[1:])
 
     def _run_launches(self, run_steps, x, keep_samples, plan, entry, middle, streams, cut_every=None, after=None):
         """ONE launch of `entry` per chunk (`_runs.run_chunks`, which takes `cut_every` and `after`), `streams` per
@@ -186,14 +184,14 @@ class DynamicsSampler:
 
     def _exchange_args(self, who, run_steps, x, temperature, replicas, swap_every, first_parity, replica0):
         """What the two exchange runs (`who`) check alike, before any launch -> (run_steps, start on the device,
-        `_temperatures`, G, swap_every, first_parity, starting labels on the host)."""
+        `_temperatures`, the run's `_runs.Exchange`)."""
         if temperature is None:
             raise ValueError(f"{who}: replicas={replicas} without temperature=: the rungs of a replica group are the "
                              "columns of a temperature ladder")
         run_steps, x, temps = self._start(who, run_steps, x, temperature)
         B = x.shape[0]
         G, k, fp, _ = _runs.check_replicas(replicas, B, swap_every, first_parity, who=who, most=self.MAX_REPLICAS)
-        return run_steps, x, temps, G, k, fp, _runs.replica_labels(replica0, B, who)
+        return run_steps, x, temps, _runs.Exchange(G, k, fp, _runs.replica_labels(replica0, B, who), B)
 
     def run_hmc_exchange(self, run_steps, x=None, keep_samples=True, temperature=None, eps=None, replicas=None,
                          swap_every=1, first_parity=0, replica0=None):
@@ -223,35 +221,29 @@ class DynamicsSampler:
             return self.run_hmc(run_steps, x, keep_samples, temperature, eps)
         who, dyn = "run_hmc_exchange", self.dynamics
         self._check_hmc(who)
-        run_steps, x, temps, G, k, parity0, labels = self._exchange_args(who, run_steps, x, temperature, replicas,
-                                                                         swap_every, first_parity, replica0)
+        run_steps, x, temps, exchange = self._exchange_args(who, run_steps, x, temperature, replicas, swap_every,
+                                                            first_parity, replica0)
         B = x.shape[0]
         step = None if eps is None else _runs.step_sizes(eps, B, who)
         if run_steps == 0:
-            out = _runs.empty_run(("px",), x, keep_samples)
-            return self._finish(_runs.exchange_histories(out, dict(swap_p=None, swapped=None, replica=None), B, G))
+            return self._finish(exchange.finish(_runs.empty_run(("px",), x, keep_samples)))
         plan, eps_chain = _runs.plan_with_step_sizes(dyn, step, x.device)
         temps_from = self._temps_from(temps, x.device)
-        n_r = run_steps // k
-        self.replica = _lib.as_dev(labels, x.device, torch.int32)
-        rounds = {"swap_p": torch.empty(n_r, B, dtype=torch.float32, device=x.device),
-                  "swapped": torch.empty(n_r, B, dtype=torch.uint8, device=x.device),
-                  "replica": torch.empty(n_r, B, dtype=torch.int32, device=x.device)}
+        self.replica = exchange.start(x.device)
+        exchange.in_launch(run_steps, x.device)
         px = torch.empty(run_steps, B, dtype=torch.float32, device=x.device)
 
         def launch(s0, n, x_in, x_next, samples_dev):
             # a chunk may end inside a swap period: it passes where in the period it starts and its first round's
             # parity, and moves the counter by its steps' streams and its rounds'
-            r0, n_rounds = s0 // k, (s0 % k + n) // k
-            hist = [rounds[name][r0:] if n_rounds else None for name in ("swap_p", "swapped", "replica")]
+            place, hist, n_rounds = exchange.chunk(s0, n)
             _lib.call("l2hmc_small_hmc_run_exchange", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
-                      *temps_from(s0), eps_chain, G, k, s0 % k, (parity0 + r0) % 2, self.replica, px[s0:], samples_dev,
-                      *hist, device=dyn._device)
+                      *temps_from(s0), eps_chain, *place, self.replica, px[s0:], samples_dev, *hist, device=dyn._device)
             dyn._draws += 2 * n + n_rounds
 
         out = _runs.run_chunks(run_steps, x, self.steps_per_launch, keep_samples, launch)
         out["px"] = px.cpu().numpy()
-        return self._finish(_runs.exchange_histories(out, rounds, B, G))
+        return self._finish(exchange.finish(out))
 
     def swap_replicas(self, x, temperature, replicas, parity):
         """ONE replica-exchange round on device state x [B, x_dim], IN PLACE (l2hmc_small_replica_swap), for a
@@ -273,16 +265,8 @@ class DynamicsSampler:
         replica = getattr(self, "replica", None)
         if replica is not None and tuple(replica.shape) != (B,):
             raise ValueError(f"swap_replicas: the sampler's labels are {tuple(replica.shape)}: expected [{B}] (or None)")
-        if (isinstance(temperature, torch.Tensor) and temperature.is_cuda and temperature.dtype == torch.float32
-                and temperature.numel() == B):
-            temps_dev, stride = temperature.reshape(-1), 1       # (a ladder that is on the device already stays there)
-        else:
-            _, t = _runs._float32(temperature)
-            if t.shape not in ((), (B,), (1, B)):
-                raise ValueError(f"swap_replicas: temperature of shape {t.shape}: expected a scalar, [{B}] or [1, {B}]")
-            if not (np.isfinite(t) & (t > 0)).all():
-                raise ValueError("swap_replicas: every temperature must be finite and > 0 (in float32)")
-            temps_dev, stride = _lib.as_dev(np.ascontiguousarray(t).reshape(-1), x.device), int(t.ndim > 0)
+        temps_dev, stride = _runs.per_chain(temperature, B, x.device, who="swap_replicas", name="temperature",
+                                            scalar="a scalar", sign="> 0")
         return self._swap_round(x, temps_dev, stride, G, parity)
 
     def _swap_round(self, x, temps_dev, chain_stride, G, parity):
@@ -317,29 +301,16 @@ class DynamicsSampler:
             raise NotImplementedError(
                 f"{who}: temperatures per chain need the one-launch path (an L2HMC dynamics the one-launch kernel "
                 "holds: not layer by layer, and steps_per_launch > 1)")
-        run_steps, x, temps, G, k, parity0, labels = self._exchange_args(who, run_steps, x, temperature, replicas,
-                                                                         swap_every, first_parity, replica0)
-        B = x.shape[0]
-        rounds = {"swap_p": [], "swapped": [], "replica": []}
+        run_steps, x, temps, exchange = self._exchange_args(who, run_steps, x, temperature, replicas, swap_every,
+                                                            first_parity, replica0)
         if run_steps == 0:
-            out = _runs.empty_run(("px",), x, keep_samples)
-            return self._finish(_runs.exchange_histories(out, rounds, B, G))
-        self.replica = _lib.as_dev(labels, x.device, torch.int32)
+            return self._finish(exchange.finish(_runs.empty_run(("px",), x, keep_samples)))
+        self.replica = exchange.start(x.device)
         temps_from = self._temps_from(temps, x.device)
-
-        def after(s, x_now):
-            if s % k == 0:
-                # the temperatures step s ran with: row s - 1 of a schedule, the only row otherwise.  The round takes
-                # one stream of the dynamics' counter; the next chunk reads the counter when it is launched
-                t, _, chain_stride = temps_from(s - 1)
-                p, sw, _ = self._swap_round(x_now, t, chain_stride, G, (parity0 + s // k - 1) % 2)
-                rounds["swap_p"].append(p)
-                rounds["swapped"].append(sw)
-                rounds["replica"].append(self.replica.clone())
-
+        # a round takes one stream of the dynamics' counter; the next chunk reads the counter when it is launched
         out = self._run_launches(run_steps, x, keep_samples, dyn._plan(), "l2hmc_small_run_tempered", temps_from,
-                                 streams=4, cut_every=k, after=after)
-        return self._finish(_runs.exchange_histories(out, rounds, B, G))
+                                 streams=4, cut_every=exchange.k, after=exchange.between(self._swap_round, temps_from))
+        return self._finish(exchange.finish(out))
 
     def generate_trajectories(self, temp=1., num_samples=500, num_steps=100, x=None):
         """mog_model.py:394-421 -> (trajectories [num_steps, num_samples, x_dim], px [num_steps, num_samples]).  As in

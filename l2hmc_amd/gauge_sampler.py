@@ -54,26 +54,14 @@ class GaugeSampler:
         `dynamics.both_directions = False` the plan carries L2HMC_PLAN_SELECTED_ONLY: each chain is integrated
         only in the direction its coin picks -- same random streams, same chains, half the work.
         `beta`: a float, or for an L2HMC dynamics one value per chain -- [B] or [1, B] as a list / array (checked:
-        finite and not negative in float32), or a float32 tensor of B elements on x's device, which is used as it is
-        (l2hmc_gauge_mcmc_step_ladder: chain c has the bits of the step of the whole batch at beta[c])."""
-        return self._step(x, beta, self._chain_betas(beta, x.shape[0], x.device))
-
-    def _chain_betas(self, beta, B, device):
-        """`step`'s beta -> None for one value, or the float32 [B] device tensor of a beta per chain.  ValueError
-        before any draw for another shape, a bad value, and a plain-HMC dynamics (`run_hmc` runs its ladders)."""
+        finite and not negative in float32), or a float32 tensor [B] or [1, B] on x's device, which is used as it is
+        (`_runs.per_chain`; l2hmc_gauge_mcmc_step_ladder: chain c has the bits of the step of the whole batch at beta[c])."""
         if _runs.ndim(beta) == 0:
-            return None
-        if self.dynamics.hmc:
+            return self._step(x, beta)
+        if self.dynamics.hmc:                              # (ValueErrors before any draw)
             raise ValueError("step: a beta per chain on a plain-HMC dynamics (hmc=True): `run_hmc` runs it")
-        if (isinstance(beta, torch.Tensor) and beta.device == device and beta.device.type != "cpu"
-                and beta.dtype == torch.float32 and tuple(beta.shape) in ((B,), (1, B))):
-            return beta.reshape(-1)                        # (a ladder that is on the device already stays there)
-        b, b32 = _runs._float32(beta)
-        if b.shape not in ((B,), (1, B)):
-            raise ValueError(f"step: beta of shape {b.shape}: expected a float, [{B}] or [1, {B}] (one per chain)")
-        if not (np.isfinite(b32) & (b32 >= 0)).all():
-            raise ValueError("step: every beta must be finite and not negative (in float32)")
-        return _lib.as_dev(np.ascontiguousarray(b32).reshape(-1), device)
+        return self._step(x, None, _runs.per_chain(beta, x.shape[0], x.device, who="step", name="beta", scalar="a float",
+                                                   sign="not negative", hint=" (one per chain)")[0])
 
     def _step(self, x, beta, beta_dev=None):
         """`step` on checked arguments: at the float `beta`, or with `beta_dev` (float32 [B] on the device, may be a
@@ -148,7 +136,7 @@ class GaugeSampler:
         shape, with an entry that is negative or not finite, and on a plain-HMC dynamics (`run_hmc` runs those)."""
         dyn = self.dynamics
         if _runs.ndim(beta) > 1:
-            return self._exchange_run(*self._run_ladder_args("run", run_steps, beta, x), keep_samples)
+            return self._exchange_run(*self._start("run", run_steps, beta, x)[:3], keep_samples)
         if x is None:
             x = _lib.as_dev(np.random.randn(dyn.batch_size, dyn.x_dim), dyn._device)
         else:
@@ -195,54 +183,60 @@ class GaugeSampler:
 
     HISTORIES = ("px", "actions", "plaqs", "charges", "charge_diff")
 
-    def _run_ladder_args(self, who, run_steps, beta, x):
-        """What `run` with a chain axis on beta and `run_exchange` refuse, before any draw or plan -> (run_steps,
-        start on the device, (`_runs.chain_axis` of beta))."""
+    def _start(self, who, run_steps, beta, x, eps=None):
+        """What `run` with a chain axis on beta, `run_exchange` and `run_hmc` (`who`; `run_hmc_exchange` checks as
+        `run_hmc`) refuse, before any draw or plan -> (run_steps, start on the device, `_runs.chain_axis` of beta,
+        `_runs.step_sizes` of eps or None)."""
         dyn = self.dynamics
-        if dyn.hmc:
+        if who == "run_hmc" and not dyn.hmc:
+            raise ValueError("run_hmc: the dynamics is an L2HMC sampler (hmc=False): `run` runs it")
+        if who != "run_hmc" and dyn.hmc:
             raise ValueError(f"{who}: the dynamics is plain HMC (hmc=True): "
                              f"`{'run_hmc_exchange' if who == 'run_exchange' else 'run_hmc'}` runs its ladders")
         run_steps = int(run_steps)
         if run_steps < 0:
             raise ValueError(f"run_steps={run_steps} must not be negative")
-        shape = (dyn.batch_size, dyn.x_dim) if x is None else tuple(x.shape)
+        shape = (dyn.batch_size, dyn.x_dim) if x is None else tuple(np.shape(x))
         if len(shape) != 2 or shape[1] != dyn.x_dim:
             raise ValueError(f"{who}: x of shape {shape}: expected [B, {dyn.x_dim}]")
         betas = _runs.chain_axis(beta, run_steps, shape[0], who=who, name="beta", positive=False)
+        step = None if eps is None else _runs.step_sizes(eps, shape[0])
         x = _lib.as_dev(np.random.randn(*shape) if x is None else x, dyn._device)
-        return run_steps, x, betas
+        return run_steps, x, betas, step
 
-    def _exchange_run(self, run_steps, x, betas, keep_samples, after=None):
-        """`run` at the betas of `_runs.chain_axis` on checked arguments, a launch per step.  The array goes to the
-        device once and every step takes its row view (or, without a chain axis, its float).  `after(s, x, beta_row)`
-        is called behind step s (from 1) with the state it left and the device view of the betas it ran with ([B], or
-        [1] without a chain axis), and returns the state the next step starts from."""
-        b64, b32, (step_stride, chain_stride) = betas
-        B = x.shape[0]
+    def _ladder_frame(self, run_steps, x, betas, keep_samples, body):
+        """What the runs at the betas of `_runs.chain_axis` share: the empty run; `body(rows)` for 1 step or more,
+        `rows` the `_runs.rows_from` of the betas, which go to the device once; `plaq_exact` at the last step's beta, a
+        float, or a [B] array where beta has a chain axis."""
+        b64, b32, strides = betas
         if run_steps == 0:
             out = _runs.empty_run(self.HISTORIES, x, keep_samples)
             out["mean_accept"] = self.stats.mean_accept()
         else:
-            beta_dev = _lib.as_dev(b32, x.device)
-
-            def row(i):
-                return beta_dev[i * step_stride:i * step_stride + (B if chain_stride else 1)]
-
-            def step(i, x_now):
-                if chain_stride:
-                    return self._step(x_now, None, row(i))
-                return self._step(x_now, float(b32[i * step_stride]))
-
-            out = self._run_steps(run_steps, x, keep_samples, step,
-                                  None if after is None else lambda s, x_now: after(s, x_now, row(s - 1)))
-        out["plaq_exact"] = self._plaq_exact_last(b64)
+            out = body(_runs.rows_from(_lib.as_dev(b32, x.device), strides))
+        last = _runs.last_step(b64)
+        out["plaq_exact"] = u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
         return out
 
-    @staticmethod
-    def _plaq_exact_last(b64):
-        """`plaq_exact` at the last step's beta: a float, or a [B] array where beta has a chain axis."""
-        last = _runs.last_step(b64)
-        return u1_plaq_exact(float(last)) if last.ndim == 0 else u1_plaq_exact(last)
+    def _exchange_run(self, run_steps, x, betas, keep_samples, exchange=None):
+        """`run` at the betas of `_runs.chain_axis` on checked arguments, a launch per step, which takes its row view
+        (or, without a chain axis, its float); with an `exchange` (`_runs.Exchange`) its rounds between the steps."""
+        b32, (step_stride, chain_stride) = betas[1:]
+
+        def body(rows):
+            def step(i, x_now):
+                if chain_stride:
+                    return self._step(x_now, None, rows(i)[0])
+                return self._step(x_now, float(b32[i * step_stride]))
+
+            after = None
+            if exchange is not None:
+                self.replica = exchange.start(x.device)
+                # (the round is in place: with `keep_samples` it gets a copy and the step's output stays the sample)
+                after = exchange.between(self._swap_round, rows, clone=keep_samples)
+            return self._run_steps(run_steps, x, keep_samples, step, after)
+
+        return self._ladder_frame(run_steps, x, betas, keep_samples, body)
 
     def run_exchange(self, run_steps, beta, x=None, keep_samples=False, replicas=None, swap_every=1, first_parity=0,
                      replica0=None):
@@ -270,38 +264,25 @@ class GaugeSampler:
                 raise ValueError("run_exchange: the dynamics is plain HMC (hmc=True): `run_hmc_exchange` runs its "
                                  "ladders")
             return self.run(run_steps, beta, x, keep_samples)
-        run_steps, x, betas = self._run_ladder_args("run_exchange", run_steps, beta, x)
+        run_steps, x, betas, _ = self._start("run_exchange", run_steps, beta, x)
         if replicas is None:
             return self._exchange_run(run_steps, x, betas, keep_samples)
-        B = x.shape[0]
-        G, k, parity0, _ = _runs.check_replicas(replicas, B, swap_every, first_parity, who="run_exchange")
-        labels = _runs.replica_labels(replica0, B, who="run_exchange")
-        rounds = {"swap_p": [], "swapped": [], "replica": []}
-        if run_steps > 0:
-            self.replica = _lib.as_dev(labels, x.device, torch.int32)
-        chain_stride = betas[2][1]
+        exchange = self._exchange(x.shape[0], replicas, swap_every, first_parity, replica0, "run_exchange")
+        return exchange.finish(self._exchange_run(run_steps, x, betas, keep_samples, exchange))
 
-        def after(s, x_now, beta_row):
-            if s % k == 0:
-                if keep_samples:
-                    x_now = x_now.clone()                  # (the round is in place: the step's output stays the sample)
-                p, sw, _ = self._swap_round(x_now, beta_row, chain_stride, G, (parity0 + s // k - 1) % 2)
-                rounds["swap_p"].append(p)
-                rounds["swapped"].append(sw)
-                rounds["replica"].append(self.replica.clone())
-            return x_now
+    @staticmethod
+    def _exchange(B, replicas, swap_every, first_parity, replica0, who):
+        """The checked replica-exchange arguments of a run (`who`) of B chains as its `_runs.Exchange`."""
+        G, k, parity0, _ = _runs.check_replicas(replicas, B, swap_every, first_parity, who=who)
+        return _runs.Exchange(G, k, parity0, _runs.replica_labels(replica0, B, who), B)
 
-        out = self._exchange_run(run_steps, x, betas, keep_samples, after)
-        return _runs.exchange_histories(out, rounds, B, G)
-
-    def _run_chunks(self, run_steps, x, keep_samples, plan, entry, front, cut_every=None, after=None, rounds=None):
+    def _run_chunks(self, run_steps, x, keep_samples, plan, entry, front, cut_every=None, after=None, exchange=None):
         """Plain-HMC steps through `_runs.run_chunks` (`cut_every`, `after`: see there), ONE launch of `entry` per
         chunk: l2hmc_gauge_hmc_run or l2hmc_gauge_hmc_run_ladder; `front(s0)` is what it takes between the plan and x_in
         for a chunk from step s0 on.  Histories, `_run_sums`, workspace: once per run.  `run`'s dictionary less
-        `plaq_exact`.  `rounds` = (G, k, parity0, swap_p, swapped, replica_hist): the entry is
-        l2hmc_gauge_hmc_run_exchange, whose chunks are not cut at the rounds -- a round follows every k-th step of the
-        run inside the launch, the chunk from step s0 on starts at phase s0 % k and fills the round histories
-        ([run_steps // k, B] device tensors) from row s0 // k on; the labels are `self.replica`."""
+        `plaq_exact`.  With an `exchange` (`_runs.Exchange`, `in_launch`) the entry is l2hmc_gauge_hmc_run_exchange,
+        whose chunks are not cut at the rounds: a round follows every k-th step of the run inside the launch, and
+        `exchange.chunk` places every chunk in that schedule; the labels are `self.replica`."""
         dyn = self.dynamics
         B, dev = x.shape[0], x.device
         hist = {k: torch.empty(run_steps, B, dtype=torch.float32, device=dev) for k in self.HISTORIES}
@@ -315,13 +296,12 @@ class GaugeSampler:
             # the draw index comes from the dynamics' counter as it stands when the chunk is launched: consecutive from
             # chunk to chunk unless `after` took a stream in between (then the next even-aligned pair).  The counter
             # moves only after the entry returned: a failed launch leaves it where it was
-            if rounds is None:
+            if exchange is None:
                 (draw, draws_after), mid, tail = _lib.run_draw_index(dyn._draws, n), (), ()
             else:
-                G, k, parity0, *round_hist = rounds
-                draw, _, draws_after = _lib.exchange_run_draw_index(dyn._draws, n, k, s0 % k)
-                mid = (G, k, s0 % k, (parity0 + s0 // k) % 2, self.replica)
-                tail = tuple(h[s0 // k:] for h in round_hist)
+                place, tail, _ = exchange.chunk(s0, n)
+                draw, _, draws_after = _lib.exchange_run_draw_index(dyn._draws, n, *place[1:3])
+                mid = (*place, self.replica)
             _lib.call(entry, C.byref(plan), *front(s0), x_in, x_next, B, dyn._seed, draw, n, *mid,
                       *(hist[k][s0:] for k in self.HISTORIES), sums[s0:], samples_dev, *tail, ws, nb,
                       device=dyn._device)
@@ -333,12 +313,6 @@ class GaugeSampler:
         out.update((k, v.cpu().numpy()) for k, v in hist.items())
         out["mean_accept"] = self.stats.mean_accept()
         return out
-
-    @staticmethod
-    def _ladder_betas(beta, run_steps, B):
-        """`run_hmc`'s `beta` by `_runs.chain_axis` -> (float64 as given, flat float32, step_stride, chain_stride)."""
-        b, flat, strides = _runs.chain_axis(beta, run_steps, B, who="run_hmc", name="beta", positive=False)
-        return b, flat, strides[0], strides[1]
 
     def run_hmc(self, run_steps, beta, x=None, eps=None, keep_samples=False):
         """`run` for a plain-HMC dynamics (`hmc=True`) with a chain axis on beta and on the step size: a scan over
@@ -352,48 +326,31 @@ class GaugeSampler:
         or not finite and an eps that is not finite and > 0; NotImplementedError for an hmc dynamics whose plan has no
         one-launch kernel (more than 1024 sites, `fused = False`): `run` takes those, one beta at a time.
         `run_hmc_exchange` is this run with replica exchange between the columns of a ladder."""
-        return self._ladder_run(*self._run_hmc_args(run_steps, beta, x, eps), keep_samples)
-
-    def _run_hmc_args(self, run_steps, beta, x, eps):
-        """What `run_hmc` refuses -> (run_steps, start on the device, `_ladder_betas`, `_runs.step_sizes` or None)."""
-        dyn = self.dynamics
-        if not dyn.hmc:
-            raise ValueError("run_hmc: the dynamics is an L2HMC sampler (hmc=False): `run` runs it")
-        run_steps = int(run_steps)
-        if run_steps < 0:
-            raise ValueError(f"run_steps={run_steps} must not be negative")
-        if x is None:
-            x = np.random.randn(dyn.batch_size, dyn.x_dim)
-        x = _lib.as_dev(x, dyn._device)
-        if x.ndim != 2 or x.shape[1] != dyn.x_dim:
-            raise ValueError(f"run_hmc: x of shape {tuple(x.shape)}: expected [B, {dyn.x_dim}]")
-        betas = self._ladder_betas(beta, run_steps, x.shape[0])
-        return run_steps, x, betas, None if eps is None else _runs.step_sizes(eps, x.shape[0])
+        return self._ladder_run(*self._start("run_hmc", run_steps, beta, x, eps), keep_samples)
 
     def _ladder_run(self, run_steps, x, betas, step, keep_samples, exchange=None, in_launch=False):
-        """What `run_hmc` means, on checked arguments.  `exchange(beta_dev)`, called once when a run of 1 step or more
-        is about to start (its betas are on the device), returns the `cut_every` and `after` of `_run_chunks`, or with
-        `in_launch` its `rounds`."""
-        b64, b32, step_stride, chain_stride = betas
-        if run_steps == 0:
-            out = _runs.empty_run(self.HISTORIES, x, keep_samples)
-            out["mean_accept"] = self.stats.mean_accept()
-        else:
+        """What `run_hmc` means, on checked arguments; with an `exchange` (`_runs.Exchange`) its rounds, between the
+        launches of the run or with `in_launch` inside them."""
+        def body(rows):
             plan, eps_chain = _runs.plan_with_step_sizes(self.dynamics, step, x.device)
             if _lib.lib().l2hmc_gauge_plan_fused(C.byref(plan)) != 1:
                 raise NotImplementedError(
                     "run_hmc: this hmc dynamics has no one-launch kernel (more than 1024 sites, or fused = False): "
                     "`run` takes it through the loop over `step`, one beta at a time")
-            beta_dev = _lib.as_dev(b32, x.device)          # goes over once; every chunk starts at its own row
-            front = lambda s0: (beta_dev[s0 * step_stride:], step_stride, chain_stride, eps_chain)
+            args = (run_steps, x, keep_samples, plan)
+            front = lambda s0: (*rows(s0), eps_chain)
+            if exchange is None:
+                return self._run_chunks(*args, "l2hmc_gauge_hmc_run_ladder", front)
+            self.replica = exchange.start(x.device)        # stays on the device from chunk to chunk
             if in_launch:
-                out = self._run_chunks(run_steps, x, keep_samples, plan, "l2hmc_gauge_hmc_run_exchange", front,
-                                       rounds=exchange(beta_dev))
-            else:
-                out = self._run_chunks(run_steps, x, keep_samples, plan, "l2hmc_gauge_hmc_run_ladder", front,
-                                       *(exchange(beta_dev) if exchange else ()))
-        out["plaq_exact"] = self._plaq_exact_last(b64)
-        return out
+                exchange.in_launch(run_steps, x.device)
+                return self._run_chunks(*args, "l2hmc_gauge_hmc_run_exchange", front, exchange=exchange)
+            # chunks cut at the multiples of k steps, one round after each of them: it takes one stream of the
+            # dynamics' counter, and the next chunk reads the counter when it is launched
+            return self._run_chunks(*args, "l2hmc_gauge_hmc_run_ladder", front, exchange.k,
+                                    exchange.between(self._swap_round, rows))
+
+        return self._ladder_frame(run_steps, x, betas, keep_samples, body)
 
     def swap_replicas(self, x, beta, replicas, parity):
         """ONE replica-exchange round on device state x [B, x_dim], IN PLACE (l2hmc_gauge_replica_swap): columns
@@ -407,14 +364,8 @@ class GaugeSampler:
         if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[1] != dyn.x_dim:
             raise ValueError(f"swap_replicas: x: expected a device tensor [B, {dyn.x_dim}] (exchanged in place)")
         B = x.shape[0]
-        G, _, _, parity = self._check_replicas(replicas, B, parity=parity, who="swap_replicas")
-        if isinstance(beta, torch.Tensor) and beta.is_cuda and beta.dtype == torch.float32 and beta.numel() == B:
-            beta_dev = beta.reshape(-1)                    # (a ladder that is on the device already stays there)
-        else:
-            b = np.asarray(beta.detach().cpu().numpy() if isinstance(beta, torch.Tensor) else beta, dtype=np.float64)
-            if b.shape not in ((B,), (1, B)):
-                raise ValueError(f"swap_replicas: beta of shape {b.shape}: expected [{B}] or [1, {B}]")
-            beta_dev = _lib.as_dev(b.reshape(-1).astype(np.float32), x.device)
+        G, _, _, parity = _runs.check_replicas(replicas, B, parity=parity, who="swap_replicas")
+        beta_dev, _ = _runs.per_chain(beta, B, x.device, who="swap_replicas", name="beta")
         return self._swap_round(x, beta_dev, 1, G, parity)
 
     def _swap_round(self, x, beta_dev, chain_stride, G, parity):
@@ -423,10 +374,6 @@ class GaugeSampler:
         out = replica_swap(x, T, X, G, parity, beta_dev, dyn._seed, dyn._draws, chain_stride, self.replica)
         dyn._draws += 1                                    # one stream, as GaugeDynamics._uniform
         return out
-
-    @staticmethod
-    def _check_replicas(replicas, B, swap_every=1, first_parity=0, parity=0, who="run_hmc_exchange"):
-        return _runs.check_replicas(replicas, B, swap_every, first_parity, parity, who)
 
     def exchange_in_launch(self, replicas):
         """Whether `run_hmc_exchange(..., replicas=replicas)` with `self.in_launch = True` is served for this dynamics
@@ -466,54 +413,18 @@ class GaugeSampler:
         Nothing is exchanged between ranks: a group lives on one rank.  ValueError, on top of `run_hmc`'s, for
         replicas < 2, a batch that is no multiple of it, swap_every < 1, first_parity not 0 or 1, and a replica0 that
         is not int32 [B]."""
-        run_steps, x, betas, step = self._run_hmc_args(run_steps, beta, x, eps)
+        run_steps, x, betas, step = self._start("run_hmc", run_steps, beta, x, eps)
         if replicas is None:
             return self._ladder_run(run_steps, x, betas, step, keep_samples)
-        B = x.shape[0]
-        G, k, parity0, _ = self._check_replicas(replicas, B, swap_every, first_parity)
-        labels = _runs.replica_labels(replica0, B)
-        if self.in_launch:
-            return self._exchange_in_launch(run_steps, x, betas, step, keep_samples, G, k, parity0, labels)
-        # the exchange layer over `_ladder_run`: chunks cut at the multiples of k steps, one round after each of them
-        step_stride, chain_stride = betas[2:]
-        rounds = {"swap_p": [], "swapped": [], "replica": []}
-
-        def exchange(beta_dev):
-            self.replica = _lib.as_dev(labels, x.device, torch.int32)
-
-            def after(s, x_now):
-                if s % k == 0:
-                    # the betas step s ran with: row s - 1 of a schedule, the only row otherwise.  The round takes one
-                    # stream of the dynamics' counter; the next chunk reads the counter when it is launched
-                    p, sw, _ = self._swap_round(x_now, beta_dev[(s - 1) * step_stride:], chain_stride, G,
-                                                (parity0 + s // k - 1) % 2)
-                    rounds["swap_p"].append(p)
-                    rounds["swapped"].append(sw)
-                    rounds["replica"].append(self.replica.clone())
-            return k, after
-
-        out = self._ladder_run(run_steps, x, betas, step, keep_samples, exchange)
-        return _runs.exchange_histories(out, rounds, B, G)
-
-    def _exchange_in_launch(self, run_steps, x, betas, step, keep_samples, G, k, parity0, labels):
-        """`run_hmc_exchange` with the rounds inside the run's launches, on checked arguments."""
-        L, B, dev = _lib.lib(), x.shape[0], x.device
-        if L.l2hmc_gauge_hmc_run_exchange_served(C.byref(self.dynamics._plan()), G) != 1:
+        exchange = self._exchange(x.shape[0], replicas, swap_every, first_parity, replica0, "run_hmc_exchange")
+        in_launch = bool(self.in_launch)
+        if in_launch and not self.exchange_in_launch(exchange.G):
             raise NotImplementedError(
-                "run_hmc_exchange with in_launch = True: " + L.l2hmc_last_error().decode() + ".  The rule: lcm(replicas, "
-                "chains per workgroup of the ladder run) x rows per chain x threads per row must not exceed 1024, on a "
-                "lattice of at most 512 sites whose plan has the one-launch kernel (`exchange_in_launch(replicas)`); "
-                "in_launch = False takes every lattice and group")
-        n_r = run_steps // k
-        hist = (torch.empty(n_r, B, dtype=torch.float32, device=dev), torch.empty(n_r, B, dtype=torch.uint8, device=dev),
-                torch.empty(n_r, B, dtype=torch.int32, device=dev))
-
-        def exchange(beta_dev):
-            self.replica = _lib.as_dev(labels, dev, torch.int32)     # stays on the device from chunk to chunk
-            return (G, k, parity0, *hist)
-
-        out = self._ladder_run(run_steps, x, betas, step, keep_samples, exchange, in_launch=True)
-        return _runs.exchange_histories(out, dict(zip(("swap_p", "swapped", "replica"), hist)), B, G)
+                "run_hmc_exchange with in_launch = True: " + _lib.lib().l2hmc_last_error().decode()
+                + ".  The rule: lcm(replicas, chains per workgroup of the ladder run) x rows per chain x threads per "
+                "row must not exceed 1024, on a lattice of at most 512 sites whose plan has the one-launch kernel "
+                "(`exchange_in_launch(replicas)`); in_launch = False takes every lattice and group")
+        return exchange.finish(self._ladder_run(run_steps, x, betas, step, keep_samples, exchange, in_launch))
 
     @staticmethod
     def run_dicts(out, beta):

@@ -160,3 +160,57 @@ def test_without_replicas_it_is_run(la, both):
         assert dyn._draws == draws
         assert_same_run(got, want, HIST + ("samples",), "replicas=None")
         assert "swap_p" not in got and np.array_equal(got["plaq_exact"], want["plaq_exact"])
+
+
+def _bits(values):
+    """The tensors of a tuple (dictionaries of tensors among them), in order, as integer arrays: NaN equals itself."""
+    flat = []
+    for v in values:
+        for t in ([v[key] for key in sorted(v)] if isinstance(v, dict) else [v]):
+            flat.append((t.view(torch.int32) if t.dtype == torch.float32 else t).cpu().numpy())
+    return flat
+
+
+def _assert_device_ladders_are_the_host_ladder(call, ladder, what):
+    """`call(ladder)` -> tensors; as a float32 device tensor [B] and [1, B] the ladder stays where it is and gives the
+    bits the NumPy array gives; [B, 1] has B elements too and is none of the documented shapes."""
+    want = _bits(call(ladder))
+    on_device = torch.as_tensor(ladder, dtype=torch.float32, device="cuda")
+    for shaped in (on_device, on_device[None, :]):
+        got = _bits(call(shaped))
+        assert len(got) == len(want) >= 4
+        assert all(np.array_equal(g, w) for g, w in zip(got, want)), (what, tuple(shaped.shape))
+    with pytest.raises(ValueError, match=f"{what}: .* of shape \\({ladder.size}, 1\\): expected"):
+        call(on_device[:, None])
+
+
+def test_a_ladder_on_the_device_is_the_same_ladder_from_the_host(la):
+    """`step` and the `swap_replicas` of both samplers, 8 chains in groups of 4 rungs: a 4 x 4 lattice and a mixture of
+    two Gaussians in 2 dimensions."""
+    from oracle import dynamics as od
+    from tests import toy_cases as tc
+    B, G = 8, 4
+    dyn = _dyn(4, 4, 2, 0.2, B)
+    smp, x0, beta = la.GaugeSampler(dyn), _x0(B, 32), _ladder(B, G)[0]
+    labels = torch.arange(B, dtype=torch.int32, device="cuda")
+
+    def step(b):
+        dyn._draws = 40
+        return smp.step(x0, b)
+
+    def swap(sampler, start):
+        def call(values):
+            sampler.dynamics._draws, sampler.replica, x = 40, labels.clone(), start.clone()
+            return (x, sampler.replica, *sampler.swap_replicas(x, values, G, 0))
+        return call
+
+    _assert_device_ladders_are_the_host_ladder(step, beta, "step")
+    _assert_device_ladders_are_the_host_ladder(swap(smp, x0), beta, "swap_replicas")
+    assert swap(smp, x0)(beta)[3].any()                    # (a round that exchanges something)
+
+    toy = la.Dynamics(2, tc.target(2, 2, tc.M)[1].get_energy_function(), trajectory_length=3, eps=0.1,
+                      use_temperature=True, seed=7, hmc=True)
+    toy.set_masks(od.make_masks(3, 2, np.random.RandomState(3)))
+    points = torch.as_tensor(tc.target_points(2, 2, tc.M, B)[0], dtype=torch.float32, device="cuda")
+    temps = np.tile(np.linspace(0.5, 4.0, G), B // G)
+    _assert_device_ladders_are_the_host_ladder(swap(la.DynamicsSampler(toy), points), temps, "swap_replicas")

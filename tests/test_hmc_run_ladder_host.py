@@ -204,8 +204,12 @@ def test_run_hmc_accepts_good_arguments_up_to_the_plan():
 
 
 def test_beta_shapes_map_to_the_stride_pairs():
-    import l2hmc_amd as la
-    f = la.GaugeSampler._ladder_betas
+    from l2hmc_amd import _runs
+
+    def f(beta, run_steps, B):
+        b, flat, (step_stride, chain_stride) = _runs.chain_axis(beta, run_steps, B, who="run_hmc", name="beta",
+                                                                positive=False)
+        return b, flat, step_stride, chain_stride
     n, B = 5, 3
     b, flat, ss, cs = f(2.5, n, B)
     assert (ss, cs) == (0, 0) and flat.dtype == np.float32 and flat.tolist() == [2.5]

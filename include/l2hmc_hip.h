@@ -290,7 +290,8 @@ int l2hmc_gauge_transition(const l2hmc_gauge_plan* plan, float beta, const float
 /* apply_transition (gauge_dynamics.py:195-259) with the library's own draws -- Philox streams (seed, 2*draw) for the
  * stacked momenta [v0_f; v0_b] and (seed, 2*draw+1) for coin | u, exactly the layout of l2hmc_gauge_mcmc_step,
  * reproducible with l2hmc_fill_normal/_uniform -- instead of caller-provided ones: what `dynamics(x, beta)` is in
- * the reference.  ONE launch for plans with a whole-trajectory kernel.  ws: l2hmc_gauge_mcmc_step_ws_bytes(plan, B). */
+ * the reference.  ONE launch for plans with a whole-trajectory kernel.  ws: l2hmc_gauge_mcmc_step_ws_bytes(plan, B).
+ * draw must be below 2^63 (the rule of l2hmc_gauge_mcmc_step; L2HMC_ERR_ARG before any device call, B == 0 included). */
 int l2hmc_gauge_transition_draw(const l2hmc_gauge_plan* plan, float beta, const float* x, int64_t B, uint64_t seed,
                                 uint64_t draw, float* x_prop, float* v_prop, float* p_accept, float* x_out,
                                 void* ws, size_t ws_bytes, l2hmc_stream_t stream);
@@ -302,7 +303,10 @@ int l2hmc_gauge_transition_draw(const l2hmc_gauge_plan* plan, float beta, const 
  * probability; actions / plaqs / charges = observables of the step's INPUT samples (as :256-266);
  * charge_diff = |Q(x_in) - Q(x_out)| (:718-725).  ONE launch when the plan has a whole-trajectory kernel: the
  * kernel generates its own draws, a workgroup owns both directions of its chains and finishes the step in its
- * epilogue (no intermediate ever reaches HBM); other plans run the same step through the public ops. */
+ * epilogue (no intermediate ever reaches HBM); other plans run the same step through the public ops.
+ * draw must be below 2^63: from there on 2*draw wraps and the step would replay the streams of draw - 2^63.
+ * l2hmc_gauge_mcmc_step, _ex, _ladder and l2hmc_gauge_transition_draw refuse such a draw with L2HMC_ERR_ARG (the
+ * message names the entry and the value) before any device call and before the B == 0 return, as the runs do. */
 size_t l2hmc_gauge_mcmc_step_ws_bytes(const l2hmc_gauge_plan* plan, int64_t B);
 int l2hmc_gauge_mcmc_step(const l2hmc_gauge_plan* plan, float beta, float* x, int64_t B, uint64_t seed,
                           uint64_t draw, float* px, float* actions, float* plaqs, float* charges,
@@ -332,7 +336,7 @@ int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta, const flo
  * instance of it that reads the chain's beta (the uniform step's kernels are left as they are), the others layer by
  * layer with the rows' betas.
  * Refused with L2HMC_ERR_ARG before any device call: NULL plan / betas / x_in / x_next, B < 0, a chain_stride other
- * than 0 or 1, hmc = 1 (l2hmc_gauge_hmc_run_ladder runs plain HMC with a beta per chain).  A workspace that is NULL or
+ * than 0 or 1, hmc = 1 (l2hmc_gauge_hmc_run_ladder runs plain HMC with a beta per chain), draw >= 2^63.  A workspace that is NULL or
  * too small: L2HMC_ERR_WORKSPACE.  On plans without a whole-step kernel the plan is then checked as
  * l2hmc_gauge_transition checks it (shapes, widths, NULL masks or weights: L2HMC_ERR_ARG), also before any device call.
  * The VALUES of betas are on the device and are not checked (as in l2hmc_gauge_hmc_run_ladder): a beta that is
@@ -642,7 +646,9 @@ int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float* x0, const 
  * l2hmc_fill_uniform(B) / l2hmc_fill_normal(B * x_dim) write with those (seed, offset) pairs, so the call equals
  * fill x 4 + l2hmc_small_trajectory(2B rows) + l2hmc_mix_accept(strict = 0) bit for bit.  Both trajectories of a
  * chain run in the same wave.  Outputs (each may be NULL): Lx, Lv [B][x_dim] the proposal selected by the direction
- * bit (forward iff uniform >= 0.5), px [B] its accept probability, x_out [B][x_dim] = Lx where px - u >= 0 else x. */
+ * bit (forward iff uniform >= 0.5), px [B] its accept probability, x_out [B][x_dim] = Lx where px - u >= 0 else x.
+ * draw0 must not exceed 2^64 - 4: beyond it the last of the four streams would wrap onto streams 0, 1, 2.  Refused
+ * with L2HMC_ERR_ARG (the message gives the value) before any device call and before the B == 0 return. */
 int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x, int64_t B, uint64_t seed, uint64_t draw0,
                         float* Lx, float* Lv, float* px, float* x_out, l2hmc_stream_t stream);
 

@@ -170,6 +170,8 @@ extern "C" int l2hmc_gauge_mcmc_step_ex(const l2hmc_gauge_plan* plan, float beta
                                         float* plaqs, float* charges, float* charge_diff, float* step_sums, void* ws,
                                         size_t ws_bytes, l2hmc_stream_t stream) {
   L2HMC_REQUIRE(plan != nullptr && B >= 0, "gauge_mcmc_step: bad arguments");
+  // the step takes the streams 2 * draw and 2 * draw + 1: from 2^63 on they would wrap onto those of draw - 2^63
+  L2HMC_REQUIRE(draw < (1ull << 63), "gauge_mcmc_step: draw = %llu is not below 2^63", (unsigned long long)draw);
   if (B == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x_in && x_next && ws, "gauge_mcmc_step: NULL pointer");
   return mcmc_step_impl("gauge_mcmc_step", plan, beta, nullptr, 0, x_in, x_next, B, seed, draw, px, actions, plaqs,
@@ -191,6 +193,7 @@ extern "C" int l2hmc_gauge_mcmc_step_ladder(const l2hmc_gauge_plan* plan, const 
                 (long long)chain_stride);
   L2HMC_REQUIRE(x_in && x_next, "%s: NULL x_in / x_next", who);
   L2HMC_REQUIRE(B >= 0, "%s: B < 0", who);
+  L2HMC_REQUIRE(draw < (1ull << 63), "%s: draw = %llu is not below 2^63", who, (unsigned long long)draw);
   if (B == 0) return L2HMC_OK;
   if (!ws) ws_bytes = 0;
   return mcmc_step_impl(who, plan, 0.f, betas, chain_stride, x_in, x_next, B, seed, draw, px, actions, plaqs, charges,
@@ -202,6 +205,7 @@ extern "C" int l2hmc_gauge_transition_draw(const l2hmc_gauge_plan* plan, float b
                                            float* p_accept, float* x_out, void* ws, size_t ws_bytes,
                                            l2hmc_stream_t stream) {
   L2HMC_REQUIRE(plan != nullptr && B >= 0, "gauge_transition_draw: bad arguments");
+  L2HMC_REQUIRE(draw < (1ull << 63), "gauge_transition_draw: draw = %llu is not below 2^63", (unsigned long long)draw);
   if (B == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x && x_prop && v_prop && p_accept && x_out && ws, "gauge_transition_draw: NULL pointer");
   const size_t need = l2hmc_gauge_mcmc_step_ws_bytes(plan, B);

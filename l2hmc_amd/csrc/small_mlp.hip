@@ -798,6 +798,9 @@ extern "C" int l2hmc_small_propose(const l2hmc_small_plan* plan, const float* x,
                                    l2hmc_stream_t stream) {
   L2HMC_REQUIRE(plan != nullptr, "small_propose: plan is NULL");
   L2HMC_REQUIRE(B >= 0, "small_propose: B < 0");
+  // the four streams draw0 .. draw0 + 3: beyond 2^64 - 4 the last ones would wrap onto streams 0, 1, 2
+  L2HMC_REQUIRE(draw0 <= UINT64_MAX - 3, "small_propose: draw0 + 3 overflows 64 bits (draw0=%llu)",
+                (unsigned long long)draw0);
   if (B == 0) return L2HMC_OK;
   L2HMC_REQUIRE(x != nullptr, "small_propose: x is NULL");
   L2HMC_REQUIRE(!plan->hmc, "small_propose: the hmc sampler proposes with the forward trajectory only "

@@ -41,6 +41,7 @@ import torch
 
 from oracle import lattice as olat, nets as onets, dynamics as ogen
 from tests import helpers as H
+from tests.philox_ref import philox as _philox_ref      # Philox4x32-10 in Python integers, for the bit-exact check
 
 pytestmark = pytest.mark.gpu
 
@@ -794,18 +795,6 @@ def test_generic_dynamics_hmc_and_quadratic_gaussian(la):
 
 
 # ----------------------------------------------------------------- RNG
-def _philox_ref(block, offset, seed):
-    """Philox4x32-10 in Python integers (Salmon et al., SC'11), for the bit-exact check."""
-    M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-    c = [block & 0xFFFFFFFF, block >> 32, offset & 0xFFFFFFFF, offset >> 32]
-    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
-    for _ in range(10):
-        p0, p1 = c[0] * M0, c[2] * M1
-        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k1, p0 & 0xFFFFFFFF]
-        k0, k1 = (k0 + W0) & 0xFFFFFFFF, (k1 + W1) & 0xFFFFFFFF
-    return c
-
-
 def test_philox_stream_bit_exact_and_statistics(la):
     from l2hmc_amd import _lib
     # Random123 known-answer vector: counter = key = 0

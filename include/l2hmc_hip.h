@@ -765,6 +765,38 @@ int l2hmc_small_hmc_run_exchange(const l2hmc_small_plan* plan, const float* x_in
                                  int32_t* replica, float* px, float* samples,
                                  float* swap_p, uint8_t* swapped, int32_t* replica_hist, l2hmc_stream_t stream);
 
+/* l2hmc_small_run_tempered with replica exchange between the columns of a temperature ladder INSIDE the launch: its
+ * contract (an L2HMC plan, the four streams of a step, px, samples, x_next that may alias x_in, temps with its strides,
+ * the form the batch size selects, no workspace, graph capture, the same bits on every run, B == 0 a no-op) with these
+ * differences.
+ * After step s of the launch one round of l2hmc_small_replica_swap (group, the rule and the arithmetic above) runs iff
+ * (swap_phase + s + 1) % swap_every == 0, on the state the step left and at the temperatures the step ran with
+ * (temps[s * step_stride + c * chain_stride]); the j-th round of the launch has parity (first_parity + j) % 2.
+ * Streams are taken in the order of the loop a caller would write: a step takes four (direction bits, forward momenta,
+ * backward momenta, Metropolis-Hastings uniforms), a round the next one -- a round without a pair takes its stream as
+ * well, so the accounting does not depend on the group size.  The launch consumes streams
+ * draw0 .. draw0 + 4 n_steps + rounds - 1, rounds = (swap_phase + n_steps) / swap_every.
+ * samples[s] and px[s] are step s's own outputs, taken BEFORE its round; the round shows in the next step's input and
+ * in x_next.  replica [B] (int32 labels, or NULL) is read on entry and written on exit.  swap_p, swapped and
+ * replica_hist (the labels after each round) are [rounds][B]; each may be NULL.
+ * ONE launch (profile class 7, none of class 8) of the run kernel's exchange instances.  The kernel gives a chain eight
+ * lanes (four of the matrix instructions times two directions) and a wave eight chains; here a wave holds
+ * (8 / group) * group chains, whole groups, so a round is a handful of cross-lane reads between two steps: for group
+ * 2, 4, 8 the placement of l2hmc_small_run_tempered, for 3, 5, 6, 7 some of a wave's eight places stay idle and the
+ * launch has more waves.  The FORM is still the one l2hmc_small_run_tempered takes for the same plan and B, so the call
+ * is bit for bit the loop l2hmc_small_run_tempered (up to the next round), l2hmc_small_replica_swap: both rounds call
+ * one device function on the fp32 state the run would store and reload.
+ * Refused with L2HMC_ERR_ARG before any device call: everything l2hmc_small_run_tempered refuses, NULL temps, group < 2
+ * or > 8 (larger groups would cross waves: they stay with the round between launches), B not a multiple of group,
+ * swap_every < 1, swap_phase outside [0, swap_every), first_parity not 0 or 1, draw0 + 4 n_steps + rounds beyond
+ * 2^64 - 1. */
+int l2hmc_small_run_exchange(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                             uint64_t seed, uint64_t draw0, int32_t n_steps,
+                             const float* temps, int64_t step_stride, int64_t chain_stride,
+                             int32_t group, int32_t swap_every, int32_t swap_phase, int32_t first_parity,
+                             int32_t* replica, float* px, float* samples,
+                             float* swap_p, uint8_t* swapped, int32_t* replica_hist, l2hmc_stream_t stream);
+
 /* One training evaluation on the toy targets (mog_model.py:324-363): `rows` = 2B stacked chains (B started at
  * x, B at z ~ N(0,1); sampler.py:28-55 picks a direction per chain, passed in `dir`), each integrated in its
  * direction; per chain v = |x0 - x_N|^2 * p + 1e-4, term = scale / v - v / scale, loss = inv_count * sum of all
@@ -875,8 +907,8 @@ int l2hmc_fill_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, l2
  *   4 = u1_action_force     5 = fused whole-trajectory kernel
  *   6 = ConvNet3D front-end 7 = toy-target trajectory kernel (l2hmc_small_*)
  *   8 = replica-exchange round on its own (l2hmc_gauge_replica_swap, l2hmc_small_replica_swap; the rounds inside
- *       l2hmc_small_hmc_run_exchange are part of its class-7 launch, those inside l2hmc_gauge_hmc_run_exchange of
- *       its class-5 launch)
+ *       l2hmc_small_hmc_run_exchange and l2hmc_small_run_exchange are part of their class-7 launch, those inside
+ *       l2hmc_gauge_hmc_run_exchange of its class-5 launch)
  * ------------------------------------------------------------------------ */
 int l2hmc_profile_begin(int32_t kernel_class);
 int l2hmc_profile_end(double* total_ms, int64_t* launches);

@@ -156,6 +156,8 @@ _PROTOS = {
                                            _P, _P]),
     "l2hmc_small_hmc_run_exchange": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _I64, _I64, _P,
                                                _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "l2hmc_small_run_exchange": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _I64, _I64,
+                                           _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "l2hmc_small_train_ws_bytes": (_SZ, [C.POINTER(SmallPlan), _I64]),
     "l2hmc_small_train_step": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64, _F, _F, _P, _P, _P, _P, _P, _P, _SZ,
                                          _P]),

@@ -143,8 +143,8 @@ __global__ __launch_bounds__(kHmcThreads) void small_hmc_run_kernel(
       next += 2;
       if (--until == 0) {                         // (uniform) on the state and at the temperatures of this step
         const int64_t row = (int64_t)round * a.B;
-        small_swap_round<MD, AN>(r, a.group, (a.first_parity + round) & 1, x, inv_temp, label, tgt, Lt, dim, K, tk,
-                                 a.seed, next, nullptr, a.swap_p ? a.swap_p + row : nullptr,
+        small_swap_round<MD, AN>(r, (int)threadIdx.x, true, a.group, (a.first_parity + round) & 1, x, inv_temp, label,
+                                 tgt, Lt, dim, K, tk, a.seed, next, nullptr, a.swap_p ? a.swap_p + row : nullptr,
                                  a.swapped ? a.swapped + row : nullptr);
         if (a.replica_hist) a.replica_hist[row + r] = label;
         next += 1;
@@ -206,8 +206,8 @@ __global__ __launch_bounds__(kHmcThreads) void small_swap_kernel(
   int32_t label = replica ? replica[r] : 0;
   SmallTarget<MD, AN> tgt;
   tgt.load(lds, dim, K);
-  if (!small_swap_round<MD, AN>(r, group, parity, x, inv_temp, label, tgt, lds, dim, K, tk, seed, stream_index,
-                                energy, swap_p, swapped))
+  if (!small_swap_round<MD, AN>(r, (int)threadIdx.x, true, group, parity, x, inv_temp, label, tgt, lds, dim, K, tk,
+                                seed, stream_index, energy, swap_p, swapped))
     return;
 #pragma unroll
   for (int d = 0; d < MD; ++d)
@@ -318,8 +318,8 @@ extern "C" int l2hmc_small_hmc_run_exchange(const l2hmc_small_plan* plan, const 
                                             l2hmc_stream_t stream) {
   const char* who = "small_hmc_run_exchange";
   if (int e = check_small_run_args(who, plan, x_in, x_next, B, draw0, n_steps, 2, step_stride, chain_stride)) return e;
-  L2HMC_REQUIRE(plan->hmc, "%s: the plan is an L2HMC sampler's (hmc == 0): its exchange run is l2hmc_small_run_tempered "
-                           "with l2hmc_small_replica_swap between launches", who);
+  L2HMC_REQUIRE(plan->hmc, "%s: the plan is an L2HMC sampler's (hmc == 0): its exchange run is "
+                           "l2hmc_small_run_exchange", who);
   if (int e = check_small_plan(plan, who, false)) return e;
   L2HMC_REQUIRE(temps != nullptr, "%s: temps is NULL (a replica group is a ladder of temperatures)", who);
   if (int e = check_small_group(who, B, group)) return e;

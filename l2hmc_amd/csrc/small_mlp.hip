@@ -15,6 +15,7 @@
 // small_mlp.h.
 #include "small_mlp.h"
 #include "lf_update.h"
+#include "small_swap.h"
 #include <atomic>
 
 namespace l2hmc {
@@ -61,6 +62,18 @@ struct SmallTrajArgs {
   const float* temps; int64_t temp_step_stride, temp_chain_stride;
   unsigned long long* stamps;           // diagnostic builds only (-DL2HMC_STAMPS, class 7), else NULL
 };
+
+// What the kernel's EXCHANGE instances take on top (l2hmc_small_run_exchange): a replica-exchange round (small_swap.h)
+// after step s of the launch iff (swap_phase + s + 1) % swap_every == 0, the j-th of them with parity
+// (first_parity + j) % 2.  A struct of its own, as SmallHmcExchangeArgs is (small_hmc.hip): the instances without
+// exchange keep their kernel arguments.
+struct SmallTrajExchangeArgs : SmallTrajArgs {
+  int32_t group, swap_every, swap_phase, first_parity;
+  int32_t* replica;                     // [prop_B] labels, read on entry and written on exit, or NULL
+  float* swap_p; uint8_t* swapped; int32_t* replica_hist;      // [rounds][prop_B]; each may be NULL
+};
+// chains of a wave (of a wave pair in the twin form) in the EXCHANGE instances: whole groups of G <= 8 rungs
+__host__ __device__ inline int traj_exchange_chains_per_wave(int G) { return (8 / G) * G; }
 
 // Per-phase cycle counters of a wave (diagnostic build only): 0 first layer (VALU), 1 hidden layer (MFMA), 2 heads
 // (MFMA + bias + store to the wave's patch), 3 patch round trip + tanh / exp(coeff), 4 target energy / gradient,
@@ -452,11 +465,21 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
 // TEMPERED (a RUN instance, l2hmc_small_run_tempered): every step reloads the chain's temperature from a.temps, where
 // the other instances hold plan.target.temperature for the launch.  A template flag as RUN is, and for its reason: the
 // untempered instances keep their code (registers per instance: profiles/small_run_tempered.txt).
+// EXCHANGE (a TEMPERED instance, l2hmc_small_run_exchange): a replica-exchange round (small_swap.h) between two steps of
+// the run.  A wave holds cpw = (8 / G) * G chains, whole groups of G <= 8 rungs (G = 2, 4, 8: the run's own placement;
+// otherwise the slots from cpw on idle), so after the step's broadcast of the accepted state the partner of a pair sits
+// in lane +- 1 of the same eight lanes.  All eight lanes of a chain, and the twin form's second wave, run the same
+// round on the same values and stay in agreement; the writer lanes store.  No barrier, no workspace, no launch.
+// Streams in the order of the loop a caller would write: four per step, the next one per round (a round without a pair
+// takes its stream as well).  A template flag once more: the other instances keep their code and their arguments
+// (registers per instance: profiles/small_run_replica_exchange.txt).
 template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false, bool RUN = false, bool AN = false,
-          bool TEMPERED = false>
-__global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTrajArgs a) {
+          bool TEMPERED = false, bool EXCHANGE = false>
+__global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(
+    std::conditional_t<EXCHANGE, SmallTrajExchangeArgs, SmallTrajArgs> a) {
   using V = MfmaNet<HP, MD, KS_, KSH_>;
   static_assert(!TEMPERED || RUN, "a temperature per step is a run's");
+  static_assert(!EXCHANGE || TEMPERED, "the rungs of a replica group are a ladder of temperatures");
   static_assert(!TW || (L1M && V::NT == 4), "the twin form is a latency form of the 64-unit instances");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const l2hmc_small_plan& P = a.plan;
@@ -503,8 +526,12 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   const int64_t gw = TW ? (int64_t)blockIdx.x * (kSmallThreads / 128) + (wave >> 1)
                         : (int64_t)blockIdx.x * (kSmallThreads / 64) + wave;
   // trajectory mode: row r of [rows]; propose mode: chain r, direction (lane & 15) >> 3
-  const int64_t r = prop ? gw * 8 + (lane & 7) : gw * 16 + (lane & 15);
-  const bool live = r < (prop ? a.prop_B : a.rows);
+  // (EXCHANGE: chain gw * cpw + (lane & 7), the slots from cpw on idle -- their lanes take part in the matrix
+  //  instructions and the permutes like those of rows beyond the batch)
+  [[maybe_unused]] int cpw = 8;
+  if constexpr (EXCHANGE) cpw = traj_exchange_chains_per_wave(a.group);
+  const int64_t r = EXCHANGE ? gw * cpw + (lane & 7) : prop ? gw * 8 + (lane & 7) : gw * 16 + (lane & 15);
+  const bool live = (!EXCHANGE || (lane & 7) < cpw) && r < (prop ? a.prop_B : a.rows);
   const int bwd = prop ? ((lane >> 3) & 1) : ((a.dir && live) ? a.dir[r] : 0);
   const float eps = P.eps;
   float inv_temp = TEMPERED ? 1.f : 1.f / P.target.temperature;      // (TEMPERED: set at the head of every step)
@@ -541,8 +568,16 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
   // lane, those of rows beyond the batch included, walks the whole loop: all of them take part in the matrix
   // instructions and the lane permutes, and only the stores are predicated.
   float* const samples = RUN ? a.samples : nullptr;
+  // EXCHANGE: the label that travels with x, the next stream, the steps until the next round and that round's index
+  [[maybe_unused]] int32_t label = 0;
+  [[maybe_unused]] uint64_t next = a.draw0;
+  [[maybe_unused]] int until = 0, round = 0;
+  if constexpr (EXCHANGE) {
+    if (a.replica && live) label = a.replica[r];
+    until = a.swap_every - a.swap_phase;
+  }
   for (int sidx = 0;; ++sidx) {
-    const uint64_t draw = a.draw0 + 4 * (uint64_t)sidx;
+    const uint64_t draw = EXCHANGE ? next : a.draw0 + 4 * (uint64_t)sidx;
     // the step's temperature: one value per chain, the same in both direction halves, in the four lanes of a row and
     // in the twin form's second wave (all of them index by r), and the same from E0 to E1 -- the step's Hamiltonian
     // difference is taken at one temperature.  The same division as above, so equal temperatures give equal bits.
@@ -669,11 +704,13 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
         if (last) {
           if (a.Lx) a.Lx[r * dim + d] = xp;
           if (a.Lv) a.Lv[r * dim + d] = fm * v[d] + bm * slot[MD + d];
-          if (a.mh_out) a.mh_out[r * dim + d] = xn[d];
+          if (!EXCHANGE && a.mh_out) a.mh_out[r * dim + d] = xn[d];      // (EXCHANGE: after the step's round, below)
         }
       }
     }
-    if (last) return;
+    if constexpr (!EXCHANGE) {
+      if (last) return;
+    }
     // the accepted state of chain c, in lane c, becomes the start of every lane with (lane & 7) == c: both direction
     // halves and the four lanes of each row.  The patch is free again once every lane has read it.
 #pragma unroll
@@ -682,6 +719,33 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTra
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if constexpr (EXCHANGE) {
+      next += 4;
+      if (--until == 0) {                           // (uniform) on the state and at the temperatures of this step
+        // every lane holds its chain's new start and lane +- 1 the neighbouring chain's: the round needs nothing else.
+        // The target's register image is formed here, once per round, and not carried through the steps
+        const int64_t row = (int64_t)round * a.prop_B;
+        SmallTarget<MD, AN> stgt;
+        stgt.load(Lt, dim, K);
+        small_swap_round<MD, AN>(r, lane & 7, live, a.group, (a.first_parity + round) & 1, x, inv_temp, label, stgt,
+                                 Lt, dim, K, tk, a.seed, next, nullptr,
+                                 (writer && a.swap_p) ? a.swap_p + row : nullptr,
+                                 (writer && a.swapped) ? a.swapped + row : nullptr);
+        if (writer && a.replica_hist) a.replica_hist[row + r] = label;
+        next += 1;
+        ++round;
+        until = a.swap_every;
+      }
+      if (last) {                                   // the state after the last step's round, if it has one
+        if (writer) {
+#pragma unroll
+          for (int d = 0; d < MD; ++d)
+            if (d < dim) a.mh_out[r * dim + d] = x[d];
+          if (a.replica) a.replica[r] = label;
+        }
+        return;
+      }
+    }
   }
   if (TW && part) return;             // both waves of a group hold the same state: the first one finishes (no barrier follows)
   if (!live || lane >= 16) return;                 // the four lanes of a chain hold the same result
@@ -704,24 +768,26 @@ static size_t small_mfma_lds(int dim, int K, int N) {
                           (size_t)(kSmallThreads / 128) * 4 * MfmaNet<HP, MD, KS_, KSH_>::NTH * 64 * 4);   // twin exchange patches
 }
 
-template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN, bool AN, bool TEMPERED = false>
-static int launch_small_mfma_kernel(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN, bool AN, bool TEMPERED = false,
+          bool EXCHANGE = false>
+static int launch_small_mfma_kernel(const std::conditional_t<EXCHANGE, SmallTrajExchangeArgs, SmallTrajArgs>& a,
+                                    dim3 grid, hipStream_t st) {
   const l2hmc_small_plan& P = a.plan;
   const size_t lds = small_mfma_lds<HP, MD, KS_, KSH_>(P.x_dim, P.target.K, P.trajectory_length);
   L2HMC_REQUIRE(lds <= 160 * 1024, "small_trajectory: LDS image %zu B too large", lds);
   static DeviceOnce attr_once;   // dynamic LDS beyond 64 KiB needs the opt-in (host-side, not a stream op)
   if (attr_once.pending()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED, EXCHANGE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_once.done();
   }
   prof_before(kProfSmall, st);
 #ifdef L2HMC_STAMPS
-  SmallTrajArgs b = a;
+  auto b = a;
   b.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED>), grid, dim3(kSmallThreads), lds, st, b);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED, EXCHANGE>), grid, dim3(kSmallThreads), lds, st, b);
 #else
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED>), grid, dim3(kSmallThreads), lds, st, a);
+  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED, EXCHANGE>), grid, dim3(kSmallThreads), lds, st, a);
 #endif
   prof_after(kProfSmall, st);
   L2HMC_CHECK_LAUNCH("small_trajectory");
@@ -742,20 +808,36 @@ static int launch_small_mfma_form(const SmallTrajArgs& a, dim3 grid, hipStream_t
   return a.n_steps > 0 ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, false>(a, grid, st)
                        : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false, false>(a, grid, st);
 }
+// (a run with replica exchange: the EXCHANGE instance of the same form)
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false>
+static int launch_small_mfma_form(const SmallTrajExchangeArgs& a, dim3 grid, hipStream_t st) {
+  return target_is_analytic(a.plan.target.is_gaussian)
+             ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, true, true, true>(a, grid, st)
+             : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, false, true, true>(a, grid, st);
+}
 
 // Three forms, chosen by the number of 16-row groups (l2hmc_small_plan::first_layer_form forces one; they walk sums in
 // different groupings and agree to rounding: tests):
 //   3  twin: two waves per group, every wave with a SIMD to itself (<= 512 groups on 1024 SIMDs; 64-unit instances)
 //   1  first layer on the matrix pipe, one wave per group (<= 1024 groups)
 //   2  first layer on the VALU: chip-filling batches
-template <int HP, int MD, int KS_, int KSH_>
-static int launch_small_mfma(const SmallTrajArgs& a, dim3 grid, hipStream_t st) {
+// A run with replica exchange (Args = SmallTrajExchangeArgs) takes the form its rows select here, as the run without
+// exchange does -- the two agree bit for bit only in the same form --, and sizes the grid by the waves (twin: wave
+// pairs) its placement needs: ceil(B / cpw), which for a group size that does not divide 8 is more than the groups.
+template <int HP, int MD, int KS_, int KSH_, class Args>
+static int launch_small_mfma(const Args& a, dim3 grid, hipStream_t st) {
+  constexpr bool exchange = std::is_same_v<Args, SmallTrajExchangeArgs>;
   const int force = a.plan.first_layer_form;
   const int64_t groups = ceil_div(a.rows, 16);
+  int64_t waves = groups;
+  if constexpr (exchange) {
+    waves = ceil_div(a.prop_B, traj_exchange_chains_per_wave(a.group));
+    grid = dim3((unsigned)ceil_div(waves, kSmallThreads / 64));
+  }
   constexpr bool can_twin = HP == 64;
   if constexpr (can_twin) {
     if (force == 3 || (force == 0 && groups <= 512)) {
-      const dim3 g2((unsigned)ceil_div(groups, kSmallThreads / 128));
+      const dim3 g2((unsigned)ceil_div(waves, kSmallThreads / 128));
       return launch_small_mfma_form<HP, MD, KS_, KSH_, true, true>(a, g2, st);
     }
   }
@@ -788,7 +870,8 @@ extern "C" int l2hmc_mog_energy_grad(const l2hmc_mog_target* tgt, const float* x
   return L2HMC_OK;
 }
 
-static int small_launch(const char* who, const l2hmc_small_plan* plan, SmallTrajArgs a, l2hmc_stream_t stream);
+template <class Args>
+static int small_launch(const char* who, const l2hmc_small_plan* plan, const Args& a, l2hmc_stream_t stream);
 static int small_run_entry(const char* who, const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
                            uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride,
                            int64_t chain_stride, bool tempered, float* px, float* samples, l2hmc_stream_t stream);
@@ -844,6 +927,45 @@ static int small_run_entry(const char* who, const l2hmc_small_plan* plan, const 
   return small_launch(who, plan, a, stream);
 }
 
+// The tempered run with the replica-exchange rounds inside the launch: the checks of small_run_entry, then those of
+// the schedule, all of them before any device call.
+extern "C" int l2hmc_small_run_exchange(const l2hmc_small_plan* plan, const float* x_in, float* x_next, int64_t B,
+                                        uint64_t seed, uint64_t draw0, int32_t n_steps, const float* temps,
+                                        int64_t step_stride, int64_t chain_stride, int32_t group, int32_t swap_every,
+                                        int32_t swap_phase, int32_t first_parity, int32_t* replica, float* px,
+                                        float* samples, float* swap_p, uint8_t* swapped, int32_t* replica_hist,
+                                        l2hmc_stream_t stream) {
+  const char* who = "small_run_exchange";
+  if (int e = check_small_run_args(who, plan, x_in, x_next, B, draw0, n_steps, 4, step_stride, chain_stride)) return e;
+  L2HMC_REQUIRE(!plan->hmc, "%s: the plan is a plain-HMC sampler's (hmc != 0), which proposes with the forward "
+                            "trajectory only (utils/sampler.py:30-32): its exchange run is l2hmc_small_hmc_run_exchange",
+                who);
+  L2HMC_REQUIRE(temps != nullptr, "%s: temps is NULL (a replica group is a ladder of temperatures)", who);
+  L2HMC_REQUIRE(group >= 2 && group <= 8,
+                "%s: group = %d: a replica group has 2 rungs or more and sits in the 8 chains of one wave (at most 8; "
+                "larger groups: l2hmc_small_run_tempered with l2hmc_small_replica_swap between launches)", who, group);
+  L2HMC_REQUIRE(B % group == 0, "%s: B = %lld is not a multiple of group = %d", who, (long long)B, group);
+  L2HMC_REQUIRE(swap_every >= 1, "%s: swap_every = %d must be 1 or more", who, swap_every);
+  L2HMC_REQUIRE(swap_phase >= 0 && swap_phase < swap_every, "%s: swap_phase = %d is not in [0, swap_every = %d)", who,
+                swap_phase, swap_every);
+  L2HMC_REQUIRE(first_parity == 0 || first_parity == 1, "%s: first_parity = %d is not 0 or 1", who, first_parity);
+  // a round after step s iff (swap_phase + s + 1) % swap_every == 0
+  const uint64_t rounds = ((uint64_t)swap_phase + (uint64_t)n_steps) / (uint64_t)swap_every;
+  L2HMC_REQUIRE(rounds <= UINT64_MAX - draw0 - 4 * (uint64_t)n_steps,
+                "%s: draw0 + 4 * n_steps + rounds overflows 64 bits (draw0=%llu, n_steps=%d, rounds=%llu)", who,
+                (unsigned long long)draw0, n_steps, (unsigned long long)rounds);
+  if (B == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(ceil_div(B, traj_exchange_chains_per_wave(group)) < (1ll << 31), "%s: too many chains", who);
+  SmallTrajExchangeArgs a{};
+  a.plan = *plan; a.x0 = x_in; a.rows = 2 * B;
+  a.prop_B = B; a.seed = seed; a.draw0 = draw0; a.px = px; a.mh_out = x_next;
+  a.n_steps = n_steps; a.samples = samples;
+  a.temps = temps; a.temp_step_stride = step_stride; a.temp_chain_stride = chain_stride;
+  a.group = group; a.swap_every = swap_every; a.swap_phase = swap_phase; a.first_parity = first_parity;
+  a.replica = replica; a.swap_p = swap_p; a.swapped = swapped; a.replica_hist = replica_hist;
+  return small_launch(who, plan, a, stream);
+}
+
 extern "C" int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float* x0, const float* v0,
                                       const int32_t* dir, int64_t rows, float* x_out, float* v_out,
                                       float* sumlogdet, float* p_accept, l2hmc_stream_t stream) {
@@ -857,7 +979,8 @@ extern "C" int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float*
   return small_launch("small_trajectory", plan, a, stream);
 }
 
-static int small_launch(const char* who, const l2hmc_small_plan* plan, SmallTrajArgs a, l2hmc_stream_t stream) {
+template <class Args>
+static int small_launch(const char* who, const l2hmc_small_plan* plan, const Args& a, l2hmc_stream_t stream) {
   if (int e = check_small_plan(plan, who, !plan->hmc)) return e;
   if (!plan->hmc)
     if (int e = check_small_nets(plan, who)) return e;

@@ -4,7 +4,7 @@
 // staged where stay with the kernels: they hand the trajectory callables.
 //
 // Who calls this today: small_hmc_run_kernel (small_hmc.hip) alone, and through small_swap.h's replica-exchange round
-// (SmallTarget at temperature 1) small_swap_kernel beside it.  small_traj_mfma_kernel (small_mlp.hip) and the
+// (SmallTarget at temperature 1) small_swap_kernel beside it and the EXCHANGE instances of small_traj_mfma_kernel.  small_traj_mfma_kernel (small_mlp.hip) and the
 // forward half of small_train_kernel (small_train.hip) spell the same statements out themselves, in the same order:
 //   - taken through small_trajectory, four of the former's 96 instances and nine of the latter's 16 gained scratch or
 //     crossed a waves-per-SIMD step;

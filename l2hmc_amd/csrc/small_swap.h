@@ -1,11 +1,16 @@
 // One replica-exchange (parallel tempering) round between neighbouring rungs of a temperature ladder on a packed toy
-// target: the ONE copy of the round, called by small_swap_kernel (l2hmc_small_replica_swap, small_hmc.hip) and between
-// two MCMC steps of small_hmc_run_kernel<.., EXCHANGE> (l2hmc_small_hmc_run_exchange).
+// target: the ONE copy of the round, called by small_swap_kernel (l2hmc_small_replica_swap, small_hmc.hip), between
+// two MCMC steps of small_hmc_run_kernel<.., EXCHANGE> (l2hmc_small_hmc_run_exchange) and between two steps of
+// small_traj_mfma_kernel<.., EXCHANGE> (l2hmc_small_run_exchange, small_mlp.hip).
 //
-// Geometry: one chain per lane, one wave per workgroup.  A workgroup holds cpw = (64 / G) * G chains, chain
-// r = blockIdx.x * cpw + lane, so with B % G == 0 and G <= 64 a replica group never straddles a wave, lane % G is the
-// rung, and both lanes of a pair are live whenever one is.  Lanes at or beyond cpw or B have left the kernel before
-// the first round: the round is collective over the rest.
+// Geometry: the caller gives every lane its SLOT among the chains its wave holds; slot % G is the rung and the partner
+// of a pair sits in lane +- 1.  The callers of small_hmc.hip hold one chain per lane, one wave per workgroup: a
+// workgroup holds cpw = (64 / G) * G chains, chain r = blockIdx.x * cpw + lane, slot = lane, so with B % G == 0 and
+// G <= 64 a replica group never straddles a wave and both lanes of a pair are live whenever one is; lanes at or beyond
+// cpw or B have left the kernel before the first round, which is collective over the rest.  small_traj_mfma_kernel holds chain
+// slot = lane & 7 in eight lanes of a wave (cpw = (8 / G) * G, G <= 8): lanes lane and lane +- 1 then hold neighbouring
+// chains in the same copy, every copy runs the same round, and the lanes of the idle slots stay in the permutes with
+// active = false.
 //
 // A round of parity pi pairs the columns (a, a + 1), a = g G + j, j = pi, pi + 2, ... with j + 1 < G (the rule of
 // l2hmc_gauge_replica_swap); the at most two chains of a group that are in no pair sit the round out (they read their
@@ -25,13 +30,16 @@ __host__ __device__ inline int swap_chains_per_wave(int G) { return (kSwapWave /
 // pairs of a group in a round of `parity` (j = parity, parity + 2, ... with j + 1 < G)
 __host__ __device__ inline int swap_pairs_per_group(int G, int parity) { return (G - parity) / 2; }
 
-// r: the lane's chain; inv_temp: the 1.f / t the step forms; label: exchanged with x (callers without labels pass a
-// dummy).  (seed, stream): u is element a of what l2hmc_fill_uniform(B, seed, stream) writes.  Outputs, each may be
+// r: the lane's chain; slot: its place among the wave's chains (above); active: false for a lane that holds no chain --
+// it proposes nothing and its outputs must be NULL; inv_temp: the 1.f / t the step forms; label: exchanged with x
+// (callers without labels pass a dummy).
+// (seed, stream): u is element a of what l2hmc_fill_uniform(B, seed, stream) writes.  Outputs, each may be
 // NULL, each written by the lane for its own chain r with plain stores -- the chains that sit out included, so nothing
 // needs a fill: energy[r] = U for the members of a pair (others untouched), swap_p[r] = p at the lower chain and NaN
 // elsewhere, swapped[r] = 1 / 0 at the lower chain and 0 elsewhere.  Returns whether this lane's chain was exchanged.
 template <int MD, bool AN>
-__device__ __forceinline__ bool small_swap_round(int64_t r, int G, int parity, float (&x)[MD], float inv_temp,
+__device__ __forceinline__ bool small_swap_round(int64_t r, int slot, bool active, int G, int parity, float (&x)[MD],
+                                                 float inv_temp,
                                                  int32_t& label, const SmallTarget<MD, AN>& tgt, const float* Lt,
                                                  int dim, int K, const TargetKind& tk, uint64_t seed, uint64_t stream,
                                                  float* energy, float* swap_p, uint8_t* swapped) {
@@ -41,9 +49,9 @@ __device__ __forceinline__ bool small_swap_round(int64_t r, int G, int parity, f
     if (swapped) swapped[r] = 0;
     return false;
   }
-  const int lane = (int)threadIdx.x, j = lane % G;
-  const bool lower = j >= parity && ((j - parity) & 1) == 0 && j + 1 < G;
-  const bool upper = j > parity && ((j - parity) & 1) == 1;
+  const int lane = (int)threadIdx.x & (kSwapWave - 1), j = slot % G;
+  const bool lower = active && j >= parity && ((j - parity) & 1) == 0 && j + 1 < G;
+  const bool upper = active && j > parity && ((j - parity) & 1) == 1;
   const int partner = lower ? lane + 1 : upper ? lane - 1 : lane;
   float U, g[MD];
   tgt.eval(Lt, dim, K, tk, 1.f, x, &U, g);

@@ -18,8 +18,13 @@ chain, so that "HMC at three eps" is one call.
 
 `run_hmc_exchange` is `run_hmc` on a temperature ladder with replica exchange (parallel tempering) between the rungs,
 the rounds inside the launch (l2hmc_small_hmc_run_exchange: a replica group sits in one wave); `swap_replicas` is one
-round on its own (l2hmc_small_replica_swap) and `run_exchange` the host composition of `run(temperature=)` and that
-round for an L2HMC dynamics."""
+round on its own (l2hmc_small_replica_swap).
+
+`run_exchange` is `run(temperature=)` of an L2HMC dynamics on such a ladder with that round after every `swap_every`
+steps: by default the host composition of the two (one launch per piece between two rounds and one per round, any
+group of up to 64 rungs), and with `in_launch = True` the rounds inside the launches (l2hmc_small_run_exchange: groups
+of 2..8 rungs, which sit in the eight chains of a wave), one launch per chunk whatever `swap_every` is.  The values are
+the same, bit for bit."""
 import ctypes as C
 
 import numpy as np
@@ -38,6 +43,10 @@ class DynamicsSampler:
         self.batch_size = batch_size
         # MCMC steps per launch of l2hmc_small_run (1 = one launch per step through `propose`, the cross-check)
         self.steps_per_launch = 256
+        # `run_exchange`: False = one launch per round between the launches of the run (groups of up to MAX_REPLICAS
+        # rungs); True = the rounds inside the run's launches (l2hmc_small_run_exchange), where `exchange_in_launch`
+        # says so
+        self.in_launch = False
         # int32 [B] labels on the device while an exchange run is followed (`run_hmc_exchange`, `run_exchange`)
         self.replica = None
 
@@ -181,6 +190,16 @@ class DynamicsSampler:
 
     # ------------------------------------------------------------------------------------------ replica exchange
     MAX_REPLICAS = 64                # a replica group sits in one wave (l2hmc_small_replica_swap)
+    MAX_REPLICAS_IN_LAUNCH = 8       # ... in the eight chains of a wave of the L2HMC kernel (l2hmc_small_run_exchange)
+
+    def exchange_in_launch(self, replicas):
+        """Whether `run_exchange(..., replicas=replicas)` with `self.in_launch = True` is served: the dynamics is on the
+        one-launch path (L2HMC, not layer by layer, steps_per_launch > 1) and a group has 2..8 rungs."""
+        try:
+            G = int(replicas)
+        except (TypeError, ValueError):
+            return False
+        return self._one_launch() and G == replicas and 2 <= G <= self.MAX_REPLICAS_IN_LAUNCH
 
     def _exchange_args(self, who, run_steps, x, temperature, replicas, swap_every, first_parity, replica0):
         """What the two exchange runs (`who`) check alike, before any launch -> (run_steps, start on the device,
@@ -284,13 +303,22 @@ class DynamicsSampler:
     def run_exchange(self, run_steps, x=None, keep_samples=True, temperature=None, replicas=None, swap_every=1,
                      first_parity=0, replica0=None):
         """`run(..., temperature=)` of an L2HMC dynamics with replica exchange between the columns of the ladder: the
-        run cut at the multiples of `swap_every` steps (one launch of l2hmc_small_run_tempered per piece of at most
-        `steps_per_launch` steps) with `swap_replicas` after each cut -- the loop `run(swap_every, temperature=)`,
-        `swap_replicas(...)`, bit for bit, with its draws (4 streams per step, 1 per round).  Arguments and the added
-        entries of the dictionary as `run_hmc_exchange`; `replicas=None` is `run` itself.  The rounds are launches of
-        their own here: the L2HMC kernel gives a chain four lanes and a wave eight chains, so a group of rungs does not
-        sit in a wave as it does in the plain-HMC kernel.  ValueError for a plain-HMC dynamics (`run_hmc_exchange`
-        runs it); NotImplementedError where `run` has no one-launch path (layer by layer, steps_per_launch = 1)."""
+        loop `run(swap_every, temperature=)`, `swap_replicas(...)`, bit for bit, with its draws (4 streams per step, 1
+        per round).  Arguments and the added entries of the dictionary as `run_hmc_exchange`; `replicas=None` is `run`
+        itself.
+        `self.in_launch = False` (the default): the run is cut at the multiples of `swap_every` steps (one launch of
+        l2hmc_small_run_tempered per piece of at most `steps_per_launch` steps) and every round is a launch of its own
+        (`swap_replicas`); groups of up to 64 rungs.
+        `self.in_launch = True` (an attribute of the sampler, like `steps_per_launch`; the signature is what it was):
+        the rounds run INSIDE the launches (l2hmc_small_run_exchange) -- chunks of `steps_per_launch` steps that are
+        not cut at the rounds, no launch per round, the same dictionary and the same `self.replica`, bit for bit.
+        Served for groups of 2..8 rungs (`exchange_in_launch(replicas)`): the L2HMC kernel gives a chain eight lanes
+        and a wave eight chains, so a group of up to 8 rungs sits in one wave and a larger one does not;
+        NotImplementedError for a larger group, before any launch.  A group size that does not divide 8 leaves some of
+        a wave's eight places idle (3 rungs: 6 of 8 used) and launches more waves: on batches that fill the chip and
+        with rounds many steps apart the round between launches can be the faster form (README).
+        ValueError for a plain-HMC dynamics (`run_hmc_exchange` runs it); NotImplementedError where `run` has no
+        one-launch path (layer by layer, steps_per_launch = 1)."""
         if replicas is None:
             return self.run(run_steps, x, keep_samples, temperature)
         who, dyn = "run_exchange", self.dynamics
@@ -303,14 +331,45 @@ class DynamicsSampler:
                 "holds: not layer by layer, and steps_per_launch > 1)")
         run_steps, x, temps, exchange = self._exchange_args(who, run_steps, x, temperature, replicas, swap_every,
                                                             first_parity, replica0)
+        in_launch = bool(self.in_launch)
+        if in_launch and not self.exchange_in_launch(exchange.G):
+            raise NotImplementedError(
+                f"{who} with in_launch = True: replicas={exchange.G}: a replica group sits in the eight chains of one "
+                f"wave of the L2HMC kernel, so it has {self.MAX_REPLICAS_IN_LAUNCH} rungs at the most "
+                "(`exchange_in_launch(replicas)`); in_launch = False takes groups of up to "
+                f"{self.MAX_REPLICAS} rungs")
         if run_steps == 0:
             return self._finish(exchange.finish(_runs.empty_run(("px",), x, keep_samples)))
         self.replica = exchange.start(x.device)
         temps_from = self._temps_from(temps, x.device)
+        if in_launch:
+            return self._finish(exchange.finish(self._run_exchange_launches(run_steps, x, keep_samples, temps_from,
+                                                                            exchange)))
         # a round takes one stream of the dynamics' counter; the next chunk reads the counter when it is launched
         out = self._run_launches(run_steps, x, keep_samples, dyn._plan(), "l2hmc_small_run_tempered", temps_from,
                                  streams=4, cut_every=exchange.k, after=exchange.between(self._swap_round, temps_from))
         return self._finish(exchange.finish(out))
+
+    def _run_exchange_launches(self, run_steps, x, keep_samples, temps_from, exchange):
+        """`run_exchange` with the rounds inside the launches: ONE launch of l2hmc_small_run_exchange per chunk of
+        `steps_per_launch` steps, as `run_hmc_exchange` launches its entry."""
+        dyn = self.dynamics
+        B = x.shape[0]
+        plan = dyn._plan()
+        exchange.in_launch(run_steps, x.device)
+        px = torch.empty(run_steps, B, dtype=torch.float32, device=x.device)
+
+        def launch(s0, n, x_in, x_next, samples_dev):
+            # a chunk may end inside a swap period: it passes where in the period it starts and its first round's
+            # parity, and moves the counter by its steps' streams and its rounds', after the entry returned
+            place, hist, n_rounds = exchange.chunk(s0, n)
+            _lib.call("l2hmc_small_run_exchange", C.byref(plan), x_in, x_next, B, dyn._seed, dyn._draws, n,
+                      *temps_from(s0), *place, self.replica, px[s0:], samples_dev, *hist, device=dyn._device)
+            dyn._draws += 4 * n + n_rounds
+
+        out = _runs.run_chunks(run_steps, x, self.steps_per_launch, keep_samples, launch)
+        out["px"] = px.cpu().numpy()
+        return out
 
     def generate_trajectories(self, temp=1., num_samples=500, num_steps=100, x=None):
         """mog_model.py:394-421 -> (trajectories [num_steps, num_samples, x_dim], px [num_steps, num_samples]).  As in

@@ -544,6 +544,39 @@ int l2hmc_gauge_loss_backward(int32_t T, int32_t X, float beta, const float* x0,
                               const float* vN, const float* p, int64_t B, int32_t metric, float loss_scale,
                               float aux_weight, float std_weight, float charge_weight, float inv_count,
                               float* terms, float* dxN, float* dvN, float* dlogdet, l2hmc_stream_t stream);
+/* The training step on a LADDER of beta: the three entries above with a beta per chain, for networks that are to
+ * serve every rung of a replica-exchange run (l2hmc_gauge_mcmc_step_ladder, l2hmc_gauge_replica_swap).  Row r of a
+ * call reads betas[(r % chains) * chain_stride]: with chains = B, rows i and B + i of the stacked 2B rows (chain i of
+ * the x batch and chain i of the z batch) train at one value.  betas is a DEVICE pointer; chain_stride is 1 (betas
+ * [chains]) or 0 (one value).  Everything else is the contract of the scalar entry: arguments, outputs, the workspace
+ * of l2hmc_gauge_train_ws_bytes, no allocation, rows == 0 / B == 0 a no-op -- with ONE exception:
+ * l2hmc_gauge_train_backward_ladder takes rows == 0 as a no-op too (plan and ladder arguments are still checked, nothing
+ * is written), where the two scalar backward entries refuse it.  The kernels run the scalar step's own
+ * fp32 operations on the row's value, so a row has the bits of the scalar entry at its beta (weight and eps gradients
+ * are sums over rows and have them where all rows share one value).  Every training plan is served: plans with a
+ * whole-trajectory kernel by instances of it, and of the fused reverse pass, that read the row's beta from LDS (the
+ * uniform entries' kernels are left as they are), the others layer by layer with the rows' betas.
+ * l2hmc_gauge_train_backward_ladder covers both scalar backward entries: on_bucket may be NULL.
+ * l2hmc_gauge_loss_backward_ladder lays the ladder on the B pairs: rows r and B + r read betas[r * chain_stride].
+ * Refused with L2HMC_ERR_ARG before any device call: NULL betas, a chain_stride other than 0 or 1, chains <= 0,
+ * rows % chains != 0, and everything the scalar entry refuses.
+ * The VALUES of betas are on the device and are not checked (as in l2hmc_gauge_mcmc_step_ladder): a beta that is
+ * negative or not finite is no beta.  Callers check: GaugeTrainer.calc_loss_and_grads does. */
+int l2hmc_gauge_train_forward_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t chain_stride,
+                                     int64_t chains, const float* x0, const float* v0, const int32_t* dir,
+                                     int64_t rows, float* x_out, float* v_out, float* sumlogdet, float* p_accept,
+                                     void* ws, size_t ws_bytes, l2hmc_stream_t stream);
+int l2hmc_gauge_train_backward_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t chain_stride,
+                                      int64_t chains, const int32_t* dir, int64_t rows, float* dx, float* dv,
+                                      const float* dlogdet, const l2hmc_dense_grads* gx, const l2hmc_dense_grads* gv,
+                                      const l2hmc_conv3d_grads* gxf, const l2hmc_conv3d_grads* gvf, float* deps,
+                                      void* ws, size_t ws_bytes, l2hmc_stream_t stream, l2hmc_bucket_fn on_bucket,
+                                      void* user);
+int l2hmc_gauge_loss_backward_ladder(int32_t T, int32_t X, const float* betas, int64_t chain_stride, const float* x0,
+                                     const float* xN, const float* vN, const float* p, int64_t B, int32_t metric,
+                                     float loss_scale, float aux_weight, float std_weight, float charge_weight,
+                                     float inv_count, float* terms, float* dxN, float* dvN, float* dlogdet,
+                                     l2hmc_stream_t stream);
 /* Reverse of the end of a transition (gauge_dynamics.py:229-257) for ANY loss: the accept probability
  * p = exp(min(A, 0)), A = H(x0, v0) - H(xN, vN) + sumlogdet, H = beta S(x) + |v|^2 / 2, and the select
  * x_out = a xN + (1 - a) x0 with a = [p > u] (strict).  What a caller's autograd needs between its cotangents of

@@ -141,6 +141,14 @@ _PROTOS = {
                                                      BUCKET_FN, _P]),
     "l2hmc_gauge_loss_backward": (C.c_int, [_I32, _I32, _F, _P, _P, _P, _P, _I64, _I32, _F, _F, _F, _F, _F, _P, _P,
                                             _P, _P, _P]),
+    "l2hmc_gauge_train_forward_ladder": (C.c_int, [C.POINTER(GaugePlan), _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P,
+                                                   _P, _P, _SZ, _P]),
+    "l2hmc_gauge_train_backward_ladder": (C.c_int, [C.POINTER(GaugePlan), _P, _I64, _I64, _P, _I64, _P, _P, _P,
+                                                    C.POINTER(DenseGrads), C.POINTER(DenseGrads),
+                                                    C.POINTER(Conv3DGrads), C.POINTER(Conv3DGrads), _P, _P, _SZ, _P,
+                                                    BUCKET_FN, _P]),
+    "l2hmc_gauge_loss_backward_ladder": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P, _P, _I64, _I32, _F, _F, _F, _F,
+                                                   _F, _P, _P, _P, _P, _P]),
     "l2hmc_gauge_accept_backward": (C.c_int, [_I32, _I32, _F, _I64] + [_P] * 15 + [_P]),
     "l2hmc_grad_sumsq": (C.c_int, [_P, _I64, _I64, _I64, _P, _I32, _P]),
     "l2hmc_adam_step": (C.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _I64, _I64, _P]),

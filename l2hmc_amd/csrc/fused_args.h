@@ -57,6 +57,11 @@ struct FusedArgs {
   // (Last in the struct: the uniform instances read what they read before, at the offsets they read it from.)
   const float* step_betas;
   int64_t step_beta_stride;
+  // The same two fields in TRAJECTORY mode, for the taped forward of a training step on a ladder
+  // (l2hmc_gauge_train_forward_ladder; the TAPE && LADDER instances): row r of the launch runs at
+  // step_betas[(r % step_beta_mod) * step_beta_stride] -- RowBeta's rule, so rows i and B + i of the stacked x and z
+  // chains share chain i's value.  Read by those instances only.
+  int64_t step_beta_mod;
 };
 
 // the sub-tile form (fused_traj4.hip): GenericNet 8x8 plans, sampling only

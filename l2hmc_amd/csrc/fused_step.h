@@ -69,7 +69,10 @@ __device__ __forceinline__ float philox_u01(uint64_t seed, uint64_t elem, uint64
 // was): the beta of a row is that of the row's CHAIN -- both directions of a chain (paired layout: rows r and
 // r + ROWS / 2; split layout: the same row of the pair's two workgroups) run at one value.  A dead row (chain >=
 // step_Bl) reads nothing and takes FusedArgs::beta.
-template <int ROWS, int THREADS, int D, int SX, bool LADDER = false>
+// LADDER && TRAJ (the taped forward of a training step on a ladder, trajectory mode, again instances of their own):
+// live row r of the launch takes step_betas[(r % step_beta_mod) * step_beta_stride], a dead row FusedArgs::beta -- 0
+// in a ladder launch (train.hip passes RowBeta's scalar slot); a dead row holds zeros and is never written back.
+template <int ROWS, int THREADS, int D, int SX, bool LADDER = false, bool TRAJ = false>
 __device__ __forceinline__ void stage_chains(const FusedArgs& p, const StepWg& w, float* xs, float* vs, int* sdir) {
   const int tid = w.tid;
   if (w.stepm) {
@@ -117,7 +120,9 @@ __device__ __forceinline__ void stage_chains(const FusedArgs& p, const StepWg& w
     if (w.stepm) d = w.split ? w.sdw : w.paired ? (tid >= ROWS / 2 ? 1 : 0) : (w.scoin[tid] > 0.5f ? 0 : 1);
     else if (tid < w.nrow) d = p.dir ? p.dir[w.row0 + tid] : (p.dir_split > 0 && w.row0 + tid >= p.dir_split) ? 1 : 0;
     sdir[tid] = d;
-    if constexpr (LADDER) {
+    if constexpr (LADDER && TRAJ) {
+      w.sbeta[tid] = tid < w.nrow ? p.step_betas[((w.row0 + tid) % p.step_beta_mod) * p.step_beta_stride] : p.beta;
+    } else if constexpr (LADDER) {
       const int64_t chain = w.cbase + (w.paired && tid >= ROWS / 2 ? tid - ROWS / 2 : tid);
       w.sbeta[tid] = chain < p.step_Bl ? p.step_betas[chain * p.step_beta_stride] : p.beta;
     }
@@ -277,7 +282,7 @@ __device__ __forceinline__ void step_accept_probs(const ChainLanes& c, const flo
 }
 
 // trajectory mode: log-det and accept probability of the live rows
-template <int ROWS, int NCH, int NLD>
+template <int ROWS, int NCH, int NLD, bool LADDER = false>
 __device__ __forceinline__ void traj_logdet_accept(const FusedArgs& p, const StepWg& w, const ChainLanes& c,
                                                    const float* ldw, const float (&act0)[NCH], const float (&act1)[NCH],
                                                    const float (&kin0)[NCH], const float (&kin1)[NCH]) {
@@ -289,7 +294,8 @@ __device__ __forceinline__ void traj_logdet_accept(const FusedArgs& p, const Ste
         const float sld = sum_logdet<ROWS, NLD>(ldw, fc);
         const int64_t rr = w.row0 + fc;
         if (p.logdet) p.logdet[rr] = p.logdet_accumulate ? p.logdet[rr] + sld : sld;
-        if (p.p_accept) p.p_accept[rr] = accept_prob(c.beta, act0[h], act1[h], kin0[h], kin1[h], sld);
+        const float beta = LADDER ? c.sbeta[fc] : c.beta;
+        if (p.p_accept) p.p_accept[rr] = accept_prob(beta, act0[h], act1[h], kin0[h], kin1[h], sld);
       }
     }
   }

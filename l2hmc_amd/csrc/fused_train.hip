@@ -63,6 +63,11 @@ struct FusedBwdArgs {
   const float* dld;                              // [rows]
   float* dcs_x; float* dcq_x; float* dcs_v; float* dcq_v;   // [workgroups][D]
   float* deps;                                   // [workgroups]
+  // A ladder of beta (l2hmc_gauge_train_backward_ladder; the LADDER instance, launched iff betas is set): row r runs at
+  // betas[(r % beta_mod) * beta_stride], a DEVICE pointer.  (Last in the struct: the uniform instance reads what it
+  // read before, at the offsets it read it from.)
+  const float* betas;
+  int64_t beta_mod, beta_stride;
 };
 
 template <int D, int H>
@@ -75,7 +80,10 @@ struct FusedBwdCfg {
   static constexpr int LDS_FLOATS = 4 * kFM * SX + kFM * SO + 2 * kFM * SH + kFM * SP + 2 * D + 4 * D + 2 * kFM + 8;
 };
 
-template <int D, int H>
+// LADDER: a beta per row (FusedBwdArgs::betas), staged once per workgroup into LDS behind the uniform instance's
+// layout (kFM more floats of dynamic LDS) and read there by the force-Hessian stencil of phase E -- the one place beta
+// enters a VNet call.  An instance of its own, so that the uniform reverse pass stays the code it was.
+template <int D, int H, bool LADDER = false>
 __global__ __launch_bounds__(kFThreads) void gauge_train_bwd_fused_kernel(FusedBwdArgs p) {
   using Cfg = FusedBwdCfg<D, H>;
   constexpr int SX = Cfg::SX, SO = Cfg::SO, SH = Cfg::SH, NT1 = Cfg::NT1, NT3 = Cfg::NT3, SP = Cfg::SP;
@@ -96,6 +104,10 @@ __global__ __launch_bounds__(kFThreads) void gauge_train_bwd_fused_kernel(FusedB
   float* sdl = ec + 4 * D;                // [16] d loss / d sumlogdet
   int* sdir = reinterpret_cast<int*>(sdl + kFM);   // [16]
   float* red = reinterpret_cast<float*>(sdir + kFM);   // [8]
+  // [16] LADDER: beta of every row.  A dead row of a partly filled tile takes p.beta, which a ladder launch leaves at 0
+  // (RowBeta's scalar slot; the uniform instance's dead rows run at the scalar): such a row holds zeros and is never
+  // written back, so its beta reaches no output.
+  [[maybe_unused]] float* sbeta = red + 8;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -107,6 +119,9 @@ __global__ __launch_bounds__(kFThreads) void gauge_train_bwd_fused_kernel(FusedB
   const int c0 = fl * 8;                           // this thread's 8 columns in the element-wise phases
   const bool live = fc < nrow;
   const int T = p.T, X = p.X, N = p.num_steps;
+  if constexpr (LADDER) {                          // (read behind the barrier that follows the staging below)
+    if (tid < kFM) sbeta[tid] = tid < nrow ? p.betas[((row0 + tid) % p.beta_mod) * p.beta_stride] : p.beta;
+  }
   const int xsh = 31 - __clz(X);       // X is a power of two whenever this kernel is chosen (fused_plan_supported)
 
   for (int i = tid; i < kFM * (D / 4); i += kFThreads) {
@@ -427,8 +442,9 @@ __global__ __launch_bounds__(kFThreads) void gauge_train_bwd_fused_kernel(FusedB
           const int i = s >> xsh, j = s & (X - 1);            // X is a power of two (T * X = 64)
           const int jm = (j == 0) ? X - 1 : j - 1, im = (i == 0) ? T - 1 : i - 1;
           const float c = spc[s];
-          dxs[fc * SX + 2 * s] += dis[fc * SI + 2 * s] + p.beta * (c - spc[i * X + jm]);
-          dxs[fc * SX + 2 * s + 1] += dis[fc * SI + 2 * s + 1] + p.beta * (-c + spc[im * X + j]);
+          const float beta = LADDER ? sbeta[fc] : p.beta;
+          dxs[fc * SX + 2 * s] += dis[fc * SI + 2 * s] + beta * (c - spc[i * X + jm]);
+          dxs[fc * SX + 2 * s + 1] += dis[fc * SI + 2 * s + 1] + beta * (-c + spc[im * X + j]);
         }
       }
       __syncthreads();
@@ -740,14 +756,21 @@ int fused_train_supported(const l2hmc_gauge_plan* p) {
 int launch_fused_train_backward(const l2hmc_gauge_plan* p, float beta, const int* dir, int64_t rows, float* dx,
                                 float* dv, const float* dld, const FusedTape& tx, const FusedTape& tv,
                                 float* const deltas_x[3], float* const deltas_v[3], float* pack_x, float* pack_v,
-                                float* const coef_parts[4], float* deps_part, hipStream_t stream) {
+                                float* const coef_parts[4], float* deps_part, hipStream_t stream,
+                                const float* betas, int64_t beta_mod, int64_t beta_stride) {
   using Cfg = FusedBwdCfg<128, 512>;
   L2HMC_REQUIRE(fused_train_supported(p), "fused training backward: unsupported plan");
+  L2HMC_REQUIRE(!betas || (beta_mod > 0 && (beta_stride == 0 || beta_stride == 1)),
+                "fused training backward: a beta per row needs a modulus > 0 and an element stride of 0 or 1");
   static DeviceOnce attr_once;
-  const size_t lds = sizeof(float) * Cfg::LDS_FLOATS;
+  const size_t lds = sizeof(float) * (Cfg::LDS_FLOATS + (betas ? kFM : 0));    // LADDER: + the rows' betas
   if (attr_once.pending()) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_train_bwd_fused_kernel<128, 512>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(sizeof(float) * Cfg::LDS_FLOATS)) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_train_bwd_fused_kernel<128, 512, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(sizeof(float) * (Cfg::LDS_FLOATS + kFM))) != hipSuccess) {
       set_error("fused training backward: cannot reserve %zu B of LDS", lds);
       return L2HMC_ERR_HIP;
     }
@@ -767,8 +790,13 @@ int launch_fused_train_backward(const l2hmc_gauge_plan* p, float beta, const int
   a.dx = dx; a.dv = dv; a.dld = dld;
   a.dcs_x = coef_parts[0]; a.dcq_x = coef_parts[1]; a.dcs_v = coef_parts[2]; a.dcq_v = coef_parts[3];
   a.deps = deps_part;
-  hipLaunchKernelGGL((gauge_train_bwd_fused_kernel<128, 512>), dim3((unsigned)ceil_div(rows, kFM)), dim3(kFThreads),
-                     lds, stream, a);
+  a.betas = betas; a.beta_mod = beta_mod; a.beta_stride = beta_stride;
+  if (betas)
+    hipLaunchKernelGGL((gauge_train_bwd_fused_kernel<128, 512, true>), dim3((unsigned)ceil_div(rows, kFM)),
+                       dim3(kFThreads), lds, stream, a);
+  else
+    hipLaunchKernelGGL((gauge_train_bwd_fused_kernel<128, 512>), dim3((unsigned)ceil_div(rows, kFM)), dim3(kFThreads),
+                       lds, stream, a);
   L2HMC_CHECK_LAUNCH("gauge_train_bwd_fused");
   return L2HMC_OK;
 }

@@ -219,6 +219,7 @@ extern "C" void l2hmc_debug_set_stagger(int cycles) { g_fused_stagger = cycles; 
 
 // TAPE: training instantiation (GenericNet plans) that also writes the per-call tape of train.hip
 // LADDER: step mode with a beta per chain (FusedArgs::step_betas), an instance of its own next to the sampling one
+// TAPE && LADDER: the taped forward of a training step on a ladder (trajectory mode, a beta per row; fused_step.h)
 template <int D, int H, int KA, bool CONV, bool TAPE = false, bool LADDER = false>
 __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_traj_fused_kernel(FusedArgs p) {
   using Cfg = FusedCfg<D, H, KA, CONV>;
@@ -285,7 +286,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   const bool STEPM = wg.stepm;
   const int sdw = wg.sdw;                                               // (SPLIT) this workgroup's direction
   float* spx = wg.spx;                                                  // [16] accept probability per row
-  stage_chains<kFM, kFThreads, D, SX, LADDER>(p, wg, xs, vs, sdir);
+  stage_chains<kFM, kFThreads, D, SX, LADDER, TAPE>(p, wg, xs, vs, sdir);
   load_consts<kFThreads, D, H>(p.xnet, cx, tid);
   load_consts<kFThreads, D, H>(p.vnet, cv, tid);
   if constexpr (CONV) {
@@ -1160,7 +1161,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
     step_write_next<kFThreads, D, SX>(p, wg, gout);
     return;
   }
-  traj_logdet_accept<kFM, 1, IMGW>(p, wg, cl, ldw, act0, act1, kin0, kin1);
+  traj_logdet_accept<kFM, 1, IMGW, TAPE && LADDER>(p, wg, cl, ldw, act0, act1, kin0, kin1);
 #ifdef L2HMC_STAMPS
   if (p.stamps && tid == 0) {
     unsigned long long rt1;
@@ -1218,7 +1219,7 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
                             const float* x0, const float* v0, const int* dir, int64_t rows, float* x_out,
                             float* v_out, float* logdet, int logdet_accumulate, float* p_accept,
                             hipStream_t stream, int64_t x_mod, int64_t dir_split, const FusedTape* tape_x,
-                            const FusedTape* tape_v) {
+                            const FusedTape* tape_v, const float* betas, int64_t beta_mod, int64_t beta_stride) {
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
   using CfgG = FusedCfg<128, 512, 128, false>;
   using CfgC = FusedCfg<128, 256, 64, true>;
@@ -1267,6 +1268,25 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
       tape_once.done();
     }
   }
+  if (betas) {
+    // a ladder: the taped instances that read a beta per row (FusedArgs::step_beta_mod); `beta` is what a dead row takes
+    L2HMC_REQUIRE(tape && beta_mod > 0 && (beta_stride == 0 || beta_stride == 1),
+                  "fused trajectory: a beta per row needs the tape, a modulus > 0 and an element stride of 0 or 1");
+    a.step_betas = betas; a.step_beta_mod = beta_mod; a.step_beta_stride = beta_stride;
+    static DeviceOnce ladder_once;
+    if (ladder_once.pending()) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused_kernel<128, 512, 128, false, true, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(sizeof(float) * CfgG::LDS_FLOATS)) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_fused_kernel<128, 256, 64, true, true, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(sizeof(float) * CfgC::LDS_FLOATS)) != hipSuccess) {
+        set_error("fused trajectory: cannot reserve %zu B of LDS", lds);
+        return L2HMC_ERR_HIP;
+      }
+      ladder_once.done();
+    }
+  }
 #ifdef L2HMC_STAMPS
   a.stamps = g_stamp_cls == 5 ? g_stamp_buf : nullptr;
   a.stagger = g_fused_stagger;
@@ -1279,7 +1299,13 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
   }
   const dim3 grid((unsigned)ceil_div(rows, kFM));
   prof_before(kProfFused, stream);
-  if (conv && tape)
+  if (conv && betas)
+    hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 256, 64, true, true, true>), grid, dim3(CfgC::THREADS), lds, stream,
+                       a);
+  else if (betas)
+    hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 512, 128, false, true, true>), grid, dim3(CfgG::THREADS), lds,
+                       stream, a);
+  else if (conv && tape)
     hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 256, 64, true, true>), grid, dim3(CfgC::THREADS), lds, stream, a);
   else if (conv)
     hipLaunchKernelGGL((gauge_traj_fused_kernel<128, 256, 64, true>), grid, dim3(CfgC::THREADS), lds, stream, a);

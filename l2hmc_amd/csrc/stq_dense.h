@@ -150,7 +150,9 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
                             const float* x0, const float* v0, const int* dir, int64_t rows, float* x_out,
                             float* v_out, float* logdet, int logdet_accumulate, float* p_accept,
                             hipStream_t stream, int64_t x_mod = 0, int64_t dir_split = 0,
-                            const FusedTape* tape_x = nullptr, const FusedTape* tape_v = nullptr);
+                            const FusedTape* tape_x = nullptr, const FusedTape* tape_v = nullptr,
+                            // DEVICE betas (taped launches only): row r at betas[(r % beta_mod) * beta_stride]
+                            const float* betas = nullptr, int64_t beta_mod = 0, int64_t beta_stride = 0);
 int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, float* x_next, int64_t B,
                       uint64_t seed, uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges,
                       float* dq, float* step_sums, float* part, void* hand, hipStream_t stream,
@@ -198,7 +200,9 @@ int fused_train_forward_supported(const l2hmc_gauge_plan* p);
 int launch_fused_train_backward(const l2hmc_gauge_plan* p, float beta, const int* dir, int64_t rows, float* dx,
                                 float* dv, const float* dld, const FusedTape& tx, const FusedTape& tv,
                                 float* const deltas_x[3], float* const deltas_v[3], float* pack_x, float* pack_v,
-                                float* const coef_parts[4], float* deps_part, hipStream_t stream);
+                                float* const coef_parts[4], float* deps_part, hipStream_t stream,
+                                // DEVICE betas: row r at betas[(r % beta_mod) * beta_stride] (the LADDER instance)
+                                const float* betas = nullptr, int64_t beta_mod = 0, int64_t beta_stride = 0);
 // one network call of a layered reverse pass in one launch (fused_train.hip: gauge_trunk_bwd_kernel)
 struct TrunkBwdArgs {
   int mode;                                      // 1: momentum update (VNet call), 2: position update (XNet call)

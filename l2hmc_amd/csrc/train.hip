@@ -84,10 +84,11 @@ __global__ __launch_bounds__(256) void train_update_kernel(int mode, const float
 
 __global__ void train_accept_kernel(const float* __restrict__ act0, const float* __restrict__ kin0,
                                     const float* __restrict__ act1, const float* __restrict__ kin1,
-                                    const float* __restrict__ ld, float beta, int64_t rows,
+                                    const float* __restrict__ ld, RowBeta rbeta, int64_t rows,
                                     float* __restrict__ sumlogdet, float* __restrict__ p) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
+  const float beta = rbeta.at(i);
   const double h0 = (double)beta * act0[i] + kin0[i], h1 = (double)beta * act1[i] + kin1[i];
   if (sumlogdet) sumlogdet[i] = ld[i];
   if (p) p[i] = accept_from_delta((float)(h0 - h1 + (double)ld[i]));
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void xnet_in_bwd_kernel(const float* __restric
 // (lattice.py:246-262 differentiated once more).  One wave per chain, chain staged in LDS.
 __global__ __launch_bounds__(256) void vnet_in_bwd_kernel(const float* __restrict__ din,
                                                           const float* __restrict__ dg,
-                                                          const float* __restrict__ in, float beta, int T,
+                                                          const float* __restrict__ in, RowBeta rbeta, int T,
                                                           int X, int64_t rows, float* dx) {
   extern __shared__ float lds[];
   const int D = 2 * T * X, sites = T * X;
@@ -224,6 +225,7 @@ __global__ __launch_bounds__(256) void vnet_in_bwd_kernel(const float* __restric
   }
   __syncthreads();
   if (row < rows) {
+    const float beta = rbeta.at(row);
     for (int s = lane; s < sites; s += kWave) {
       const int i = s / X, j = s - i * X;
       const int jl = (j == 0) ? X - 1 : j - 1, iu = (i == 0) ? T - 1 : i - 1;
@@ -555,7 +557,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 // One wave per (x, z) pair.
 // =====================================================================
 struct LossBwdArgs {
-  int T, X; int64_t B; float beta;
+  int T, X; int64_t B;
   const float* x0;   // [2B][D] initial states (x rows, then z rows)
   const float* xN; const float* vN;   // [2B][D] proposed states
   const float* p;    // [2B]
@@ -602,11 +604,13 @@ __device__ __forceinline__ float plaq_at(const float* xs, int s, int T, int X) {
   return xs[2 * s] - xs[2 * s + 1] - xs[2 * (i * X + jr)] + xs[2 * (id * X + j) + 1];
 }
 
-__global__ __launch_bounds__(64) void loss_bwd_kernel(LossBwdArgs p) {
+// rbeta: the beta of pair b -- of its x row b and its z row B + b (a ladder: RowBeta(betas, B, stride))
+__global__ __launch_bounds__(64) void loss_bwd_kernel(LossBwdArgs p, RowBeta rbeta) {
   extern __shared__ float lds[];
   const int T = p.T, X = p.X, sites = T * X, D = 2 * sites;
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
+  const float beta = rbeta.at(b);
   float* xs = lds;            // [D] staged chain
   float* cp = xs + D;         // [sites] d q / d plaquette of x'
   float* sp = cp + sites;     // [sites] sin(plaquette)
@@ -682,7 +686,7 @@ __global__ __launch_bounds__(64) void loss_bwd_kernel(LossBwdArgs p) {
     for (int mu = 0; mu < 2; ++mu) {
       const int c = 2 * s + mu;
       const float dq = mu == 0 ? cp[s] - cp[sl] : -cp[s] + cp[su];
-      const float frc = p.beta * (mu == 0 ? sp[s] - sp[sl] : -sp[s] + sp[su]);
+      const float frc = beta * (mu == 0 ? sp[s] - sp[sl] : -sp[s] + sp[su]);
       const float a = xs[c];
       p.dxN[b * D + c] = ax * px * metric_db(p.metric, x[c], a) + az * pz * metric_db(p.metric, z[c], a) +
                          dqp * dq - ddx * frc;
@@ -701,8 +705,8 @@ __global__ __launch_bounds__(64) void loss_bwd_kernel(LossBwdArgs p) {
     const int jl = (j == 0) ? X - 1 : j - 1, iu = (i == 0) ? T - 1 : i - 1;
     const int sl = i * X + jl, su = iu * X + j;
     const int64_t o = (p.B + b) * D + 2 * s;
-    p.dxN[o] = -ddz * p.beta * (sp[s] - sp[sl]);
-    p.dxN[o + 1] = -ddz * p.beta * (-sp[s] + sp[su]);
+    p.dxN[o] = -ddz * beta * (sp[s] - sp[sl]);
+    p.dxN[o + 1] = -ddz * beta * (-sp[s] + sp[su]);
     p.dvN[o] = -ddz * p.vN[o];
     p.dvN[o + 1] = -ddz * p.vN[o + 1];
   }
@@ -1138,10 +1142,22 @@ extern "C" size_t l2hmc_gauge_train_ws_bytes(const l2hmc_gauge_plan* plan, int64
   return carve_train_ws(plan, rows, nullptr).bytes;
 }
 
-extern "C" int l2hmc_gauge_train_forward(const l2hmc_gauge_plan* plan, float beta, const float* x0, const float* v0,
-                                         const int32_t* dir, int64_t rows, float* x_out, float* v_out,
-                                         float* sumlogdet, float* p_accept, void* ws, size_t ws_bytes,
-                                         l2hmc_stream_t stream) {
+// The refusals the three _ladder entries add to those of their scalar forms (`rows`: the rows the ladder is laid on,
+// a whole number of `chains`)
+static int check_ladder(const char* who, const float* betas, int64_t chain_stride, int64_t chains, int64_t rows) {
+  L2HMC_REQUIRE(betas != nullptr, "%s: NULL betas", who);
+  L2HMC_REQUIRE(chain_stride == 0 || chain_stride == 1, "%s: chain_stride = %lld is not 0 or 1", who,
+                (long long)chain_stride);
+  L2HMC_REQUIRE(chains > 0, "%s: chains = %lld is not > 0", who, (long long)chains);
+  L2HMC_REQUIRE(rows % chains == 0, "%s: rows = %lld is no whole number of chains = %lld", who, (long long)rows,
+                (long long)chains);
+  return L2HMC_OK;
+}
+
+// l2hmc_gauge_train_forward with the beta of every row (RowBeta: the scalar of the public entry, or a ladder)
+static int train_forward_impl(const l2hmc_gauge_plan* plan, RowBeta beta, const float* x0, const float* v0,
+                              const int32_t* dir, int64_t rows, float* x_out, float* v_out, float* sumlogdet,
+                              float* p_accept, void* ws, size_t ws_bytes, l2hmc_stream_t stream) {
   if (int e = check_train_plan(plan)) return e;
   L2HMC_REQUIRE(rows >= 0, "train_forward: rows < 0");
   if (rows == 0) return L2HMC_OK;
@@ -1168,7 +1184,8 @@ extern "C" int l2hmc_gauge_train_forward(const l2hmc_gauge_plan* plan, float bet
   if (fused_train_forward_supported(plan)) {
     // whole-trajectory kernel (fused_traj.hip) writing the same tape: one launch instead of ~6 per network call
     const FusedTape tx{w.x.in, w.x.h1, w.x.h2, w.x.stq, w.x.st, w.x.feat, w.x.gate}, tv{w.v.in, w.v.h1, w.v.h2, w.v.stq, w.v.st, w.v.feat, w.v.gate};
-    return launch_fused_trajectory(plan, beta, 0, N, x, v, dir, rows, x, v, sumlogdet, 0, p_accept, s, 0, 0, &tx, &tv);
+    return launch_fused_trajectory(plan, beta.beta, 0, N, x, v, dir, rows, x, v, sumlogdet, 0, p_accept, s, 0, 0, &tx, &tv,
+                                   beta.betas, beta.mod, beta.stride);
   }
   if (int e = launch_u1_action_force(x, rows, plan->T, plan->X, beta, w.act0, nullptr, nullptr, nullptr, s)) return e;
   if (int e = l2hmc_kinetic_energy(v, rows, D, w.kin0, stream)) return e;
@@ -1205,7 +1222,24 @@ extern "C" int l2hmc_gauge_train_forward(const l2hmc_gauge_plan* plan, float bet
   return L2HMC_OK;
 }
 
-static int train_backward_impl(const l2hmc_gauge_plan* plan, float beta, const int32_t* dir, int64_t rows,
+extern "C" int l2hmc_gauge_train_forward(const l2hmc_gauge_plan* plan, float beta, const float* x0, const float* v0,
+                                         const int32_t* dir, int64_t rows, float* x_out, float* v_out,
+                                         float* sumlogdet, float* p_accept, void* ws, size_t ws_bytes,
+                                         l2hmc_stream_t stream) {
+  return train_forward_impl(plan, RowBeta(beta), x0, v0, dir, rows, x_out, v_out, sumlogdet, p_accept, ws, ws_bytes,
+                            stream);
+}
+
+extern "C" int l2hmc_gauge_train_forward_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t chain_stride,
+                                                int64_t chains, const float* x0, const float* v0, const int32_t* dir,
+                                                int64_t rows, float* x_out, float* v_out, float* sumlogdet,
+                                                float* p_accept, void* ws, size_t ws_bytes, l2hmc_stream_t stream) {
+  if (int e = check_ladder("train_forward_ladder", betas, chain_stride, chains, rows)) return e;
+  return train_forward_impl(plan, RowBeta(betas, chains, chain_stride), x0, v0, dir, rows, x_out, v_out, sumlogdet,
+                            p_accept, ws, ws_bytes, stream);
+}
+
+static int train_backward_impl(const l2hmc_gauge_plan* plan, RowBeta beta, const int32_t* dir, int64_t rows,
                                float* dx, float* dv, const float* dlogdet,
                                const l2hmc_dense_grads* gx, const l2hmc_dense_grads* gv,
                                const l2hmc_conv3d_grads* gxf, const l2hmc_conv3d_grads* gvf, float* deps,
@@ -1310,8 +1344,8 @@ static int train_backward_impl(const l2hmc_gauge_plan* plan, float beta, const i
     float* const dxs_[3] = {w.x.dout, w.x.d2, w.x.d1};
     float* const dvs_[3] = {w.v.dout, w.v.d2, w.v.d1};
     float* const coef[4] = {w.x.dcs_part, w.x.dcq_part, w.v.dcs_part, w.v.dcq_part};
-    if (int e = launch_fused_train_backward(plan, beta, dir, rows, dx, dv, dlogdet, tx, tv, dxs_, dvs_, w.x.bpack,
-                                            w.v.bpack, coef, w.eps_part, s))
+    if (int e = launch_fused_train_backward(plan, beta.beta, dir, rows, dx, dv, dlogdet, tx, tv, dxs_, dvs_, w.x.bpack,
+                                            w.v.bpack, coef, w.eps_part, s, beta.betas, beta.mod, beta.stride))
       return e;
     ncoef = ceil_div(rows, 16);
   } else {
@@ -1429,23 +1463,59 @@ extern "C" int l2hmc_gauge_train_backward_buckets(const l2hmc_gauge_plan* plan, 
                              on_bucket, user);
 }
 
+extern "C" int l2hmc_gauge_train_backward_ladder(const l2hmc_gauge_plan* plan, const float* betas,
+                                                 int64_t chain_stride, int64_t chains, const int32_t* dir,
+                                                 int64_t rows, float* dx, float* dv, const float* dlogdet,
+                                                 const l2hmc_dense_grads* gx, const l2hmc_dense_grads* gv,
+                                                 const l2hmc_conv3d_grads* gxf, const l2hmc_conv3d_grads* gvf,
+                                                 float* deps, void* ws, size_t ws_bytes, l2hmc_stream_t stream,
+                                                 l2hmc_bucket_fn on_bucket, void* user) {
+  if (int e = check_ladder("train_backward_ladder", betas, chain_stride, chains, rows)) return e;
+  if (rows == 0) {      // an empty batch is a no-op here, as in the forward and loss entries (nothing is written)
+    if (int e = check_train_plan(plan)) return e;
+    return L2HMC_OK;
+  }
+  return train_backward_impl(plan, RowBeta(betas, chains, chain_stride), dir, rows, dx, dv, dlogdet, gx, gv, gxf, gvf,
+                             deps, ws, ws_bytes, stream, on_bucket, user);
+}
+
+// l2hmc_gauge_loss_backward with the beta of every pair (beta.at(b): x row b and z row B + b)
+static int loss_backward_impl(int32_t T, int32_t X, RowBeta beta, const float* x0, const float* xN, const float* vN,
+                              const float* p, int64_t B, int32_t metric, float loss_scale, float aux_weight,
+                              float std_weight, float charge_weight, float inv_count, float* terms, float* dxN,
+                              float* dvN, float* dlogdet, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(T > 0 && X > 0 && B >= 0 && metric >= 0 && metric <= 4, "loss_backward: bad arguments");
+  if (B == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x0 && xN && vN && p && dxN && dvN && dlogdet, "loss_backward: NULL pointer");
+  LossBwdArgs a{};
+  a.T = T; a.X = X; a.B = B; a.x0 = x0; a.xN = xN; a.vN = vN; a.p = p; a.metric = metric;
+  a.loss_scale = loss_scale; a.aux_weight = aux_weight; a.std_weight = std_weight; a.charge_weight = charge_weight;
+  a.inv_count = inv_count; a.terms = terms; a.dxN = dxN; a.dvN = dvN; a.dld = dlogdet;
+  const size_t lds = sizeof(float) * (size_t)(2 * T * X + 2 * T * X);
+  L2HMC_REQUIRE(lds <= 64 * 1024, "loss_backward: lattice too large for one workgroup's LDS");
+  hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, a, beta);
+  L2HMC_CHECK_LAUNCH("loss_bwd");
+  return L2HMC_OK;
+}
+
 extern "C" int l2hmc_gauge_loss_backward(int32_t T, int32_t X, float beta, const float* x0, const float* xN,
                                          const float* vN, const float* p, int64_t B, int32_t metric,
                                          float loss_scale, float aux_weight, float std_weight, float charge_weight,
                                          float inv_count, float* terms, float* dxN, float* dvN, float* dlogdet,
                                          l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(T > 0 && X > 0 && B >= 0 && metric >= 0 && metric <= 4, "loss_backward: bad arguments");
-  if (B == 0) return L2HMC_OK;
-  L2HMC_REQUIRE(x0 && xN && vN && p && dxN && dvN && dlogdet, "loss_backward: NULL pointer");
-  LossBwdArgs a{};
-  a.T = T; a.X = X; a.B = B; a.beta = beta; a.x0 = x0; a.xN = xN; a.vN = vN; a.p = p; a.metric = metric;
-  a.loss_scale = loss_scale; a.aux_weight = aux_weight; a.std_weight = std_weight; a.charge_weight = charge_weight;
-  a.inv_count = inv_count; a.terms = terms; a.dxN = dxN; a.dvN = dvN; a.dld = dlogdet;
-  const size_t lds = sizeof(float) * (size_t)(2 * T * X + 2 * T * X);
-  L2HMC_REQUIRE(lds <= 64 * 1024, "loss_backward: lattice too large for one workgroup's LDS");
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, a);
-  L2HMC_CHECK_LAUNCH("loss_bwd");
-  return L2HMC_OK;
+  return loss_backward_impl(T, X, RowBeta(beta), x0, xN, vN, p, B, metric, loss_scale, aux_weight, std_weight,
+                            charge_weight, inv_count, terms, dxN, dvN, dlogdet, stream);
+}
+
+extern "C" int l2hmc_gauge_loss_backward_ladder(int32_t T, int32_t X, const float* betas, int64_t chain_stride,
+                                                const float* x0, const float* xN, const float* vN, const float* p,
+                                                int64_t B, int32_t metric, float loss_scale, float aux_weight,
+                                                float std_weight, float charge_weight, float inv_count, float* terms,
+                                                float* dxN, float* dvN, float* dlogdet, l2hmc_stream_t stream) {
+  // (the ladder lies on the B pairs: one beta per pair, so `chains` is B wherever B > 0)
+  if (int e = check_ladder("loss_backward_ladder", betas, chain_stride, B > 0 ? B : 1, B)) return e;
+  return loss_backward_impl(T, X, RowBeta(betas, B > 0 ? B : 1, chain_stride), x0, xN, vN, p, B, metric, loss_scale,
+                            aux_weight, std_weight, charge_weight, inv_count, terms, dxN, dvN, dlogdet, stream);
 }
 
 extern "C" int l2hmc_gauge_accept_backward(int32_t T, int32_t X, float beta, int64_t rows, const float* x0,

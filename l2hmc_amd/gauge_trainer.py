@@ -21,13 +21,14 @@ forward and the reverse of ONE step body (`calc_loss_and_grads`: stack, forward,
 they share the draws, the flat buffer, the data-parallel exchange and the optimiser (l2hmc_amd/_flat_trainer.py)."""
 import ctypes as C
 
+import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, _runs, ops
 from . import layered_train as _layered_train
 from ._flat_trainer import FlatTrainer, stack_chains
 from .dist import active as _active_dist
-from .lattice import u1_observables
+from .lattice import replica_swap, u1_observables
 
 METRICS = {'l1': 0, 'l2': 1, 'cos': 2, 'cos2': 3, 'cos_diff': 4}
 
@@ -126,12 +127,17 @@ class GaugeTrainer(FlatTrainer):
     # ---- loss + gradients ----------------------------------------------------------
     def calc_loss_and_grads(self, x, beta, z=None, draws_x=None, draws_z=None):
         """gauge_model.py:799-830 -> (loss, x_out, accept_prob, x_dq); gradients land in self.grads.
-        draws_*: optional (momentum_f, momentum_b, coin, u) for the x and the z transition."""
+        draws_*: optional (momentum_f, momentum_b, coin, u) for the x and the z transition.
+        beta: a scalar, or a LADDER [B] / [1, B] (`_runs.per_chain`; a float32 tensor on the device stays there):
+        chain i of the x batch and chain i of the z batch then train at beta[i], through the `_ladder` training entries
+        on every path (fused, tiled, layered); everything else -- draws, loss, its normalisation, the exchange -- is the
+        scalar step's.  ValueError for another shape, a negative or a non-finite beta, before any draw is taken."""
         dyn = self.dynamics
         dev = dyn._device
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
         x = dyn._x(x)
         B, D = x.shape
+        betas = self._chain_betas(beta, B, "calc_loss_and_grads")      # None: one beta, today's entries
         z = dyn._normal((B, D)) if z is None else dyn._x(z)
 
         def draw(d):
@@ -144,23 +150,39 @@ class GaugeTrainer(FlatTrainer):
         if layered:          # one taped layered trajectory per direction, on the rows that run it
             if self._walk is None:
                 self._walk = _layered_train.LayeredWalk(dev)
-            fw = self._walk.forward(self._lattice_walk(float(beta)), x0, v0, fwd,
-                                    lambda *a: dyn._compute_accept_prob(*a, float(beta)))
+            if betas is None:
+                fw = self._walk.forward(self._lattice_walk(float(beta)), x0, v0, fwd,
+                                        lambda *a: dyn._compute_accept_prob(*a, float(beta)))
+            else:            # rows i and B + i at beta[i]: the beta = 1 force and its Hessian scaled per row
+                rb = betas.repeat(2)
+
+                def accept(xs, vs, xe, ve, lj, idx):        # gauge_dynamics.py:592-609 with the rows' betas
+                    old = rb[idx] * dyn.potential(xs) + dyn.kinetic_energy(vs)
+                    new = rb[idx] * dyn.potential(xe) + dyn.kinetic_energy(ve)
+                    return ops.accept_prob(old, new, lj)
+                fw = self._walk.forward(self._lattice_walk(1.0, rb), x0, v0, fwd, accept, accept_rows=True)
             xN, vN, p = fw.xN, fw.vN, fw.p
         else:
             xN, vN = torch.empty_like(x0), torch.empty_like(x0)
             sld, p = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
             plan = dyn._plan()
             ws, nb = self._ws.get(L.l2hmc_gauge_train_ws_bytes(C.byref(plan), R), dev)
-            _lib.call("l2hmc_gauge_train_forward", C.byref(plan), float(beta), x0, v0, dirs, R, xN, vN, sld, p, ws, nb,
-                      device=dev)
+            if betas is None:
+                _lib.call("l2hmc_gauge_train_forward", C.byref(plan), float(beta), x0, v0, dirs, R, xN, vN, sld, p, ws,
+                          nb, device=dev)
+            else:
+                _lib.call("l2hmc_gauge_train_forward_ladder", C.byref(plan), betas, 1, B, x0, v0, dirs, R, xN, vN, sld,
+                          p, ws, nb, device=dev)
         terms = torch.empty(B, dtype=torch.float32, device=dev)
         dxN, dvN = torch.empty_like(x0), torch.empty_like(x0)
         dld = torch.empty(R, dtype=torch.float32, device=dev)
         w = self.weights
-        _lib.call("l2hmc_gauge_loss_backward", T, X, float(beta), x0, xN, vN, p, B, METRICS[self.metric],
-                  self.loss_scale, w['aux_weight'], w['std_weight'], w['charge_weight'], 1.0 / (B * self.world), terms,
-                  dxN, dvN, dld, device=dev)
+        loss_tail = (x0, xN, vN, p, B, METRICS[self.metric], self.loss_scale, w['aux_weight'], w['std_weight'],
+                     w['charge_weight'], 1.0 / (B * self.world), terms, dxN, dvN, dld)
+        if betas is None:
+            _lib.call("l2hmc_gauge_loss_backward", T, X, float(beta), *loss_tail, device=dev)
+        else:
+            _lib.call("l2hmc_gauge_loss_backward_ladder", T, X, betas, 1, *loss_tail, device=dev)
         buf = torch.stack([terms.sum(dtype=torch.float32),
                            torch.full((), float(B), dtype=torch.float32, device=dev)])
         # Bucketed exchange: `send(ranges)` puts ranges of the flat buffer on the wire as soon as the reverse has
@@ -178,24 +200,26 @@ class GaugeTrainer(FlatTrainer):
             if bucketed:
                 send([(n0 + n1, n0 + n1 + 1)])
         else:
-            bargs = (C.byref(plan), float(beta), dirs, R, dxN, dvN, dld,
+            bargs = (C.byref(plan), *((float(beta),) if betas is None else (betas, 1, B)), dirs, R, dxN, dvN, dld,
                      C.byref(self._grad_structs[0]), C.byref(self._grad_structs[1]),
                      *(C.byref(g) if g is not None else None for g in self._conv_grad_structs),
                      self.grads[n0 + n1:], ws, nb)
-            if bucketed:
-                errors = []
+            errors = []
 
-                def on_bucket(_user, b):           # host thread, right after bucket b's producers were enqueued
-                    try:
-                        send(self._buckets[int(b)])
-                    except Exception as e:          # noqa: BLE001 -- a ctypes callback cannot raise: re-raised below
-                        errors.append(e)
-                cb = _lib.BUCKET_FN(on_bucket)
+            def on_bucket(_user, b):           # host thread, right after bucket b's producers were enqueued
+                try:
+                    send(self._buckets[int(b)])
+                except Exception as e:          # noqa: BLE001 -- a ctypes callback cannot raise: re-raised below
+                    errors.append(e)
+            cb = _lib.BUCKET_FN(on_bucket) if bucketed else _lib.BUCKET_FN()      # (not bucketed: a NULL callback)
+            if betas is not None:               # one entry for both: its callback may be NULL
+                _lib.call("l2hmc_gauge_train_backward_ladder", *bargs, device=dev, tail=(cb, None))
+            elif bucketed:
                 _lib.call("l2hmc_gauge_train_backward_buckets", *bargs, device=dev, tail=(cb, None))
-                if errors:
-                    raise errors[0]
             else:
                 _lib.call("l2hmc_gauge_train_backward", *bargs, device=dev)
+            if errors:
+                raise errors[0]
         if bucketed:
             self.dist.all_reduce(buf, op=self.dist.ReduceOp.SUM)
             for wk in works:
@@ -246,42 +270,90 @@ class GaugeTrainer(FlatTrainer):
             for lo, hi in ranges:
                 works.append(self.dist.all_reduce(self.grads[lo:hi], op=self.dist.ReduceOp.SUM, async_op=True))
 
-    def _lattice_walk(self, beta):
+    def _lattice_walk(self, beta, row_betas=None):
         """The lattice as l2hmc_amd/layered_train.py sees it: beta * force feeds the momentum update and VNet, with
-        ops.u1_force_hvp as its Hessian-vector product."""
+        ops.u1_force_hvp as its Hessian-vector product.  A ladder is beta = 1 with `row_betas` [2B] as the walk's row
+        factor: both kernels form beta * (a difference of sines), so the host's product has the bits of theirs."""
         dyn = self.dynamics
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
         return _layered_train.Walk(dyn.position_fn, dyn.momentum_fn, dyn.eps, dyn.num_steps, dyn._format_time,
                                    dyn._get_mask_while,
                                    lambda x: ops.u1_action_force(x, T, X, beta, want_observables=False)[1],
-                                   lambda x, u: ops.u1_force_hvp(x, u, T, X, beta))
+                                   lambda x, u: ops.u1_force_hvp(x, u, T, X, beta), row_scale=row_betas)
+
+    def _chain_betas(self, beta, B, who):
+        """None for one beta (a number or a 0-d array / tensor: the scalar entries, untouched); else the ladder as a
+        float32 device tensor [B] (`_runs.per_chain`: ValueError for another shape or a value that is negative or not
+        finite in float32; a float32 tensor [B] or [1, B] on the device stays there, unchecked)."""
+        nd = beta.ndim if isinstance(beta, torch.Tensor) else np.ndim(beta)
+        if nd == 0:
+            return None
+        return _runs.per_chain(beta, B, self.dynamics._device, who=f"GaugeTrainer.{who}", name="beta",
+                               sign="not negative")[0]
 
     def update_beta(self, step, beta_init=2., beta_final=4., train_steps=10000):
-        """gauge_model.py:1039-1046: linear annealing of 1/beta."""
+        """gauge_model.py:1039-1046: linear annealing of 1/beta (elementwise: a ladder anneals rung by rung)."""
         temp = (1. / beta_init - 1. / beta_final) * (1. - step / float(train_steps)) + 1. / beta_final
         return 1. / temp
 
+    @staticmethod
+    def swap_schedule(n_steps, swap_every):
+        """The exchange rounds of `train(..., replicas=G, swap_every=k)` over n_steps steps: {s: parity} for every
+        step s (counting from 1 within the call) that a round follows -- the samplers' schedule, `_runs.Exchange`
+        with first parity 0, read out step by step."""
+        ex = _runs.Exchange(2, int(swap_every), 0, None, 2)
+        return {s: ex.parity_after(s) for s in range(1, int(n_steps) + 1) if ex.parity_after(s) is not None}
+
     def train(self, train_steps, samples_init=None, beta_init=2., beta_final=4., initial_step=0, print_steps=0,
-              log=print):
+              log=print, replicas=None, swap_every=1):
         """gauge_model.py:1119-1300 without the file / TensorBoard side effects: per step anneal beta, run the
         train op on the current samples, wrap the new samples to [0, 2 pi) (device side), record loss, accept
         probability, step size, learning rate and the observables of the step's INPUT samples (:256-266).
         Returns {'loss', 'accept_prob', 'eps', 'lr', 'beta', 'actions', 'plaqs', 'charges', 'charge_diff',
-        'samples'} with per-step NumPy histories; the chain state never leaves the device inside the loop."""
-        import numpy as np
+        'samples'} with per-step NumPy histories; the chain state never leaves the device inside the loop.
+        beta_init / beta_final: each a scalar or [B] (one per chain): with an array the step trains on the ladder
+        update_beta gives it (`calc_loss_and_grads`) and out['beta'] is [steps, B] instead of [steps].
+        replicas=G: replica exchange between the rungs WHILE the networks train -- the frozen high-beta rungs see what
+        tunnelled at low beta.  Columns [g G, (g + 1) G) are one group; after the wrap of every step s (from 1 within
+        the call) with s % swap_every == 0 ONE round of l2hmc_gauge_replica_swap runs on the x chains at that step's
+        betas, with parity (s // swap_every - 1) % 2 and one stream of the dynamics' counter
+        (`GaugeSampler.swap_replicas`'s round, bit for bit).  out gains 'swap_rate' [G - 1] and 'swapped' [rounds, B].
+        A group lives on one rank; the gradient all-reduce is what it was.  replicas=None: no round."""
         dyn = self.dynamics
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
         if samples_init is None:
             samples_init = np.asarray(dyn.lattice.samples, dtype=np.float32).reshape(dyn.batch_size, dyn.x_dim)
         x = dyn._x(samples_init).clone()
+        B = x.shape[0]
+        ladder = np.ndim(beta_init) > 0 or np.ndim(beta_final) > 0
+        if ladder:
+            beta_init, beta_final = (np.asarray(b, dtype=np.float64) for b in (beta_init, beta_final))
+            for name, b in (("beta_init", beta_init), ("beta_final", beta_final)):
+                if b.shape not in ((), (B,)):
+                    raise ValueError(f"GaugeTrainer.train: {name} of shape {b.shape}: expected a scalar or [{B}]")
+            beta_init, beta_final = np.broadcast_to(beta_init, (B,)), np.broadcast_to(beta_final, (B,))
+        ex = None                # the samplers' exchange schedule and histories (_runs.Exchange), first parity 0
+        if replicas is not None:
+            G, k, _, _ = _runs.check_replicas(replicas, B, swap_every, who="GaugeTrainer.train")
+            ex = _runs.Exchange(G, k, 0, None, B)
         hist = {k: [] for k in ("loss", "accept_prob", "eps", "lr", "beta", "actions", "plaqs", "charges",
                                 "charge_diff")}
         for step in range(initial_step, train_steps):
             beta = self.update_beta(step, beta_init, beta_final, train_steps)
             lr = self.learning_rate()
             obs = u1_observables(x, T, X)
-            loss, x_out, px, x_dq = self.train_step(x, beta)
+            # (a ladder goes to the device once per step: the step and the round read the same float32 values)
+            beta_dev = self._chain_betas(beta, B, "train") if ladder else None
+            loss, x_out, px, x_dq = self.train_step(x, beta if beta_dev is None else beta_dev)
             ops.wrap_angle(x_out, out=x)
+            parity = ex.parity_after(step - initial_step + 1) if ex is not None else None
+            if parity is not None:
+                if beta_dev is None:
+                    beta_dev = torch.full((B,), float(beta), dtype=torch.float32, device=x.device)
+                swap_p, swapped, _ = replica_swap(x, T, X, G, parity, beta_dev, dyn._seed, dyn._draws)
+                dyn._draws += 1                                # one stream, as GaugeSampler._swap_round takes it
+                ex.rounds["swap_p"].append(swap_p)
+                ex.rounds["swapped"].append(swapped)
             for k, v in (("loss", loss), ("accept_prob", px.mean()), ("actions", obs["action"].mean()),
                          ("plaqs", obs["avg_plaq"].mean()), ("charges", obs["top_charge"]),
                          ("charge_diff", x_dq.sum() / float(x_dq.numel()))):
@@ -291,18 +363,20 @@ class GaugeTrainer(FlatTrainer):
             hist["beta"].append(beta)
             if print_steps and step % print_steps == 0:
                 log(f"{step:>5g}/{train_steps:<6g} loss {float(loss):^9.4g} acc {float(px.mean()):^9.4g} "
-                    f"eps {float(dyn.eps):^9.4g} beta {beta:^9.4g} plaq {float(obs['avg_plaq'].mean()):^9.4g} "
-                    f"lr {lr:^9.4g}")
+                    f"eps {float(dyn.eps):^9.4g} beta {float(np.mean(beta)):^9.4g} "
+                    f"plaq {float(obs['avg_plaq'].mean()):^9.4g} lr {lr:^9.4g}")
         out = {k: (torch.stack(v).cpu().numpy() if v and isinstance(v[0], torch.Tensor) else np.asarray(v))
                for k, v in hist.items()}
         out["samples"] = x
+        if ex is not None:       # (the trainer keeps no labels: of the samplers' histories, `swapped` and its rate)
+            rounds = ex.finish({})
+            out["swapped"], out["swap_rate"] = rounds["swapped"], rounds["swap_rate"]
         return out
 
     # ---- resumable state (gauge_model.py:519-556 `_current_state` + save_weights; .npz, never a pickle) ----
     def save_state(self, path, samples=None, beta=None):
         """Everything a resumed run needs: weights and Adam moments in the flat layout, step size, counters,
-        masks, and optionally the chain state and beta of `_current_state`."""
-        import numpy as np
+        masks, and optionally the chain state and beta (a scalar or a ladder [B]) of `_current_state`."""
         d = {"xnet": self._nets[0].flat_params()[0], "vnet": self._nets[1].flat_params()[0], "adam_m": self._m,
              "adam_v": self._v, "eps": self._step_dev, "masks": self.dynamics.mask}
         out = {k: v.detach().cpu().numpy() for k, v in d.items()}
@@ -312,12 +386,11 @@ class GaugeTrainer(FlatTrainer):
         if samples is not None:
             out["samples"] = samples.detach().cpu().numpy() if isinstance(samples, torch.Tensor) else np.asarray(samples)
         if beta is not None:
-            out["beta"] = np.float64(beta)
+            out["beta"] = np.asarray(beta, dtype=np.float64)       # a scalar, or a ladder [B] as given
         np.savez(path, **out)
 
     def load_state(self, path):
         """Inverse of save_state; returns {'samples', 'beta'} when they were stored."""
-        import numpy as np
         dyn = self.dynamics
         with np.load(path if str(path).endswith(".npz") else str(path) + ".npz", allow_pickle=False) as f:
             for net, key in zip(self._nets, ("xnet", "vnet")):
@@ -342,16 +415,17 @@ class GaugeTrainer(FlatTrainer):
         """The reference's `_current_state` dict (gauge_model.py:370-376, :1190-1194) with its own keys --
         {'samples', 'eps', 'step', 'beta', 'lr'} -- from this trainer; `save_state` writes the same keys (plus the
         optimiser state the reference leaves to the TF checkpoint) into its .npz."""
-        import numpy as np
         if isinstance(samples, torch.Tensor):
             samples = samples.detach().cpu().numpy()
         return {'samples': samples, 'eps': float(self.dynamics.eps), 'step': int(self.global_step),
-                'beta': None if beta is None else float(beta), 'lr': float(self.learning_rate() / self.world)}
+                'beta': (None if beta is None else float(beta) if np.ndim(beta) == 0
+                         else np.asarray(beta, dtype=np.float64)), 'lr': float(self.learning_rate() / self.world)}
 
     @staticmethod
     def train_data_dict(out, initial_step=0):
         """`train()` histories -> the reference's `train_data_dict` (gauge_model.py:362-369, :1196-1205):
         {'loss' | 'actions' | 'plaqs' | 'charges' | 'charge_diff' | 'accept_prob': {(step, beta): value}}."""
-        keys = [(initial_step + i, float(b)) for i, b in enumerate(out['beta'])]
+        keys = [(initial_step + i, float(b) if np.ndim(b) == 0 else tuple(float(v) for v in b))     # (a ladder: its
+                for i, b in enumerate(out['beta'])]                                                   #  rungs)
         return {name: {k: out[name][i] for i, k in enumerate(keys)}
                 for name in ('loss', 'actions', 'plaqs', 'charges', 'charge_diff', 'accept_prob')}

@@ -85,15 +85,27 @@ class Walk:
     the two networks, eps, the trajectory length, per step the time input `format_time(step) -> [[t_cos, t_sin]]`
     (the dynamics' `_format_time`) and the masks `masks(step) -> (m, 1 - m)` ([D] device tensors), and the gradient
     that feeds the momentum update and VNet's second input, `grad(x)`, with its Hessian-vector product `hvp(x, u)`
-    (toy targets: grad E / temperature and energy_hvp; the lattice: beta * force and ops.u1_force_hvp)."""
+    (toy targets: grad E / temperature and energy_hvp; the lattice: beta * force and ops.u1_force_hvp).
+    `row_scale` ([R] device tensor over the stacked rows, or None): a factor per row on `grad` and `hvp` -- the
+    lattice's beta on a ladder, where `grad` and `hvp` are those of beta = 1."""
 
-    def __init__(self, xnet, vnet, eps, num_steps, format_time, masks, grad, hvp):
+    def __init__(self, xnet, vnet, eps, num_steps, format_time, masks, grad, hvp, row_scale=None):
         self.xnet, self.vnet, self.eps, self.num_steps = xnet, vnet, float(eps), int(num_steps)
         self.format_time, self.masks, self.grad, self.hvp = format_time, masks, grad, hvp
+        self.row_scale = row_scale
 
     def time(self, step):
         t = self.format_time(step)
         return float(t[0, 0]), float(t[0, 1])
+
+    def on_rows(self, idx):
+        """The walk of the rows `idx` of the stacked batch (one direction's run): itself, or with `row_scale` the walk
+        whose `grad` and `hvp` carry those rows' factors."""
+        if self.row_scale is None:
+            return self
+        s = self.row_scale[idx][:, None]
+        return Walk(self.xnet, self.vnet, self.eps, self.num_steps, self.format_time, self.masks,
+                    lambda x: self.grad(x) * s, lambda x, u: self.hvp(x, u) * s)
 
 
 # What LayeredWalk.forward hands to LayeredWalk.backward: the Walk, both tapes, per direction run (d, row indices,
@@ -109,6 +121,7 @@ class LayeredWalk:
     def __init__(self, device):
         self.device = device
         self._ws_bwd, self._ws_wg = _lib.Workspace(), _lib.Workspace()
+        self.start_cotangents = None        # (d loss / d x_0, d loss / d v_0) of the last `backward`, stacked order
 
     def tapes(self, w, rows):
         """(XNet tape, VNet tape) for trajectories over `rows` rows in all."""
@@ -164,10 +177,11 @@ class LayeredWalk:
             v = self._sub_v(w, x, v, tc, ts, d, lj, tv, subs)
         return x, v, lj, subs
 
-    def forward(self, w, x0, v0, fwd, accept):
+    def forward(self, w, x0, v0, fwd, accept, accept_rows=False):
         """The stacked chains x0, v0 [R][D], each in the direction fwd [R] (bool, True = forward) gives it: one taped
         trajectory per direction over the rows that run it, scattered back into the stacked order, with
-        p = accept(x_start, v_start, x_end, v_end, sumlogdet) of those rows.  -> Forward."""
+        p = accept(x_start, v_start, x_end, v_end, sumlogdet) of those rows (accept_rows: `accept` also takes the rows'
+        indices in the stacked order, for a target whose energy depends on the row).  -> Forward."""
         R = x0.shape[0]
         tx, tv = self.tapes(w, R)
         xN, vN = torch.empty_like(x0), torch.empty_like(x0)
@@ -177,9 +191,9 @@ class LayeredWalk:
             if idx.numel() == 0:
                 continue
             xs, vs = x0[idx].contiguous(), v0[idx].contiguous()
-            xe, ve, lj, subs = self.trajectory(w, xs, vs, d, tx, tv)
+            xe, ve, lj, subs = self.trajectory(w.on_rows(idx), xs, vs, d, tx, tv)
             xN[idx], vN[idx], sld[idx] = xe, ve, lj
-            p[idx] = accept(xs, vs, xe, ve, lj)
+            p[idx] = accept(xs, vs, xe, ve, lj, idx) if accept_rows else accept(xs, vs, xe, ve, lj)
             runs.append((d, idx, subs))
         return Forward(w, tx, tv, runs, xN, vN, sld, p)
 
@@ -196,7 +210,7 @@ class LayeredWalk:
 
     def reverse(self, w, subs, d, dx, dv, dld, tx, tv):
         """Walk one trajectory's sub-updates backwards from the cotangents of (x_N, v_N, sumlogdet); fills the tapes'
-        cotangent slices and returns the per-row d/d eps partials of every sub-update."""
+        cotangent slices and returns (the per-row d/d eps partials of every sub-update, d loss / d (x_0, v_0))."""
         eps = w.eps
         parts = []
         for kind, sl, xin, vin, g, keep in reversed(subs):
@@ -221,7 +235,7 @@ class LayeredWalk:
                 dv = (dv + dv_part + din[:, :D]).contiguous()
             dx, dv = dx.contiguous(), dv.contiguous()
             parts.append(de)
-        return parts
+        return parts, dx, dv
 
     def weight_grads(self, net, tape, g):
         """Weight gradients of `net` over every row of its tape into the l2hmc_dense_grads `g` (overwritten)."""
@@ -236,11 +250,15 @@ class LayeredWalk:
         """From the cotangents of (x_N, v_N, sumlogdet) in the stacked row order: the reverse walk of every run of
         `fw`, then the weight gradients of XNet into the l2hmc_dense_grads `gx` and of VNet into `gv`;
         `after_net(k)` is called right after network k's products were enqueued.  -> d/d eps summed over all
-        sub-updates (a device scalar)."""
+        sub-updates (a device scalar).  `self.start_cotangents` keeps d loss / d (x_0, v_0) in the stacked row order (what
+        the tiled entries leave in dx, dv)."""
         parts = []
+        dx0, dv0 = torch.empty_like(dxN), torch.empty_like(dvN)
         for d, idx, subs in fw.runs:
-            parts += self.reverse(fw.w, subs, d, dxN[idx].contiguous(), dvN[idx].contiguous(), dld[idx].contiguous(),
-                                  fw.tx, fw.tv)
+            de, dx0[idx], dv0[idx] = self.reverse(fw.w.on_rows(idx), subs, d, dxN[idx].contiguous(),
+                                                  dvN[idx].contiguous(), dld[idx].contiguous(), fw.tx, fw.tv)
+            parts += de
+        self.start_cotangents = (dx0, dv0)
         for k, (net, tape, g) in enumerate(((fw.w.xnet, fw.tx, gx), (fw.w.vnet, fw.tv, gv))):
             self.weight_grads(net, tape, g)
             if after_net is not None:

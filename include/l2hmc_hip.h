@@ -843,6 +843,20 @@ int l2hmc_small_train_step(const l2hmc_small_plan* plan, const float* x0, const 
                            int64_t rows, float scale, float inv_count, float* x_out, float* v_out,
                            float* p_accept, float* terms, float* grads, void* ws, size_t ws_bytes,
                            l2hmc_stream_t stream);
+/* l2hmc_small_train_step on a LADDER of temperatures: row r runs at temps[(r % chains) * chain_stride], temps a DEVICE
+ * array (the convention of l2hmc_gauge_train_forward_ladder).  With the stacked batch [x | z] of rows = 2 * chains,
+ * chain i of x and chain i of z share temps[i]; chain_stride 0 = one value for every row, read from the device.
+ * plan->target.temperature is IGNORED.  Everything else -- outputs, the layout and the fixed summation order of grads,
+ * the launch geometry, the workspace (l2hmc_small_train_ws_bytes(plan, rows), unchanged) -- is l2hmc_small_train_step's:
+ * a row has the bits of that entry at its temperature, and equal temperatures give its gradient buffer bit for bit.
+ * Refused with L2HMC_ERR_ARG before any launch: everything l2hmc_small_train_step refuses, NULL temps, chains <= 0,
+ * rows that are no whole number of chains, a chain_stride that is negative (or anything but 0 or 1).  The VALUES of
+ * temps are on the device and are not checked here (DynamicsTrainer checks them: finite and > 0 in float32). */
+int l2hmc_small_train_step_tempered(const l2hmc_small_plan* plan, const float* temps, int64_t chain_stride,
+                                    int64_t chains, const float* x0, const float* v0, const int32_t* dir,
+                                    int64_t rows, float scale, float inv_count, float* x_out, float* v_out,
+                                    float* p_accept, float* terms, float* grads, void* ws, size_t ws_bytes,
+                                    l2hmc_stream_t stream);
 /* Vector-Jacobian product of l2hmc_small_trajectory for ANY cotangents: what a caller's autograd needs to
  * differentiate a loss of its own through Dynamics.forward / .backward / propose.  Per row r (direction dir[r],
  * NULL = all forward) the forward from (x0, v0) is recomputed on-chip, then the reverse pass of

@@ -169,6 +169,8 @@ _PROTOS = {
     "l2hmc_small_train_ws_bytes": (_SZ, [C.POINTER(SmallPlan), _I64]),
     "l2hmc_small_train_step": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64, _F, _F, _P, _P, _P, _P, _P, _P, _SZ,
                                          _P]),
+    "l2hmc_small_train_step_tempered": (C.c_int, [C.POINTER(SmallPlan), _P, _I64, _I64, _P, _P, _P, _I64, _F, _F, _P, _P,
+                                                  _P, _P, _P, _P, _SZ, _P]),
     "l2hmc_small_vjp": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64] + [_P] * 11 + [_P, _SZ, _P]),
     "l2hmc_mog_energy_hvp": (C.c_int, [C.POINTER(MogTarget), _P, _P, _I64, _P, _P]),
     "l2hmc_u1_force_hvp": (C.c_int, [_P, _P, _I64, _I32, _I32, _F, _P, _P]),

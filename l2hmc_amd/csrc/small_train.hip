@@ -311,13 +311,30 @@ struct SmallTrainArgs {
   const float* g_x; const float* g_v; const float* g_logdet; const float* g_p;
   float* dx0; float* dv0; float* sumlogdet;       // outputs of the VJP instance, each may be NULL
 };
+// the LADDER instances' arguments: row r runs at temps[(r % chains) * chain_stride], a DEVICE array.  A type of its own,
+// so that the uniform instances keep the argument block (and with it the code) they had.
+struct SmallTrainLadderArgs : SmallTrainArgs {
+  const float* temps; int64_t chain_stride; int64_t chains;
+};
+template <bool LADDER> using SmallTrainArgsOf = std::conditional_t<LADDER, SmallTrainLadderArgs, SmallTrainArgs>;
+
+// 1 / temperature of row r: the plan's, or (LADDER) the row's own, read once; a dead row loads nothing
+template <bool LADDER>
+__device__ __forceinline__ float row_inv_temp(const SmallTrainArgsOf<LADDER>& a, bool live, int64_t r) {
+  if constexpr (LADDER) return live ? 1.f / a.temps[(r % a.chains) * a.chain_stride] : 1.f;
+  else return 1.f / a.plan.target.temperature;
+}
 
 // VJP = false: the reverse pass is seeded by the squared-jump-distance loss (l2hmc_small_train_step);
 // VJP = true: by the caller's cotangents of (x_N, v_N, sumlogdet, p) (l2hmc_small_vjp), and the gradient with
 // respect to the start state is written out.  Everything else is the same code.
 // AN: the instance of the analytic target kinds (small_mlp.h: energy_grad).
-template <int HP, int MD, int TH, bool VJP, bool AN>
-__global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
+// LADDER (l2hmc_small_train_step_tempered; loss seed only): the row's temperature is read from a.temps instead of the
+// plan, once, before the first energy_grad; every use of inv_temp below is the same statement in both instances, so a
+// row has the bits of the uniform instance at its temperature.
+template <int HP, int MD, int TH, bool VJP, bool AN, bool LADDER = false>
+__global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgsOf<LADDER> a) {
+  static_assert(!(LADDER && VJP), "the ladder instance is the loss-seeded step's");
   constexpr int kSlots = TH / kLPC, kSmallThreads = TH, SS = kSlots + 4;
   // diagnostic cycle shares (class 7): 0 prologue, 1 forward, 2 loss, 3 net re-evaluation, 4 sub-update + head deltas,
   // 5 hidden deltas (d2, d1, input gradients), 6 owner pass, 7 total
@@ -362,7 +379,7 @@ __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgs a) {
   float* mytape = tape + (size_t)slot * ncalls * 3 * dim;
   const int bwd = (a.dir && live) ? a.dir[r] : 0;
   const float eps = P.eps;
-  const float inv_temp = 1.f / P.target.temperature;
+  const float inv_temp = row_inv_temp<LADDER>(a, live, r);
   const TargetKind tk = target_kind(P.target);
   const int K = P.target.K;
   const int n0 = lsub * UPL;
@@ -748,8 +765,9 @@ static int small_train_check(const l2hmc_small_plan* plan, int64_t rows, const c
 }
 
 // small_train_kernel (loss or VJP seed) over `rows`, then the ordered reduction of the workgroup partials into grads
-template <bool VJP>
-static int small_train_launch(const l2hmc_small_plan* plan, SmallTrainArgs a, float* grads, size_t ws_bytes,
+// (LADDER: a.temps / chain_stride / chains are set, and the row's temperature is read from them)
+template <bool VJP, bool LADDER = false>
+static int small_train_launch(const l2hmc_small_plan* plan, SmallTrainArgsOf<LADDER> a, float* grads, size_t ws_bytes,
                               hipStream_t s, const char* who) {
   const int dim = plan->x_dim, H = plan->num_nodes, N = plan->trajectory_length;
   const int64_t rows = a.rows;
@@ -769,7 +787,7 @@ static int small_train_launch(const l2hmc_small_plan* plan, SmallTrainArgs a, fl
     L2HMC_REQUIRE(lds <= 160 * 1024, "%s: LDS image %zu B too large (trajectory too long?)", who, lds);
     static DeviceOnce attr_once;
     if (attr_once.pending()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_train_kernel<HPc, MDc, 256, VJP, AN>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_train_kernel<HPc, MDc, 256, VJP, AN, LADDER>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       attr_once.done();
     }
@@ -777,7 +795,7 @@ static int small_train_launch(const l2hmc_small_plan* plan, SmallTrainArgs a, fl
     a.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
 #endif
     nwg = (int)ceil_div(rows, 256 / kLPC);
-    hipLaunchKernelGGL((small_train_kernel<HPc, MDc, 256, VJP, AN>), dim3(nwg), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((small_train_kernel<HPc, MDc, 256, VJP, AN, LADDER>), dim3(nwg), dim3(256), lds, s, a);
     return L2HMC_OK;
   };
   auto run = [&](auto hp, auto md) -> int {
@@ -813,6 +831,32 @@ extern "C" int l2hmc_small_train_step(const l2hmc_small_plan* plan, const float*
   SmallTrainArgs a{*plan, x0, v0, dir, rows, scale, inv_count, x_out, v_out, p_accept, terms, static_cast<float*>(ws),
                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   return small_train_launch<false>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
+}
+
+// l2hmc_small_train_step with a temperature per chain, read on the device: row r at temps[(r % chains) * chain_stride]
+extern "C" int l2hmc_small_train_step_tempered(const l2hmc_small_plan* plan, const float* temps, int64_t chain_stride,
+                                               int64_t chains, const float* x0, const float* v0, const int32_t* dir,
+                                               int64_t rows, float scale, float inv_count, float* x_out, float* v_out,
+                                               float* p_accept, float* terms, float* grads, void* ws, size_t ws_bytes,
+                                               l2hmc_stream_t stream) {
+  const char* who = "small_train_step_tempered";
+  if (int rc = small_train_check(plan, rows, who)) return rc;
+  L2HMC_REQUIRE(scale > 0.f, "small_train_step_tempered: bad rows / scale");
+  L2HMC_REQUIRE(temps != nullptr, "small_train_step_tempered: NULL temps");
+  L2HMC_REQUIRE(chain_stride == 0 || chain_stride == 1,
+                "small_train_step_tempered: chain_stride = %lld: 0 (one value) or 1 (one per chain)",
+                (long long)chain_stride);
+  L2HMC_REQUIRE(chains > 0, "small_train_step_tempered: chains = %lld: must be positive", (long long)chains);
+  L2HMC_REQUIRE(rows % chains == 0, "small_train_step_tempered: rows = %lld is no whole number of chains = %lld",
+                (long long)rows, (long long)chains);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x0 && v0 && x_out && v_out && p_accept && terms && grads && ws,
+                "small_train_step_tempered: NULL pointer");
+  if (int rc = check_small_nets(plan, who)) return rc;
+  SmallTrainLadderArgs a{{*plan, x0, v0, dir, rows, scale, inv_count, x_out, v_out, p_accept, terms,
+                          static_cast<float*>(ws), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+                         temps, chain_stride, chains};
+  return small_train_launch<false, true>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
 }
 
 extern "C" int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, const float* v0, const int32_t* dir,

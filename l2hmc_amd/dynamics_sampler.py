@@ -34,6 +34,26 @@ from . import _lib, _runs
 from .sampler import propose
 
 
+def replica_swap(dyn, x, temps_dev, chain_stride, G, parity, replica=None):
+    """ONE replica-exchange round of l2hmc_small_replica_swap on device state x [B, x_dim], IN PLACE, at the float32
+    device temperatures `temps_dev` (column c at temps_dev[c * chain_stride]); the uniforms are one stream of the
+    dynamics' counter (`_draws`, then + 1); `replica` (int32 [B] on the device, or None) is exchanged too.  What
+    `DynamicsSampler.swap_replicas` and `DynamicsTrainer.train` run.  -> (swap_p, swapped bool, energy), each [B]."""
+    B = x.shape[0]
+    plan = dyn._plan()
+    swap_p = torch.empty(B, dtype=torch.float32, device=x.device)
+    swapped = torch.empty(B, dtype=torch.uint8, device=x.device)
+    energy = torch.full((B,), float("nan"), dtype=torch.float32, device=x.device)
+    _lib.call("l2hmc_small_replica_swap", C.byref(plan), x, B, G, parity, temps_dev, chain_stride, dyn._seed,
+              dyn._draws, replica, energy, swap_p, swapped, device=dyn._device)
+    dyn._draws += 1
+    return swap_p, swapped.view(torch.bool), energy
+
+
+LAYERED_SWAP_MESSAGE = ("swap_replicas: this dynamics runs layer by layer (arbitrary energy function or "
+                        "x_dim > 8): the round needs a packed target")
+
+
 class DynamicsSampler:
     def __init__(self, dynamics, distribution=None, batch_size=None):
         """`distribution`: anything with `get_samples(n)` (l2hmc_amd.distributions), the start of
@@ -275,8 +295,7 @@ class DynamicsSampler:
         swapped [B] bool; energy [B], U of the chains that were in a pair, NaN elsewhere) as tensors."""
         dyn = self.dynamics
         if dyn.layered:
-            raise NotImplementedError("swap_replicas: this dynamics runs layer by layer (arbitrary energy function or "
-                                      "x_dim > 8): the round needs a packed target")
+            raise NotImplementedError(LAYERED_SWAP_MESSAGE)
         if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[1] != dyn.x_dim:
             raise ValueError(f"swap_replicas: x: expected a device tensor [B, {dyn.x_dim}] (exchanged in place)")
         B = x.shape[0]
@@ -289,16 +308,7 @@ class DynamicsSampler:
         return self._swap_round(x, temps_dev, stride, G, parity)
 
     def _swap_round(self, x, temps_dev, chain_stride, G, parity):
-        dyn = self.dynamics
-        B = x.shape[0]
-        plan = dyn._plan()
-        swap_p = torch.empty(B, dtype=torch.float32, device=x.device)
-        swapped = torch.empty(B, dtype=torch.uint8, device=x.device)
-        energy = torch.full((B,), float("nan"), dtype=torch.float32, device=x.device)
-        _lib.call("l2hmc_small_replica_swap", C.byref(plan), x, B, G, parity, temps_dev, chain_stride, dyn._seed,
-                  dyn._draws, getattr(self, "replica", None), energy, swap_p, swapped, device=dyn._device)
-        dyn._draws += 1
-        return swap_p, swapped.view(torch.bool), energy
+        return replica_swap(self.dynamics, x, temps_dev, chain_stride, G, parity, getattr(self, "replica", None))
 
     def run_exchange(self, run_steps, x=None, keep_samples=True, temperature=None, replicas=None, swap_every=1,
                      first_parity=0, replica0=None):

@@ -56,14 +56,15 @@ class _NetTape:
         return sl
 
 
-def energy_hvp(dyn, x, u):
+def energy_hvp(dyn, x, u, temperature=None):
     """Hess(energy / temperature)(x) . u per row: l2hmc_mog_energy_hvp for a packed target, torch double-backward of
-    the caller's energy otherwise."""
+    the caller's energy otherwise.  `temperature`: None = the dynamics' own (`_temp`)."""
+    temp = dyn._temp() if temperature is None else float(temperature)
     if x.shape[0] == 0:
         return torch.zeros_like(x)
     if dyn._target is not None:
         out = torch.empty_like(x)
-        st = dyn._target.struct(dyn._temp())
+        st = dyn._target.struct(temp)
         _lib.call("l2hmc_mog_energy_hvp", C.byref(st), x, u.contiguous(), x.shape[0], out, device=dyn._device)
         return out
     with torch.enable_grad():
@@ -77,7 +78,7 @@ def energy_hvp(dyn, x, u):
         (hv,) = torch.autograd.grad(g, xg, grad_outputs=u, allow_unused=True)
     if hv is None:
         return torch.zeros_like(x)
-    return (hv.to(torch.float32) / dyn._temp()).contiguous()
+    return (hv.to(torch.float32) / temp).contiguous()
 
 
 class Walk:
@@ -87,7 +88,8 @@ class Walk:
     that feeds the momentum update and VNet's second input, `grad(x)`, with its Hessian-vector product `hvp(x, u)`
     (toy targets: grad E / temperature and energy_hvp; the lattice: beta * force and ops.u1_force_hvp).
     `row_scale` ([R] device tensor over the stacked rows, or None): a factor per row on `grad` and `hvp` -- the
-    lattice's beta on a ladder, where `grad` and `hvp` are those of beta = 1."""
+    lattice's beta on a ladder, where `grad` and `hvp` are those of beta = 1, and the toy targets' 1 / temperature,
+    where they are those of temperature 1."""
 
     def __init__(self, xnet, vnet, eps, num_steps, format_time, masks, grad, hvp, row_scale=None):
         self.xnet, self.vnet, self.eps, self.num_steps = xnet, vnet, float(eps), int(num_steps)
@@ -274,14 +276,33 @@ class LayeredStep:
         self.tr = trainer
         self.walk = LayeredWalk(trainer.dynamics._device)
 
-    def __call__(self, x0, v0, fwd, inv_count):
+    def __call__(self, x0, v0, fwd, inv_count, row_temps=None):
         """x0, v0 [2B][D] stacked start states, fwd [2B] bool (True = forward).  Writes the trainer's gradient buffer
-        ([xnet | vnet | d/d eps]) and returns (x_N, p, terms) in the stacked row order."""
+        ([xnet | vnet | d/d eps]) and returns (x_N, p, terms) in the stacked row order.
+        row_temps ([2B] float32 device tensor, or None = the dynamics' own temperature): a temperature per stacked row.
+        Energy, its gradient and the Hessian-vector product are then formed at temperature 1 and multiplied by the
+        row's 1 / temperature, formed as the scalar path forms it -- a packed target's kernels multiply by the float32
+        quotient 1.f / temperature; torch, dividing a callable energy's values by a scalar, multiplies by the float64
+        quotient rounded to float32 --, so a row has the bits of the scalar step at its (float32) temperature."""
         tr = self.tr
         dyn = tr.dynamics
-        w = Walk(dyn.XNet, dyn.VNet, dyn.eps, dyn.trajectory_length, dyn._format_time, dyn._get_mask, dyn.grad_energy,
-                 lambda x, u: energy_hvp(dyn, x, u))
-        fw = self.walk.forward(w, x0, v0, fwd, dyn.p_accept)
+        if row_temps is None:
+            grad_energy, accept, accept_rows, inv = dyn.grad_energy, dyn.p_accept, False, None
+            hvp = lambda x, u: energy_hvp(dyn, x, u)                      # noqa: E731
+        else:
+            inv = 1.0 / row_temps if dyn._target is not None else (1.0 / row_temps.double()).float()
+            grad1, energy1 = self._at_temperature_one(dyn)
+            grad_energy = grad1                                            # (Walk.on_rows lays the rows' factors on it)
+            hvp = lambda x, u: energy_hvp(dyn, x, u, temperature=1.0)     # noqa: E731
+
+            def accept(xs, vs, xe, ve, lj, idx):        # utils/dynamics.py:312-319 with the rows' temperatures
+                old = energy1(xs) * inv[idx] + dyn.kinetic(vs)
+                new = energy1(xe) * inv[idx] + dyn.kinetic(ve)
+                return ops.accept_prob(old, new, lj)
+            accept_rows = True
+        w = Walk(dyn.XNet, dyn.VNet, dyn.eps, dyn.trajectory_length, dyn._format_time, dyn._get_mask, grad_energy, hvp,
+                 row_scale=inv)
+        fw = self.walk.forward(w, x0, v0, fwd, accept, accept_rows=accept_rows)
         xN, vN, p = fw.xN, fw.vN, fw.p
         # loss (mog_model.py:336-355) and its cotangents at (x_N, v_N, sumlogdet)
         scale = tr.scale
@@ -295,9 +316,27 @@ class LayeredStep:
         zero = torch.zeros_like(x0)
         gE = torch.zeros_like(x0)
         if bool(live.any()):
-            gE = dyn.grad_energy(xN)
+            gE = dyn.grad_energy(xN) if inv is None else grad_energy(xN) * inv[:, None]
         dxN = torch.where(live, (dvv * p)[:, None] * 2.0 * (xN - x0) - dD[:, None] * gE, zero)
         dvN = torch.where(live, -dD[:, None] * vN, zero)
         dld = dD.contiguous()
         tr.grads[-1] = self.walk.backward(fw, dxN, dvN, dld, *tr._grad_structs)
         return xN, p, terms
+
+    @staticmethod
+    def _at_temperature_one(dyn):
+        """(grad E, E) of the dynamics' target at temperature 1, whatever `dyn.temperature` is: `Dynamics.grad_energy`
+        and `.energy` with their own expressions."""
+        if dyn._target is not None:
+            return (lambda x: dyn._target.energy_grad(x, 1.0)[1],
+                    lambda x: dyn._target.energy_grad(x, 1.0, want_grad=False)[0])
+
+        def grad1(x):
+            with torch.enable_grad():
+                xg = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim).detach().clone().requires_grad_(True)
+                e = dyn._fn(xg)
+                if e.shape != (xg.shape[0],):
+                    raise ValueError(f"energy_function must return one energy per row: got {tuple(e.shape)}")
+                (g,) = torch.autograd.grad(e.sum(), xg)
+            return g.contiguous()
+        return grad1, lambda x: dyn._fn(_lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim))

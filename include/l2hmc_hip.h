@@ -287,6 +287,21 @@ int l2hmc_gauge_transition(const l2hmc_gauge_plan* plan, float beta, const float
                            int32_t both_directions, float* x_prop, float* v_prop, float* p_accept,
                            float* x_out, void* ws, size_t ws_bytes, l2hmc_stream_t stream);
 
+/* l2hmc_gauge_transition (the caller's draws) with a beta per chain: chain c reads betas[c * chain_stride], betas a
+ * DEVICE pointer, chain_stride 1 (betas [B]) or 0 (one value) -- the convention of l2hmc_gauge_mcmc_step_ladder with
+ * chains = B, so rows c and B + c of the stacked [forward; backward] trajectories run at chain c's beta.  The
+ * whole-trajectory kernels take one beta, so this entry ALWAYS runs layer by layer, whatever plan->flags says (it
+ * runs on a copy of the plan with L2HMC_PLAN_LAYERED set; l2hmc_gauge_mcmc_step_ladder is the one-launch ladder
+ * step).  A chain has the bits of l2hmc_gauge_transition on a L2HMC_PLAN_LAYERED plan at its beta.  Everything else is
+ * l2hmc_gauge_transition's: arguments, outputs, the workspace of l2hmc_gauge_transition_ws_bytes, B == 0 a no-op after
+ * the checks.  Refused with L2HMC_ERR_ARG before any device call: NULL betas, a chain_stride other than 0 or 1,
+ * plan->hmc = 1 (l2hmc_gauge_hmc_run_ladder is that path), and everything l2hmc_gauge_transition refuses.  The VALUES
+ * of betas are on the device and are not checked; GaugeDynamics.apply_transition checks them. */
+int l2hmc_gauge_transition_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t chain_stride,
+                                  const float* x, const float* v0_f, const float* v0_b, const float* coin,
+                                  const float* u, int64_t B, int32_t both_directions, float* x_prop, float* v_prop,
+                                  float* p_accept, float* x_out, void* ws, size_t ws_bytes, l2hmc_stream_t stream);
+
 /* apply_transition (gauge_dynamics.py:195-259) with the library's own draws -- Philox streams (seed, 2*draw) for the
  * stacked momenta [v0_f; v0_b] and (seed, 2*draw+1) for coin | u, exactly the layout of l2hmc_gauge_mcmc_step,
  * reproducible with l2hmc_fill_normal/_uniform -- instead of caller-provided ones: what `dynamics(x, beta)` is in
@@ -593,6 +608,19 @@ int l2hmc_gauge_accept_backward(int32_t T, int32_t X, float beta, int64_t rows, 
                                 const float* g_xprop, const float* g_vprop, const float* g_p, const float* g_xout,
                                 float* dxN, float* dvN, float* dlogdet, float* dx0, float* dv0,
                                 l2hmc_stream_t stream);
+/* l2hmc_gauge_accept_backward with a beta per row: F = beta_r dS/dx in the dxN and dx0 terms, beta_r =
+ * betas[(r % chains) * chain_stride] (betas a DEVICE pointer, chain_stride 1 or 0: the convention of
+ * l2hmc_gauge_train_forward_ladder, between whose forward and l2hmc_gauge_train_backward_ladder it stands).  An
+ * instance of the same kernel: a row has the bits of the scalar entry at its beta, a row with g = 0 still never forms
+ * 0 * F (and does not read its beta), the LDS bound and the lattices served are the scalar entry's.  rows == 0 is a
+ * no-op after the checks.  Refused with L2HMC_ERR_ARG before any device call: NULL betas, a chain_stride other than 0
+ * or 1, chains <= 0, rows % chains != 0, and everything the scalar entry refuses.  The VALUES of betas are not
+ * checked. */
+int l2hmc_gauge_accept_backward_ladder(int32_t T, int32_t X, const float* betas, int64_t chain_stride, int64_t chains,
+                                       int64_t rows, const float* x0, const float* v0, const float* xN,
+                                       const float* vN, const float* p, const float* u, const float* g_xprop,
+                                       const float* g_vprop, const float* g_p, const float* g_xout, float* dxN,
+                                       float* dvN, float* dlogdet, float* dx0, float* dv0, l2hmc_stream_t stream);
 /* *out (device) = [*out +] sum g[i]^2, elements in [tri_lo, tri_hi) counted three times (the packed
  * first-layer bias stands for three reference variables); fixed summation order. */
 int l2hmc_grad_sumsq(const float* g, int64_t n, int64_t tri_lo, int64_t tri_hi, float* out, int32_t accumulate,
@@ -672,6 +700,19 @@ int l2hmc_mog_energy_grad(const l2hmc_mog_target* tgt, const float* x, int64_t r
 int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float* x0, const float* v0,
                            const int32_t* dir, int64_t rows, float* x_out, float* v_out,
                            float* sumlogdet, float* p_accept, l2hmc_stream_t stream);
+/* l2hmc_small_trajectory on a LADDER of temperatures: row r runs at temps[(r % chains) * chain_stride], temps a DEVICE
+ * array, chain_stride 1 (temps [chains]) or 0 (one value) -- the convention of l2hmc_small_train_step_tempered.  With
+ * both directions of B chains stacked (rows = 2 B, chains = B) rows i and B + i share temps[i].
+ * plan->target.temperature is IGNORED (it must still be > 0).  Every plan l2hmc_small_trajectory serves is served: all
+ * four target kinds, every first_layer_form, hmc plans; the form is chosen by the rows as there.  The row's 1 / t is
+ * formed once, by the division the other instances use: a row has the bits of l2hmc_small_trajectory on a plan at its
+ * temperature.  rows == 0 is a no-op after the checks.  Refused with L2HMC_ERR_ARG before any launch: NULL temps, a
+ * chain_stride other than 0 or 1, chains <= 0, rows % chains != 0, and everything l2hmc_small_trajectory refuses.  The
+ * VALUES of temps are not checked here (Dynamics / propose check them: finite and > 0 in float32). */
+int l2hmc_small_trajectory_tempered(const l2hmc_small_plan* plan, const float* temps, int64_t chain_stride,
+                                    int64_t chains, const float* x0, const float* v0, const int32_t* dir,
+                                    int64_t rows, float* x_out, float* v_out, float* sumlogdet, float* p_accept,
+                                    l2hmc_stream_t stream);
 
 /* utils/sampler.py:28-55 `propose` (and :57-59 `tf_accept` when x_out != NULL) in ONE launch for the L2HMC sampler
  * (plan->hmc == 0).  Chain c's direction bit, forward momentum, backward momentum and Metropolis-Hastings uniform are
@@ -873,6 +914,19 @@ int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, const float* 
                     int64_t rows, const float* g_x, const float* g_v, const float* g_logdet, const float* g_p,
                     float* dx0, float* dv0, float* grads, float* x_out, float* v_out, float* sumlogdet,
                     float* p_accept, void* ws, size_t ws_bytes, l2hmc_stream_t stream);
+/* l2hmc_small_vjp on a LADDER of temperatures (the reverse of l2hmc_small_trajectory_tempered): row r at
+ * temps[(r % chains) * chain_stride], temps a DEVICE array, chain_stride 1 or 0; plan->target.temperature is IGNORED.
+ * The direct term dx0 += dD grad E(x0) uses the row's tempered energy.  The VJP instance of the kernel
+ * l2hmc_small_train_step_tempered runs: same launch geometry, no atomics, the workspace of
+ * l2hmc_small_train_ws_bytes(plan, rows); dx0, dv0 and the recomputed forward of a row have the bits of l2hmc_small_vjp
+ * at its temperature, and equal temperatures give its grads buffer bit for bit.  rows == 0 is a no-op after the checks.
+ * Refused with L2HMC_ERR_ARG before any launch: NULL temps, a chain_stride other than 0 or 1, chains <= 0,
+ * rows % chains != 0, and everything l2hmc_small_vjp refuses.  The VALUES of temps are not checked here. */
+int l2hmc_small_vjp_tempered(const l2hmc_small_plan* plan, const float* temps, int64_t chain_stride, int64_t chains,
+                             const float* x0, const float* v0, const int32_t* dir, int64_t rows, const float* g_x,
+                             const float* g_v, const float* g_logdet, const float* g_p, float* dx0, float* dv0,
+                             float* grads, float* x_out, float* v_out, float* sumlogdet, float* p_accept, void* ws,
+                             size_t ws_bytes, l2hmc_stream_t stream);
 
 /* Hessian-vector product of the packed target's tempered energy: out[r] = Hess(energy / temperature)(x[r]) . u[r],
  * x, u, out [rows][dim] (the closed form of the second derivative of distributions.py:151-158 / :63-68).  What a

@@ -107,6 +107,8 @@ _PROTOS = {
     "l2hmc_gauge_transition_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64, _I32]),
     "l2hmc_gauge_transition": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _P, _P, _P, _P, _I64, _I32, _P, _P,
                                          _P, _P, _P, _SZ, _P]),
+    "l2hmc_gauge_transition_ladder": (C.c_int, [C.POINTER(GaugePlan), _P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _P, _P,
+                                                _P, _P, _P, _SZ, _P]),
     "l2hmc_gauge_transition_draw": (C.c_int, [C.POINTER(GaugePlan), _F, _P, _I64, _U64, _U64, _P, _P, _P, _P, _P, _SZ,
                                               _P]),
     "l2hmc_gauge_mcmc_step_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64]),
@@ -150,10 +152,13 @@ _PROTOS = {
     "l2hmc_gauge_loss_backward_ladder": (C.c_int, [_I32, _I32, _P, _I64, _P, _P, _P, _P, _I64, _I32, _F, _F, _F, _F,
                                                    _F, _P, _P, _P, _P, _P]),
     "l2hmc_gauge_accept_backward": (C.c_int, [_I32, _I32, _F, _I64] + [_P] * 15 + [_P]),
+    "l2hmc_gauge_accept_backward_ladder": (C.c_int, [_I32, _I32, _P, _I64, _I64, _I64] + [_P] * 15 + [_P]),
     "l2hmc_grad_sumsq": (C.c_int, [_P, _I64, _I64, _I64, _P, _I32, _P]),
     "l2hmc_adam_step": (C.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _F, _I64, _I64, _P]),
     "l2hmc_mog_energy_grad": (C.c_int, [C.POINTER(MogTarget), _P, _I64, _P, _P, _P]),
     "l2hmc_small_trajectory": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "l2hmc_small_trajectory_tempered": (C.c_int, [C.POINTER(SmallPlan), _P, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P, _P,
+                                                  _P]),
     "l2hmc_small_propose": (C.c_int, [C.POINTER(SmallPlan), _P, _I64, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P]),
     "l2hmc_small_run": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _P, _P]),
     "l2hmc_small_run_tempered": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _I64, _I64, _P, _P,
@@ -172,6 +177,8 @@ _PROTOS = {
     "l2hmc_small_train_step_tempered": (C.c_int, [C.POINTER(SmallPlan), _P, _I64, _I64, _P, _P, _P, _I64, _F, _F, _P, _P,
                                                   _P, _P, _P, _P, _SZ, _P]),
     "l2hmc_small_vjp": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _P, _I64] + [_P] * 11 + [_P, _SZ, _P]),
+    "l2hmc_small_vjp_tempered": (C.c_int, [C.POINTER(SmallPlan), _P, _I64, _I64, _P, _P, _P, _I64] + [_P] * 11
+                                 + [_P, _SZ, _P]),
     "l2hmc_mog_energy_hvp": (C.c_int, [C.POINTER(MogTarget), _P, _P, _I64, _P, _P]),
     "l2hmc_u1_force_hvp": (C.c_int, [_P, _P, _I64, _I32, _I32, _F, _P, _P]),
     "l2hmc_stq_dense_taped": (C.c_int, [C.POINTER(DenseNet), _P, _P, _P, _F, _F, _I64, _P, _P, _P, _P, _P, _P]),

@@ -8,6 +8,11 @@ dynamics.variables) gives the reference for ANY loss its caller writes around `d
                                           and the direct part of d(x)
             l2hmc_gauge_train_backward    -> weight, step-size and start-state gradients through the trajectory
 
+With a beta per chain (`dyn(x, ladder)`, ladder [B]) the same three steps run on the `_ladder` entries
+(l2hmc_gauge_train_forward_ladder, l2hmc_gauge_accept_backward_ladder, l2hmc_gauge_train_backward_ladder; chains = B,
+stride 1): chain i is differentiated at ladder[i], with the bits of the scalar call at that value.  The ladder's values
+are not differentiated.
+
 Every call owns its tape (a train workspace), the plan and the packed weight buffers it ran with, so several
 transitions may be differentiated by one backward (the reference loss runs two: x and z).  The tape is freed
 after the backward; a second backward through the same graph is an error."""
@@ -51,11 +56,9 @@ def check_differentiable(dyn):
                              "multiples of 32 (a T x X lattice has D = 2*T*X)")
 
 
-def transition(dyn, x, beta, momentum_f=None, momentum_b=None, coin=None, u=None):
-    """Differentiable apply_transition -> (x_prop, v_prop, p_accept, x_out).  `x`: [B, D] fp32 on dyn's device."""
-    check_differentiable(dyn)
-    B, D = x.shape
-    dev = x.device
+def draws(dyn, B, D, dev, momentum_f=None, momentum_b=None, coin=None, u=None):
+    """(v0_f, v0_b, coin, u) of a transition: the library's own where none is injected, else the injected ones and
+    single streams of the counter for the rest."""
     if momentum_f is None and momentum_b is None and coin is None and u is None:
         # the draws of l2hmc_gauge_transition_draw: (seed, 2d) = [v0_f; v0_b], (seed, 2d+1) = coin | u
         d, dyn._draws = _lib.step_draw_index(dyn._draws)
@@ -67,8 +70,17 @@ def transition(dyn, x, beta, momentum_f=None, momentum_b=None, coin=None, u=None
         v0b = dyn._x(momentum_b) if momentum_b is not None else dyn._normal((B, D))
         coin = _lib.as_dev(coin, dyn._device) if coin is not None else dyn._uniform((B,))
         u = _lib.as_dev(u, dyn._device) if u is not None else dyn._uniform((B,))
+    return v0f, v0b, coin, u
+
+
+def transition(dyn, x, beta, momentum_f=None, momentum_b=None, coin=None, u=None):
+    """Differentiable apply_transition -> (x_prop, v_prop, p_accept, x_out).  `x`: [B, D] fp32 on dyn's device; `beta`:
+    a float, or the ladder [B] as a float32 tensor on that device (chain i at beta[i]; not differentiated)."""
+    check_differentiable(dyn)
+    B, D = x.shape
+    v0f, v0b, coin, u = draws(dyn, B, D, x.device, momentum_f, momentum_b, coin, u)
     xs, vs = dyn.position_fn.state_dict(), dyn.momentum_fn.state_dict()
-    out = _Transition.apply(dyn, float(beta), list(xs), list(vs), x, v0f.detach(), v0b.detach(), coin.detach(),
+    out = _Transition.apply(dyn, beta, list(xs), list(vs), x, v0f.detach(), v0b.detach(), coin.detach(),
                             u.detach(), dyn.eps, *xs.values(), *vs.values())
     if dyn.check_numerics and not bool(torch.isfinite(out[0]).all() & torch.isfinite(out[1]).all()):
         raise FloatingPointError("check_numerics: non-finite value in the proposed configuration")
@@ -93,8 +105,13 @@ class _Transition(torch.autograd.Function):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         xN, vN = torch.empty_like(x), torch.empty_like(x)
         sld, p = (torch.empty(B, dtype=torch.float32, device=x.device) for _ in range(2))
-        _lib.call("l2hmc_gauge_train_forward", C.byref(plan), beta, x, v0, dirs, B, xN, vN, sld, p, ws, nbytes,
-                  device=x.device)
+        ladder = isinstance(beta, torch.Tensor)           # [B] on the device: chain i at beta[i]
+        if ladder:
+            _lib.call("l2hmc_gauge_train_forward_ladder", C.byref(plan), beta, 1, B, x, v0, dirs, B, xN, vN, sld, p, ws,
+                      nbytes, device=x.device)
+        else:
+            _lib.call("l2hmc_gauge_train_forward", C.byref(plan), beta, x, v0, dirs, B, xN, vN, sld, p, ws, nbytes,
+                      device=x.device)
         x_out = torch.where((p > u)[:, None], xN, x)      # strict >, gauge_dynamics.py:244-257
         ctx.save_for_backward(x, v0, xN, vN, p, u, eps, *weights)
         ctx.set_materialize_grads(False)
@@ -120,8 +137,13 @@ class _Transition(torch.autograd.Function):
         dxN, dvN = torch.empty_like(x), torch.empty_like(x)
         dld = torch.empty(B, dtype=torch.float32, device=dev)
         dx0 = torch.empty_like(x) if ctx.needs_input_grad[4] else None
-        _lib.call("l2hmc_gauge_accept_backward", T, X, ctx.beta, B, x, v0, xN, vN, p, u, *gs, dxN, dvN, dld, dx0, None,
-                  device=dev)
+        ladder = isinstance(ctx.beta, torch.Tensor)
+        if ladder:
+            _lib.call("l2hmc_gauge_accept_backward_ladder", T, X, ctx.beta, 1, B, B, x, v0, xN, vN, p, u, *gs,
+                      dxN, dvN, dld, dx0, None, device=dev)
+        else:
+            _lib.call("l2hmc_gauge_accept_backward", T, X, ctx.beta, B, x, v0, xN, vN, p, u, *gs, dxN, dvN, dld, dx0,
+                      None, device=dev)
         nets = [net for _, net in _nets(dyn)]
         keys = _lib.DenseGrads._fields_
         dense = [_grad_buffers(b, [k for k, _ in keys]) for b in ctx.bufs]
@@ -130,12 +152,17 @@ class _Transition(torch.autograd.Function):
         if B > 0:
             gstruct = [_lib.DenseGrads(**{k: v.data_ptr() for k, v in g.items()}) for g in dense]
             cstruct = [None if g is None else _lib.Conv3DGrads(**{k: v.data_ptr() for k, v in g.items()}) for g in conv]
-            _lib.call("l2hmc_gauge_train_backward", C.byref(plan), ctx.beta, ctx.dirs, B, dxN, dvN, dld,
-                      C.byref(gstruct[0]), C.byref(gstruct[1]), *(None if c is None else C.byref(c) for c in cstruct),
-                      deps, ctx.ws, ctx.ws.numel(), device=dev)
+            tail = (C.byref(gstruct[0]), C.byref(gstruct[1]), *(None if c is None else C.byref(c) for c in cstruct),
+                    deps, ctx.ws, ctx.ws.numel())
+            if ladder:                     # (its bucket callback may be NULL)
+                _lib.call("l2hmc_gauge_train_backward_ladder", C.byref(plan), ctx.beta, 1, B, ctx.dirs, B, dxN, dvN, dld,
+                          *tail, device=dev, tail=(_lib.BUCKET_FN(), None))
+            else:
+                _lib.call("l2hmc_gauge_train_backward", C.byref(plan), ctx.beta, ctx.dirs, B, dxN, dvN, dld, *tail,
+                          device=dev)
         else:
             dxN.zero_()
-        ctx.ws = ctx.plan = ctx.bufs = ctx.front = ctx.mask = ctx.dyn = None
+        ctx.ws = ctx.plan = ctx.bufs = ctx.front = ctx.mask = ctx.dyn = ctx.beta = None
         grad_x = dx0 + dxN if dx0 is not None else None
         wgrads = []
         for net, names, g, c in zip(nets, ctx.names, dense, conv):

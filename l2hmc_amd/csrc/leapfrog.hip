@@ -710,6 +710,31 @@ extern "C" int l2hmc_gauge_transition(const l2hmc_gauge_plan* plan, float beta, 
                                v_prop, p_accept, x_out, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// l2hmc_gauge_transition with a beta per chain.  The whole-trajectory kernels keep the scalar slot (trajectory_inplace),
+// so the ladder runs on a copy of the plan with L2HMC_PLAN_LAYERED set, whatever the caller's plan says: it never
+// reaches a fused launch.  The workspace does not depend on that flag (carve_gauge_ws).
+extern "C" int l2hmc_gauge_transition_ladder(const l2hmc_gauge_plan* plan, const float* betas, int64_t chain_stride,
+                                             const float* x, const float* v0_f, const float* v0_b, const float* coin,
+                                             const float* u, int64_t B, int32_t both_directions, float* x_prop,
+                                             float* v_prop, float* p_accept, float* x_out, void* ws, size_t ws_bytes,
+                                             l2hmc_stream_t stream) {
+  const char* who = "gauge_transition_ladder";
+  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  L2HMC_REQUIRE(!plan->hmc, "%s: plan.hmc = 1: l2hmc_gauge_hmc_run_ladder runs plain HMC with a beta per chain", who);
+  L2HMC_REQUIRE(betas != nullptr, "%s: NULL betas", who);
+  L2HMC_REQUIRE(chain_stride == 0 || chain_stride == 1, "%s: chain_stride = %lld is not 0 or 1", who,
+                (long long)chain_stride);
+  if (int e = check_plan(plan)) return e;
+  L2HMC_REQUIRE(B >= 0, "%s: B < 0", who);
+  if (B == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x && v0_f && v0_b && coin && u && x_prop && v_prop && p_accept && x_out && ws, "%s: NULL pointer", who);
+  l2hmc_gauge_plan layered = *plan;
+  layered.flags |= L2HMC_PLAN_LAYERED;
+  // (rows c and B + c of the stacked [forward; backward] trajectories are chain c)
+  return gauge_transition_rows(who, &layered, RowBeta(betas, B, chain_stride), x, v0_f, v0_b, coin, u, B,
+                               both_directions, x_prop, v_prop, p_accept, x_out, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int l2hmc::gauge_check_plan(const l2hmc_gauge_plan* plan) { return check_plan(plan); }
 
 // The transition on checked pointers and B > 0; the plan is checked here, ahead of every device call.  beta: one value,

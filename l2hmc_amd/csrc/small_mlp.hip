@@ -63,6 +63,13 @@ struct SmallTrajArgs {
   unsigned long long* stamps;           // diagnostic builds only (-DL2HMC_STAMPS, class 7), else NULL
 };
 
+// What the kernel's LADDER instances take on top (l2hmc_small_trajectory_tempered): trajectory mode with row r at
+// temperature temps[(r % chains) * temp_chain_stride] instead of plan.target.temperature.  A struct of its own, as
+// SmallTrajExchangeArgs is: the other instances keep their kernel arguments.
+struct SmallTrajLadderArgs : SmallTrajArgs {
+  int64_t chains;
+};
+
 // What the kernel's EXCHANGE instances take on top (l2hmc_small_run_exchange): a replica-exchange round (small_swap.h)
 // after step s of the launch iff (swap_phase + s + 1) % swap_every == 0, the j-th of them with parity
 // (first_parity + j) % 2.  A struct of its own, as SmallHmcExchangeArgs is (small_hmc.hip): the instances without
@@ -473,12 +480,22 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
 // Streams in the order of the loop a caller would write: four per step, the next one per round (a round without a pair
 // takes its stream as well).  A template flag once more: the other instances keep their code and their arguments
 // (registers per instance: profiles/small_run_replica_exchange.txt).
+// LADDER (trajectory mode only, l2hmc_small_trajectory_tempered): the row's temperature is loaded once from a.temps, by
+// the division the TEMPERED instances use, where the uniform instances divide by plan.target.temperature; every use of
+// inv_temp is the same statement, so a row has the bits of the uniform instance at its temperature.  A template flag
+// and an argument type of its own for the same reason again (registers per instance: profiles/autograd_ladder.txt;
+// measured and dropped: a kernel of its own name around a shared __device__ body, which keeps the other instances'
+// symbols but changes the registers of 108 of the 128).
+template <bool EXCHANGE, bool LADDER>
+using SmallTrajArgsOf = std::conditional_t<EXCHANGE, SmallTrajExchangeArgs,
+                                           std::conditional_t<LADDER, SmallTrajLadderArgs, SmallTrajArgs>>;
+
 template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false, bool RUN = false, bool AN = false,
-          bool TEMPERED = false, bool EXCHANGE = false>
-__global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(
-    std::conditional_t<EXCHANGE, SmallTrajExchangeArgs, SmallTrajArgs> a) {
+          bool TEMPERED = false, bool EXCHANGE = false, bool LADDER = false>
+__global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(SmallTrajArgsOf<EXCHANGE, LADDER> a) {
   using V = MfmaNet<HP, MD, KS_, KSH_>;
   static_assert(!TEMPERED || RUN, "a temperature per step is a run's");
+  static_assert(!LADDER || !RUN, "a temperature per row of a single trajectory: a run has its TEMPERED instance");
   static_assert(!EXCHANGE || TEMPERED, "the rungs of a replica group are a ladder of temperatures");
   static_assert(!TW || (L1M && V::NT == 4), "the twin form is a latency form of the 64-unit instances");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -535,6 +552,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_traj_mfma_kernel(
   const int bwd = prop ? ((lane >> 3) & 1) : ((a.dir && live) ? a.dir[r] : 0);
   const float eps = P.eps;
   float inv_temp = TEMPERED ? 1.f : 1.f / P.target.temperature;      // (TEMPERED: set at the head of every step)
+  if constexpr (LADDER) inv_temp = 1.f / (live ? a.temps[(r % a.chains) * a.temp_chain_stride] : 1.f);
   const TargetKind tk = target_kind(P.target);
   const int K = P.target.K;
   [[maybe_unused]] unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -769,15 +787,15 @@ static size_t small_mfma_lds(int dim, int K, int N) {
 }
 
 template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW, bool RUN, bool AN, bool TEMPERED = false,
-          bool EXCHANGE = false>
-static int launch_small_mfma_kernel(const std::conditional_t<EXCHANGE, SmallTrajExchangeArgs, SmallTrajArgs>& a,
-                                    dim3 grid, hipStream_t st) {
+          bool EXCHANGE = false, bool LADDER = false>
+static int launch_small_mfma_kernel(const SmallTrajArgsOf<EXCHANGE, LADDER>& a, dim3 grid, hipStream_t st) {
   const l2hmc_small_plan& P = a.plan;
   const size_t lds = small_mfma_lds<HP, MD, KS_, KSH_>(P.x_dim, P.target.K, P.trajectory_length);
   L2HMC_REQUIRE(lds <= 160 * 1024, "small_trajectory: LDS image %zu B too large", lds);
+  constexpr auto kernel = &small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED, EXCHANGE, LADDER>;
   static DeviceOnce attr_once;   // dynamic LDS beyond 64 KiB needs the opt-in (host-side, not a stream op)
   if (attr_once.pending()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED, EXCHANGE>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_once.done();
   }
@@ -785,9 +803,9 @@ static int launch_small_mfma_kernel(const std::conditional_t<EXCHANGE, SmallTraj
 #ifdef L2HMC_STAMPS
   auto b = a;
   b.stamps = g_stamp_cls == 7 ? g_stamp_buf : nullptr;
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED, EXCHANGE>), grid, dim3(kSmallThreads), lds, st, b);
+  hipLaunchKernelGGL(kernel, grid, dim3(kSmallThreads), lds, st, b);
 #else
-  hipLaunchKernelGGL((small_traj_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, RUN, AN, TEMPERED, EXCHANGE>), grid, dim3(kSmallThreads), lds, st, a);
+  hipLaunchKernelGGL(kernel, grid, dim3(kSmallThreads), lds, st, a);
 #endif
   prof_after(kProfSmall, st);
   L2HMC_CHECK_LAUNCH("small_trajectory");
@@ -814,6 +832,14 @@ static int launch_small_mfma_form(const SmallTrajExchangeArgs& a, dim3 grid, hip
   return target_is_analytic(a.plan.target.is_gaussian)
              ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, true, true, true>(a, grid, st)
              : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, true, false, true, true>(a, grid, st);
+}
+
+// (a trajectory with a temperature per row: the LADDER instance of the same form)
+template <int HP, int MD, int KS_, int KSH_, bool L1M, bool TW = false>
+static int launch_small_mfma_form(const SmallTrajLadderArgs& a, dim3 grid, hipStream_t st) {
+  return target_is_analytic(a.plan.target.is_gaussian)
+             ? launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false, true, false, false, true>(a, grid, st)
+             : launch_small_mfma_kernel<HP, MD, KS_, KSH_, L1M, TW, false, false, false, false, true>(a, grid, st);
 }
 
 // Three forms, chosen by the number of 16-row groups (l2hmc_small_plan::first_layer_form forces one; they walk sums in
@@ -977,6 +1003,29 @@ extern "C" int l2hmc_small_trajectory(const l2hmc_small_plan* plan, const float*
   a.plan = *plan; a.x0 = x0; a.v0 = v0; a.dir = dir; a.rows = rows;
   a.x_out = x_out; a.v_out = v_out; a.sumlogdet = sumlogdet; a.p_accept = p_accept;
   return small_launch("small_trajectory", plan, a, stream);
+}
+
+// l2hmc_small_trajectory with a temperature per row, read on the device: row r at temps[(r % chains) * chain_stride]
+extern "C" int l2hmc_small_trajectory_tempered(const l2hmc_small_plan* plan, const float* temps, int64_t chain_stride,
+                                               int64_t chains, const float* x0, const float* v0, const int32_t* dir,
+                                               int64_t rows, float* x_out, float* v_out, float* sumlogdet,
+                                               float* p_accept, l2hmc_stream_t stream) {
+  const char* who = "small_trajectory_tempered";
+  L2HMC_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  L2HMC_REQUIRE(rows >= 0, "%s: rows < 0", who);
+  L2HMC_REQUIRE(temps != nullptr, "%s: NULL temps", who);
+  L2HMC_REQUIRE(chain_stride == 0 || chain_stride == 1, "%s: chain_stride = %lld: 0 (one value) or 1 (one per chain)",
+                who, (long long)chain_stride);
+  L2HMC_REQUIRE(chains > 0, "%s: chains = %lld: must be positive", who, (long long)chains);
+  L2HMC_REQUIRE(rows % chains == 0, "%s: rows = %lld is no whole number of chains = %lld", who, (long long)rows,
+                (long long)chains);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x0 && v0 && x_out && v_out, "%s: NULL pointer", who);
+  SmallTrajLadderArgs a{};
+  a.plan = *plan; a.x0 = x0; a.v0 = v0; a.dir = dir; a.rows = rows;
+  a.x_out = x_out; a.v_out = v_out; a.sumlogdet = sumlogdet; a.p_accept = p_accept;
+  a.temps = temps; a.temp_chain_stride = chain_stride; a.chains = chains;
+  return small_launch(who, plan, a, stream);
 }
 
 template <class Args>

@@ -329,12 +329,12 @@ __device__ __forceinline__ float row_inv_temp(const SmallTrainArgsOf<LADDER>& a,
 // VJP = true: by the caller's cotangents of (x_N, v_N, sumlogdet, p) (l2hmc_small_vjp), and the gradient with
 // respect to the start state is written out.  Everything else is the same code.
 // AN: the instance of the analytic target kinds (small_mlp.h: energy_grad).
-// LADDER (l2hmc_small_train_step_tempered; loss seed only): the row's temperature is read from a.temps instead of the
-// plan, once, before the first energy_grad; every use of inv_temp below is the same statement in both instances, so a
-// row has the bits of the uniform instance at its temperature.
+// LADDER (l2hmc_small_train_step_tempered, and with VJP l2hmc_small_vjp_tempered): the row's temperature is read from
+// a.temps instead of the plan, once, before the first energy_grad; every use of inv_temp below -- the direct term
+// dx0 += dD grad E(x0) of the VJP instance included -- is the same statement in both instances, so a row has the bits
+// of the uniform instance at its temperature.
 template <int HP, int MD, int TH, bool VJP, bool AN, bool LADDER = false>
 __global__ __launch_bounds__(TH) void small_train_kernel(SmallTrainArgsOf<LADDER> a) {
-  static_assert(!(LADDER && VJP), "the ladder instance is the loss-seeded step's");
   constexpr int kSlots = TH / kLPC, kSmallThreads = TH, SS = kSlots + 4;
   // diagnostic cycle shares (class 7): 0 prologue, 1 forward, 2 loss, 3 net re-evaluation, 4 sub-update + head deltas,
   // 5 hidden deltas (d2, d1, input gradients), 6 owner pass, 7 total
@@ -871,6 +871,30 @@ extern "C" int l2hmc_small_vjp(const l2hmc_small_plan* plan, const float* x0, co
   SmallTrainArgs a{*plan, x0, v0, dir, rows, 0.f, 0.f, x_out, v_out, p_accept, nullptr, static_cast<float*>(ws),
                    nullptr, g_x, g_v, g_logdet, g_p, dx0, dv0, sumlogdet};
   return small_train_launch<true>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
+}
+
+// l2hmc_small_vjp with a temperature per row, read on the device: row r at temps[(r % chains) * chain_stride]
+extern "C" int l2hmc_small_vjp_tempered(const l2hmc_small_plan* plan, const float* temps, int64_t chain_stride,
+                                        int64_t chains, const float* x0, const float* v0, const int32_t* dir,
+                                        int64_t rows, const float* g_x, const float* g_v, const float* g_logdet,
+                                        const float* g_p, float* dx0, float* dv0, float* grads, float* x_out,
+                                        float* v_out, float* sumlogdet, float* p_accept, void* ws, size_t ws_bytes,
+                                        l2hmc_stream_t stream) {
+  const char* who = "small_vjp_tempered";
+  if (int rc = small_train_check(plan, rows, who)) return rc;
+  L2HMC_REQUIRE(temps != nullptr, "small_vjp_tempered: NULL temps");
+  L2HMC_REQUIRE(chain_stride == 0 || chain_stride == 1,
+                "small_vjp_tempered: chain_stride = %lld: 0 (one value) or 1 (one per chain)", (long long)chain_stride);
+  L2HMC_REQUIRE(chains > 0, "small_vjp_tempered: chains = %lld: must be positive", (long long)chains);
+  L2HMC_REQUIRE(rows % chains == 0, "small_vjp_tempered: rows = %lld is no whole number of chains = %lld",
+                (long long)rows, (long long)chains);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x0 && v0 && grads && ws, "small_vjp_tempered: NULL pointer (x0, v0, grads and ws are required)");
+  if (int rc = check_small_nets(plan, who)) return rc;
+  SmallTrainLadderArgs a{{*plan, x0, v0, dir, rows, 0.f, 0.f, x_out, v_out, p_accept, nullptr, static_cast<float*>(ws),
+                          nullptr, g_x, g_v, g_logdet, g_p, dx0, dv0, sumlogdet},
+                         temps, chain_stride, chains};
+  return small_train_launch<true, true>(plan, a, grads, ws_bytes, (hipStream_t)stream, who);
 }
 
 extern "C" int l2hmc_mog_energy_hvp(const l2hmc_mog_target* tgt, const float* x, const float* u, int64_t rows,

@@ -725,8 +725,17 @@ struct AcceptBwdArgs {
   float* dxN; float* dvN; float* dld; float* dx0; float* dv0;            // dx0, dv0 may be NULL
 };
 
+// the LADDER instance's arguments (l2hmc_gauge_accept_backward_ladder): row r at betas[(r % chains) * chain_stride], a
+// DEVICE array, and `beta` is not read.  A type of its own, so that the uniform instance keeps its argument block.
+struct AcceptBwdLadderArgs : AcceptBwdArgs {
+  const float* betas; int64_t chain_stride; int64_t chains;
+};
+
 // one wave per chain; the chain whose force is needed is staged in LDS
-__global__ __launch_bounds__(64) void accept_bwd_kernel(AcceptBwdArgs p) {
+// LADDER: the row's beta is read from a.betas once (a row with g = 0 needs none and loads none); every use below is
+// the same statement in both instances, so a row has the bits of the uniform instance at its beta.
+template <bool LADDER>
+__global__ __launch_bounds__(64) void accept_bwd_kernel(std::conditional_t<LADDER, AcceptBwdLadderArgs, AcceptBwdArgs> p) {
   extern __shared__ float lds[];
   const int T = p.T, X = p.X, sites = T * X, D = 2 * sites;
   const int lane = threadIdx.x;
@@ -739,6 +748,8 @@ __global__ __launch_bounds__(64) void accept_bwd_kernel(AcceptBwdArgs p) {
   // wave-uniform: rows with g = 0 never form 0 * F (a non-finite proposal has p = 0 and stays NaN-free)
   const float g = (p.gp != nullptr && pb > 0.f && pb < 1.f) ? p.gp[b] * pb : 0.f;
   if (lane == 0) p.dld[b] = g;
+  float beta = p.beta;
+  if constexpr (LADDER) beta = g != 0.f ? p.betas[(b % p.chains) * p.chain_stride] : 0.f;     // (wave-uniform)
   // stages `src` and leaves sin(plaquette) of it in sp
   auto stage = [&](const float* src) {
     __syncthreads();
@@ -750,8 +761,8 @@ __global__ __launch_bounds__(64) void accept_bwd_kernel(AcceptBwdArgs p) {
   // F = beta dS/dx at link c = 2 s + mu (the `force` of l2hmc_u1_action_force)
   auto force = [&](int s, int mu) {
     const int i = s / X, j = s - i * X;
-    if (mu == 0) return p.beta * (sp[s] - sp[i * X + ((j == 0) ? X - 1 : j - 1)]);
-    return p.beta * (-sp[s] + sp[((i == 0) ? T - 1 : i - 1) * X + j]);
+    if (mu == 0) return beta * (sp[s] - sp[i * X + ((j == 0) ? X - 1 : j - 1)]);
+    return beta * (-sp[s] + sp[((i == 0) ? T - 1 : i - 1) * X + j]);
   };
   if (g != 0.f) stage(p.xN + o);
   for (int c = lane; c < D; c += 64) {
@@ -1518,26 +1529,50 @@ extern "C" int l2hmc_gauge_loss_backward_ladder(int32_t T, int32_t X, const floa
                             aux_weight, std_weight, charge_weight, inv_count, terms, dxN, dvN, dlogdet, stream);
 }
 
+// l2hmc_gauge_accept_backward on `a` (everything but the betas set by the entry): the checks both entries share, then
+// the launch of the instance Args selects
+template <class Args>
+static int accept_backward_impl(const char* who, Args a, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(a.T > 0 && a.X > 0 && a.rows >= 0, "%s: bad arguments", who);
+  if (a.rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(a.x0 && a.xN && a.vN && a.p && a.u && a.dxN && a.dvN && a.dld, "%s: NULL pointer", who);
+  L2HMC_REQUIRE(!a.dv0 || a.v0, "%s: dv0 needs v0", who);
+  L2HMC_REQUIRE(a.rows <= 0x7fffffff, "%s: rows %lld exceeds the grid", who, (long long)a.rows);
+  const size_t lds = sizeof(float) * (size_t)(2 * a.T * a.X + a.T * a.X);
+  L2HMC_REQUIRE(lds <= 64 * 1024, "%s: lattice too large for one workgroup's LDS", who);
+  constexpr bool ladder = std::is_same_v<Args, AcceptBwdLadderArgs>;
+  hipLaunchKernelGGL(accept_bwd_kernel<ladder>, dim3((unsigned)a.rows), dim3(64), lds, (hipStream_t)stream, a);
+  L2HMC_CHECK_LAUNCH("accept_bwd");
+  return L2HMC_OK;
+}
+
 extern "C" int l2hmc_gauge_accept_backward(int32_t T, int32_t X, float beta, int64_t rows, const float* x0,
                                            const float* v0, const float* xN, const float* vN, const float* p,
                                            const float* u, const float* g_xprop, const float* g_vprop,
                                            const float* g_p, const float* g_xout, float* dxN, float* dvN,
                                            float* dlogdet, float* dx0, float* dv0, l2hmc_stream_t stream) {
-  L2HMC_REQUIRE(T > 0 && X > 0 && rows >= 0, "accept_backward: bad arguments");
-  if (rows == 0) return L2HMC_OK;
-  L2HMC_REQUIRE(x0 && xN && vN && p && u && dxN && dvN && dlogdet, "accept_backward: NULL pointer");
-  L2HMC_REQUIRE(!dv0 || v0, "accept_backward: dv0 needs v0");
-  L2HMC_REQUIRE(rows <= 0x7fffffff, "accept_backward: rows %lld exceeds the grid", (long long)rows);
   AcceptBwdArgs a{};
   a.T = T; a.X = X; a.rows = rows; a.beta = beta;
   a.x0 = x0; a.v0 = v0; a.xN = xN; a.vN = vN; a.p = p; a.u = u;
   a.gxp = g_xprop; a.gvp = g_vprop; a.gp = g_p; a.gxo = g_xout;
   a.dxN = dxN; a.dvN = dvN; a.dld = dlogdet; a.dx0 = dx0; a.dv0 = dv0;
-  const size_t lds = sizeof(float) * (size_t)(2 * T * X + T * X);
-  L2HMC_REQUIRE(lds <= 64 * 1024, "accept_backward: lattice too large for one workgroup's LDS");
-  hipLaunchKernelGGL(accept_bwd_kernel, dim3((unsigned)rows), dim3(64), lds, (hipStream_t)stream, a);
-  L2HMC_CHECK_LAUNCH("accept_bwd");
-  return L2HMC_OK;
+  return accept_backward_impl("accept_backward", a, stream);
+}
+
+extern "C" int l2hmc_gauge_accept_backward_ladder(int32_t T, int32_t X, const float* betas, int64_t chain_stride,
+                                                  int64_t chains, int64_t rows, const float* x0, const float* v0,
+                                                  const float* xN, const float* vN, const float* p, const float* u,
+                                                  const float* g_xprop, const float* g_vprop, const float* g_p,
+                                                  const float* g_xout, float* dxN, float* dvN, float* dlogdet,
+                                                  float* dx0, float* dv0, l2hmc_stream_t stream) {
+  if (int e = check_ladder("accept_backward_ladder", betas, chain_stride, chains, rows)) return e;
+  AcceptBwdLadderArgs a{};
+  a.T = T; a.X = X; a.rows = rows; a.beta = 0.f;
+  a.x0 = x0; a.v0 = v0; a.xN = xN; a.vN = vN; a.p = p; a.u = u;
+  a.gxp = g_xprop; a.gvp = g_vprop; a.gp = g_p; a.gxo = g_xout;
+  a.dxN = dxN; a.dvN = dvN; a.dld = dlogdet; a.dx0 = dx0; a.dv0 = dv0;
+  a.betas = betas; a.chain_stride = chain_stride; a.chains = chains;
+  return accept_backward_impl("accept_backward_ladder", a, stream);
 }
 
 extern "C" int l2hmc_grad_sumsq(const float* g, int64_t n, int64_t tri_lo, int64_t tri_hi, float* out,

@@ -8,12 +8,13 @@ Two paths behind it, chosen per instance (`Dynamics.layered`):
     `net_factory` of any `num_nodes`): per sub-update of utils/dynamics.py:120-225 one S/T/Q evaluation through
     l2hmc_stq_dense (any width) and one ops.lf_update_v / _x launch; the energy gradient comes from the packed target's
     kernel or, for an arbitrary callable on torch tensors, from torch.autograd (the reference's tf.gradients, :241-242)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, _runs, ops
 from . import autograd_toy as _autograd
 
 
@@ -99,6 +100,50 @@ class Dynamics(object):
     def _temp(self):
         return float(self.temperature) if self.use_temperature else 1.0
 
+    def _chain_temperatures(self, temperature, B, who):
+        """`temperature=` of a call -> (scalar or None, ladder or None): None for the dynamics' own; a number or a 0-d
+        array / tensor -> its float32 value as a float; [B] or [1, B] -> the ladder as a float32 device tensor [B]
+        (`_runs.per_chain`: a float32 tensor of that shape on the device stays there, unchecked).  ValueError for
+        another shape, for a value that in float32 is not finite or not > 0, for a ladder tensor that requires grad
+        (its values are not differentiated) and for any temperature on a dynamics built with use_temperature=False.
+        Host-side: a caller runs it before it takes a draw."""
+        if temperature is None:
+            return None, None
+        if not self.use_temperature:
+            raise ValueError(f"{who}: temperature= on a Dynamics built with use_temperature=False, which ignores "
+                             "temperatures (Dynamics._temp): build it with use_temperature=True")
+        if isinstance(temperature, torch.Tensor) and temperature.requires_grad:
+            raise ValueError(f"{who}: temperature requires grad; temperatures are not differentiated (detach it)")
+        if _runs.ndim(temperature) == 0:
+            t32 = np.float32(float(temperature))
+            if not (np.isfinite(t32) and t32 > 0):
+                raise ValueError(f"{who}: every temperature must be finite and > 0 (in float32)")
+            return float(temperature), None
+        return None, _runs.per_chain(temperature, B, self._device, who=who, name="temperature", sign="> 0")[0]
+
+    def _call_temperature(self, temperature, B, who):
+        """`temperature=` of forward / backward / both / propose -> what autograd_toy and `_plan` take: None, a float,
+        or the ladder [B] on the device.  `_chain_temperatures`' refusals, and NotImplementedError for a ladder on a
+        layer-by-layer Dynamics (DynamicsTrainer trains one on a ladder)."""
+        t_scalar, t_ladder = self._chain_temperatures(temperature, B, who)
+        if t_ladder is not None and self.layered:
+            raise NotImplementedError(f"{who}: a temperature per chain on a Dynamics that runs layer by layer; only the "
+                                      "one-launch toy targets take a ladder here (DynamicsTrainer trains a "
+                                      "layer-by-layer Dynamics on one)")
+        return t_scalar if t_ladder is None else t_ladder
+
+    @contextlib.contextmanager
+    def _at(self, temp):
+        """A layer-by-layer call at the scalar `temp` (None: as it is): the layered stages read `self.temperature`,
+        which is set for the call and put back (DynamicsTrainer's rule)."""
+        saved = self.temperature
+        if temp is not None:
+            self.temperature = temp
+        try:
+            yield
+        finally:
+            self.temperature = saved
+
     def kinetic(self, v):
         return ops.kinetic_energy(_lib.as_dev(v, self._device))
 
@@ -161,7 +206,9 @@ class Dynamics(object):
                 v = self._sub_v(x, v, t, 1, lj)
         return (x, v, lj) if log_jac else (x, v, self.p_accept(x0, v0, x, v, lj))
 
-    def _plan(self):
+    def _plan(self, temperature=None):
+        """The plan struct of the one-launch kernels; `temperature` (a float) goes into this struct alone, where
+        `self.temperature` stays as it was."""
         if self.layered:
             raise NotImplementedError(
                 "this Dynamics runs layer by layer (arbitrary energy function, x_dim > 8 or more than 64 hidden units): "
@@ -172,6 +219,8 @@ class Dynamics(object):
         if not self.hmc:
             p.xnet, p.vnet = self.XNet.pack(), self.VNet.pack()
             p.num_nodes = p.xnet.H
+        if temperature is not None:
+            p.target.temperature = temperature
         return p
 
     def _normal(self, shape):
@@ -179,56 +228,78 @@ class Dynamics(object):
         self._draws += 1
         return out
 
-    def _run(self, x, init_v, backward, log_jac):
+    def _run(self, x, init_v, backward, log_jac, temperature=None):
         x = _lib.as_dev(x, self._device).reshape(-1, self.x_dim)
+        temp = self._call_temperature(temperature, x.shape[0], "Dynamics.backward" if backward else "Dynamics.forward")
         if _autograd.wants_grad(self, x, init_v):
             _autograd.check_differentiable(self)          # before any draw
             v = _lib.as_dev(init_v, self._device) if init_v is not None else self._normal(tuple(x.shape))
-            return _autograd.run(self, x, v, backward, log_jac)
+            return _autograd.run(self, x, v, backward, log_jac, temp)
         v = _lib.as_dev(init_v, self._device) if init_v is not None else self._normal(tuple(x.shape))
         if self.layered:
-            return self._layered_run(x, v, backward, log_jac)
+            with self._at(temp):
+                return self._layered_run(x, v, backward, log_jac)
         rows = x.shape[0]
         X, V = torch.empty_like(x), torch.empty_like(x)
         lj = torch.empty(rows, dtype=torch.float32, device=x.device)
         p = torch.empty_like(lj)
         dirs = torch.full((rows,), 1, dtype=torch.int32, device=x.device) if backward else None
-        plan = self._plan()
-        _lib.call("l2hmc_small_trajectory", C.byref(plan), x, v, dirs, rows, X, V, lj, p, device=self._device)
+        self._trajectory(temp, x, v, dirs, rows, X, V, lj, p)
         return (X, V, lj) if log_jac else (X, V, p)
 
-    def both(self, x, init_v_forward=None, init_v_backward=None, log_jac=False):
+    def _trajectory(self, temp, x, v, dirs, rows, X, V, lj, p):
+        """l2hmc_small_trajectory at `temp` (None or a float: on the plan), or with the ladder `temp` [C], rows a
+        multiple of C, l2hmc_small_trajectory_tempered: row r at temp[r % C]."""
+        if isinstance(temp, torch.Tensor):
+            plan = self._plan()
+            _lib.call("l2hmc_small_trajectory_tempered", C.byref(plan), temp, 1, temp.numel(), x, v, dirs, rows, X, V,
+                      lj, p, device=self._device)
+        else:
+            plan = self._plan(temp)
+            _lib.call("l2hmc_small_trajectory", C.byref(plan), x, v, dirs, rows, X, V, lj, p, device=self._device)
+
+    def both(self, x, init_v_forward=None, init_v_backward=None, log_jac=False, temperature=None):
         """forward(x) and backward(x) of the same chains in ONE launch (rows stacked, per-row direction):
-        what `propose` needs (sampler.py:38-39).  Returns ((Xf, Vf, pf), (Xb, Vb, pb))."""
+        what `propose` needs (sampler.py:38-39).  Returns ((Xf, Vf, pf), (Xb, Vb, pb)).  temperature: as `forward`'s;
+        a ladder [B] runs chain i at temperature[i] in both directions.  No graph is recorded here."""
         x = _lib.as_dev(x, self._device).reshape(-1, self.x_dim)
         B = x.shape[0]
+        temp = self._call_temperature(temperature, B, "Dynamics.both")
         vf = _lib.as_dev(init_v_forward, self._device) if init_v_forward is not None else self._normal(tuple(x.shape))
         vb = _lib.as_dev(init_v_backward, self._device) if init_v_backward is not None else self._normal(tuple(x.shape))
         if self.layered:
-            return self._layered_run(x, vf, False, log_jac), self._layered_run(x, vb, True, log_jac)
+            with self._at(temp):
+                return self._layered_run(x, vf, False, log_jac), self._layered_run(x, vb, True, log_jac)
         xx, vv = torch.cat([x, x]), torch.cat([vf, vb])
         dirs = torch.cat([torch.zeros(B, dtype=torch.int32, device=x.device),
                           torch.ones(B, dtype=torch.int32, device=x.device)])
         X, V = torch.empty_like(xx), torch.empty_like(xx)
         lj = torch.empty(2 * B, dtype=torch.float32, device=x.device)
         p = torch.empty_like(lj)
-        plan = self._plan()
-        _lib.call("l2hmc_small_trajectory", C.byref(plan), xx, vv, dirs, 2 * B, X, V, lj, p, device=self._device)
+        self._trajectory(temp, xx, vv, dirs, 2 * B, X, V, lj, p)
         third = lj if log_jac else p
         return (X[:B], V[:B], third[:B]), (X[B:], V[B:], third[B:])
 
-    def forward(self, x, init_v=None, aux=None, log_path=False, log_jac=False):
+    def forward(self, x, init_v=None, aux=None, log_path=False, log_jac=False, temperature=None):
         """:255-281.  Differentiable (torch.autograd, l2hmc_amd/autograd_toy.py) when grad mode is on and x, init_v,
-        alpha or a network weight requires grad."""
-        if aux is not None:
-            raise NotImplementedError("aux inputs are only used by the out-of-scope VAE scripts")
-        return self._run(x, init_v, False, log_jac)
+        alpha or a network weight requires grad.
 
-    def backward(self, x, init_v=None, aux=None, log_jac=False):
-        """:283-310.  Differentiable as `forward`."""
+        temperature: None = the call as it is, at the dynamics' own temperature; a scalar = this call at that
+        temperature, on a copy of the plan (`self.temperature` stays as it was: DynamicsTrainer's rule); [B] or [1, B]
+        = a ladder, chain i at temperature[i] (l2hmc_small_trajectory_tempered, and l2hmc_small_vjp_tempered under
+        grad) with the bits of the scalar call at that value.  The temperatures are NOT differentiated.  Refused before
+        any draw is taken: ValueError for another shape, for a value that in float32 is not finite or not > 0, for a
+        ladder tensor that requires grad and for any temperature on use_temperature=False; NotImplementedError for a
+        ladder on a layer-by-layer Dynamics."""
         if aux is not None:
             raise NotImplementedError("aux inputs are only used by the out-of-scope VAE scripts")
-        return self._run(x, init_v, True, log_jac)
+        return self._run(x, init_v, False, log_jac, temperature)
+
+    def backward(self, x, init_v=None, aux=None, log_jac=False, temperature=None):
+        """:283-310.  Differentiable as `forward`; temperature: as `forward`'s."""
+        if aux is not None:
+            raise NotImplementedError("aux inputs are only used by the out-of-scope VAE scripts")
+        return self._run(x, init_v, True, log_jac, temperature)
 
     def p_accept(self, x0, v0, x1, v1, log_jac, aux=None):
         """:312-319."""

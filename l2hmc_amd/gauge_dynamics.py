@@ -15,7 +15,7 @@ import numpy as np
 import numpy.random as npr
 import torch
 
-from . import _lib, ops
+from . import _lib, _runs, ops
 from . import autograd as _autograd
 from .network import ConvNet3D, GenericNet
 
@@ -186,6 +186,21 @@ class GaugeDynamics:
         self._draws += 1
         return out
 
+    def _beta(self, beta, B):
+        """`beta` of a transition -> (beta, None) for one value (untouched: the scalar call reads float(beta) as it
+        always did), or (None, the ladder as a float32 device tensor [B]) for [B] / [1, B] (`_runs.per_chain`: a
+        float32 tensor of that shape on the device stays there, unchecked).  Host-side, before any draw."""
+        size = beta.numel() if isinstance(beta, torch.Tensor) else np.size(beta)
+        if _runs.ndim(beta) == 0 or (size == 1 and B != 1):      # (one value in brackets: float() takes it, as before)
+            return beta, None
+        who = "GaugeDynamics.apply_transition"
+        if isinstance(beta, torch.Tensor) and beta.requires_grad:
+            raise ValueError(f"{who}: the beta ladder requires grad; its values are not differentiated (detach it)")
+        if self.hmc:
+            raise NotImplementedError(f"{who}: a beta per chain on hmc=True dynamics: GaugeSampler.run_hmc runs plain "
+                                      "HMC on a ladder (l2hmc_gauge_hmc_run_ladder)")
+        return None, _runs.per_chain(beta, B, self._device, who=who, name="beta", sign="not negative")[0]
+
     def _dir(self, rows, backward):
         return torch.full((rows,), int(backward), dtype=torch.int32, device=self._device)
 
@@ -197,11 +212,33 @@ class GaugeDynamics:
 
     def apply_transition(self, position, beta, momentum_f=None, momentum_b=None, coin=None, u=None):
         """:195-259 -> (position_post, momentum_post, accept_prob, position_out).  Differentiable (torch.autograd,
-        l2hmc_amd/autograd.py) when grad mode is on and the position, eps or a weight requires grad."""
+        l2hmc_amd/autograd.py) when grad mode is on and the position, eps or a weight requires grad.
+
+        beta: a scalar, or one value per chain, [B] or [1, B] (a ladder of a replica-exchange run): chain i runs, and
+        is differentiated, at beta[i], with the bits of the scalar call at that value; draws and the draw counter are
+        the scalar call's.  The ladder's values are NOT differentiated.  Without a graph the ladder call takes the
+        draws of `l2hmc_gauge_transition_draw` with fill_normal / fill_uniform and runs LAYER BY LAYER
+        (l2hmc_gauge_transition_ladder) whatever `fused` says: `GaugeSampler.step` is the one-launch ladder step.
+        Refused before any draw is taken: ValueError for a ladder of another shape, with an entry that in float32 is
+        not finite or is negative, or that requires grad; NotImplementedError for a ladder on hmc=True."""
         x = self._x(position)
+        beta, ladder = self._beta(beta, x.shape[0])
         if _autograd.wants_grad(self, x):
-            return _autograd.transition(self, x, beta, momentum_f, momentum_b, coin, u)
+            return _autograd.transition(self, x, float(beta) if ladder is None else ladder, momentum_f, momentum_b,
+                                        coin, u)
         B, D = x.shape
+        if ladder is not None:
+            v0f, v0b, coin, u = _autograd.draws(self, B, D, x.device, momentum_f, momentum_b, coin, u)
+            x_prop, v_prop, x_out = (torch.empty_like(x) for _ in range(3))
+            p = torch.empty(B, dtype=torch.float32, device=x.device)
+            plan, L = self._plan(), _lib.lib()
+            both = int(bool(self.both_directions))
+            ws, nb = self._ws.get(L.l2hmc_gauge_transition_ws_bytes(C.byref(plan), B, both), x.device)
+            _lib.call("l2hmc_gauge_transition_ladder", C.byref(plan), ladder, 1, x, v0f.contiguous(), v0b.contiguous(),
+                      coin, u, B, both, x_prop, v_prop, p, x_out, ws, nb, device=self._device)
+            if self.check_numerics and not bool(torch.isfinite(x_prop).all() & torch.isfinite(v_prop).all()):
+                raise FloatingPointError("check_numerics: non-finite value in the proposed configuration")
+            return x_prop, v_prop, p, x_out
         if momentum_f is None and momentum_b is None and coin is None and u is None:
             # no draw injected: the library draws for itself (one stream pair from this object's counter, the
             # layout of the native MCMC step) -- one kernel launch where the plan has a whole-trajectory kernel

@@ -788,6 +788,39 @@ int l2hmc_small_hmc_run(const l2hmc_small_plan* plan, const float* x_in, float* 
                         uint64_t draw0, int32_t n_steps, const float* temps, int64_t step_stride, int64_t chain_stride,
                         const float* eps_chain, float* px, float* samples, l2hmc_stream_t stream);
 
+/* Annealed importance sampling (utils/ais.py:30-82, after Wu et al. 2016) on a packed toy target: a RUN of n_steps
+ * annealing steps in ONE launch.  E1 is the plan target's energy at the plan's temperature -- exactly what
+ * l2hmc_small_hmc_run integrates; every kind, x_dim <= 8 -- and E0 the energy of `init`, a target of kind
+ * L2HMC_TARGET_GAUSSIAN and the plan's dim, evaluated at temperature 1 whatever its field says.  The launch estimates
+ * log(Z1 / Z0), Z = integral of exp(-E): the mean over chains of exp(log_w), taken by the caller.
+ * betas is a DEVICE float[n_steps + 1]: step s of the launch (0 <= s < n_steps) reads betas[s] as b_{s-1} and
+ * betas[s + 1] as b_s, so a run cut into launches passes the same array at an offset.  Per chain, step s does
+ *   log_w += ((double)b_s - (double)b_{s-1}) * ((double)E0(x) - (double)E1(x))   on the state step s - 1 left (:56-57)
+ *   momentum: fresh N(0, I) (:55); with v given, v * sqrt(1 - refreshment) + n * sqrt(refreshment), n ~ N(0, I) (:53)
+ *   one forward plain-HMC trajectory (the plan's masks, eps, trajectory_length) on E_s = (1.f - b_s) * E0 + b_s * E1,
+ *   formed in float32 like that, the gradient likewise: at b_s = 1 the step has the bits of l2hmc_small_hmc_run on the
+ *   plan, at b_s = 0 those of a run on a plan whose target is `init` at temperature 1
+ *   p = exp(min(0, H_s(x, v) - H_s(Lx, Lv))), a non-finite value gives 0; accepted iff p - u >= 0 (:61)
+ *   accepted: x <- Lx, v <- Lv; rejected: x stays, v <- -Lv -- the PROPOSED momentum negated (:63), not the one the step
+ *   started from
+ * Draws: two streams per step in the layout of l2hmc_small_hmc_run: the momenta, or the noise n, are elements
+ * c * x_dim + d of stream (seed, draw0 + 2 s), the Metropolis-Hastings uniform is element c of (seed, draw0 + 2 s + 1).
+ * log_w is a DEVICE double[B], read and written (a fresh anneal starts it at 0); the increment and the sum are formed in
+ * double, so a run cut into launches has the bits of the uncut one.  v is a DEVICE float[B][x_dim], read and written,
+ * or NULL: fresh momenta every step, and refreshment is not read.  px (or NULL) is [n_steps][B].  The final state goes
+ * to x_next [B][x_dim], which may alias x_in.
+ * A kernel of its own (small_ais.hip) in the geometry of l2hmc_small_hmc_run: one thread per chain with x, v, the
+ * gradient and log_w in registers for the whole launch, one wave per workgroup, both targets and the masks staged once.
+ * No workspace, no host synchronisation; the call can be captured into a HIP graph.  The VALUES of betas are not
+ * checked (callers check: finite, in [0, 1], non-decreasing; DynamicsSampler.ais does).
+ * Refused with L2HMC_ERR_ARG before any device call: NULL plan / init / x_in / x_next / betas / log_w, B < 0,
+ * n_steps <= 0, an L2HMC plan (hmc == 0), what l2hmc_small_hmc_run refuses of a plan and its target, an init of another
+ * kind or dim (or with NULL mu / prec), refreshment outside (0, 1] when v is given, draw0 + 2 n_steps beyond 2^64 - 1,
+ * targets and masks beyond 64 KiB of LDS.  B == 0 is a no-op. */
+int l2hmc_small_ais_run(const l2hmc_small_plan* plan, const l2hmc_mog_target* init, const float* x_in, float* x_next,
+                        float* v, float refreshment, int64_t B, uint64_t seed, uint64_t draw0, int32_t n_steps,
+                        const float* betas, double* log_w, float* px, l2hmc_stream_t stream);
+
 /* ONE replica-exchange (parallel tempering) round between neighbouring rungs of a temperature ladder on a packed toy
  * target, in place on x [B][x_dim].  Any plan with a packed target is served, an L2HMC sampler's included: of the plan
  * only x_dim and target are read.  Columns [g * group, (g + 1) * group) form one replica group and column c is at

@@ -12,4 +12,5 @@ from .gauge_sampler import GaugeSampler  # noqa: F401
 from .gauge_trainer import GaugeTrainer  # noqa: F401
 from .dynamics_trainer import DynamicsTrainer  # noqa: F401
 from .dynamics_sampler import DynamicsSampler  # noqa: F401
+from .ais import ais_estimate  # noqa: F401
 from . import stats  # noqa: F401

@@ -165,6 +165,8 @@ _PROTOS = {
                                            _P]),
     "l2hmc_small_hmc_run": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _I64, _I64, _P, _P, _P,
                                       _P]),
+    "l2hmc_small_ais_run": (C.c_int, [C.POINTER(SmallPlan), C.POINTER(MogTarget), _P, _P, _P, _F, _I64, _U64, _U64,
+                                      _I32, _P, _P, _P, _P]),
     "l2hmc_small_replica_swap": (C.c_int, [C.POINTER(SmallPlan), _P, _I64, _I32, _I32, _P, _I64, _U64, _U64, _P, _P, _P,
                                            _P, _P]),
     "l2hmc_small_hmc_run_exchange": (C.c_int, [C.POINTER(SmallPlan), _P, _P, _I64, _U64, _U64, _I32, _P, _I64, _I64, _P,

@@ -3,7 +3,8 @@
 // step around it (utils/sampler.py:28-59).  How a chain is spread over lanes, how a network is evaluated and what is
 // staged where stay with the kernels: they hand the trajectory callables.
 //
-// Who calls this today: small_hmc_run_kernel (small_hmc.hip) alone, and through small_swap.h's replica-exchange round
+// Who calls this today: small_hmc_run_kernel (small_hmc.hip) and small_ais_run_kernel (small_ais.hip, whose target
+// callable interpolates between two SmallTargets), and through small_swap.h's replica-exchange round
 // (SmallTarget at temperature 1) small_swap_kernel beside it and the EXCHANGE instances of small_traj_mfma_kernel.  small_traj_mfma_kernel (small_mlp.hip) and the
 // forward half of small_train_kernel (small_train.hip) spell the same statements out themselves, in the same order:
 //   - taken through small_trajectory, four of the former's 96 instances and nine of the latter's 16 gained scratch or
@@ -78,9 +79,9 @@ struct NoNet {
 //   netx / netv(tc, ts, a, b, S, T, Q)   the position / momentum network on inputs (a, b); NoNet for plain HMC
 //   target(x, E or nullptr, g)           energy and gradient at the chain's temperature
 // Exp: lf_update.h's exponential flavour.  Every lane that holds the chain calls this with the same values; the
-// callables may be collective.  The one caller today is the plain-HMC run, which needs neither direction, time nor
-// networks: those are the interface of the two kernels that spell this loop out (header), kept so that the three
-// bodies can be read against each other line by line.
+// callables may be collective.  The callers today are the plain-HMC run and the annealed-importance-sampling run, which
+// need neither direction, time nor networks: those are the interface of the two kernels that spell this loop out
+// (header), kept so that the three bodies can be read against each other line by line.
 template <class Exp, int MD, class Time, class NetX, class NetV, class Target>
 __device__ __forceinline__ SmallTraj small_trajectory(int dim, int N, int bwd, float eps, const float* Lm,
                                                       float (&x)[MD], float (&v)[MD], float (&g)[MD], Time time,

@@ -16,6 +16,9 @@ step, per chain, or both, where `dynamics.temperature` is one value for the laun
 chain): the values of `run` on an `hmc=True` dynamics, bit for bit, and beyond them a temperature and a step size per
 chain, so that "HMC at three eps" is one call.
 
+`ais` is the reference's annealed importance sampling (utils/ais.py) on such a dynamics, `steps_per_launch` annealing
+steps per launch (l2hmc_small_ais_run, the geometry of the plain-HMC run): an estimate of a normalising constant.
+
 `run_hmc_exchange` is `run_hmc` on a temperature ladder with replica exchange (parallel tempering) between the rungs,
 the rounds inside the launch (l2hmc_small_hmc_run_exchange: a replica group sits in one wave); `swap_replicas` is one
 round on its own (l2hmc_small_replica_swap).
@@ -208,8 +211,104 @@ class DynamicsSampler:
         return self._finish(self._run_launches(run_steps, x, keep_samples, plan, "l2hmc_small_hmc_run",
                                                lambda s0: (*temps_from(s0), eps_chain), streams=2))
 
+    # ------------------------------------------------------------------------------------------ annealed importance sampling
+    @staticmethod
+    def ais_schedule(anneal_steps, betas=None, who="ais"):
+        """`ais`'s `betas` -> the float32 array [anneal_steps] of b_1 .. b_n.  None: the reference's schedule
+        (utils/ais.py:43: linspace(0, 1, n + 1)[1:]), formed in float32.  ValueError for another shape and for an entry
+        that, in float32, is not finite, lies outside [0, 1] or is smaller than the one before."""
+        n = int(anneal_steps)
+        if n != anneal_steps or n < 1:
+            raise ValueError(f"{who}: anneal_steps={anneal_steps} must be a whole number, 1 or more")
+        if betas is None:
+            return np.linspace(0., 1., n + 1, dtype=np.float32)[1:]
+        v, b = _runs._float32(betas)
+        if b.shape != (n,):
+            raise ValueError(f"{who}: betas of shape {v.shape}: expected [{n}] (b_1 .. b_n; b_0 = 0)")
+        if not (np.isfinite(b) & (b >= 0) & (b <= 1)).all() or (np.diff(b) < 0).any():
+            raise ValueError(f"{who}: betas must be finite, in [0, 1] and non-decreasing (in float32)")
+        return np.ascontiguousarray(b)
+
+    def ais(self, anneal_steps, init, x, betas=None, refresh=None):
+        """Annealed importance sampling (utils/ais.py:30-82, after Wu et al. 2016) from `init`, a `Gaussian`, to the
+        dynamics' target at the dynamics' temperature, with the transitions of this plain-HMC dynamics (`hmc=True`: its
+        masks, eps, trajectory_length), `steps_per_launch` annealing steps per launch (l2hmc_small_ais_run): an
+        estimate of log(Z1 / Z0), Z = integral of exp(-E).  `x` [B, x_dim]: the chains' starts, drawn from `init` by the
+        caller (the reference's `initial_x`); it is not advanced in place.  With b_0 = 0 and b_1 <= .. <= b_n = `betas`
+        (None: linspace(0, 1, n + 1)[1:] in float32), step s adds (b_s - b_{s-1}) (E0(x) - E1(x)) to the chain's log
+        weight, draws a momentum and runs one Metropolis-Hastings HMC step on (1 - b_s) E0 + b_s E1.
+        `refresh`: None -- a fresh N(0, I) momentum every step; a float rho in (0, 1] -- the momentum persists as
+        v sqrt(1 - rho) + n sqrt(rho), n ~ N(0, I), from a start v that is one `fill_normal` stream of the dynamics'
+        counter; an accepted step keeps the proposed momentum and a rejected one its negative (DESIGN.md quirk list).
+        Draws: `_draws` advances by 2 per step (momenta or noise, uniforms), plus 1 with `refresh`.  Any
+        `steps_per_launch` gives the same bits.  Returns a dictionary:
+          log_w [B] float64         the chains' log weights
+          log_ratio                 logsumexp(log_w) - log(B): the estimate of log(Z1 / Z0)
+          log_z                     log_ratio + 0.5 logdet(2 pi Sigma_init): the estimate of log Z1
+          se                        the delta-method standard error of log_ratio, std(w~, ddof=1) / (sqrt(B) mean(w~))
+                                    with w~ = exp(log_w - max log_w)
+          ess                       (sum w~)^2 / sum w~^2
+          px [n, B], mean_accept    every step's accept probabilities and their mean
+          samples_out [B, x_dim]    the final state on the device;  v_out [B, x_dim] with `refresh`
+        ValueError for an L2HMC dynamics, an `init` that is no `Gaussian` of the dynamics' dimension, a bad schedule or
+        `refresh`, and a `dynamics.temperature` other than 1 on a dynamics built with use_temperature=False (which
+        ignores it); NotImplementedError for a dynamics that runs layer by layer.  All before any draw."""
+        from . import ops
+        from .distributions import Gaussian
+        who, dyn = "ais", self.dynamics
+        self._check_hmc(who)
+        if not dyn.use_temperature and float(dyn.temperature) != 1.0:
+            raise ValueError(f"{who}: temperature={dyn.temperature} on a Dynamics built with use_temperature=False, "
+                             "which ignores temperatures (Dynamics._temp): build it with use_temperature=True")
+        if not isinstance(init, Gaussian) or np.shape(init.mu) != (dyn.x_dim,):
+            raise ValueError(f"{who}: init must be a Gaussian of dimension {dyn.x_dim} (the chains start from its "
+                             f"samples): got {type(init).__name__}"
+                             + (f" of dimension {np.shape(init.mu)}" if isinstance(init, Gaussian) else ""))
+        sched = self.ais_schedule(anneal_steps, betas, who)
+        n = sched.shape[0]
+        if refresh is not None:
+            ok = not isinstance(refresh, bool) and np.ndim(refresh) == 0
+            rho = float(np.float32(refresh)) if ok else float("nan")
+            if not (0.0 < rho <= 1.0):
+                raise ValueError(f"{who}: refresh={refresh}: expected None (fresh momenta) or a number in (0, 1]")
+        if x is None:
+            raise ValueError(f"{who}: pass the start `x` [B, {dyn.x_dim}], drawn from init")
+        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        B, dev = x.shape[0], x.device
+        plan = dyn._plan()
+        init_target = init.get_energy_function().target.to(dev)      # (kept alive until the last launch returned)
+        init_struct = init_target.struct(1.0)
+        betas_dev = _lib.as_dev(np.concatenate([np.zeros(1, np.float32), sched]), dev)
+        log_w = torch.zeros(B, dtype=torch.float64, device=dev)
+        px = torch.empty(n, B, dtype=torch.float32, device=dev)
+        # the start momentum is the stream at the counter; the counter moves only after a launch returned
+        v = None if refresh is None else ops.fill_normal((B, dyn.x_dim), dyn._seed, dyn._draws, dev)
+        taken = [0 if v is None else 1]                            # streams taken ahead of the next launch
+
+        def launch(s0, m, x_in, x_next, _):
+            _lib.call("l2hmc_small_ais_run", C.byref(plan), C.byref(init_struct), x_in, x_next, v,
+                      0.0 if refresh is None else rho, B, dyn._seed, dyn._draws + taken[0], m, betas_dev[s0:],
+                      log_w.data_ptr(), px[s0:], device=dyn._device)
+            dyn._draws += taken[0] + 2 * m
+            taken[0] = 0
+
+        out = _runs.run_chunks(n, x, self.steps_per_launch, False, launch)
+        out["px"] = px.cpu().numpy()
+        out["log_w"] = lw = log_w.cpu().numpy()
+        if refresh is not None:
+            out["v_out"] = v
+        with np.errstate(all="ignore"):
+            top = lw.max() if B else np.float64("nan")
+            wt = np.exp(lw - top)
+            mean = wt.mean() if B else np.float64("nan")
+            out["log_ratio"] = float(top + np.log(mean))
+            out["se"] = float(wt.std(ddof=1) / (np.sqrt(B) * mean)) if B > 1 else float("nan")
+            out["ess"] = float(wt.sum() ** 2 / np.square(wt).sum()) if B else float("nan")
+        out["log_z"] = out["log_ratio"] + 0.5 * float(np.linalg.slogdet(2 * np.pi * np.asarray(init.sigma, np.float64))[1])
+        return self._finish(out)
+
     # ------------------------------------------------------------------------------------------ replica exchange
-    MAX_REPLICAS = 64                # a replica group sits in one wave (l2hmc_small_replica_swap)
+    MAX_REPLICAS = 64               # a replica group sits in one wave (l2hmc_small_replica_swap)
     MAX_REPLICAS_IN_LAUNCH = 8       # ... in the eight chains of a wave of the L2HMC kernel (l2hmc_small_run_exchange)
 
     def exchange_in_launch(self, replicas):

@@ -168,6 +168,23 @@ int l2hmc_lf_update_x(const float* x, const float* v, const float* keep, const f
                       const float* T, const float* Q, float eps, int32_t dir, int64_t rows,
                       int32_t D, float* x_out, float* logdet, l2hmc_stream_t stream);
 
+/* Position sub-update of the torus-exact mode (L2HMC_PLAN_PERIODIC; no reference counterpart).  With e_s = exp(+-eps S)
+ * (+ dir 0, - dir 1), drift = eps (exp(eps Q) v + T) and w = x (dir 0) or x - drift (dir 1):
+ *   y = 2 atan2(e_s sin(w / 2), cos(w / 2)) [+ drift for dir 0],   x' = keep x + (1 - keep) y,
+ *   logdet[r] = sum_d (1 - keep) (+-eps S - log(cos^2(w / 2) + e_s^2 sin^2(w / 2))).
+ * atan2 takes its principal value, so x' is defined modulo 2 pi.  S, T, Q may be NULL (= 0); out may alias in. */
+int l2hmc_lf_update_x_ncp(const float* x, const float* v, const float* keep, const float* S,
+                          const float* T, const float* Q, float eps, int32_t dir, int64_t rows,
+                          int32_t D, float* x_out, float* logdet, l2hmc_stream_t stream);
+
+/* out[r] = [cos x[r] | sin x[r]] ([rows][2D]) for x [rows][D]: the form in which the networks of a periodic plan see
+ * the link angles.  _vjp: dx[r][c] += -sin x[r][c] dfeat[r][c] + cos x[r][c] dfeat[r][D + c], dfeat with row stride
+ * ldf >= 2D (a slice of a wider cotangent).  Any D; 16-byte accesses when D (and ldf) are multiples of 4 and the
+ * bases aligned. */
+int l2hmc_u1_angle_features(const float* x, int64_t rows, int32_t D, float* out, l2hmc_stream_t stream);
+int l2hmc_u1_angle_features_vjp(const float* x, const float* dfeat, int64_t ldf, int64_t rows, int32_t D, float* dx,
+                                l2hmc_stream_t stream);
+
 /* gauge_dynamics.py:592-609 / utils/dynamics.py:312-319:
  * p = exp(min(h_old - h_new + sumlogdet, 0)), non-finite -> 0. */
 int l2hmc_accept_prob(const float* h_old, const float* h_new, const float* sumlogdet, int64_t n,
@@ -206,6 +223,14 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
 #define L2HMC_PLAN_SINGLE_KICKS 128  /* whole-step kernel, 16-row GenericNet sampling form: the second momentum half-kick of a
                                       * leapfrog step and the first of the next one stay two network calls instead of one
                                       * pass over two time slices (same bits).  A/B switch */
+#define L2HMC_PLAN_PERIODIC 256      /* torus-exact L2HMC (GenericNet only; ignored with hmc = 1): the networks see every link
+                                      * angle through [cos x | sin x] -- VNet has Ka = 2D, Kb = D (its first input is x),
+                                      * XNet has Ka = D, Kb = 2D (its second input is the masked x, the mask applied to both
+                                      * halves) -- and the position sub-update is l2hmc_lf_update_x_ncp, a map of the circle
+                                      * onto itself.  The proposal then commutes with 2 pi shifts of any link, so the wrap
+                                      * between MCMC steps is harmless and the chain exact for any weights.  Runs layer by
+                                      * layer, every first-layer product formed anew: l2hmc_gauge_plan_fused() == 0, and the
+                                      * l2hmc_gauge_train_* entries refuse the plan */
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */
@@ -1000,6 +1025,12 @@ int l2hmc_lf_update_x_vjp(const float* x, const float* v, const float* keep, con
                           const float* Q, float eps, int32_t dir, int64_t rows, int32_t D, const float* dx_out,
                           const float* dlogdet, float* dx, float* dv, float* dS, float* dT, float* dQ, float* deps,
                           l2hmc_stream_t stream);
+
+/* The same for l2hmc_lf_update_x_ncp. */
+int l2hmc_lf_update_x_ncp_vjp(const float* x, const float* v, const float* keep, const float* S, const float* T,
+                              const float* Q, float eps, int32_t dir, int64_t rows, int32_t D, const float* dx_out,
+                              const float* dlogdet, float* dx, float* dv, float* dS, float* dT, float* dQ, float* deps,
+                              l2hmc_stream_t stream);
 
 /* Backward-data of one network call.  Input: the call's S, Q, the cotangents dS, dT, dQ [rows][D] and its taped
  * h1, h2 [rows][H].  Outputs: dpre [rows][3D] the head pre-activation cotangents (tanh' and exp(coeff) applied),

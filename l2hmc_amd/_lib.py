@@ -19,6 +19,7 @@ MAX_MIX, MAX_SMALL_DIM, MAX_SMALL_NODES = 8, 8, 64
 PLAN_LAYERED, PLAN_CONV3D, PLAN_SELECTED_ONLY, PLAN_RECOMPUTE, PLAN_TILES16_ONLY, PLAN_ALL_COLUMNS = 1, 2, 4, 8, 16, 32
 PLAN_FULL_L1 = 64
 PLAN_SINGLE_KICKS = 128
+PLAN_PERIODIC = 256
 GRAD_BUCKET_REST = 6
 BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32)
 
@@ -186,6 +187,10 @@ _PROTOS = {
     "l2hmc_stq_dense_taped": (C.c_int, [C.POINTER(DenseNet), _P, _P, _P, _F, _F, _I64, _P, _P, _P, _P, _P, _P]),
     "l2hmc_lf_update_v_vjp": (C.c_int, [_P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P] + [_P] * 6 + [_P]),
     "l2hmc_lf_update_x_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P] + [_P] * 6 + [_P]),
+    "l2hmc_lf_update_x_ncp": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P, _P]),
+    "l2hmc_lf_update_x_ncp_vjp": (C.c_int, [_P, _P, _P, _P, _P, _P, _F, _I32, _I64, _I32, _P, _P] + [_P] * 6 + [_P]),
+    "l2hmc_u1_angle_features": (C.c_int, [_P, _I64, _I32, _P, _P]),
+    "l2hmc_u1_angle_features_vjp": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _P]),
     "l2hmc_dense_backward_data_ws_bytes": (_SZ, [C.POINTER(DenseNet)]),
     "l2hmc_dense_backward_data": (C.c_int, [C.POINTER(DenseNet)] + [_P] * 7 + [_I64] + [_P] * 6 + [_SZ, _P]),
     "l2hmc_dense_weight_grads_ws_bytes": (_SZ, [C.POINTER(DenseNet), _I64]),

@@ -45,6 +45,11 @@ def check_differentiable(dyn):
     if dyn.hmc:
         raise NotImplementedError("autograd through GaugeDynamics: hmc=True dynamics have no networks; the "
                                   "training entries take L2HMC plans only")
+    if getattr(dyn, "periodic", False):
+        raise NotImplementedError("autograd through GaugeDynamics: periodic=True dynamics have no tiled training "
+                                  "entries; they would need the layered reverse walk, which torch.autograd is refused "
+                                  "at today for every shape whose widths are no multiples of 32 (GaugeTrainer trains "
+                                  "them)")
     for name, net in _nets(dyn):
         if getattr(net, "_flat", None) is not None:
             raise ValueError(f"autograd through GaugeDynamics: a GaugeTrainer owns the weights of {name} (flat master "

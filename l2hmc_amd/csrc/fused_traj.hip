@@ -1209,6 +1209,7 @@ static int device_cu_count() {
 }
 int fused_plan_supported(const l2hmc_gauge_plan* p) {
   if (p->hmc || !p->xnet.packed || !p->vnet.packed || 2 * p->T * p->X != 128 || (p->X & (p->X - 1)) != 0) return 0;
+  if (p->flags & L2HMC_PLAN_PERIODIC) return 0;      // the torus-exact mode runs layer by layer (leapfrog.hip)
   if (p->flags & L2HMC_PLAN_CONV3D)
     return fused_conv_net(&p->xnet) && fused_conv_net(&p->vnet) && p->T == 8 && p->X == 8 && p->xfront.F == 8 &&
            p->vfront.F == 8;

@@ -63,6 +63,29 @@ __global__ __launch_bounds__(256) void lf_update_x_vjp_kernel(
   if (lane == 0) deps[row] = de;
 }
 
+// reverse of lf_update_x_ncp_kernel (lf_drift_ncp_vjp of lf_update.h): lf_update_x_vjp_kernel's outputs
+__global__ __launch_bounds__(256) void lf_update_x_ncp_vjp_kernel(
+    const float* __restrict__ x, const float* __restrict__ v, const float* __restrict__ keep,
+    const float* __restrict__ S, const float* __restrict__ T, const float* __restrict__ Q, float eps, int d,
+    int64_t rows, int D, const float* __restrict__ dxo, const float* __restrict__ dld, float* __restrict__ dx,
+    float* __restrict__ dv, float* __restrict__ dS, float* __restrict__ dT, float* __restrict__ dQ,
+    float* __restrict__ deps) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float dl = dld ? dld[row] : 0.f;
+  float de = 0.f;
+  for (int c = lane; c < D; c += kWave) {
+    const int64_t i = row * D + c;
+    float dt, eq;
+    lf_drift_ncp_vjp(x[i], v[i], keep[c], S[i], T[i], Q[i], eps, d, dxo[i], dl, dx[i], dS[i], dt, dQ[i], eq, de);
+    dT[i] = dt;
+    dv[i] = dt * eq;
+  }
+  de = wave_sum(de);
+  if (lane == 0) deps[row] = de;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // heads: S = e^{cs} tanh(zS), T = zT, Q = e^{cq} tanh(zQ) (q_tanh) or e^{cq} zQ.  Cotangents of (S, T, Q) ->
 // dpre = [dzS | dzT | dzQ] per row, and (optional) dsq = [dS S | dQ Q] per row: d/dcs and d/dcq before the sum over
@@ -324,6 +347,21 @@ extern "C" int l2hmc_lf_update_x_vjp(const float* x, const float* v, const float
   hipLaunchKernelGGL(lf_update_x_vjp_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, x,
                      v, keep, S, T, Q, eps, dir, rows, D, dx_out, dlogdet, dx, dv, dS, dT, dQ, deps);
   L2HMC_CHECK_LAUNCH("lf_update_x_vjp");
+  return L2HMC_OK;
+}
+
+extern "C" int l2hmc_lf_update_x_ncp_vjp(const float* x, const float* v, const float* keep, const float* S,
+                                         const float* T, const float* Q, float eps, int32_t dir, int64_t rows, int32_t D,
+                                         const float* dx_out, const float* dlogdet, float* dx, float* dv, float* dS,
+                                         float* dT, float* dQ, float* deps, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(rows >= 0 && D > 0 && (dir == 0 || dir == 1),
+                "lf_update_x_ncp_vjp: bad arguments (rows=%lld, D=%d, dir=%d)", (long long)rows, D, dir);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x && v && keep && S && T && Q && dx_out && dx && dv && dS && dT && dQ && deps,
+                "lf_update_x_ncp_vjp: NULL pointer");
+  hipLaunchKernelGGL(lf_update_x_ncp_vjp_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream,
+                     x, v, keep, S, T, Q, eps, dir, rows, D, dx_out, dlogdet, dx, dv, dS, dT, dQ, deps);
+  L2HMC_CHECK_LAUNCH("lf_update_x_ncp_vjp");
   return L2HMC_OK;
 }
 

@@ -56,6 +56,37 @@ __global__ __launch_bounds__(256) void lf_update_x_kernel(
   if (lane == 0 && logdet) logdet[row] = accumulate ? logdet[row] + ld : ld;
 }
 
+// the torus form of lf_update_x_kernel (lf_drift_ncp of lf_update.h): same rows, same log-det slot
+__global__ __launch_bounds__(256) void lf_update_x_ncp_kernel(
+    const float* x, const float* __restrict__ v, const float* __restrict__ keep, const float* __restrict__ S,
+    const float* __restrict__ T, const float* __restrict__ Q, float eps, int d, int64_t rows, int D, float* x_out,
+    float* __restrict__ logdet) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float ld = 0.f;
+  for (int c = lane; c < D; c += kWave) {
+    const int64_t i = row * D + c;
+    const float Sv = S ? S[i] : 0.f, Tv = T ? T[i] : 0.f, Qv = Q ? Q[i] : 0.f;
+    float s, omk;
+    x_out[i] = lf_drift_ncp<ExpLibm>(x[i], v[i], keep[c], Sv, Tv, Qv, eps, d, s, omk);
+    ld += omk * s;
+  }
+  ld = wave_sum(ld);
+  if (lane == 0 && logdet) logdet[row] = ld;
+}
+
+// periodic plans: the masks of the feature input [cos x | sin x], m2[s][j] = m[s][j mod D], and their inverses
+__global__ void double_mask_kernel(const float* __restrict__ m, int num_steps, int D, float* __restrict__ m2,
+                                   float* __restrict__ m2_inv) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= num_steps * 2 * D) return;
+  const int s = i / (2 * D), j = i - s * 2 * D;
+  const float k = m[s * D + (j < D ? j : j - D)];
+  m2[i] = k;
+  m2_inv[i] = 1.f - k;
+}
+
 // keep_inv[c] = 1 - keep[c]   (the m-bar of gauge_dynamics.py:671-673), for all steps at once
 __global__ void invert_mask_kernel(const float* __restrict__ m, float* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -181,8 +212,14 @@ struct GaugeWs {
   float* act0; float* kin0; float* act1; float* kin1;
   float* pre_v; float* pre_x;      // kept first-layer products [rows][H] (NULL when the plan recomputes them)
   int* act_cols; int* act_cnt;     // [num_steps][2][D] / [num_steps][2]: columns a position sub-update moves (stq_dense.h)
+  float* feat;                     // periodic plans: [rows][2D] = [cos x | sin x] of the current x (NULL otherwise)
+  float* mask2; float* mask2_inv;  // periodic plans: [num_steps][2D] masks of the feature input and their inverses
   size_t bytes;
 };
+
+// L2HMC_PLAN_PERIODIC: the networks read x through [cos x | sin x] and the position update is lf_drift_ncp.  Plain HMC
+// has no networks and no scaling: there the flag changes nothing.
+static bool plan_periodic(const l2hmc_gauge_plan* p) { return !p->hmc && (p->flags & L2HMC_PLAN_PERIODIC) != 0; }
 
 // Recurring first-layer products of a leapfrog step (gauge_dynamics.py:412-483 evaluates every one of them anew):
 //   * the two position sub-updates of a step call XNet on (v, m.x) and (v, m_inv.x) with the SAME v: the momentum
@@ -227,12 +264,19 @@ static GaugeWs carve_gauge_ws(const l2hmc_gauge_plan* p, int64_t rows, void* ws)
   w.kin0 = take(rows);
   w.act1 = take(rows);
   w.kin1 = take(rows);
-  const bool keep = !p->hmc && !(p->flags & L2HMC_PLAN_RECOMPUTE) && dense_net_tileable(&p->xnet) &&
-                    dense_net_tileable(&p->vnet);
+  // (periodic plans form every first-layer product anew: DESIGN.md section 4)
+  const bool keep = !p->hmc && !(p->flags & (L2HMC_PLAN_RECOMPUTE | L2HMC_PLAN_PERIODIC)) &&
+                    dense_net_tileable(&p->xnet) && dense_net_tileable(&p->vnet);
   w.pre_v = keep ? take((size_t)rows * p->vnet.H) : nullptr;
   w.pre_x = keep ? take((size_t)rows * p->xnet.H) : nullptr;
   w.act_cols = reinterpret_cast<int*>(take((size_t)p->num_steps * 2 * D));
   w.act_cnt = reinterpret_cast<int*>(take((size_t)p->num_steps * 2));
+  w.feat = w.mask2 = w.mask2_inv = nullptr;
+  if (plan_periodic(p)) {           // (other plans: not a byte more)
+    w.feat = take((size_t)rows * 2 * D);
+    w.mask2 = take((size_t)p->num_steps * 2 * D);
+    w.mask2_inv = take((size_t)p->num_steps * 2 * D);
+  }
   w.bytes = off;
   return w;
 }
@@ -243,6 +287,8 @@ static int check_plan(const l2hmc_gauge_plan* p) {
   L2HMC_REQUIRE(p->masks != nullptr, "plan: masks is NULL");
   const int D = 2 * p->T * p->X;
   if (!p->hmc) {
+    L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC) || !(p->flags & L2HMC_PLAN_CONV3D),
+                  "plan: L2HMC_PLAN_PERIODIC takes GenericNet networks only (no ConvNet3D front-end of [cos x | sin x])");
     const l2hmc_dense_net* nets[2] = {&p->xnet, &p->vnet};
     for (const l2hmc_dense_net* n : nets) {
       L2HMC_REQUIRE(n->D == D, "plan: net D=%d != lattice x_dim=%d", n->D, D);
@@ -257,6 +303,11 @@ static int check_plan(const l2hmc_gauge_plan* p) {
                       n->Kb);
         L2HMC_REQUIRE(f->w1_a && f->b1_a && f->w2_a && f->b2_a && f->w1_b && f->b1_b && f->w2_b && f->b2_b,
                       "plan: conv front-end has NULL weight pointer");
+      } else if (p->flags & L2HMC_PLAN_PERIODIC) {
+        // x enters as [cos x | sin x]: VNet's first input, XNet's (masked) second
+        const int ka = n == &p->vnet ? 2 * D : D, kb = n == &p->vnet ? D : 2 * D;
+        L2HMC_REQUIRE(n->Ka == ka && n->Kb == kb, "plan: periodic %s expects Ka=%d, Kb=%d at x_dim=%d (got %d, %d)",
+                      n == &p->vnet ? "VNet" : "XNet", ka, kb, D, n->Ka, n->Kb);
       } else {
         L2HMC_REQUIRE(n->Ka == D && n->Kb == D, "plan: generic net expects Ka=Kb=x_dim (got %d, %d)", n->Ka,
                       n->Kb);
@@ -326,6 +377,7 @@ static int net_update(const l2hmc_gauge_plan* plan, const l2hmc_dense_net* net, 
   h.q_tanh = net->q_tanh; h.D = net->D; h.rows = rows; h.mode = mode;
   h.x = x; h.v = v; h.g = g; h.dir = dir; h.keep_f = keep_f; h.keep_b = keep_b; h.eps = eps;
   h.ld_part = w.ld_part; h.ncb = ncb;
+  h.ncp = mode == 2 && plan_periodic(plan);
   if (mode == 2 && dir_split >= 0 && !(plan->flags & L2HMC_PLAN_ALL_COLUMNS)) {
     // only the columns this sub-update moves (the others' S, T, Q are multiplied by 1 - keep = 0)
     h.cols_f = cols_f; h.cols_b = cols_b; h.cnt_f = cnt_f; h.cnt_b = cnt_b; h.dir_split = dir_split;
@@ -364,6 +416,10 @@ static int leapfrog_step(const l2hmc_gauge_plan* p, RowBeta beta, int step, floa
   const float* mi_b = w.mask_inv + (size_t)sb * D;
   const int ncb = gauge_ncb(p);
   const unsigned rgrid = (unsigned)ceil_div(rows, 4);
+  // periodic plans: w.feat = [cos x | sin x] of the current x (the caller's at entry, refreshed after every position
+  // sub-update below) is VNet's first input and, under the doubled masks, XNet's second
+  const bool per = plan_periodic(p);
+  const float* xin = per ? w.feat : x;
 
   for (int half = 0; half < 2; ++half) {
     if (half == 1) {
@@ -381,10 +437,15 @@ static int leapfrog_step(const l2hmc_gauge_plan* p, RowBeta beta, int step, floa
           const int wf = sub == 0 ? 0 : 1, wb = sub == 0 ? 1 : 0;
           const int* lf = w.act_cols + ((size_t)sf * 2 + wf) * D;
           const int* lb = w.act_cols + ((size_t)sb * 2 + wb) * D;
-          if (int e = net_update(p, &p->xnet, v, x, kf, kb, dir, tcs, rows, /*mode x*/ 2, x, v, nullptr, kf, kb,
+          // the first layer's masks on XNet's second input: the keep masks, or their doubled form over the features
+          const float* cf = !per ? kf : (sub == 0 ? w.mask2 : w.mask2_inv) + (size_t)sf * 2 * D;
+          const float* cb = !per ? kb : (sub == 0 ? w.mask2_inv : w.mask2) + (size_t)sb * 2 * D;
+          if (int e = net_update(p, &p->xnet, v, xin, cf, cb, dir, tcs, rows, /*mode x*/ 2, x, v, nullptr, kf, kb,
                                  p->eps, w, ncb, stream, !carry ? kCarryNone : sub == 0 ? kCarryXFirst : kCarrySecond,
                                  lf, lb, w.act_cnt + sf * 2 + wf, w.act_cnt + sb * 2 + wb, dir_split))
             return e;
+          if (per)
+            if (int e = launch_u1_angle_features(x, rows, D, w.feat, stream)) return e;
         }
       }
     }
@@ -398,7 +459,7 @@ static int leapfrog_step(const l2hmc_gauge_plan* p, RowBeta beta, int step, floa
                          nullptr, p->eps, dir, 0, rows, D, v, nullptr, 0);
       L2HMC_CHECK_LAUNCH("lf_update_v");
     } else {
-      if (int e = net_update(p, &p->vnet, x, w.g, nullptr, nullptr, dir, tcs, rows, /*mode v*/ 1, x, v, w.g,
+      if (int e = net_update(p, &p->vnet, xin, w.g, nullptr, nullptr, dir, tcs, rows, /*mode v*/ 1, x, v, w.g,
                              nullptr, nullptr, p->eps, w, ncb, stream,
                              reuse ? kCarryVUse : (half == 1 && keep_last) ? kCarryVSave : kCarryNone))
         return e;
@@ -407,7 +468,8 @@ static int leapfrog_step(const l2hmc_gauge_plan* p, RowBeta beta, int step, floa
   return L2HMC_OK;
 }
 
-static int prepare_ws(const l2hmc_gauge_plan* p, int64_t rows, const GaugeWs& w, hipStream_t stream) {
+// x: the state the walk starts from (periodic plans form its features here)
+static int prepare_ws(const l2hmc_gauge_plan* p, const float* x, int64_t rows, const GaugeWs& w, hipStream_t stream) {
   const int D = 2 * p->T * p->X;
   const int n = p->num_steps * D;
   hipLaunchKernelGGL(invert_mask_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, p->masks,
@@ -417,6 +479,13 @@ static int prepare_ws(const l2hmc_gauge_plan* p, int64_t rows, const GaugeWs& w,
   if (hipMemsetAsync(w.ld_part, 0, sizeof(float) * (size_t)rows * gauge_ncb(p), stream) != hipSuccess) {
     set_error("hipMemsetAsync(ld_part) failed");
     return L2HMC_ERR_HIP;
+  }
+  if (plan_periodic(p)) {
+    const int n2 = 2 * n;
+    hipLaunchKernelGGL(double_mask_kernel, dim3((unsigned)ceil_div(n2, 256)), dim3(256), 0, stream, p->masks,
+                       p->num_steps, D, w.mask2, w.mask2_inv);
+    L2HMC_CHECK_LAUNCH("double_mask");
+    if (int e = launch_u1_angle_features(x, rows, D, w.feat, stream)) return e;
   }
   return L2HMC_OK;
 }
@@ -437,7 +506,7 @@ static int trajectory_inplace(const l2hmc_gauge_plan* p, RowBeta rbeta, float* x
   if (use_fused(p))
     return launch_fused_trajectory(p, beta, 0, p->num_steps, x, v, dir, rows, x, v, sumlogdet, 0, p_accept,
                                    stream);
-  if (int e = prepare_ws(p, rows, w, stream)) return e;
+  if (int e = prepare_ws(p, x, rows, w, stream)) return e;
   if (p_accept) {
     if (int e = launch_u1_action_force(x, rows, p->T, p->X, rbeta, w.act0, nullptr, nullptr, nullptr, stream))
       return e;
@@ -499,6 +568,18 @@ extern "C" int l2hmc_lf_update_x(const float* x, const float* v, const float* ke
   hipLaunchKernelGGL(lf_update_x_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream,
                      x, v, keep, keep, S, T, Q, eps, nullptr, dir, rows, D, x_out, logdet, 0);
   L2HMC_CHECK_LAUNCH("lf_update_x");
+  return L2HMC_OK;
+}
+
+extern "C" int l2hmc_lf_update_x_ncp(const float* x, const float* v, const float* keep, const float* S,
+                                     const float* T, const float* Q, float eps, int32_t dir, int64_t rows,
+                                     int32_t D, float* x_out, float* logdet, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(rows >= 0 && D > 0 && (dir == 0 || dir == 1), "lf_update_x_ncp: bad arguments");
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x && v && keep && x_out, "lf_update_x_ncp: NULL pointer");
+  hipLaunchKernelGGL(lf_update_x_ncp_kernel, dim3((unsigned)ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream,
+                     x, v, keep, S, T, Q, eps, dir, rows, D, x_out, logdet);
+  L2HMC_CHECK_LAUNCH("lf_update_x_ncp");
   return L2HMC_OK;
 }
 
@@ -648,7 +729,7 @@ extern "C" int l2hmc_gauge_leapfrog_steps(const l2hmc_gauge_plan* plan, float be
     return launch_hmc_trajectory(plan, beta, step_begin, step_end, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
   if (use_fused(plan))
     return launch_fused_trajectory(plan, beta, step_begin, step_end, x, v, dir, rows, x, v, logdet, 1, nullptr, s);
-  if (int e = prepare_ws(plan, rows, w, s)) return e;
+  if (int e = prepare_ws(plan, x, rows, w, s)) return e;
   for (int step = step_begin; step < step_end; ++step)
     if (int e = leapfrog_step(plan, beta, step, x, v, dir, rows, w, s, carry_possible(plan, x, v, w), false, false,
                               dir ? -1 : rows))

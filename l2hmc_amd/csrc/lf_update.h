@@ -59,6 +59,29 @@ __device__ __forceinline__ float lf_drift(float x, float v, float keep, float S,
   return keep * x + omk * upd;
 }
 
+// position sub-update of the torus-exact mode (L2HMC_PLAN_PERIODIC): the scaling x e^s of lf_drift becomes the map of
+// the circle onto itself  x -> 2 atan2(e^s sin(x / 2), cos(x / 2)),  whose derivative is e^s / r2 with
+// r2 = cos^2(x / 2) + e^{2s} sin^2(x / 2).  With w = x (dir 0) or x - drift (dir 1):
+//   y = 2 atan2(e^s sin(w / 2), cos(w / 2)) [+ drift, dir 0],   x' = keep x + (1 - keep) y   (principal value of atan2)
+// Returns x'; the element's log-det term is omk * s, where s here is +-eps S - log r2 (the same site statement as
+// lf_drift's).  sin, cos, atan2 and log are libm's in every site: only the exponentials follow Exp.
+template <class Exp>
+__device__ __forceinline__ float lf_drift_ncp(float x, float v, float keep, float S, float T, float Q, float eps, int d,
+                                              float& s, float& omk) {
+  const float se = (d ? -eps : eps) * S;
+  const float drift = eps * (Exp::f(eps * Q) * v + T);
+  const float es = Exp::f(se);
+  const float w = d ? x - drift : x;
+  float sh, ch;
+  sincosf(0.5f * w, &sh, &ch);
+  const float a = es * sh;
+  const float y = 2.f * atan2f(a, ch);
+  const float upd = d ? y : y + drift;
+  s = se - logf(ch * ch + a * a);
+  omk = 1.f - keep;
+  return keep * x + omk * upd;
+}
+
 // reverse of lf_kick<ExpLibm>: u = d/dv', dl = d/dlogdet -> cotangents of v, g, S, T, Q; deps += d/deps
 __device__ __forceinline__ void lf_kick_vjp(float v, float g, float S, float T, float Q, float eps, int d, float u,
                                             float dl, float& dv, float& dg, float& dS, float& dT, float& dQ,
@@ -105,6 +128,33 @@ __device__ __forceinline__ void lf_drift_vjp(float x, float v, float keep, float
     const float dw = dy * es;
     const float ds = dy * (es * w) + dl * mi;
     dx = keep * u + dw;
+    dS = -eps * ds; dT = -dw * eps; dQ = -dw * eps * eq * v * eps;
+    deps += -S * ds - dw * (eq * v + T) - dw * eps * v * eq * Q;
+  }
+}
+
+// reverse of lf_drift_ncp<ExpLibm>, with lf_drift_vjp's conventions (the cotangent of v is dT * eq).  With h = w / 2,
+// a = e^s sin h, c = cos h, r2 = c^2 + a^2:  dy/dw = e^s / r2,  dy/ds = 2 a c / r2,  and for the log-det term
+// L = s - log r2:  dL/dw = -sin h cos h (e^{2s} - 1) / r2,  dL/ds = 1 - 2 a^2 / r2
+__device__ __forceinline__ void lf_drift_ncp_vjp(float x, float v, float keep, float S, float T, float Q, float eps,
+                                                 int d, float u, float dl, float& dx, float& dS, float& dT, float& dQ,
+                                                 float& eq, float& deps) {
+  const float mi = 1.f - keep;
+  eq = expf(eps * Q);
+  const float es = expf((d ? -eps : eps) * S);
+  const float w = d ? x - eps * (eq * v + T) : x;
+  float sh, ch;
+  sincosf(0.5f * w, &sh, &ch);
+  const float a = es * sh;
+  const float ir = 1.f / (ch * ch + a * a);
+  const float dy = mi * u, dL = dl * mi;
+  const float dw = dy * es * ir - dL * sh * ch * (es * es - 1.f) * ir;
+  const float ds = dy * 2.f * a * ch * ir + dL * (1.f - 2.f * a * a * ir);
+  dx = keep * u + dw;
+  if (!d) {
+    dS = eps * ds; dT = dy * eps; dQ = dy * eps * eq * v * eps;
+    deps += ds * S + dy * (eq * v + T) + dy * eps * v * eq * Q;
+  } else {
     dS = -eps * ds; dT = -dw * eps; dQ = -dw * eps * eq * v * eps;
     deps += -S * ds - dw * (eq * v + T) - dw * eps * v * eq * Q;
   }

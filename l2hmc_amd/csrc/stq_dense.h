@@ -61,6 +61,7 @@ struct HeadsArgs {
   // cols_f / cols_b: ascending column lists for forward / backward rows, *cnt_f / *cnt_b their lengths (device
   // memory, written by active_cols_kernel); rows >= dir_split are the backward ones (a multiple of the row tile).
   const int* cols_f; const int* cols_b; const int* cnt_f; const int* cnt_b; int64_t dir_split;
+  int ncp;                               // mode 2: 1 = the circle-preserving position update (lf_drift_ncp: periodic plans)
 };
 
 // In-kernel cycle stamps (cdna_hip_programming.md section 7): compiled in only with
@@ -236,6 +237,8 @@ struct RowBeta {
 };
 int launch_u1_action_force(const float* x, int64_t rows, int T, int X, RowBeta beta, float* action,
                            float* force, float* avg_plaq, float* top_charge, hipStream_t stream);
+// out [rows][2D] = [cos x | sin x] (u1_lattice.hip): the network input of periodic plans
+int launch_u1_angle_features(const float* x, int64_t rows, int D, float* out, hipStream_t stream);
 // l2hmc_gauge_transition with the beta of every row (leapfrog.hip): the plan is checked as every public entry of the
 // layer-by-layer path checks it (gauge_check_plan: L2HMC_ERR_ARG before any device call), pointers and B > 0 are the
 // caller's; `who` words the workspace message

@@ -475,7 +475,10 @@ __device__ __forceinline__ float heads_element(const HeadsArgs& p, const HeadsCo
     return s;
   }
   // gauge_dynamics.py:519-531 (fwd), :574-584 (bwd)
-  p.x[idx] = lf_drift<ExpFast>(p.x[idx], p.v[idx], d ? c.kb : c.kf, S, T, Q, p.eps, d, s, omk);
+  if (p.ncp)
+    p.x[idx] = lf_drift_ncp<ExpFast>(p.x[idx], p.v[idx], d ? c.kb : c.kf, S, T, Q, p.eps, d, s, omk);
+  else
+    p.x[idx] = lf_drift<ExpFast>(p.x[idx], p.v[idx], d ? c.kb : c.kf, S, T, Q, p.eps, d, s, omk);
   return omk * s;
 }
 

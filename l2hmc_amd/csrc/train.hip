@@ -941,6 +941,9 @@ static int check_train_plan(const l2hmc_gauge_plan* p) {
   L2HMC_REQUIRE(p != nullptr, "train: NULL plan");
   L2HMC_REQUIRE(p->T > 0 && p->X > 0 && p->num_steps > 0 && p->masks != nullptr, "train: bad plan");
   L2HMC_REQUIRE(!p->hmc, "train: hmc plans have no trainable networks");
+  L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC),
+                "train: L2HMC_PLAN_PERIODIC plans train through the layered-training entries (l2hmc_stq_dense_taped, "
+                "l2hmc_lf_update_x_ncp_vjp, l2hmc_u1_angle_features_vjp); the tiled entries have no such form");
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
   const int D = 2 * p->T * p->X;
   const l2hmc_dense_net* nets[2] = {&p->xnet, &p->vnet};

@@ -350,9 +350,107 @@ int launch_u1_action_force(const float* x, int64_t rows, int T, int X, RowBeta b
   return L2HMC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Angle features of the torus-exact mode: out[r] = [cos x[r] | sin x[r]] ([rows][2D]), the only form in which a periodic
+// plan's networks see a link angle, and the reverse, dx[r][c] += -sin x dcos + cos x dsin.  One thread per four
+// consecutive columns of a row; VEC: 16-byte loads and stores (D and the row strides multiples of 4, bases aligned).
+template <bool VEC>
+__global__ __launch_bounds__(256) void u1_angle_features_kernel(const float* __restrict__ x, int64_t rows, int D,
+                                                                float* __restrict__ out) {
+  const int q = (D + 3) / 4;
+  const int64_t n = rows * q;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / q;
+    const int c = (int)(i - r * q) * 4;
+    const float* xi = x + r * D + c;
+    float* oc = out + r * 2 * D + c;
+    if (VEC) {
+      const float4 xv = *reinterpret_cast<const float4*>(xi);
+      float4 cv, sv;
+      sincosf(xv.x, &sv.x, &cv.x); sincosf(xv.y, &sv.y, &cv.y);
+      sincosf(xv.z, &sv.z, &cv.z); sincosf(xv.w, &sv.w, &cv.w);
+      *reinterpret_cast<float4*>(oc) = cv;
+      *reinterpret_cast<float4*>(oc + D) = sv;
+    } else {
+      for (int e = 0; e < 4 && c + e < D; ++e) sincosf(xi[e], &oc[D + e], &oc[e]);
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void u1_angle_features_vjp_kernel(const float* __restrict__ x,
+                                                                    const float* __restrict__ dfeat, int64_t ldf,
+                                                                    int64_t rows, int D, float* __restrict__ dx) {
+  const int q = (D + 3) / 4;
+  const int64_t n = rows * q;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / q;
+    const int c = (int)(i - r * q) * 4;
+    const float* xi = x + r * D + c;
+    const float* dc = dfeat + r * ldf + c;
+    float* di = dx + r * D + c;
+    if (VEC) {
+      const float4 xv = *reinterpret_cast<const float4*>(xi);
+      const float4 gc = *reinterpret_cast<const float4*>(dc), gs = *reinterpret_cast<const float4*>(dc + D);
+      float4 o = *reinterpret_cast<const float4*>(di);
+      float s, co;
+      sincosf(xv.x, &s, &co); o.x += co * gs.x - s * gc.x;
+      sincosf(xv.y, &s, &co); o.y += co * gs.y - s * gc.y;
+      sincosf(xv.z, &s, &co); o.z += co * gs.z - s * gc.z;
+      sincosf(xv.w, &s, &co); o.w += co * gs.w - s * gc.w;
+      *reinterpret_cast<float4*>(di) = o;
+    } else {
+      for (int e = 0; e < 4 && c + e < D; ++e) {
+        float s, co;
+        sincosf(xi[e], &s, &co);
+        di[e] += co * dc[D + e] - s * dc[e];
+      }
+    }
+  }
+}
+
+int launch_u1_angle_features(const float* x, int64_t rows, int D, float* out, hipStream_t stream) {
+  const int64_t n = rows * ((D + 3) / 4);
+  const unsigned grid = (unsigned)hmin(ceil_div(n, 256), 4096);
+  const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(u1_angle_features_kernel<true>, dim3(grid), dim3(256), 0, stream, x, rows, D, out);
+  else
+    hipLaunchKernelGGL(u1_angle_features_kernel<false>, dim3(grid), dim3(256), 0, stream, x, rows, D, out);
+  L2HMC_CHECK_LAUNCH("u1_angle_features");
+  return L2HMC_OK;
+}
+
 }  // namespace l2hmc
 
 using namespace l2hmc;
+
+extern "C" int l2hmc_u1_angle_features(const float* x, int64_t rows, int32_t D, float* out, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(rows >= 0 && D > 0, "u1_angle_features: bad shape rows=%lld D=%d", (long long)rows, D);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x && out, "u1_angle_features: NULL pointer");
+  return launch_u1_angle_features(x, rows, D, out, (hipStream_t)stream);
+}
+
+extern "C" int l2hmc_u1_angle_features_vjp(const float* x, const float* dfeat, int64_t ldf, int64_t rows, int32_t D,
+                                           float* dx, l2hmc_stream_t stream) {
+  L2HMC_REQUIRE(rows >= 0 && D > 0 && ldf >= 2 * (int64_t)D, "u1_angle_features_vjp: bad shape rows=%lld D=%d ldf=%lld",
+                (long long)rows, D, (long long)ldf);
+  if (rows == 0) return L2HMC_OK;
+  L2HMC_REQUIRE(x && dfeat && dx, "u1_angle_features_vjp: NULL pointer");
+  const int64_t n = rows * ((D + 3) / 4);
+  const unsigned grid = (unsigned)hmin(ceil_div(n, 256), 4096);
+  const bool vec = D % 4 == 0 && ldf % 4 == 0 &&
+                   ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dfeat) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(u1_angle_features_vjp_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, dfeat, ldf,
+                       rows, D, dx);
+  else
+    hipLaunchKernelGGL(u1_angle_features_vjp_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, dfeat,
+                       ldf, rows, D, dx);
+  L2HMC_CHECK_LAUNCH("u1_angle_features_vjp");
+  return L2HMC_OK;
+}
 
 extern "C" int l2hmc_u1_action_force(const float* x, int64_t rows, int32_t T, int32_t X, float beta,
                                      float* action, float* force, float* avg_plaq, float* top_charge,

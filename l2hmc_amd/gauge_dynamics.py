@@ -15,7 +15,7 @@ import numpy as np
 import numpy.random as npr
 import torch
 
-from . import _lib, _runs, ops
+from . import _lib, _runs, ops, ops_periodic
 from . import autograd as _autograd
 from .network import ConvNet3D, GenericNet
 
@@ -40,9 +40,18 @@ class GaugeDynamics:
         self.all_columns = False         # True: layer-by-layer path forms S/T/Q for every column of a position sub-update
         self.full_l1 = False             # True: whole-step kernel forms XNet's first-layer x product over all D columns (A/B)
         self.single_kicks = False        # True: whole-step kernel runs every momentum half-kick as a network call of its own (A/B)
+        # True: the torus-exact mode (no reference counterpart).  The networks read every link angle as
+        # [cos x | sin x] and the position sub-update scales on the circle (ops_periodic.lf_update_x_ncp), so the
+        # proposal commutes with 2 pi shifts of any link and Metropolis-Hastings makes the wrapped chain exact for any
+        # weights.  GenericNet only; runs layer by layer; with hmc=True there are no networks and nothing changes.
+        self.periodic = False
         for key, val in kwargs.items():
             if key != 'eps':             # :73-75
                 setattr(self, key, val)
+        self.periodic = bool(self.periodic)
+        if self.periodic and not self.hmc and self.network_arch == 'conv3D':
+            raise NotImplementedError("periodic=True takes network_arch='generic' only: ConvNet3D has no front-end "
+                                      "over [cos x | sin x]")
         self._device = kwargs.get('device') or torch.device("cuda", torch.cuda.current_device())
         if getattr(potential_fn, "u1_lattice", None) is None:
             raise NotImplementedError(
@@ -72,9 +81,13 @@ class GaugeDynamics:
         """:169-187."""
         kwargs = {'x_dim': self.x_dim, 'links_shape': self.lattice.links.shape,
                   'num_hidden': int(4 * self.x_dim), 'name_scope': 'position', 'factor': 2.}
+        if self.periodic:                # XNet([v, m . x, t]): x is the second input; VNet([x, force, t]): the first
+            kwargs['angle_input'] = 'second'
         self.position_fn = GenericNet(model_name='XNet', device=self._device, **kwargs)
         kwargs['factor'] = 1.
         kwargs['name_scope'] = 'momentum'
+        if self.periodic:
+            kwargs['angle_input'] = 'first'
         self.momentum_fn = GenericNet(model_name='VNet', device=self._device, **kwargs)
 
     def _build_conv_nets_3D(self):
@@ -142,7 +155,8 @@ class GaugeDynamics:
                            | (_lib.PLAN_TILES16_ONLY if self.tiles16_only else 0)
                            | (_lib.PLAN_ALL_COLUMNS if self.all_columns else 0)
                            | (_lib.PLAN_FULL_L1 if self.full_l1 else 0)
-                           | (_lib.PLAN_SINGLE_KICKS if self.single_kicks else 0),
+                           | (_lib.PLAN_SINGLE_KICKS if self.single_kicks else 0)
+                           | (_lib.PLAN_PERIODIC if self.periodic and not self.hmc else 0),
                            masks=_lib.dev_ptr(self.mask, name="mask"))
         if not self.hmc:
             p.xnet = self.position_fn.pack()
@@ -314,7 +328,7 @@ class GaugeDynamics:
     def _update_momentum(self, position, momentum, beta, t, backward):
         x, v = self._x(position), self._x(momentum)
         grad = self.grad_potential(x, beta)
-        S, T, Q = self._stq(self.momentum_fn, x, grad, t)           # :493-495
+        S, T, Q = self._stq(self.momentum_fn, self._net_x(x), grad, t)           # :493-495
         return ops.lf_update_v(v, grad, self._x(S), self._x(T), self._x(Q), self.eps, backward)
 
     def _update_momentum_forward(self, position, momentum, beta, t):
@@ -328,8 +342,15 @@ class GaugeDynamics:
     def _update_position(self, position, momentum, t, mask, mask_inv, backward):
         x, v = self._x(position), self._x(momentum)
         keep = _lib.as_dev(mask, self._device).reshape(-1)
+        if self.periodic and not self.hmc:
+            S, T, Q = self._stq(self.position_fn, v, keep.repeat(2)[None, :] * self._net_x(x), t)
+            return ops_periodic.lf_update_x_ncp(x, v, keep, self._x(S), self._x(T), self._x(Q), self.eps, backward)
         S, T, Q = self._stq(self.position_fn, v, keep[None, :] * x, t)   # :515-517
         return ops.lf_update_x(x, v, keep, self._x(S), self._x(T), self._x(Q), self.eps, backward)
+
+    def _net_x(self, x):
+        """A configuration as the networks read it: x itself, or [cos x | sin x] on a periodic dynamics."""
+        return ops_periodic.u1_angle_features(x) if self.periodic and not self.hmc else x
 
     def _update_position_forward(self, position, momentum, t, mask, mask_inv):
         """:511-534."""

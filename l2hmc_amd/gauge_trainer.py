@@ -248,6 +248,11 @@ class GaugeTrainer(FlatTrainer):
         return loss, x_out, px, x_dq
 
     def _use_layered(self):
+        if getattr(self.dynamics, "periodic", False):      # the tiled entries have no torus-exact form
+            if self.layered is not None and not self.layered:
+                raise NotImplementedError("GaugeTrainer.layered = False on a periodic=True dynamics: the tiled "
+                                          "training entries refuse L2HMC_PLAN_PERIODIC plans; the layered walk trains them")
+            return True
         if self.layered is not None:
             use = bool(self.layered)
         else:
@@ -279,7 +284,8 @@ class GaugeTrainer(FlatTrainer):
         return _layered_train.Walk(dyn.position_fn, dyn.momentum_fn, dyn.eps, dyn.num_steps, dyn._format_time,
                                    dyn._get_mask_while,
                                    lambda x: ops.u1_action_force(x, T, X, beta, want_observables=False)[1],
-                                   lambda x, u: ops.u1_force_hvp(x, u, T, X, beta), row_scale=row_betas)
+                                   lambda x, u: ops.u1_force_hvp(x, u, T, X, beta), row_scale=row_betas,
+                                   periodic=getattr(dyn, "periodic", False))
 
     def _chain_betas(self, beta, B, who):
         """None for one beta (a number or a 0-d array / tensor: the scalar entries, untouched); else the ladder as a

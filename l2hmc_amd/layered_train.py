@@ -32,7 +32,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ops_periodic
 
 
 class _NetTape:
@@ -89,12 +89,15 @@ class Walk:
     (toy targets: grad E / temperature and energy_hvp; the lattice: beta * force and ops.u1_force_hvp).
     `row_scale` ([R] device tensor over the stacked rows, or None): a factor per row on `grad` and `hvp` -- the
     lattice's beta on a ladder, where `grad` and `hvp` are those of beta = 1, and the toy targets' 1 / temperature,
-    where they are those of temperature 1."""
+    where they are those of temperature 1.
+    `periodic`: the torus-exact lattice mode (GaugeDynamics(periodic=True)) -- x reaches the networks as
+    [cos x | sin x] (VNet's first input, XNet's masked second one), the position sub-update is
+    ops_periodic.lf_update_x_ncp, and the reverse walk carries the features' cotangents back into dx."""
 
-    def __init__(self, xnet, vnet, eps, num_steps, format_time, masks, grad, hvp, row_scale=None):
+    def __init__(self, xnet, vnet, eps, num_steps, format_time, masks, grad, hvp, row_scale=None, periodic=False):
         self.xnet, self.vnet, self.eps, self.num_steps = xnet, vnet, float(eps), int(num_steps)
         self.format_time, self.masks, self.grad, self.hvp = format_time, masks, grad, hvp
-        self.row_scale = row_scale
+        self.row_scale, self.periodic = row_scale, bool(periodic)
 
     def time(self, step):
         t = self.format_time(step)
@@ -107,7 +110,7 @@ class Walk:
             return self
         s = self.row_scale[idx][:, None]
         return Walk(self.xnet, self.vnet, self.eps, self.num_steps, self.format_time, self.masks,
-                    lambda x: self.grad(x) * s, lambda x, u: self.hvp(x, u) * s)
+                    lambda x: self.grad(x) * s, lambda x, u: self.hvp(x, u) * s, periodic=self.periodic)
 
 
 # What LayeredWalk.forward hands to LayeredWalk.backward: the Walk, both tapes, per direction run (d, row indices,
@@ -135,11 +138,13 @@ class LayeredWalk:
         n, D = x.shape
         g = w.grad(x)
         sl = tape.take(n)
-        tape.inp[sl, :D] = x
-        tape.inp[sl, D:] = g
+        a = ops_periodic.u1_angle_features(x) if w.periodic else x
+        Ka = a.shape[1]
+        tape.inp[sl, :Ka] = a
+        tape.inp[sl, Ka:] = g
         tape.tcs[sl, 0], tape.tcs[sl, 1] = tc, ts
         S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
-        _lib.call("l2hmc_stq_dense_taped", C.byref(w.vnet.pack()), x, g, None, tc, ts, n, S, T, Q, tape.h1[sl],
+        _lib.call("l2hmc_stq_dense_taped", C.byref(w.vnet.pack()), a, g, None, tc, ts, n, S, T, Q, tape.h1[sl],
                   tape.h2[sl], device=self.device)
         out, ld = ops.lf_update_v(v, g, S, T, Q, w.eps, d)
         lj += ld
@@ -148,7 +153,7 @@ class LayeredWalk:
 
     def _sub_x(self, w, x, v, keep, tc, ts, d, lj, tape, subs):
         n, D = x.shape
-        b = keep * x
+        b = keep.repeat(2) * ops_periodic.u1_angle_features(x) if w.periodic else keep * x
         sl = tape.take(n)
         tape.inp[sl, :D] = v
         tape.inp[sl, D:] = b
@@ -156,7 +161,7 @@ class LayeredWalk:
         S, T, Q = tape.S[sl], tape.T[sl], tape.Q[sl]
         _lib.call("l2hmc_stq_dense_taped", C.byref(w.xnet.pack()), v, b, None, tc, ts, n, S, T, Q, tape.h1[sl],
                   tape.h2[sl], device=self.device)
-        out, ld = ops.lf_update_x(x, v, keep, S, T, Q, w.eps, d)
+        out, ld = (ops_periodic.lf_update_x_ncp if w.periodic else ops.lf_update_x)(x, v, keep, S, T, Q, w.eps, d)
         lj += ld
         subs.append(("x", sl, x, v, None, keep))
         return out
@@ -226,14 +231,21 @@ class LayeredWalk:
                 _lib.call("l2hmc_lf_update_v_vjp", vin, g, S, T, Q, eps, d, n, D, dv, dld, dv_in, dg, dS, dT, dQ, de,
                           device=self.device)
                 din = self._backward_data(w.vnet, tape, sl, dS, dT, dQ)
-                dx = dx + din[:, :D] + w.hvp(xin, (dg + din[:, D:]).contiguous())
+                if w.periodic:       # VNet read [cos x | sin x] (2 D wide) and the force
+                    dx = (dx + w.hvp(xin, (dg + din[:, 2 * D:]).contiguous())).contiguous()
+                    ops_periodic.u1_angle_features_vjp(xin, din[:, :2 * D].contiguous(), dx)
+                else:
+                    dx = dx + din[:, :D] + w.hvp(xin, (dg + din[:, D:]).contiguous())
                 dv = dv_in
             else:
                 dx_in, dv_part = torch.empty_like(dx), torch.empty_like(dx)
-                _lib.call("l2hmc_lf_update_x_vjp", xin, vin, keep, S, T, Q, eps, d, n, D, dx, dld, dx_in, dv_part, dS,
-                          dT, dQ, de, device=self.device)
+                _lib.call("l2hmc_lf_update_x_ncp_vjp" if w.periodic else "l2hmc_lf_update_x_vjp", xin, vin, keep, S, T,
+                          Q, eps, d, n, D, dx, dld, dx_in, dv_part, dS, dT, dQ, de, device=self.device)
                 din = self._backward_data(w.xnet, tape, sl, dS, dT, dQ)
-                dx = (dx_in + keep * din[:, D:]).contiguous()
+                if w.periodic:       # XNet read keep . [cos x | sin x]
+                    dx = ops_periodic.u1_angle_features_vjp(xin, (keep.repeat(2) * din[:, D:]).contiguous(), dx_in)
+                else:
+                    dx = (dx_in + keep * din[:, D:]).contiguous()
                 dv = (dv + dv_part + din[:, :D]).contiguous()
             dx, dv = dx.contiguous(), dv.contiguous()
             parts.append(de)

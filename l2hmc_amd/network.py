@@ -81,7 +81,12 @@ class _DenseSTQ:
             W = _lib.as_dev(state[n + "/W"], dev)
             b = _lib.as_dev(state[n + "/b"], dev)
             if W.shape != layer.kernel.shape or b.shape != layer.bias.shape:
-                raise ValueError(f"{n}: shape {tuple(W.shape)} != {tuple(layer.kernel.shape)}")
+                hint = ""
+                if W.dim() == 2 and W.shape[1:] == layer.kernel.shape[1:] and \
+                        (W.shape[0] == 2 * layer.kernel.shape[0] or 2 * W.shape[0] == layer.kernel.shape[0]):
+                    hint = (": the state is of the other `periodic` mode (a periodic net reads x as [cos x | sin x], "
+                            "twice as wide)")
+                raise ValueError(f"{n}: shape {tuple(W.shape)} != {tuple(layer.kernel.shape)}{hint}")
             layer.kernel, layer.bias = W, b
         for n in self._coeff_names:
             c = _lib.as_dev(state[n], dev).reshape(1, -1)
@@ -276,9 +281,15 @@ class GenericNet(_DenseSTQ):
             self.name_scope = model_name
         self._device = device or torch.device("cuda", torch.cuda.current_device())
         dev, D, H = self._device, int(self.x_dim), int(self.num_hidden)
+        # angle_input (GaugeDynamics(periodic=True)): which network input is a link configuration and arrives as
+        # [cos x | sin x], 2 D wide -- 'second' (XNet: x_layer reads the masked x) or 'first' (VNet: the reference's
+        # VNet is called on (x, force), so ITS v_layer reads x); None = the reference's D-wide layers
+        angle = getattr(self, "angle_input", None)
+        if angle not in (None, 'first', 'second'):
+            raise ValueError(f"angle_input: expected None, 'first' or 'second', got {angle!r}")
         # creation order follows generic_net.py:39-90 (it fixes the RNG stream order)
-        self.x_layer = Dense(D, H, self.factor / 3., 'x_layer', rng, dev)
-        self.v_layer = Dense(D, H, 1. / 3., 'v_layer', rng, dev)
+        self.x_layer = Dense(2 * D if angle == 'second' else D, H, self.factor / 3., 'x_layer', rng, dev)
+        self.v_layer = Dense(2 * D if angle == 'first' else D, H, 1. / 3., 'v_layer', rng, dev)
         self.t_layer = Dense(2, H, 1. / 3., 't_layer', rng, dev)
         self.h_layer = Dense(H, H, 1., 'h_layer', rng, dev)
         self.scale_layer = Dense(H, D, 0.001, 'scale_layer', rng, dev)

@@ -8,6 +8,18 @@ import torch
 from . import _lib
 
 
+def check_draws(draws, B, D, name, who):
+    """A trainer's `draws_x` / `draws_z` (None: not injected): exactly four tensors, [B, D], [B, D], (B,), (B,) --
+    momentum forward, momentum backward, coin or direction bit, u.  ValueError on the host, before any draw."""
+    if draws is None:
+        return
+    if len(draws) != 4:
+        raise ValueError(f"{who}: {name} of {len(draws)} tensors: expected 4 (momentum forward, momentum backward, "
+                         "coin or direction bit, u)")
+    for i, (t, shape) in enumerate(zip(draws, ((B, D), (B, D), (B,), (B,)))):
+        _lib.expect_shape(t, shape, f"{name}[{i}]", who)
+
+
 def stack_chains(x, z, draws_x, draws_z):
     """The x and z chains as one batch of 2B rows, from the (momentum_f, momentum_b, coin / direction bit, u) draws
     of each: -> (x0, v0, fwd [2B] bool, dirs [2B] int32 (1 = backward), u of the x chains).  A chain starts from the

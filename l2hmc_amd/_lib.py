@@ -7,6 +7,7 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -256,6 +257,35 @@ def dev_ptr(t, dtype=torch.float32, name="tensor"):
     if not t.is_contiguous():
         raise ValueError(f"{name}: tensor must be contiguous")
     return t.data_ptr()
+
+
+def _shape_text(shape):
+    return "(" + ", ".join("*" if s is None else str(s) for s in shape) + ("," if len(shape) == 1 else "") + ")"
+
+
+def expect_shape(t, shape, name, who=None, fold=False):
+    """Refuse a caller tensor `t` (tensor, array or nested list; None passes: an optional argument that was left out)
+    whose shape is not `shape`, a tuple in which None matches any extent.  `fold`: `shape` is [rows, width] and any
+    [rows, ...] whose trailing extents multiply to width matches too (a position given as [B, T, X, 2]).  The C ABI
+    takes raw pointers and sizes its launches from one argument, so this is what keeps a kernel from reading past the
+    end of another.  Host arithmetic on shape tuples only: no torch.cuda call, no synchronisation, no allocation.
+    ValueError: `name: expected shape (..), got (..)` for the stateless operators, `who: name of shape (..): expected
+    (..)` for a method `who`.  Returns t."""
+    if t is None:
+        return t
+    got = tuple(t.shape) if hasattr(t, "shape") else np.shape(t)
+    seen = got
+    if fold and len(got) > 2:
+        width = 1
+        for n in got[1:]:
+            width *= n
+        seen = (got[0], width)
+    if len(seen) != len(shape) or any(e is not None and e != g for e, g in zip(shape, seen)):
+        if who is None:
+            raise ValueError(f"{name}: expected shape {_shape_text(shape)}, got {_shape_text(got)}")
+        raise ValueError(f"{who}: {name} of shape {_shape_text(got)}: expected {_shape_text(shape)}"
+                         + (" (or any trailing extents with that product)" if fold else ""))
+    return t
 
 
 def stream_ptr(device=None):

@@ -52,6 +52,15 @@ def rows_from(flat_dev, strides):
     return lambda s0: (flat_dev[s0 * step_stride:], step_stride, chain_stride)
 
 
+def position(x, x_dim, device, who, name="x", rows=None):
+    """The samplers' gate for a caller's state (GaugeDynamics._x's rule) -> a float32 device tensor [B, x_dim]: [B, x_dim]
+    passes, and so does any [B, ...] whose trailing extents multiply to x_dim; `rows`: the B it must have.  ValueError
+    (`_lib.expect_shape`) otherwise, on the host, before the value is copied, a draw is taken or a plan is built."""
+    _lib.expect_shape(x, (rows, x_dim), name, who, fold=True)
+    x = _lib.as_dev(x, device)
+    return x if x.ndim == 2 else x.reshape(x.shape[0], -1)
+
+
 def per_chain(value, B, device, *, who, name, scalar=None, sign=None, hint=""):
     """One value per chain (`step`'s and `swap_replicas`' beta or temperature) -> (float32 device tensor, chain_stride):
     [B] or [1, B] -> ([B], 1); one value -> ([1], 0) where `scalar` (the word the message has for it) is given.  A

@@ -61,9 +61,19 @@ def check_differentiable(dyn):
                              "multiples of 32 (a T x X lattice has D = 2*T*X)")
 
 
+def check_draws(dyn, B, momentum_f=None, momentum_b=None, coin=None, u=None, who="GaugeDynamics.apply_transition"):
+    """Refuse injected draws that do not fit B chains (None: not injected): the momenta go through the dynamics'
+    position gate with the position's rows, coin and u are (B,).  Shapes only, on the host, before any draw."""
+    for name, v in (("momentum_f", momentum_f), ("momentum_b", momentum_b)):
+        _lib.expect_shape(v, (B, dyn.x_dim), name, who, fold=True)
+    for name, c in (("coin", coin), ("u", u)):
+        _lib.expect_shape(c, (B,), name, who)
+
+
 def draws(dyn, B, D, dev, momentum_f=None, momentum_b=None, coin=None, u=None):
     """(v0_f, v0_b, coin, u) of a transition: the library's own where none is injected, else the injected ones and
     single streams of the counter for the rest."""
+    check_draws(dyn, B, momentum_f, momentum_b, coin, u)
     if momentum_f is None and momentum_b is None and coin is None and u is None:
         # the draws of l2hmc_gauge_transition_draw: (seed, 2d) = [v0_f; v0_b], (seed, 2d+1) = coin | u
         d, dyn._draws = _lib.step_draw_index(dyn._draws)

@@ -150,7 +150,10 @@ class Dynamics(object):
     def energy(self, x, aux=None):
         """:227-236."""
         if self._target is None:
-            return self._fn(_lib.as_dev(x, self._device).reshape(-1, self.x_dim)) / self._temp()
+            x = _lib.as_dev(x, self._device).reshape(-1, self.x_dim)
+            e = _lib.expect_shape(self._fn(x), (x.shape[0],), "energy_function(x)", "Dynamics.energy")
+            # (one contiguous float32 per row, whatever the callable returned: p_accept hands its address to a kernel)
+            return e.to(torch.float32).contiguous() / self._temp()
         return self._target.energy_grad(x, self._temp(), want_grad=False)[0]
 
     def hamiltonian(self, x, v, aux=None):
@@ -162,11 +165,9 @@ class Dynamics(object):
         if self._target is None:
             with torch.enable_grad():
                 xg = _lib.as_dev(x, self._device).reshape(-1, self.x_dim).detach().clone().requires_grad_(True)
-                e = self._fn(xg)
-                if e.shape != (xg.shape[0],):
-                    raise ValueError(f"energy_function must return one energy per row: got {tuple(e.shape)}")
+                e = _lib.expect_shape(self._fn(xg), (xg.shape[0],), "energy_function(x)", "Dynamics.grad_energy")
                 (g,) = torch.autograd.grad(e.sum(), xg)
-            return (g / self._temp()).contiguous()
+            return (g / self._temp()).to(torch.float32).contiguous()
         return self._target.energy_grad(x, self._temp())[1]
 
     # ---- layer-by-layer path (utils/dynamics.py:120-225 sub-update by sub-update) ------------------------------------
@@ -230,7 +231,9 @@ class Dynamics(object):
 
     def _run(self, x, init_v, backward, log_jac, temperature=None):
         x = _lib.as_dev(x, self._device).reshape(-1, self.x_dim)
-        temp = self._call_temperature(temperature, x.shape[0], "Dynamics.backward" if backward else "Dynamics.forward")
+        who = "Dynamics.backward" if backward else "Dynamics.forward"
+        temp = self._call_temperature(temperature, x.shape[0], who)
+        _lib.expect_shape(init_v, tuple(x.shape), "init_v", who)
         if _autograd.wants_grad(self, x, init_v):
             _autograd.check_differentiable(self)          # before any draw
             v = _lib.as_dev(init_v, self._device) if init_v is not None else self._normal(tuple(x.shape))
@@ -265,6 +268,8 @@ class Dynamics(object):
         x = _lib.as_dev(x, self._device).reshape(-1, self.x_dim)
         B = x.shape[0]
         temp = self._call_temperature(temperature, B, "Dynamics.both")
+        for name, v in (("init_v_forward", init_v_forward), ("init_v_backward", init_v_backward)):     # before any draw
+            _lib.expect_shape(v, tuple(x.shape), name, "Dynamics.both")
         vf = _lib.as_dev(init_v_forward, self._device) if init_v_forward is not None else self._normal(tuple(x.shape))
         vb = _lib.as_dev(init_v_backward, self._device) if init_v_backward is not None else self._normal(tuple(x.shape))
         if self.layered:
@@ -303,5 +308,10 @@ class Dynamics(object):
 
     def p_accept(self, x0, v0, x1, v1, log_jac, aux=None):
         """:312-319."""
+        who = "Dynamics.p_accept"
+        x0 = _lib.as_dev(x0, self._device).reshape(-1, self.x_dim)
+        for name, t in (("v0", v0), ("x1", x1), ("v1", v1)):
+            _lib.expect_shape(t, tuple(x0.shape), name, who)
+        _lib.expect_shape(log_jac, (x0.shape[0],), "log_jac", who)
         e_new, e_old = self.hamiltonian(x1, v1), self.hamiltonian(x0, v0)
         return ops.accept_prob(e_old, e_new, _lib.as_dev(log_jac, self._device))

@@ -94,7 +94,7 @@ class DynamicsSampler:
             if self.batch_size is None:
                 raise ValueError(f"{who}: pass the start `x`, or give the sampler a batch_size to start from N(0, 1)")
             x = np.random.randn(int(self.batch_size), dyn.x_dim)
-        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        x = _runs.position(x, dyn.x_dim, dyn._device, f"DynamicsSampler.{who}")
         temps = None if temperature is None else self._temperatures(temperature, run_steps, x.shape[0])
         return run_steps, x, temps
 
@@ -273,7 +273,7 @@ class DynamicsSampler:
                 raise ValueError(f"{who}: refresh={refresh}: expected None (fresh momenta) or a number in (0, 1]")
         if x is None:
             raise ValueError(f"{who}: pass the start `x` [B, {dyn.x_dim}], drawn from init")
-        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        x = _runs.position(x, dyn.x_dim, dyn._device, "DynamicsSampler.ais")
         B, dev = x.shape[0], x.device
         plan = dyn._plan()
         init_target = init.get_energy_function().target.to(dev)      # (kept alive until the last launch returned)
@@ -395,8 +395,9 @@ class DynamicsSampler:
         dyn = self.dynamics
         if dyn.layered:
             raise NotImplementedError(LAYERED_SWAP_MESSAGE)
-        if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[1] != dyn.x_dim:
+        if not isinstance(x, torch.Tensor):
             raise ValueError(f"swap_replicas: x: expected a device tensor [B, {dyn.x_dim}] (exchanged in place)")
+        _lib.expect_shape(x, (None, dyn.x_dim), "x", "DynamicsSampler.swap_replicas")     # (in place: no other form)
         B = x.shape[0]
         G, _, _, parity = _runs.check_replicas(replicas, B, parity=parity, who="swap_replicas", most=self.MAX_REPLICAS)
         replica = getattr(self, "replica", None)
@@ -495,7 +496,7 @@ class DynamicsSampler:
             if self.distribution is None:
                 raise ValueError("generate_trajectories: pass the start `x`, or give the sampler a distribution")
             x = self.distribution.get_samples(int(num_samples))
-        x = _lib.as_dev(x, dyn._device).reshape(-1, dyn.x_dim)
+        x = _runs.position(x, dyn.x_dim, dyn._device, "DynamicsSampler.generate_trajectories")
         saved = dyn.temperature
         dyn.temperature = temp
         try:

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _runs, ops
 from . import layered_train as _layered_train
-from ._flat_trainer import FlatTrainer, stack_chains
+from ._flat_trainer import FlatTrainer, check_draws, stack_chains
 from .dist import active as _active_dist
 from .dynamics_sampler import LAYERED_SWAP_MESSAGE, DynamicsSampler, replica_swap
 
@@ -105,7 +105,11 @@ class DynamicsTrainer(FlatTrainer):
         dev = dyn._device
         x = _lib.as_dev(x, dev).reshape(-1, dyn.x_dim)
         B, D = x.shape
-        t_scalar, t_ladder = self._chain_temperatures(temperature, B, "DynamicsTrainer.calc_loss_and_grads")
+        who = "DynamicsTrainer.calc_loss_and_grads"
+        t_scalar, t_ladder = self._chain_temperatures(temperature, B, who)
+        _lib.expect_shape(z, (B, D), "z", who)                           # (every shape, before the first draw)
+        check_draws(draws_x, B, D, "draws_x", who)
+        check_draws(draws_z, B, D, "draws_z", who)
         z = dyn._normal((B, D)) if z is None else _lib.as_dev(z, dev).reshape(B, D)
 
         def uniform(n):

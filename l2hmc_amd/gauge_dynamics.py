@@ -20,6 +20,13 @@ from . import autograd as _autograd
 from .network import ConvNet3D, GenericNet
 
 
+def _gate(dyn, a, name, who, rows=None):
+    """`dyn._x(a)` for the argument `name` of the method `who`: the same rule, worded for the caller, and with `rows`
+    the rows it must have (a momentum: its position's)."""
+    _lib.expect_shape(a, (rows, dyn.x_dim), name, who, fold=True)
+    return dyn._x(a)
+
+
 class GaugeDynamics:
     """Dynamics engine of the L2HMC sampler on the 2D U(1) lattice."""
 
@@ -187,8 +194,14 @@ class GaugeDynamics:
         return h[2].data_ptr()
 
     def _x(self, a):
+        """The ONE gate for positions and momenta -> a float32 device tensor [rows, x_dim].  [B, x_dim] passes, and so
+        does any [B, ...] whose trailing extents multiply to x_dim ([B, T, X, 2]).  ValueError otherwise
+        (`_lib.expect_shape`), before the value is copied anywhere: every kernel behind this object reads x_dim floats
+        per row, whatever the tensor holds.  The methods come through `_gate`, which names the argument and its method
+        and fixes a momentum's rows to its position's."""
+        _lib.expect_shape(a, (None, self.x_dim), "position", "GaugeDynamics", fold=True)
         a = _lib.as_dev(a, self._device)
-        return a.reshape(a.shape[0], -1)
+        return a if a.ndim == 2 else a.reshape(a.shape[0], -1)
 
     def _normal(self, shape):
         out = ops.fill_normal(shape, self._seed, self._draws, self._device)
@@ -235,7 +248,9 @@ class GaugeDynamics:
         (l2hmc_gauge_transition_ladder) whatever `fused` says: `GaugeSampler.step` is the one-launch ladder step.
         Refused before any draw is taken: ValueError for a ladder of another shape, with an entry that in float32 is
         not finite or is negative, or that requires grad; NotImplementedError for a ladder on hmc=True."""
-        x = self._x(position)
+        who = "GaugeDynamics.apply_transition"
+        x = _gate(self, position, "position", who)
+        _autograd.check_draws(self, x.shape[0], momentum_f, momentum_b, coin, u, who)     # all three branches below
         beta, ladder = self._beta(beta, x.shape[0])
         if _autograd.wants_grad(self, x):
             return _autograd.transition(self, x, float(beta) if ladder is None else ladder, momentum_f, momentum_b,
@@ -267,8 +282,8 @@ class GaugeDynamics:
             if self.check_numerics and not bool(torch.isfinite(x_prop).all() & torch.isfinite(v_prop).all()):
                 raise FloatingPointError("check_numerics: non-finite value in the proposed configuration")
             return x_prop, v_prop, p, x_out
-        v0f = self._x(momentum_f) if momentum_f is not None else self._normal((B, D))
-        v0b = self._x(momentum_b) if momentum_b is not None else self._normal((B, D))
+        v0f = _gate(self, momentum_f, "momentum_f", who, B) if momentum_f is not None else self._normal((B, D))
+        v0b = _gate(self, momentum_b, "momentum_b", who, B) if momentum_b is not None else self._normal((B, D))
         coin = _lib.as_dev(coin, self._device) if coin is not None else self._uniform((B,))
         u = _lib.as_dev(u, self._device) if u is not None else self._uniform((B,))
         x_prop, v_prop, x_out = (torch.empty_like(x) for _ in range(3))
@@ -286,9 +301,10 @@ class GaugeDynamics:
 
     def transition_kernel(self, position, beta, forward=True, momentum=None, return_logdet=False):
         """:261-313 -> (position_post, momentum_post, accept_prob)."""
-        x = self._x(position)
+        who = "GaugeDynamics.transition_kernel"
+        x = _gate(self, position, "position", who)
         rows, D = x.shape
-        v0 = self._x(momentum) if momentum is not None else self._normal((rows, D))
+        v0 = _gate(self, momentum, "momentum", who, rows) if momentum is not None else self._normal((rows, D))
         x_out, v_out = torch.empty_like(x), torch.empty_like(x)
         sld = torch.empty(rows, dtype=torch.float32, device=x.device)
         p = torch.empty_like(sld)
@@ -303,8 +319,9 @@ class GaugeDynamics:
 
     def _lf(self, position, momentum, beta, step, backward, step_end=None):
         """Leapfrog step `step` (or the steps [step, step_end) in one call) -> (x, v, log-det)."""
-        x, v = self._x(position).clone(), self._x(momentum).clone()
+        x = _gate(self, position, "position", "GaugeDynamics._lf")
         rows = x.shape[0]
+        x, v = x.clone(), _gate(self, momentum, "momentum", "GaugeDynamics._lf", rows).clone()
         logdet = torch.zeros(rows, dtype=torch.float32, device=x.device)
         plan, L = self._plan(), _lib.lib()
         dirs = self._dir(rows, True) if backward else None
@@ -326,7 +343,8 @@ class GaugeDynamics:
         return fn([a, b, t])
 
     def _update_momentum(self, position, momentum, beta, t, backward):
-        x, v = self._x(position), self._x(momentum)
+        x = _gate(self, position, "position", "GaugeDynamics._update_momentum")
+        v = _gate(self, momentum, "momentum", "GaugeDynamics._update_momentum", x.shape[0])
         grad = self.grad_potential(x, beta)
         S, T, Q = self._stq(self.momentum_fn, self._net_x(x), grad, t)           # :493-495
         return ops.lf_update_v(v, grad, self._x(S), self._x(T), self._x(Q), self.eps, backward)
@@ -340,8 +358,10 @@ class GaugeDynamics:
         return self._update_momentum(position, momentum, beta, t, True)
 
     def _update_position(self, position, momentum, t, mask, mask_inv, backward):
-        x, v = self._x(position), self._x(momentum)
-        keep = _lib.as_dev(mask, self._device).reshape(-1)
+        who = "GaugeDynamics._update_position"
+        x = _gate(self, position, "position", who)
+        v = _gate(self, momentum, "momentum", who, x.shape[0])
+        keep = _lib.as_dev(mask, self._device).reshape(-1)       # (its length: ops.lf_update_x checks `keep`)
         if self.periodic and not self.hmc:
             S, T, Q = self._stq(self.position_fn, v, keep.repeat(2)[None, :] * self._net_x(x), t)
             return ops_periodic.lf_update_x_ncp(x, v, keep, self._x(S), self._x(T), self._x(Q), self.eps, backward)
@@ -362,8 +382,15 @@ class GaugeDynamics:
 
     def _compute_accept_prob(self, position, momentum, position_post, momentum_post, sumlogdet, beta):
         """:592-609."""
-        old = self.hamiltonian(position, momentum, beta)
-        new = self.hamiltonian(position_post, momentum_post, beta)
+        who = "GaugeDynamics._compute_accept_prob"
+        x = _gate(self, position, "position", who)
+        rows = x.shape[0]
+        v = _gate(self, momentum, "momentum", who, rows)
+        x1 = _gate(self, position_post, "position_post", who, rows)
+        v1 = _gate(self, momentum_post, "momentum_post", who, rows)
+        _lib.expect_shape(sumlogdet, (rows,), "sumlogdet", who)
+        old = self.hamiltonian(x, v, beta)
+        new = self.hamiltonian(x1, v1, beta)
         return ops.accept_prob(old, new, _lib.as_dev(sumlogdet, self._device))
 
     def _get_time(self, i):
@@ -382,11 +409,11 @@ class GaugeDynamics:
 
     def potential_energy(self, position, beta):
         """:675-681."""
-        return float(beta) * self.potential(self._x(position))
+        return float(beta) * self.potential(_gate(self, position, "position", "GaugeDynamics.potential_energy"))
 
     def kinetic_energy(self, v):
         """:683-689."""
-        return ops.kinetic_energy(self._x(v))
+        return ops.kinetic_energy(_gate(self, v, "v", "GaugeDynamics.kinetic_energy"))
 
     def hamiltonian(self, position, momentum, beta):
         """:691-696."""
@@ -394,4 +421,4 @@ class GaugeDynamics:
 
     def grad_potential(self, position, beta, check_numerics=True):
         """:698-709 -- closed form of the autodiff the reference runs."""
-        return self.lattice.grad_action(self._x(position), beta)
+        return self.lattice.grad_action(_gate(self, position, "position", "GaugeDynamics.grad_potential"), beta)

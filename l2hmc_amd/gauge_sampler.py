@@ -56,6 +56,7 @@ class GaugeSampler:
         `beta`: a float, or for an L2HMC dynamics one value per chain -- [B] or [1, B] as a list / array (checked:
         finite and not negative in float32), or a float32 tensor [B] or [1, B] on x's device, which is used as it is
         (`_runs.per_chain`; l2hmc_gauge_mcmc_step_ladder: chain c has the bits of the step of the whole batch at beta[c])."""
+        x = _runs.position(x, self.dynamics.x_dim, self.dynamics._device, "GaugeSampler.step")
         if _runs.ndim(beta) == 0:
             return self._step(x, beta)
         if self.dynamics.hmc:                              # (ValueErrors before any draw)
@@ -105,9 +106,11 @@ class GaugeSampler:
             raise AttributeError(f"metric={metric}. Expected one of: 'l1', 'l2', 'cos', 'cos2', or 'cos_diff'.")
         dyn = self.dynamics
         T, X = self.lattice.time_size, self.lattice.space_size
-        x = _lib.as_dev(x, dyn._device)
+        x = _runs.position(x, dyn.x_dim, dyn._device, "GaugeSampler.calc_loss")
+        if z is not None:                                  # (refused before the x transition takes its draws)
+            z = _runs.position(z, dyn.x_dim, dyn._device, "GaugeSampler.calc_loss", "z", x.shape[0])
         x_prop, _, px, x_out = dyn(x, beta)
-        z = dyn._normal(tuple(x.shape)) if z is None else _lib.as_dev(z, dyn._device)
+        z = dyn._normal(tuple(x.shape)) if z is None else z
         _, _, pz, _ = dyn(z, beta)
         terms = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
         _lib.call("l2hmc_gauge_loss_terms", x, x_prop, px, z, pz, x.shape[0], T, X, self.METRICS[metric],
@@ -140,7 +143,7 @@ class GaugeSampler:
         if x is None:
             x = _lib.as_dev(np.random.randn(dyn.batch_size, dyn.x_dim), dyn._device)
         else:
-            x = _lib.as_dev(x, dyn._device)
+            x = _runs.position(x, dyn.x_dim, dyn._device, "GaugeSampler.run")
         per_step = _runs.ndim(beta) > 0
         betas = [float(b) for b in beta] if per_step else [beta] * run_steps
         if len(betas) != run_steps:
@@ -196,12 +199,11 @@ class GaugeSampler:
         run_steps = int(run_steps)
         if run_steps < 0:
             raise ValueError(f"run_steps={run_steps} must not be negative")
-        shape = (dyn.batch_size, dyn.x_dim) if x is None else tuple(np.shape(x))
-        if len(shape) != 2 or shape[1] != dyn.x_dim:
-            raise ValueError(f"{who}: x of shape {shape}: expected [B, {dyn.x_dim}]")
+        _lib.expect_shape(x, (None, dyn.x_dim), "x", f"GaugeSampler.{who}", fold=True)
+        shape = (dyn.batch_size, dyn.x_dim) if x is None else (np.shape(x)[0], dyn.x_dim)
         betas = _runs.chain_axis(beta, run_steps, shape[0], who=who, name="beta", positive=False)
         step = None if eps is None else _runs.step_sizes(eps, shape[0])
-        x = _lib.as_dev(np.random.randn(*shape) if x is None else x, dyn._device)
+        x = _runs.position(np.random.randn(*shape) if x is None else x, dyn.x_dim, dyn._device, f"GaugeSampler.{who}")
         return run_steps, x, betas, step
 
     def _ladder_frame(self, run_steps, x, betas, keep_samples, body):
@@ -361,8 +363,9 @@ class GaugeSampler:
         on the device) the round exchanges them too.  Returns (swap_p [B], NaN off the lower chain of a pair;
         swapped [B] bool; action [B], sum (1 - cos P) of the chains that were in a pair, NaN elsewhere) as tensors."""
         dyn = self.dynamics
-        if not isinstance(x, torch.Tensor) or x.ndim != 2 or x.shape[1] != dyn.x_dim:
+        if not isinstance(x, torch.Tensor):
             raise ValueError(f"swap_replicas: x: expected a device tensor [B, {dyn.x_dim}] (exchanged in place)")
+        _lib.expect_shape(x, (None, dyn.x_dim), "x", "GaugeSampler.swap_replicas")        # (in place: no other form)
         B = x.shape[0]
         G, _, _, parity = _runs.check_replicas(replicas, B, parity=parity, who="swap_replicas")
         beta_dev, _ = _runs.per_chain(beta, B, x.device, who="swap_replicas", name="beta")

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib, _runs, ops
 from . import layered_train as _layered_train
-from ._flat_trainer import FlatTrainer, stack_chains
+from ._flat_trainer import FlatTrainer, check_draws, stack_chains
 from .dist import active as _active_dist
 from .lattice import replica_swap, u1_observables
 
@@ -135,9 +135,14 @@ class GaugeTrainer(FlatTrainer):
         dyn = self.dynamics
         dev = dyn._device
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
+        who = "GaugeTrainer.calc_loss_and_grads"
+        _lib.expect_shape(x, (None, 2 * T * X), "x", who, fold=True)
         x = dyn._x(x)
         B, D = x.shape
         betas = self._chain_betas(beta, B, "calc_loss_and_grads")      # None: one beta, today's entries
+        _lib.expect_shape(z, (B, D), "z", who, fold=True)               # (every shape, before the first draw)
+        check_draws(draws_x, B, D, "draws_x", who)
+        check_draws(draws_z, B, D, "draws_z", who)
         z = dyn._normal((B, D)) if z is None else dyn._x(z)
 
         def draw(d):
@@ -329,6 +334,7 @@ class GaugeTrainer(FlatTrainer):
         T, X = dyn.lattice.time_size, dyn.lattice.space_size
         if samples_init is None:
             samples_init = np.asarray(dyn.lattice.samples, dtype=np.float32).reshape(dyn.batch_size, dyn.x_dim)
+        _lib.expect_shape(samples_init, (None, dyn.x_dim), "samples_init", "GaugeTrainer.train", fold=True)
         x = dyn._x(samples_init).clone()
         B = x.shape[0]
         ladder = np.ndim(beta_init) > 0 or np.ndim(beta_final) > 0

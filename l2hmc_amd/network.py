@@ -248,12 +248,31 @@ class _DenseSTQ:
         return [bufs[k] for k in ("w1_t", "wt", "b1", "wh_t", "bh", "whd_t", "bhd", "coeff_s", "coeff_q")]
 
     # ---- standalone evaluation: (S, T, Q) = net([a, b, t])
-    def __call__(self, inputs):
+    def _inputs(self, inputs, Ka, Kb):
+        """[a, b, t(, aux)] of a call -> (a [rows, Ka], b [rows, Kb] on the device, cos, sin of the ONE time every row
+        runs at).  a and b may carry their width as any trailing extents ([rows, T, X, 2]); t has one row, or `rows`
+        rows that all equal the first (the reference tiles it): only t[0] reaches the kernel, so rows that differ are
+        refused, not misread.  ValueError (`_lib.expect_shape`) before the weights are packed or the library is
+        touched: the kernels read Ka and Kb floats per row whatever the tensors hold."""
         a, b, t = inputs[0], inputs[1], inputs[2]
-        a = _lib.as_dev(a, self._device).reshape(a.shape[0], -1)
-        b = _lib.as_dev(b, self._device).reshape(b.shape[0], -1)
-        t = torch.as_tensor(t, dtype=torch.float32).reshape(-1, 2)
-        tc, ts = float(t[0, 0]), float(t[0, 1])
+        who = f"{type(self).__name__}.__call__"
+        _lib.expect_shape(a, (None, Ka), "a", who, fold=True)
+        rows = a.shape[0]
+        _lib.expect_shape(b, (rows, Kb), "b", who, fold=True)
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if t.numel() != 2:
+            _lib.expect_shape(t, (rows, 2), "t", who)
+            if not bool((t == t[0]).all()):
+                raise ValueError(f"{who}: t of shape {tuple(t.shape)} has rows that differ: expected one (cos, sin) "
+                                 "pair for every row")
+        t = t.reshape(-1, 2)
+        a = _lib.as_dev(a, self._device).reshape(rows, -1)
+        b = _lib.as_dev(b, self._device).reshape(rows, -1)
+        return a, b, float(t[0, 0]), float(t[0, 1])
+
+    def __call__(self, inputs):
+        la, lb = self._layers()[:2]
+        a, b, tc, ts = self._inputs(inputs, la.kernel.shape[0], lb.kernel.shape[0])
         st = self.pack()
         rows = a.shape[0]
         S, T, Q = (torch.empty(rows, st.D, dtype=torch.float32, device=a.device) for _ in range(3))
@@ -434,18 +453,15 @@ class ConvNet3D(_DenseSTQ):
 
     def __call__(self, inputs):
         """conv_net.py:247-280: (scale, translation, transformation) = net([v, x, t])."""
-        a, b, t = inputs[0], inputs[1], inputs[2]
-        a = _lib.as_dev(a, self._device).reshape(a.shape[0], -1)
-        b = _lib.as_dev(b, self._device).reshape(b.shape[0], -1)
-        t = torch.as_tensor(t, dtype=torch.float32).reshape(-1, 2)
-        st, fr = self.pack(), self.pack_front()
         T, X = int(self.links_shape[0]), int(self.links_shape[1])
+        a, b, tc, ts = self._inputs(inputs, 2 * T * X, 2 * T * X)
+        st, fr = self.pack(), self.pack_front()
         rows = a.shape[0]
         S, Tr, Q = (torch.empty(rows, st.D, dtype=torch.float32, device=a.device) for _ in range(3))
         L = _lib.lib()
         ws, nb = self._ws.get(L.l2hmc_stq_conv3d_ws_bytes(rows, st.H, T, X, fr.F), a.device)
-        _lib.call("l2hmc_stq_conv3d", C.byref(fr), C.byref(st), T, X, a, b, None, float(t[0, 0]), float(t[0, 1]), rows,
-                  S, Tr, Q, ws, nb, device=self._device)
+        _lib.call("l2hmc_stq_conv3d", C.byref(fr), C.byref(st), T, X, a, b, None, tc, ts, rows, S, Tr, Q, ws, nb,
+                  device=self._device)
         return S, Tr, Q
 
     call = __call__

@@ -17,10 +17,23 @@ def _uniform(dynamics, n):
 
 def tf_accept(x, Lx, px, u=None, dynamics=None):
     """:57-59 -- accept iff px - u >= 0."""
+    _lib.expect_shape(x, (None, None), "x", "tf_accept")
+    _lib.expect_shape(Lx, tuple(x.shape), "Lx", "tf_accept")
+    for name, t in (("px", px), ("u", u)):
+        _lib.expect_shape(t, (x.shape[0],), name, "tf_accept")
     x, Lx, px = (_lib.as_dev(t) for t in (x, Lx, px))
     u = _lib.as_dev(u) if u is not None else _uniform(dynamics, px.numel())
     # forward slot carries Lx with coin=1; strict=0 selects the sampler.py comparison
     return ops.mix_accept(x, Lx, Lx, px, Lx, Lx, px, torch.ones_like(px), u, 0, want_proposal=False)[3]
+
+
+def _check_draws(x, init_v, init_v_backward, dir_bits, u):
+    """`propose`'s injected draws against x [rows, x_dim] (None: not injected): momenta [rows, x_dim], direction bits
+    and uniforms (rows,).  ValueError (`_lib.expect_shape`), on the host, before any draw."""
+    for name, v in (("init_v", init_v), ("init_v_backward", init_v_backward)):
+        _lib.expect_shape(v, tuple(x.shape), name, "propose")
+    for name, t in (("dir_bits", dir_bits), ("u", u)):
+        _lib.expect_shape(t, (x.shape[0],), name, "propose")
 
 
 def propose(x, dynamics, init_v=None, aux=None, do_mh_step=False, log_jac=False, *,
@@ -37,6 +50,7 @@ def propose(x, dynamics, init_v=None, aux=None, do_mh_step=False, log_jac=False,
     l2hmc_small_propose takes.  The temperatures are NOT differentiated.  Refused before any draw: what
     `Dynamics.forward` refuses."""
     x = _lib.as_dev(x, dynamics._device)
+    _check_draws(x.reshape(-1, dynamics.x_dim), init_v, init_v_backward, dir_bits, u)
     temp = None
     if temperature is not None:
         temp = dynamics._call_temperature(temperature, x.reshape(-1, dynamics.x_dim).shape[0], "propose")
@@ -87,6 +101,7 @@ def _propose_grad(x, dynamics, init_v, do_mh_step, log_jac, init_v_backward, dir
     dev = dynamics._device
     x = x.reshape(-1, dynamics.x_dim)
     B = x.shape[0]
+    _check_draws(x, init_v, init_v_backward, dir_bits, u)
     mask = (_uniform(dynamics, B) >= 0.5).to(torch.float32) if dir_bits is None else _lib.as_dev(dir_bits, dev)
     vf = _lib.as_dev(init_v, dev) if init_v is not None else dynamics._normal(tuple(x.shape))
     vb = init_v_backward if init_v_backward is not None else init_v

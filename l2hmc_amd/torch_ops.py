@@ -2,8 +2,11 @@
 `extern "C"` / `TORCH_LIBRARY(l2hmc)` as the boundary; the C ABI of include/l2hmc_hip.h is the boundary, this file makes
 the same entry points visible to callers that compose torch operators).  Every op takes contiguous fp32 CUDA (ROCm)
 tensors, launches on torch's current stream, allocates only its outputs and has NO CPU implementation: called with a CPU
-tensor it raises like every other entry of this package.  Networks travel as the flat tuple of their packed device
-buffers (`_DenseSTQ.flat_tensors()` order: w1_t, wt, b1, wh_t, bh, whd_t, bhd, coeff_s, coeff_q).
+tensor it raises like every other entry of this package.  Each validates every caller-supplied tensor before the library
+is touched: device, dtype and contiguity (`_lib.dev_ptr`) and its shape (`_lib.expect_shape`, through `ops`; stq_dense
+checks all nine weight shapes against (H, Ka + Kb) and D, and a [rows, Ka], b [rows, Kb] against them).  Networks travel
+as the flat tuple of their packed device buffers (`_DenseSTQ.flat_tensors()` order: w1_t, wt, b1, wh_t, bh, whd_t, bhd,
+coeff_s, coeff_q).
 
     import l2hmc_amd.torch_ops            # registers the library
     action, force, plaq, charge = torch.ops.l2hmc.u1_action_force(x, T, X, beta)
@@ -26,16 +29,25 @@ _WEIGHT_FIELDS = ("w1_t", "wt", "b1", "wh_t", "bh", "whd_t", "bhd", "coeff_s", "
 
 
 def _net_struct(weights, q_tanh):
+    """struct l2hmc_dense_net over `weights` after their checks: all nine shapes follow from w1_t [H, Ka + Kb] (Ka = Kb)
+    and the D of whd_t [3, D, H]."""
     if len(weights) != len(_WEIGHT_FIELDS):
         raise ValueError(f"weights: expected {len(_WEIGHT_FIELDS)} tensors {_WEIGHT_FIELDS}, got {len(weights)}")
-    w1_t, wt, _, wh_t, _, whd_t = weights[:6]
+    ptrs = [_lib.dev_ptr(t, name=f) for f, t in zip(_WEIGHT_FIELDS, weights)]
+    w1_t, whd_t = weights[0], weights[5]
+    _lib.expect_shape(w1_t, (None, None), "w1_t")
     H, K = w1_t.shape
+    if K % 2:
+        raise ValueError(f"w1_t: expected shape (H, Ka + Kb) with Ka = Kb, got {tuple(w1_t.shape)}")
+    _lib.expect_shape(whd_t, (3, None, H), "whd_t")
     D = whd_t.shape[1]
-    if wh_t.shape != (H, H) or whd_t.shape != (3, D, H) or tuple(wt.shape) != (2, H) or K % 2:
-        raise ValueError("weights: shapes do not form a packed S/T/Q network (include/l2hmc_hip.h: l2hmc_dense_net)")
-    st = _lib.DenseNet(D=D, H=H, Ka=K // 2, Kb=K // 2, q_tanh=int(q_tanh), reserved=0, packed=None)
+    shapes = dict(wt=(2, H), b1=(H,), wh_t=(H, H), bh=(H,), bhd=(3, D), coeff_s=(D,), coeff_q=(D,))
     for f, t in zip(_WEIGHT_FIELDS, weights):
-        setattr(st, f, _lib.dev_ptr(t, name=f))
+        if f in shapes:
+            _lib.expect_shape(t, shapes[f], f)
+    st = _lib.DenseNet(D=D, H=H, Ka=K // 2, Kb=K // 2, q_tanh=int(q_tanh), reserved=0, packed=None)
+    for f, ptr in zip(_WEIGHT_FIELDS, ptrs):
+        setattr(st, f, ptr)
     return st
 
 
@@ -52,7 +64,9 @@ def stq_dense(a: torch.Tensor, b: torch.Tensor, weights: List[torch.Tensor], q_t
     """generic_net.py:129-146 / utils/network.py:89-114 (q_tanh = 1): (S, T, Q) = net([a, b, t])."""
     st = _net_struct(weights, q_tanh)
     pa, pb = _lib.dev_ptr(a, name="a"), _lib.dev_ptr(b, name="b")
+    _lib.expect_shape(a, (None, st.Ka), "a")
     rows = a.shape[0]
+    _lib.expect_shape(b, (rows, st.Kb), "b")
     S, T, Q = (torch.empty(rows, st.D, dtype=torch.float32, device=a.device) for _ in range(3))
     nb = _lib.lib().l2hmc_stq_ws_bytes(rows, st.H)
     ws = torch.empty(max(int(nb), 16), dtype=torch.uint8, device=a.device)

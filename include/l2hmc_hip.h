@@ -229,8 +229,18 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
                                       * halves) -- and the position sub-update is l2hmc_lf_update_x_ncp, a map of the circle
                                       * onto itself.  The proposal then commutes with 2 pi shifts of any link, so the wrap
                                       * between MCMC steps is harmless and the chain exact for any weights.  Runs layer by
-                                      * layer, every first-layer product formed anew: l2hmc_gauge_plan_fused() == 0, and the
+                                      * layer, every first-layer product formed anew: l2hmc_gauge_plan_fused() == 0 (unless
+                                      * L2HMC_PLAN_PERIODIC_STEP selects the mode's whole-step kernel), and the
                                       * l2hmc_gauge_train_* entries refuse the plan */
+#define L2HMC_PLAN_PERIODIC_STEP 512 /* with L2HMC_PLAN_PERIODIC only (without it an hmc = 0 plan is refused; ignored with
+                                      * hmc = 1; L2HMC_PLAN_LAYERED wins over it): where the plan has the kernel -- GenericNet,
+                                      * D = 128 with X a power of two (8x8, 4x16, ...), H = 512, both nets' .packed set -- the
+                                      * trajectory, leapfrog, transition-draw and MCMC-step entries run the periodic plan in ONE
+                                      * launch (l2hmc_gauge_plan_fused() == 1; a beta ladder in l2hmc_gauge_mcmc_step_ladder
+                                      * too), 16 rows per workgroup at every batch size.  Any other plan carries the flag and
+                                      * runs layer by layer.  L2HMC_PLAN_RECOMPUTE switches the kept first-layer products of
+                                      * that kernel off (same bits); TILES16_ONLY, ALL_COLUMNS, FULL_L1 and SINGLE_KICKS do
+                                      * nothing there.  l2hmc_gauge_transition_ladder and the training entries are unchanged */
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */

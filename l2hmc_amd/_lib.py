@@ -21,6 +21,7 @@ PLAN_LAYERED, PLAN_CONV3D, PLAN_SELECTED_ONLY, PLAN_RECOMPUTE, PLAN_TILES16_ONLY
 PLAN_FULL_L1 = 64
 PLAN_SINGLE_KICKS = 128
 PLAN_PERIODIC = 256
+PLAN_PERIODIC_STEP = 512     # with PLAN_PERIODIC only: the torus-exact mode's whole-step kernel where the plan has it
 GRAD_BUCKET_REST = 6
 BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32)
 

@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libl2hmc_hip.so")
-SOURCES = ["capi.hip", "u1_lattice.hip", "stq_dense.hip", "leapfrog.hip", "small_mlp.hip", "small_hmc.hip", "small_ais.hip", "fused_traj.hip", "fused_traj4.hip", "fused_traj32.hip", "hmc_step.hip", "replica_swap.hip",
+SOURCES = ["capi.hip", "u1_lattice.hip", "stq_dense.hip", "leapfrog.hip", "small_mlp.hip", "small_hmc.hip", "small_ais.hip", "fused_traj.hip", "fused_traj4.hip", "fused_traj32.hip", "fused_traj_ncp.hip", "hmc_step.hip", "replica_swap.hip",
            "conv3d_front.hip", "mcmc_step.hip", "loss.hip", "train.hip", "small_train.hip", "fused_train.hip",
            "layered_train.hip"]
 # every header is a dependency of every object (coarse, but never stale)

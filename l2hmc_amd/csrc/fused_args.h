@@ -75,4 +75,11 @@ int launch_fused4(const FusedArgs& a, int rows_per_wg, hipStream_t stream);
 int fused32_supported(const l2hmc_dense_net* n);
 int launch_fused32(const FusedArgs& a, hipStream_t stream);
 
+// the torus-exact mode's whole-step kernel (fused_traj_ncp.hip): plans with L2HMC_PLAN_PERIODIC and
+// L2HMC_PLAN_PERIODIC_STEP on D = 128, one 16-row form for every batch; reads the 4-wave image of l2hmc_dense_pack.
+// recompute: form every first-layer product anew (L2HMC_PLAN_RECOMPUTE)
+int fused_ncp_net_supported(const l2hmc_dense_net* n);
+int fused_ncp_plan(const l2hmc_gauge_plan* p);
+int launch_fused_ncp(const FusedArgs& a, int recompute, hipStream_t stream);
+
 }  // namespace l2hmc

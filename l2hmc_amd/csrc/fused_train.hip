@@ -747,7 +747,8 @@ size_t fused_bwd_pack_floats(const l2hmc_dense_net* n) {
 // latency, and this kernel runs one wave per SIMD (measured in-kernel: 12.9 ms against 4.4 ms for the
 // standalone conv3d_front_bwd_kernel over the same 40 calls), so conv plans keep the layered reverse pass.
 int fused_train_forward_supported(const l2hmc_gauge_plan* p) {
-  return !(p->flags & L2HMC_PLAN_LAYERED) && fused_plan_supported(p);
+  // (a torus-exact plan's whole-step kernel has no tape: check_train_plan refuses such plans, and nothing here sizes one)
+  return !(p->flags & (L2HMC_PLAN_LAYERED | L2HMC_PLAN_PERIODIC)) && fused_plan_supported(p);
 }
 int fused_train_supported(const l2hmc_gauge_plan* p) {
   return !(p->flags & L2HMC_PLAN_CONV3D) && fused_train_forward_supported(p);

@@ -1191,7 +1191,10 @@ static int fused_generic_net(const l2hmc_dense_net* n) {
 static int fused_conv_net(const l2hmc_dense_net* n) {
   return n->D == 128 && n->H == 256 && n->Ka == 64 && n->Kb == 64;
 }
-int fused_net_supported(const l2hmc_dense_net* n) { return fused_generic_net(n) || fused_conv_net(n); }
+// ... and the two GenericNet shapes of a torus-exact plan on D = 128 (fused_traj_ncp.hip; K1 = 3 D)
+int fused_net_supported(const l2hmc_dense_net* n) {
+  return fused_generic_net(n) || fused_conv_net(n) || fused_ncp_net_supported(n);
+}
 
 // L2HMC_PLAN_TILES16_ONLY keeps every batch on the 16-row form (A/B and the bit-identity test)
 static bool subtile_enabled(const l2hmc_gauge_plan* p) { return !(p->flags & L2HMC_PLAN_TILES16_ONLY); }
@@ -1209,7 +1212,8 @@ static int device_cu_count() {
 }
 int fused_plan_supported(const l2hmc_gauge_plan* p) {
   if (p->hmc || !p->xnet.packed || !p->vnet.packed || 2 * p->T * p->X != 128 || (p->X & (p->X - 1)) != 0) return 0;
-  if (p->flags & L2HMC_PLAN_PERIODIC) return 0;      // the torus-exact mode runs layer by layer (leapfrog.hip)
+  // the torus-exact mode runs layer by layer (leapfrog.hip) unless the plan asks for its whole-step kernel and has it
+  if (p->flags & L2HMC_PLAN_PERIODIC) return fused_ncp_plan(p);
   if (p->flags & L2HMC_PLAN_CONV3D)
     return fused_conv_net(&p->xnet) && fused_conv_net(&p->vnet) && p->T == 8 && p->X == 8 && p->xfront.F == 8 &&
            p->vfront.F == 8;
@@ -1221,6 +1225,17 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
                             float* v_out, float* logdet, int logdet_accumulate, float* p_accept,
                             hipStream_t stream, int64_t x_mod, int64_t dir_split, const FusedTape* tape_x,
                             const FusedTape* tape_v, const float* betas, int64_t beta_mod, int64_t beta_stride) {
+  if (fused_ncp_plan(p)) {
+    // torus-exact plans: their own kernel, one form for every batch (fused_traj_ncp.hip), ahead of any form selection
+    L2HMC_REQUIRE(!tape_x && !tape_v && !betas, "fused trajectory: periodic plans have no taped or per-row-beta form");
+    FusedArgs a{};
+    a.T = p->T; a.X = p->X; a.num_steps = p->num_steps; a.step_begin = step_begin; a.step_end = step_end;
+    a.eps = p->eps; a.beta = beta; a.masks = p->masks; a.xnet = p->xnet; a.vnet = p->vnet;
+    a.x0 = x0; a.v0 = v0; a.dir = dir; a.rows = rows; a.x_out = x_out; a.v_out = v_out;
+    a.x_mod = x_mod; a.dir_split = dir_split;
+    a.logdet = logdet; a.logdet_accumulate = logdet_accumulate; a.p_accept = p_accept;
+    return launch_fused_ncp(a, (p->flags & L2HMC_PLAN_RECOMPUTE) != 0, stream);
+  }
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
   using CfgG = FusedCfg<128, 512, 128, false>;
   using CfgC = FusedCfg<128, 256, 64, true>;
@@ -1374,6 +1389,23 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
                       uint64_t seed, uint64_t draw, int both, float* px, float* actions, float* plaqs, float* charges,
                       float* dq, float* step_sums, float* part, void* hand, hipStream_t stream, float* x_prop,
                       float* v_prop, float* x_out, const float* betas, int64_t chain_stride) {
+  if (fused_ncp_plan(p)) {
+    // torus-exact plans: ONE launch of their own kernel (fused_traj_ncp.hip) for the whole batch -- 8 chains x both
+    // directions or 16 chains per workgroup; no parts, no split form, no heads image, no ticket to clear
+    L2HMC_REQUIRE(x_in && (x_next || x_out) && B > 0 && (!step_sums || part), "fused step: bad arguments");
+    const int cpw = both ? kFM / 2 : kFM;
+    FusedArgs a{};
+    a.T = p->T; a.X = p->X; a.num_steps = p->num_steps; a.step_begin = 0; a.step_end = p->num_steps;
+    a.eps = p->eps; a.beta = beta; a.masks = p->masks; a.xnet = p->xnet; a.vnet = p->vnet;
+    a.x0 = x_in; a.rows = ceil_div(B, (int64_t)cpw) * kFM;
+    a.step_x_next = x_next; a.step_xprop = x_prop; a.step_vprop = v_prop; a.step_xout = x_out;
+    a.step_B = B; a.step_Bl = B; a.step_chain0 = 0; a.step_sums_acc = 0;
+    a.step_seed = seed; a.step_draw = draw; a.step_both = both;
+    a.step_betas = betas; a.step_beta_stride = chain_stride;
+    a.step_px = px; a.step_act = actions; a.step_plq = plaqs; a.step_chg = charges; a.step_dq = dq;
+    a.step_sums = step_sums; a.step_part = part;
+    return launch_fused_ncp(a, (p->flags & L2HMC_PLAN_RECOMPUTE) != 0, stream);
+  }
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
   using CfgG = FusedCfg<128, 512, 128, false>;
   using CfgC = FusedCfg<128, 256, 64, true>;

@@ -287,6 +287,9 @@ static int check_plan(const l2hmc_gauge_plan* p) {
   L2HMC_REQUIRE(p->masks != nullptr, "plan: masks is NULL");
   const int D = 2 * p->T * p->X;
   if (!p->hmc) {
+    L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_STEP) || (p->flags & L2HMC_PLAN_PERIODIC),
+                  "plan: L2HMC_PLAN_PERIODIC_STEP selects the whole-step kernel of a torus-exact plan and needs "
+                  "L2HMC_PLAN_PERIODIC with it");
     L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC) || !(p->flags & L2HMC_PLAN_CONV3D),
                   "plan: L2HMC_PLAN_PERIODIC takes GenericNet networks only (no ConvNet3D front-end of [cos x | sin x])");
     const l2hmc_dense_net* nets[2] = {&p->xnet, &p->vnet};

@@ -50,12 +50,21 @@ class GaugeDynamics:
         # True: the torus-exact mode (no reference counterpart).  The networks read every link angle as
         # [cos x | sin x] and the position sub-update scales on the circle (ops_periodic.lf_update_x_ncp), so the
         # proposal commutes with 2 pi shifts of any link and Metropolis-Hastings makes the wrapped chain exact for any
-        # weights.  GenericNet only; runs layer by layer; with hmc=True there are no networks and nothing changes.
+        # weights.  GenericNet only; runs layer by layer unless `whole_step` is set; with hmc=True there are no networks
+        # and nothing changes.
         self.periodic = False
+        # True (with periodic=True): the torus-exact mode's whole-step kernel (L2HMC_PLAN_PERIODIC_STEP) -- one launch
+        # per trajectory or MCMC step where the plan has it (x_dim = 128 with a power-of-two space extent: 8x8, 4x16,
+        # ...); any other lattice carries the flag and runs layer by layer.  Sampling only: training is unchanged.
+        self.whole_step = False
         for key, val in kwargs.items():
             if key != 'eps':             # :73-75
                 setattr(self, key, val)
         self.periodic = bool(self.periodic)
+        self.whole_step = bool(self.whole_step)
+        if self.whole_step and not self.periodic and not self.hmc:
+            raise ValueError("whole_step=True selects the whole-step kernel of the torus-exact mode and needs "
+                             "periodic=True (the reference mode's one-launch step is `fused`, on by default)")
         if self.periodic and not self.hmc and self.network_arch == 'conv3D':
             raise NotImplementedError("periodic=True takes network_arch='generic' only: ConvNet3D has no front-end "
                                       "over [cos x | sin x]")
@@ -163,7 +172,8 @@ class GaugeDynamics:
                            | (_lib.PLAN_ALL_COLUMNS if self.all_columns else 0)
                            | (_lib.PLAN_FULL_L1 if self.full_l1 else 0)
                            | (_lib.PLAN_SINGLE_KICKS if self.single_kicks else 0)
-                           | (_lib.PLAN_PERIODIC if self.periodic and not self.hmc else 0),
+                           | (_lib.PLAN_PERIODIC if self.periodic and not self.hmc else 0)
+                           | (_lib.PLAN_PERIODIC_STEP if self.whole_step and self.periodic and not self.hmc else 0),
                            masks=_lib.dev_ptr(self.mask, name="mask"))
         if not self.hmc:
             p.xnet = self.position_fn.pack()

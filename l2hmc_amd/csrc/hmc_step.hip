@@ -180,7 +180,8 @@ struct HmcRowLds {
 // [p.step_begin, p.step_end) at the ROW's beta with the row's step size (be; p.beta and p.eps are not read); returns
 // the row's accept probability (0 unless want_p).  Every thread of the workgroup calls it.  On return the row's x is
 // also in its xs row (published ahead of the last sin P pass).
-template <int SPT, class BE>
+// HOLD_LDS: where the thread's shares of the action and the kinetic energy at the start wait for the end (see below).
+template <int SPT, bool HOLD_LDS, class BE>
 __device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLanes<SPT>& g, const BE be, const int d,
                                                 const bool want_p, float (&x0)[SPT], float (&x1)[SPT],
                                                 float (&v0)[SPT], float (&v1)[SPT]) {
@@ -239,8 +240,22 @@ __device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLan
   };
 
   publish_x();
-  float act0 = sin_pass(), kin0 = kinetic();
-  if (want_p) hmc_row_sum2(act0, kin0, g.tsh, g.r, fl, g.red);
+  // The Hamiltonian difference is summed over the row as the DIFFERENCES of the threads' own shares of the action and
+  // of the kinetic energy at the two ends (O(dH) in all), not as totals of O(sites) that are subtracted afterwards: an
+  // fp32 total of 1000 carries 6e-5 of rounding, and p = exp(dH) takes all of it once p lies inside (0, 1); a thread's
+  // share is of O(10), its rounding 5e-7.  The row is summed once, not twice.
+  // The shares at the start wait (HOLD_LDS) in the thread's own two words of the row's v planes, which nobody reads or
+  // writes before the step's epilogue (whose last read of them lies behind a barrier); a lane without a first site has
+  // no site at all, and its shares are 0.  Only the run kernels of four sites per thread keep them in the two
+  // registers that held the totals: with the pair in LDS they take 130 VGPRs and lose their second workgroup per CU
+  // (with the pair in registers the step kernel of two sites per thread takes 81 and loses its third; hipcc of ROCm
+  // 7.2.0 at -O3).  The values are the same either way.
+  float* hold = g.vs + g.r * D + fl;
+  const float act0 = sin_pass(), kin0 = want_p ? kinetic() : 0.f;
+  if (HOLD_LDS && want_p && g.ok[0]) {
+    hold[0] = act0;
+    hold[sites] = kin0;
+  }
   float act1 = act0;
   const int N = p.num_steps;
   for (int step = p.step_begin; step < p.step_end; ++step) {
@@ -274,9 +289,18 @@ __device__ __forceinline__ float hmc_trajectory(const FusedArgs& p, const HmcLan
   }
   float pr = 0.f;
   if (want_p) {
-    float kin1 = kinetic();
-    hmc_row_sum2(act1, kin1, g.tsh, g.r, fl, g.red);
-    pr = accept_prob(be.beta(), act0, act1, 0.5f * kin0, 0.5f * kin1, 0.f);
+    float dact = act1, dkin = kinetic();
+    if (HOLD_LDS) {
+      if (g.ok[0]) {
+        dact -= hold[0];
+        dkin -= hold[sites];
+      }
+    } else {
+      dact -= act0;
+      dkin -= kin0;
+    }
+    hmc_row_sum2(dact, dkin, g.tsh, g.r, fl, g.red);
+    pr = accept_prob(be.beta(), 0.f, dact, 0.f, 0.5f * dkin, 0.f);         // H(start) - H(end) = -(beta dS + dK)
   }
   return pr;
 }
@@ -317,7 +341,7 @@ __device__ __forceinline__ void hmc_load_x(const FusedArgs& p, const HmcLanes<SP
 // ngrp, npart: the workgroup fills ngrp slots of the step's npart partial sums (fused_step.h: step_sums), one per
 // w.cpw / ngrp of its chains: 1 and the grid size everywhere but in hmc_run_exchange_kernel, whose workgroup holds the
 // chains of ngrp workgroups of the ladder run and leaves the partial sums those would.
-template <int SPT, class BE>
+template <int SPT, bool HOLD_LDS, class BE>
 __device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>& g, const StepWg& w, const BE be,
                                          const int k, const int64_t grow, const bool live, float (&x0)[SPT],
                                          float (&x1)[SPT], const int ngrp, const int npart) {
@@ -358,7 +382,7 @@ __device__ __forceinline__ void hmc_step(const FusedArgs& p, const HmcLanes<SPT>
     xi1[j] = x1[j];
   }
 
-  const float pr = hmc_trajectory<SPT>(p, g, be, d, true, x0, x1, v0, v1);
+  const float pr = hmc_trajectory<SPT, HOLD_LDS>(p, g, be, d, true, x0, x1, v0, v1);
 
   // ---- mix the directions, Metropolis-Hastings (gauge_dynamics.py:221-257, mask * a + (1 - mask) * b) ----
   // xs rows hold the final x already (published ahead of the last sin P pass); v rows and p join them
@@ -508,7 +532,7 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
     bool live;
     hmc_step_row<SPT>(p, g, w, k, grow, live);
     hmc_load_x<SPT>(p, g, grow, live, x0, x1);
-    hmc_step<SPT>(p, g, w, HmcRowValues{p.beta, p.eps}, k, grow, live, x0, x1, 1, (int)gridDim.x);
+    hmc_step<SPT, true>(p, g, w, HmcRowValues{p.beta, p.eps}, k, grow, live, x0, x1, 1, (int)gridDim.x);
     return;
   }
   // ---- trajectory mode: x, v, sumlogdet (exactly 0), p of the live rows ----
@@ -526,7 +550,8 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_step_kernel(const FusedArg
       v1[j] = vr[1];
     }
   }
-  const float pr = hmc_trajectory<SPT>(p, g, HmcRowValues{p.beta, p.eps}, d, p.p_accept != nullptr, x0, x1, v0, v1);
+  const float pr =
+      hmc_trajectory<SPT, true>(p, g, HmcRowValues{p.beta, p.eps}, d, p.p_accept != nullptr, x0, x1, v0, v1);
   if (live) {
 #pragma unroll
     for (int j = 0; j < SPT; ++j) {
@@ -614,8 +639,8 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(
     // VGPRs, half its workgroups per CU.  z is 0 (a draw index does not reach 2^63), which the compiler cannot know,
     // so the addresses are formed where they are used, as in the step kernel; the neighbour tables stay hoisted.
     // The host refuses a run whose draw indices reach 2^63 (HmcRunArgs).  The register counts depend on the compiler:
-    // 78 / 96 / 127 VGPRs (SPT 1 / 2 / 4), no scratch, with hipcc of ROCm 7.2.0 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0) at -O3;
-    // the ladder instances 80 / 98 / 126 (profiles/hmc_run_ladder.txt).
+    // 75 / 93 / 127 VGPRs (SPT 1 / 2 / 4), no scratch, with hipcc of ROCm 7.2.0 (HIP 7.2.26015, AMD clang 22.0.0git roc-7.2.0) at -O3;
+    // the ladder instances 77 / 95 / 126 (profiles/hmc_run_ladder.txt, taken three registers earlier at SPT 1 and 2).
     const int z = (int)(q.step_draw >> 63);
     HmcLanes<SPT> gs = g;
     if (SPT == 4) {
@@ -647,12 +672,12 @@ __global__ __launch_bounds__(kHmcMaxThreads) void hmc_run_kernel(
           rb[0] = beta;
           rb[1] = eps;
         }
-        hmc_step<SPT>(q, gs, ws, HmcRowLds{rb}, k + z, c, live, x0, x1, 1, (int)gridDim.x);
+        hmc_step<SPT, SPT != 4>(q, gs, ws, HmcRowLds{rb}, k + z, c, live, x0, x1, 1, (int)gridDim.x);
       } else {
-        hmc_step<SPT>(q, gs, ws, HmcRowValues{beta, eps}, k + z, c, live, x0, x1, 1, (int)gridDim.x);
+        hmc_step<SPT, SPT != 4>(q, gs, ws, HmcRowValues{beta, eps}, k + z, c, live, x0, x1, 1, (int)gridDim.x);
       }
     } else {
-      hmc_step<SPT>(q, gs, ws, HmcRowValues{q.beta, q.eps}, k + z, grow + z, live, x0, x1, 1, (int)gridDim.x);
+      hmc_step<SPT, SPT != 4>(q, gs, ws, HmcRowValues{q.beta, q.eps}, k + z, grow + z, live, x0, x1, 1, (int)gridDim.x);
     }
     if (w.paired) {
       // the chain's new state is in its forward row's registers: hand it to the backward row through that row's
@@ -832,7 +857,7 @@ int launch_hmc_run_ladder(const l2hmc_gauge_plan* p, const float* betas, int64_t
 //   * Streams: a step at draw index d takes 2 d and 2 d + 1, a round after it 2 d + 2, and the next step is d + 2
 //     (2 d + 3 is skipped) -- the loop `run_hmc(k)`, `swap_replicas` on one counter.  A pairless round (group 2 at parity
 //     1) takes its stream too.  PRECONDITION (host): step_draw + n_steps + rounds <= 2^63, HmcRunArgs' bit-63 rule.
-//   * Registers (hipcc of ROCm 7.2.0 at -O3, profiles/hmc_run_exchange.txt): 99 / 118 VGPRs at SPT 1 / 2, no scratch,
+//   * Registers (hipcc of ROCm 7.2.0 at -O3, profiles/hmc_run_exchange.txt): 97 / 117 VGPRs at SPT 1 / 2, no scratch,
 //     under the 128 that sixteen waves per CU leave.  SPT 4 (513 .. 1024 sites) takes 128 VGPRs AND scratch -- its
 //     ladder form already sits at 126 --, so it is not shipped: those lattices are not served.  To read its resources,
 //     compile this file with -DL2HMC_HMC_EXCHANGE_SPT4 (an explicit instantiation at the end of the file, nothing else).
@@ -896,7 +921,7 @@ __global__ __launch_bounds__(kHmcExchangeThreads) void hmc_run_exchange_kernel(c
       // the pair of the row's chain, as the ladder run reads it; a dead row (x = v = 0) reads neither array
       const float beta = live ? bs[c * ra.chain_stride] : 0.f;
       const float eps = live && ra.eps_chain ? ra.eps_chain[c] : p.eps;
-      hmc_step<SPT>(q, gs, ws, HmcRowValues{beta, eps}, kz, c, live, x0, x1, ra.ngrp, ra.npart);
+      hmc_step<SPT, SPT != 4>(q, gs, ws, HmcRowValues{beta, eps}, kz, c, live, x0, x1, ra.ngrp, ra.npart);
     }
     const bool round = (ra.swap_phase + s + 1) % ra.swap_every == 0;  // uniform over the grid
     if (round) {

@@ -15,7 +15,10 @@
  *   - nothing allocates, frees or synchronises: work is enqueued on `stream`
  *     (a hipStream_t passed as void*; NULL = the default stream); scratch
  *     comes from the caller through (ws, ws_bytes), sized by the *_ws_bytes
- *     queries, so calls are hipGraph-capturable;
+ *     queries, so calls are hipGraph-capturable; a workspace's content on
+ *     entry is arbitrary and is not preserved (no entry reads what an earlier
+ *     call left there, but a train_backward its train_forward's tape): only
+ *     the documented ticket words of step_sums must be zero on entry;
  *   - inputs are never written; outputs never alias inputs unless documented;
  *   - return value: L2HMC_OK or an error code; l2hmc_last_error() gives text.
  *     Shape/argument violations are rejected on the host before any launch;

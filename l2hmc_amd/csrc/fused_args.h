@@ -45,7 +45,7 @@ struct FusedArgs {
   // step_hand and take the pair's ticket; the one that arrives last mixes, accepts and measures the 16 chains.
   int step_split;
   float* step_hand;                      // [workgroups][2 * 16 * D + 16]: x rows, v rows, accept probabilities
-  int* step_ticket;                      // [workgroups / 2], zero on entry (a memset ahead of the launch)
+  int* step_ticket;                      // [workgroups / 2], zero on entry (a clear kernel ahead of the launch), left 0
   const int* heads_meta;                 // l2hmc_gauge_pack_heads image (step_split only), or NULL = all columns:
   const float* heads_img;                //   [N][2] eligibility, [N][2][D / 2] columns, [N][D] compact k; [N][2] packed heads sections
   const float* l1_img;                   // its [N][2] kept-column first-layer sections (needs heads_img), or NULL = full K

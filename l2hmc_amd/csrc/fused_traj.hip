@@ -1121,6 +1121,9 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         if (got == 1) {
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          // nobody takes this ticket again in this launch: it is left at 0, as the step sums' ticket is (the clear
+          // kernel ahead of the launch stays: a workspace holds anything on entry)
+          __hip_atomic_store(p.step_ticket + (blockIdx.x >> 1), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         is_last[0] = got == 1;
       }
@@ -1173,6 +1176,12 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
   }
 #endif
   traj_write_back<kFM, kFThreads, D, SX>(p, wg, xs, vs);
+}
+
+// the split form's pair tickets -> 0, launched on the step's stream right ahead of the split kernel
+__global__ __launch_bounds__(256) void clear_tickets_kernel(int* __restrict__ tickets, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) tickets[i] = 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1493,10 +1502,11 @@ int launch_fused_step(const l2hmc_gauge_plan* p, float beta, const float* x_in, 
       a.heads_meta = hmeta;
       a.heads_img = himg;
       a.l1_img = l1img;
-      if (hipMemsetAsync(a.step_ticket, 0, sizeof(int) * (size_t)pairs, stream) != hipSuccess) {
-        set_error("fused step: cannot clear the hand-off tickets");
-        return L2HMC_ERR_HIP;
-      }
+      // the tickets are cleared by a kernel of the step itself, never by a memset: a captured step is kernel nodes
+      // only, each ordered behind the one before it, and the workspace may hold anything on entry
+      hipLaunchKernelGGL(clear_tickets_kernel, dim3((unsigned)ceil_div(pairs, (int64_t)256)), dim3(256), 0, stream,
+                         a.step_ticket, pairs);
+      L2HMC_CHECK_LAUNCH("fused step: clear of the hand-off tickets");
     }
     const unsigned nwg = (unsigned)(a.rows / kFM);
     prof_before(kProfFused, stream);

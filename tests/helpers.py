@@ -1,5 +1,7 @@
 """Shared builders for the parity tests: an oracle and a HIP-backed dynamics
 object holding the same weights, masks and step size."""
+import ctypes as C
+
 import numpy as np
 
 from oracle import nets
@@ -86,3 +88,32 @@ def mlp_weights(x_dim, num_nodes, seed=106, regime="stress"):
     kw = REGIMES[regime]
     return (nets.init_mlp_net(rng, x_dim, 2., num_nodes, **kw),
             nets.init_mlp_net(rng, x_dim, 1., num_nodes, **kw))
+
+
+# ---- HIP graph capture (shared by the capture tests)
+def _hip():
+    """The HIP runtime this process already runs on (torch's own copy first, if it ships one)."""
+    paths = sorted({l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l}, key=lambda p: "torch" not in p)
+    assert paths, "the HIP runtime is not mapped into this process"
+    return C.CDLL(paths[0])
+
+
+def _graph_shape(hip, stream):
+    """(kernel nodes, other nodes, edges) of the graph `stream` is capturing into."""
+    status, gid, graph = C.c_int(), C.c_ulonglong(), C.c_void_p()
+    deps, ndeps = C.c_void_p(), C.c_size_t()
+    assert hip.hipStreamGetCaptureInfo_v2(C.c_void_p(stream), C.byref(status), C.byref(gid), C.byref(graph),
+                                          C.byref(deps), C.byref(ndeps)) == 0
+    assert status.value == 1 and graph.value                        # hipStreamCaptureStatusActive
+    n = C.c_size_t()
+    assert hip.hipGraphGetNodes(graph, None, C.byref(n)) == 0
+    nodes = (C.c_void_p * max(n.value, 1))()
+    assert hip.hipGraphGetNodes(graph, nodes, C.byref(n)) == 0
+    kernels = 0
+    for i in range(n.value):
+        kind = C.c_int()
+        assert hip.hipGraphNodeGetType(C.c_void_p(nodes[i]), C.byref(kind)) == 0
+        kernels += kind.value == 0                                  # hipGraphNodeTypeKernel
+    e = C.c_size_t()
+    assert hip.hipGraphGetEdges(graph, None, None, C.byref(e)) == 0
+    return kernels, n.value - kernels, e.value

@@ -294,9 +294,9 @@ def test_rungs_order_their_plaquettes(la, both):
 def test_a_ladder_step_is_graph_capturable(la, kind, both):
     """No allocation and no synchronisation inside the entry: one ladder step -- one launch, or the three kernel
     launches of a cut batch -- is captured into a HIP graph and replayed twice, and every output equals the eager
-    step's.  (The cut batch is taken selected-only: with both directions its 16-row part is the split form, whose graph
-    holds a memset node for the hand-off tickets ahead of the kernel; that is launch_fused_step's, shared with the
-    uniform step and covered by its capture test, not the ladder's.)"""
+    step's.  (The cut batch is taken selected-only: with both directions its 16-row part is the split form with its
+    hand-off tickets; that is launch_fused_step's, shared with the uniform step, and
+    tests/test_gpu_workspace_state.py replays it, at one beta and on a ladder.)"""
     from l2hmc_amd import _lib
     B, _ = _batch(kind, both)
     dyn = _dyn(8, 8, 2, 0.2, B, both=both)

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import helpers as H
+from tests.helpers import _graph_shape, _hip            # noqa: F401  (tests/test_gpu_small_run_exchange.py imports them from here)
 from tests.run_cases import assert_same_run, count_launches
 
 pytestmark = pytest.mark.gpu
@@ -222,34 +223,6 @@ def test_generate_trajectories_sets_and_restores_the_temperature(la):
 
 
 # ----------------------------------------------------------------- 7. graph capture
-def _hip():
-    """The HIP runtime this process already runs on (torch's own copy first, if it ships one)."""
-    paths = sorted({l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l}, key=lambda p: "torch" not in p)
-    assert paths, "the HIP runtime is not mapped into this process"
-    return C.CDLL(paths[0])
-
-
-def _graph_shape(hip, stream):
-    """(kernel nodes, other nodes, edges) of the graph `stream` is capturing into."""
-    status, gid, graph = C.c_int(), C.c_ulonglong(), C.c_void_p()
-    deps, ndeps = C.c_void_p(), C.c_size_t()
-    assert hip.hipStreamGetCaptureInfo_v2(C.c_void_p(stream), C.byref(status), C.byref(gid), C.byref(graph),
-                                          C.byref(deps), C.byref(ndeps)) == 0
-    assert status.value == 1 and graph.value                        # hipStreamCaptureStatusActive
-    n = C.c_size_t()
-    assert hip.hipGraphGetNodes(graph, None, C.byref(n)) == 0
-    nodes = (C.c_void_p * max(n.value, 1))()
-    assert hip.hipGraphGetNodes(graph, nodes, C.byref(n)) == 0
-    kernels = 0
-    for i in range(n.value):
-        kind = C.c_int()
-        assert hip.hipGraphNodeGetType(C.c_void_p(nodes[i]), C.byref(kind)) == 0
-        kernels += kind.value == 0                                  # hipGraphNodeTypeKernel
-    e = C.c_size_t()
-    assert hip.hipGraphGetEdges(graph, None, None, C.byref(e)) == 0
-    return kernels, n.value - kernels, e.value
-
-
 def test_a_run_is_captured_as_one_kernel_node_and_replays_the_eager_bits(la):
     from l2hmc_amd import _lib
     L, n, B = _lib.lib(), 4, 70

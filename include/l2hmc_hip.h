@@ -234,7 +234,7 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
                                       * between MCMC steps is harmless and the chain exact for any weights.  Runs layer by
                                       * layer, every first-layer product formed anew: l2hmc_gauge_plan_fused() == 0 (unless
                                       * L2HMC_PLAN_PERIODIC_STEP selects the mode's whole-step kernel), and the
-                                      * l2hmc_gauge_train_* entries refuse the plan */
+                                      * l2hmc_gauge_train_* entries refuse the plan (unless L2HMC_PLAN_PERIODIC_TRAIN is set) */
 #define L2HMC_PLAN_PERIODIC_STEP 512 /* with L2HMC_PLAN_PERIODIC only (without it an hmc = 0 plan is refused; ignored with
                                       * hmc = 1; L2HMC_PLAN_LAYERED wins over it): where the plan has the kernel -- GenericNet,
                                       * D = 128 with X a power of two (8x8, 4x16, ...), H = 512, both nets' .packed set -- the
@@ -244,6 +244,16 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
                                       * runs layer by layer.  L2HMC_PLAN_RECOMPUTE switches the kept first-layer products of
                                       * that kernel off (same bits); TILES16_ONLY, ALL_COLUMNS, FULL_L1 and SINGLE_KICKS do
                                       * nothing there.  l2hmc_gauge_transition_ladder and the training entries are unchanged */
+#define L2HMC_PLAN_PERIODIC_TRAIN 1024 /* with L2HMC_PLAN_PERIODIC only (without it an hmc = 0 plan is refused; ignored with
+                                      * hmc = 1): the l2hmc_gauge_train_* entries take the torus-exact plan instead of
+                                      * refusing it, layer by layer on the tiled kernels -- GenericNet with D and H multiples
+                                      * of 32 (T * X a multiple of 16: 4x4, 2x8, 4x8, 8x8, 16x16, ...), XNet Ka = D, Kb = 2D,
+                                      * VNet Ka = 2D, Kb = D; other widths are refused with the widths named.  The taped
+                                      * first-layer input of a call is 3D wide, [cos x | sin x | beta force] for VNet and
+                                      * [v | keep cos x | keep sin x] for XNet, and the position sub-update and its reverse are
+                                      * l2hmc_lf_update_x_ncp's.  Every sampling entry ignores the flag (same bits, same
+                                      * l2hmc_gauge_ws_bytes); it composes with L2HMC_PLAN_PERIODIC_STEP.  Workspace: see
+                                      * l2hmc_gauge_train_ws_bytes */
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */
@@ -558,6 +568,13 @@ typedef struct l2hmc_conv3d_grads {
   float* w1_b; float* b1_b; float* w2_b; float* b2_b;   /* second input */
 } l2hmc_conv3d_grads;
 
+/* Bytes of the tape and scratch of one training step over `rows` rows (0 for hmc = 1).  A plan with
+ * L2HMC_PLAN_PERIODIC | L2HMC_PLAN_PERIODIC_TRAIN tapes a first-layer input of 3D columns per network call instead of
+ * 2D and carries a [rows][3D] input cotangent instead of [rows][2D]; against the same plan without
+ * L2HMC_PLAN_PERIODIC_TRAIN it takes, with N = num_steps and D = 2*T*X (a multiple of 32),
+ *   2 * (2 N * rows * D * 4)  +  round_up(rows * 3 D * 4, 256) - rows * 2 D * 4   bytes more
+ * (both networks' input tapes, and the input cotangent rounded to the 256-byte grid every section starts on).  No other
+ * plan's size depends on the flag. */
 size_t l2hmc_gauge_train_ws_bytes(const l2hmc_gauge_plan* plan, int64_t rows);
 /* Same outputs as l2hmc_gauge_trajectory (dir: per-row 0 forward / 1 backward, NULL = all forward);
  * `ws` must stay untouched until the matching l2hmc_gauge_train_backward has run. */

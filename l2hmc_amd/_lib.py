@@ -22,6 +22,7 @@ PLAN_FULL_L1 = 64
 PLAN_SINGLE_KICKS = 128
 PLAN_PERIODIC = 256
 PLAN_PERIODIC_STEP = 512     # with PLAN_PERIODIC only: the torus-exact mode's whole-step kernel where the plan has it
+PLAN_PERIODIC_TRAIN = 1024   # with PLAN_PERIODIC only: the tiled training entries take the plan (widths multiples of 32)
 GRAD_BUCKET_REST = 6
 BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32)
 

@@ -13,6 +13,9 @@ With a beta per chain (`dyn(x, ladder)`, ladder [B]) the same three steps run on
 stride 1): chain i is differentiated at ladder[i], with the bits of the scalar call at that value.  The ladder's values
 are not differentiated.
 
+A torus-exact dynamics (`periodic=True`) is differentiated only with `tiled_train=True` (L2HMC_PLAN_PERIODIC_TRAIN), where
+the same entries take its plan; without the flag, or at widths that are no multiples of 32, it is refused.
+
 Every call owns its tape (a train workspace), the plan and the packed weight buffers it ran with, so several
 transitions may be differentiated by one backward (the reference loss runs two: x and z).  The tape is freed
 after the backward; a second backward through the same graph is an error."""
@@ -45,7 +48,8 @@ def check_differentiable(dyn):
     if dyn.hmc:
         raise NotImplementedError("autograd through GaugeDynamics: hmc=True dynamics have no networks; the "
                                   "training entries take L2HMC plans only")
-    if getattr(dyn, "periodic", False):
+    # (tiled_train=True -- L2HMC_PLAN_PERIODIC_TRAIN -- lets the mode through to the width check below)
+    if getattr(dyn, "periodic", False) and not getattr(dyn, "tiled_train", False):
         raise NotImplementedError("autograd through GaugeDynamics: periodic=True dynamics have no tiled training "
                                   "entries; they would need the layered reverse walk, which torch.autograd is refused "
                                   "at today for every shape whose widths are no multiples of 32 (GaugeTrainer trains "

@@ -290,6 +290,9 @@ static int check_plan(const l2hmc_gauge_plan* p) {
     L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_STEP) || (p->flags & L2HMC_PLAN_PERIODIC),
                   "plan: L2HMC_PLAN_PERIODIC_STEP selects the whole-step kernel of a torus-exact plan and needs "
                   "L2HMC_PLAN_PERIODIC with it");
+    L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_TRAIN) || (p->flags & L2HMC_PLAN_PERIODIC),
+                  "plan: L2HMC_PLAN_PERIODIC_TRAIN opens the tiled training entries to a torus-exact plan and needs "
+                  "L2HMC_PLAN_PERIODIC with it");
     L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC) || !(p->flags & L2HMC_PLAN_CONV3D),
                   "plan: L2HMC_PLAN_PERIODIC takes GenericNet networks only (no ConvNet3D front-end of [cos x | sin x])");
     const l2hmc_dense_net* nets[2] = {&p->xnet, &p->vnet};

@@ -237,6 +237,188 @@ __global__ __launch_bounds__(256) void vnet_in_bwd_kernel(const float* __restric
   }
 }
 
+// =====================================================================
+// torus-exact plans (L2HMC_PLAN_PERIODIC | L2HMC_PLAN_PERIODIC_TRAIN): the element-wise stages around the same
+// products.  x reaches a network as [cos x | sin x], so a call's first-layer input is 3D wide, and the position
+// sub-update is lf_drift_ncp.  Kernels of their own: the reference mode's instances above stay the code they are.
+// =====================================================================
+
+// XNET: in[row] = [v | keep cos x | keep sin x] (o = v, keep of the row's direction), st[row] = x
+// VNet: in[row] = [cos x | sin x | g]            (o = g = beta * force),               st[row] = v
+// sincosf is libm's, as in l2hmc_u1_angle_features (one wave per row)
+template <bool XNET>
+__global__ __launch_bounds__(256) void tape_in_ncp_kernel(const float* __restrict__ x, const float* __restrict__ o,
+                                                          const float* __restrict__ keep_f,
+                                                          const float* __restrict__ keep_b,
+                                                          const int* __restrict__ dir,
+                                                          const float* __restrict__ state, int64_t rows, int D,
+                                                          float* __restrict__ in, float* __restrict__ st) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int d = dir ? dir[row] : 0;
+  const float* keep = XNET ? (d ? keep_b : keep_f) : nullptr;
+  float* r = in + row * 3 * D;
+  for (int c = lane; c < D; c += kWave) {
+    float sn, cs;
+    sincosf(x[row * D + c], &sn, &cs);
+    if (XNET) {
+      const float k = keep[c];
+      r[c] = o[row * D + c];
+      r[D + c] = k * cs;
+      r[2 * D + c] = k * sn;
+    } else {
+      r[c] = cs;
+      r[D + c] = sn;
+      r[2 * D + c] = o[row * D + c];
+    }
+    st[row * D + c] = state[row * D + c];
+  }
+}
+
+// position sub-update on the circle from materialised S/T/Q, in place, logdet += (one wave per row)
+__global__ __launch_bounds__(256) void train_update_ncp_kernel(const float* __restrict__ stq, int64_t plane,
+                                                               const float* __restrict__ keep_f,
+                                                               const float* __restrict__ keep_b,
+                                                               const int* __restrict__ dir, float eps, int64_t rows,
+                                                               int D, float* x, const float* __restrict__ v,
+                                                               float* ld) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int d = dir ? dir[row] : 0;
+  float acc = 0.f;
+  for (int c = lane; c < D; c += kWave) {
+    const int64_t i = row * D + c;
+    float s, omk;
+    x[i] = lf_drift_ncp<ExpLibm>(x[i], v[i], (d ? keep_b : keep_f)[c], stq[i], stq[plane + i], stq[2 * plane + i], eps,
+                                 d, s, omk);
+    acc += omk * s;
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) ld[row] += acc;
+}
+
+// update_bwd_kernel for the torus-exact plan: `in` is [rows][3D] -- (cos x, sin x, g) in mode 1, (v, m cos x, m sin x)
+// in mode 2 -- and the position update's reverse is lf_drift_ncp_vjp.  Same ownership of columns and rows, same sums.
+__global__ __launch_bounds__(256) void update_bwd_ncp_kernel(UpdBwdArgs p) {
+  __shared__ float red[4];
+  const int D = p.D;
+  const int64_t r0 = (int64_t)blockIdx.x * kUpdRows;
+  const int64_t r1 = r0 + kUpdRows < p.rows ? r0 + kUpdRows : p.rows;
+  const float eps = p.eps;
+  float deps = 0.f;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) {
+    const float ecs = expf(p.cs[c]), ecq = expf(p.cq[c]);
+    float dcs = 0.f, dcq = 0.f;
+    for (int64_t row = r0; row < r1; ++row) {
+      const int64_t i = row * D + c;
+      const int d = p.dir ? p.dir[row] : 0;
+      const float S = p.stq[i], T = p.stq[p.plane + i], Q = p.stq[2 * p.plane + i];
+      const float dl = p.dld[row];
+      float dS, dT, dQ;
+      if (p.mode == 1) {
+        lf_kick_vjp(p.st[i], p.in[row * 3 * D + 2 * D + c], S, T, Q, eps, d, p.dv[i], dl, p.dv[i], p.dg[i], dS, dT, dQ, deps);
+      } else {
+        float eq;
+        lf_drift_ncp_vjp(p.st[i], p.in[row * 3 * D + c], (d ? p.keep_b : p.keep_f)[c], S, T, Q, eps, d, p.dx[i], dl,
+                         p.dx[i], dS, dT, dQ, eq, deps);
+        p.dv[i] += dT * eq;
+      }
+      // through tanh(.) * exp(coeff) (generic_net.py:139-144)
+      const float th = S / ecs;
+      float daq = dQ * ecq;
+      if (p.q_tanh) {
+        const float tq = Q / ecq;
+        daq *= 1.f - tq * tq;
+      }
+      dcs += dS * S;
+      dcq += dQ * Q;
+      float* o = p.dout + row * 3 * D + c;
+      o[0] = dS * ecs * (1.f - th * th);
+      o[D] = dT;
+      o[2 * D] = daq;
+    }
+    p.dcs_part[(int64_t)blockIdx.x * D + c] += dcs;
+    p.dcq_part[(int64_t)blockIdx.x * D + c] += dcq;
+  }
+  deps = wave_sum(deps);
+  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[wave] = deps;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < nw; ++i) t += red[i];
+    p.deps_part[blockIdx.x] += t;
+  }
+}
+
+// position-network inputs (v, m cos x, m sin x): dv += din[:, :D], dx += -(m sin x) dcos + (m cos x) dsin -- the taped
+// masked features are those factors (m is 0 or 1)
+__global__ __launch_bounds__(256) void xnet_in_bwd_ncp_kernel(const float* __restrict__ din,
+                                                              const float* __restrict__ in, int64_t rows, int D,
+                                                              float* dx, float* dv) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* f = in + row * 3 * D;
+  const float* g = din + row * 3 * D;
+  for (int c = lane; c < D; c += kWave) {
+    dv[row * D + c] += g[c];
+    dx[row * D + c] += f[D + c] * g[2 * D + c] - f[2 * D + c] * g[D + c];
+  }
+}
+
+// momentum-network inputs (cos x, sin x, g = beta * grad_action(x)):
+//   dx += -sin x . din[:, :D] + cos x . din[:, D:2D] + beta * Hess(action)(x) . (dg + din[:, 2D:])
+// The Hessian-vector product is vnet_in_bwd_kernel's.  It needs the plaquettes of x, and the tape holds only the
+// features: x is recovered as atan2(sin x, cos x) -- its principal value, which is enough for a force that is
+// 2 pi-periodic in every link.  One wave per chain, chain staged in LDS.
+__global__ __launch_bounds__(256) void vnet_in_bwd_ncp_kernel(const float* __restrict__ din,
+                                                              const float* __restrict__ dg,
+                                                              const float* __restrict__ in, RowBeta rbeta, int T,
+                                                              int X, int64_t rows, float* dx) {
+  extern __shared__ float lds[];
+  const int D = 2 * T * X, sites = T * X;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+  float* xs = lds + (size_t)wave * (2 * D + sites);
+  float* us = xs + D;
+  float* cp = us + D;
+  const float* f = in + row * 3 * D;
+  const float* g = din + row * 3 * D;
+  if (row < rows) {
+    for (int c = lane; c < D; c += kWave) {
+      xs[c] = atan2f(f[D + c], f[c]);
+      us[c] = dg[row * D + c] + g[2 * D + c];
+    }
+  }
+  __syncthreads();
+  if (row < rows) {
+    for (int s = lane; s < sites; s += kWave) {
+      const int i = s / X, j = s - i * X;
+      const int jr = (j + 1 == X) ? 0 : j + 1, id = (i + 1 == T) ? 0 : i + 1;
+      const int e = 2 * s, er = 2 * (i * X + jr), ed = 2 * (id * X + j);
+      const float P = xs[e] - xs[e + 1] - xs[er] + xs[ed + 1];
+      const float Pu = us[e] - us[e + 1] - us[er] + us[ed + 1];
+      cp[s] = cosf(P) * Pu;
+    }
+  }
+  __syncthreads();
+  if (row < rows) {
+    const float beta = rbeta.at(row);
+    for (int s = lane; s < sites; s += kWave) {
+      const int i = s / X, j = s - i * X;
+      const int jl = (j == 0) ? X - 1 : j - 1, iu = (i == 0) ? T - 1 : i - 1;
+      const float c = cp[s];
+      const float h0 = c - cp[i * X + jl], h1 = -c + cp[iu * X + j];
+      const int e = 2 * s;
+      dx[row * D + e] += (f[e] * g[D + e] - f[D + e] * g[e]) + beta * h0;
+      dx[row * D + e + 1] += (f[e + 1] * g[D + e + 1] - f[D + e + 1] * g[e + 1]) + beta * h1;
+    }
+  }
+}
+
 // column sums of a taped [calls * rows][n] array (bias gradients), optionally also weighted by the
 // (cos, sin) time input of each (call, row) -- the t_layer kernel's gradient (generic_net.py:131).
 // HBM-bound: every thread streams 16-byte pieces of consecutive rows; a workgroup covers up to 1024
@@ -866,6 +1048,11 @@ static int tn_splits(int mt, int nt, int64_t R) {
   return (int)hmin(s, maxs);
 }
 
+// torus-exact plans the tiled entries take: the element-wise stages are the _ncp kernels, `in` and `din` are 3D wide
+static bool plan_ncp_train(const l2hmc_gauge_plan* p) {
+  return (p->flags & L2HMC_PLAN_PERIODIC) && (p->flags & L2HMC_PLAN_PERIODIC_TRAIN);
+}
+
 static TrainWs carve_train_ws(const l2hmc_gauge_plan* p, int64_t rows, void* ws) {
   TrainWs w{};
   const int D = 2 * p->T * p->X;
@@ -880,6 +1067,7 @@ static TrainWs carve_train_ws(const l2hmc_gauge_plan* p, int64_t rows, void* ws)
   const l2hmc_dense_net* nets[2] = {&p->xnet, &p->vnet};
   const l2hmc_conv3d_front* fronts[2] = {&p->xfront, &p->vfront};
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
+  const bool ncp = plan_ncp_train(p);                  // (every other plan: not a byte more)
   NetTape* tapes[2] = {&w.x, &w.v};
   size_t part_max = 0;
   int kin_max = 2 * D;
@@ -889,7 +1077,7 @@ static TrainWs carve_train_ws(const l2hmc_gauge_plan* p, int64_t rows, void* ws)
     kin_max = hmax(kin_max, Kin);
     NetTape& t = *tapes[k];
     const size_t cr = (size_t)C * rows;
-    t.in = take(cr * 2 * D);
+    t.in = take(cr * (ncp ? Kin : 2 * D));
     t.h1 = take(cr * H);
     t.h2 = take(cr * H);
     t.stq = take(cr * 3 * D);
@@ -921,7 +1109,7 @@ static TrainWs carve_train_ws(const l2hmc_gauge_plan* p, int64_t rows, void* ws)
   w.act0 = take(rows); w.kin0 = take(rows); w.act1 = take(rows); w.kin1 = take(rows);
   w.g = take((size_t)rows * D);
   w.dg = take((size_t)rows * D);
-  w.din = take((size_t)rows * 2 * D);
+  w.din = take((size_t)rows * (ncp ? kin_max : 2 * D));
   w.dfeat = conv ? take((size_t)rows * kin_max) : nullptr;
   w.part = take(part_max);
   // the += accumulators of the reverse pass, contiguous: one memset clears them all
@@ -941,20 +1129,33 @@ static int check_train_plan(const l2hmc_gauge_plan* p) {
   L2HMC_REQUIRE(p != nullptr, "train: NULL plan");
   L2HMC_REQUIRE(p->T > 0 && p->X > 0 && p->num_steps > 0 && p->masks != nullptr, "train: bad plan");
   L2HMC_REQUIRE(!p->hmc, "train: hmc plans have no trainable networks");
-  L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC),
+  L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_TRAIN) || (p->flags & L2HMC_PLAN_PERIODIC),
+                "train: L2HMC_PLAN_PERIODIC_TRAIN opens the tiled training entries to a torus-exact plan and needs "
+                "L2HMC_PLAN_PERIODIC with it");
+  const bool ncp = plan_ncp_train(p);
+  L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC) || ncp,
                 "train: L2HMC_PLAN_PERIODIC plans train through the layered-training entries (l2hmc_stq_dense_taped, "
                 "l2hmc_lf_update_x_ncp_vjp, l2hmc_u1_angle_features_vjp); the tiled entries have no such form");
   const bool conv = (p->flags & L2HMC_PLAN_CONV3D) != 0;
+  L2HMC_REQUIRE(!ncp || !conv, "train: L2HMC_PLAN_PERIODIC_TRAIN takes GenericNet networks only (no ConvNet3D "
+                "front-end of [cos x | sin x])");
   const int D = 2 * p->T * p->X;
   const l2hmc_dense_net* nets[2] = {&p->xnet, &p->vnet};
   const l2hmc_conv3d_front* fronts[2] = {&p->xfront, &p->vfront};
   for (int k = 0; k < 2; ++k) {
     const l2hmc_dense_net* n = nets[k];
     const int kin = conv ? conv3d_nflat(p->T, p->X, fronts[k]->F) : D;
-    // the training kernels (taped forward, TN weight-gradient products, column sums) stage 32-wide k-tiles only
-    L2HMC_REQUIRE(dense_net_tileable(n) && n->D % 32 == 0 && n->D == D && n->Ka == kin && n->Kb == kin,
-                  "train: network widths (D=%d Ka=%d Kb=%d H=%d) must be multiples of 32 with Ka = Kb = %d",
-                  n->D, n->Ka, n->Kb, n->H, kin);
+    if (ncp) {        // x enters as [cos x | sin x]: XNet's (masked) second input, VNet's first
+      const int ka = k == 1 ? 2 * D : D, kb = k == 1 ? D : 2 * D;
+      L2HMC_REQUIRE(dense_net_tileable(n) && n->D % 32 == 0 && n->D == D && n->Ka == ka && n->Kb == kb,
+                    "train: periodic %s widths (D=%d Ka=%d Kb=%d H=%d) must be multiples of 32 with D = %d, Ka = %d, "
+                    "Kb = %d", k == 1 ? "VNet" : "XNet", n->D, n->Ka, n->Kb, n->H, D, ka, kb);
+    } else {
+      // the training kernels (taped forward, TN weight-gradient products, column sums) stage 32-wide k-tiles only
+      L2HMC_REQUIRE(dense_net_tileable(n) && n->D % 32 == 0 && n->D == D && n->Ka == kin && n->Kb == kin,
+                    "train: network widths (D=%d Ka=%d Kb=%d H=%d) must be multiples of 32 with Ka = Kb = %d",
+                    n->D, n->Ka, n->Kb, n->H, kin);
+    }
     if (conv) {
       const l2hmc_conv3d_front* f = fronts[k];
       L2HMC_REQUIRE(f->F > 0 && f->w1_a && f->b1_a && f->w2_a && f->b2_a && f->w1_b && f->b1_b && f->w2_b && f->b2_b,
@@ -978,16 +1179,26 @@ static int taped_call(const l2hmc_gauge_plan* p, const l2hmc_dense_net* net, con
                       const float* keep_f, const float* keep_b, const int* dir, const float tcs[4], int64_t rows,
                       float* x, float* v, const TrainWs& w, hipStream_t s) {
   const int D = net->D, H = net->H;
+  const int Kin = net->Ka + net->Kb;
+  const bool ncp = plan_ncp_train(p);
   const size_t cr = (size_t)call * rows;
-  float* in = t.in + cr * 2 * D;
+  float* in = t.in + cr * (ncp ? Kin : 2 * D);
   float* h1 = t.h1 + cr * H;
   float* h2 = t.h2 + cr * H;
   float* stq = t.stq + cr * 3 * D;
   const unsigned rgrid = (unsigned)ceil_div(rows, 4);
-  hipLaunchKernelGGL(tape_in_kernel, dim3(rgrid), dim3(256), 0, s, a, b, cm_f, cm_b, dir, state, rows, D, in,
-                     t.st + cr * D);
+  if (ncp) {          // mode 2: XNet on (v, keep . [cos x | sin x]); mode 1: VNet on ([cos x | sin x], g)
+    if (mode == 2)
+      hipLaunchKernelGGL(tape_in_ncp_kernel<true>, dim3(rgrid), dim3(256), 0, s, b, a, cm_f, cm_b, dir, state, rows, D,
+                         in, t.st + cr * D);
+    else
+      hipLaunchKernelGGL(tape_in_ncp_kernel<false>, dim3(rgrid), dim3(256), 0, s, a, b, nullptr, nullptr, dir, state,
+                         rows, D, in, t.st + cr * D);
+  } else {
+    hipLaunchKernelGGL(tape_in_kernel, dim3(rgrid), dim3(256), 0, s, a, b, cm_f, cm_b, dir, state, rows, D, in,
+                       t.st + cr * D);
+  }
   L2HMC_CHECK_LAUNCH("tape_in");
-  const int Kin = net->Ka + net->Kb;
   const float* first_in = in;
   if (p->flags & L2HMC_PLAN_CONV3D) {
     // conv_net.py:251-262 on the taped (already masked) inputs; the features are taped for the first layer's
@@ -1022,8 +1233,12 @@ static int taped_call(const l2hmc_gauge_plan* p, const l2hmc_dense_net* net, con
   h.q_tanh = net->q_tanh; h.D = D; h.rows = rows; h.mode = kHeadsMaterialise;
   h.S = stq; h.T = stq + (size_t)rows * D; h.Q = stq + 2 * (size_t)rows * D;
   if (int e = launch_heads(h, s)) return e;
-  hipLaunchKernelGGL(train_update_kernel, dim3(rgrid), dim3(256), 0, s, mode, stq, (int64_t)rows * D, w.g, keep_f,
-                     keep_b, dir, p->eps, rows, D, x, v, w.ld);
+  if (ncp && mode == 2)
+    hipLaunchKernelGGL(train_update_ncp_kernel, dim3(rgrid), dim3(256), 0, s, stq, (int64_t)rows * D, keep_f, keep_b,
+                       dir, p->eps, rows, D, x, v, w.ld);
+  else
+    hipLaunchKernelGGL(train_update_kernel, dim3(rgrid), dim3(256), 0, s, mode, stq, (int64_t)rows * D, w.g, keep_f,
+                       keep_b, dir, p->eps, rows, D, x, v, w.ld);
   L2HMC_CHECK_LAUNCH("train_update");
   return L2HMC_OK;
 }
@@ -1312,8 +1527,11 @@ static int train_backward_impl(const l2hmc_gauge_plan* plan, RowBeta beta, const
   const unsigned rgrid = (unsigned)ceil_div(rows, 4);
   const size_t vlds = sizeof(float) * 4 * (size_t)(2 * D + D / 2);
   L2HMC_REQUIRE(vlds <= 160 * 1024, "train_backward: lattice too large for the force-Hessian kernel's LDS");
+  const bool ncp = plan_ncp_train(plan);
+  const int inw = ncp ? 3 * D : 2 * D;                    // width of a taped first-layer input row
   if (vlds > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vnet_in_bwd_kernel),
+    (void)hipFuncSetAttribute(ncp ? reinterpret_cast<const void*>(&vnet_in_bwd_ncp_kernel)
+                                  : reinterpret_cast<const void*>(&vnet_in_bwd_kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlds);
   const int ublock = (int)hmin(256, (int64_t)align_up((size_t)D, 64));
   if (trunk) {
@@ -1341,13 +1559,14 @@ static int train_backward_impl(const l2hmc_gauge_plan* plan, RowBeta beta, const
     UpdBwdArgs a{};
     a.mode = mode; a.rows = rows; a.D = D; a.eps = plan->eps;
     a.stq = t.stq + cr * 3 * D; a.plane = (int64_t)rows * D;
-    a.st = t.st + cr * D; a.in = t.in + cr * 2 * D;
+    a.st = t.st + cr * D; a.in = t.in + cr * inw;
     a.keep_f = kf; a.keep_b = kb; a.dir = dir;
     a.cs = net->coeff_s; a.cq = net->coeff_q; a.q_tanh = net->q_tanh;
     a.dld = dlogdet; a.dx = dx; a.dv = dv; a.dg = w.dg;
     a.dout = t.dout + cr * 3 * D;
     a.dcs_part = t.dcs_part; a.dcq_part = t.dcq_part; a.deps_part = w.eps_part;
-    hipLaunchKernelGGL(update_bwd_kernel, dim3((unsigned)nblk), dim3(ublock), 0, s, a);
+    if (ncp) hipLaunchKernelGGL(update_bwd_ncp_kernel, dim3((unsigned)nblk), dim3(ublock), 0, s, a);
+    else hipLaunchKernelGGL(update_bwd_kernel, dim3((unsigned)nblk), dim3(ublock), 0, s, a);
     L2HMC_CHECK_LAUNCH("update_bwd");
     return call_backward_data(plan, net, t, call, rows, w, s);
   };
@@ -1372,15 +1591,23 @@ static int train_backward_impl(const l2hmc_gauge_plan* plan, RowBeta beta, const
       for (int half = 1; half >= 0; --half) {
         const int vc = 2 * step + half;
         if (int e = upd(&plan->vnet, w.v, vc, 1, nullptr, nullptr)) return e;
-        hipLaunchKernelGGL(vnet_in_bwd_kernel, dim3(rgrid), dim3(256), vlds, s, w.din,
-                           w.dg, w.v.in + (size_t)vc * rows * 2 * D, beta, plan->T, plan->X, rows, dx);
+        if (ncp)
+          hipLaunchKernelGGL(vnet_in_bwd_ncp_kernel, dim3(rgrid), dim3(256), vlds, s, w.din, w.dg,
+                             w.v.in + (size_t)vc * rows * inw, beta, plan->T, plan->X, rows, dx);
+        else
+          hipLaunchKernelGGL(vnet_in_bwd_kernel, dim3(rgrid), dim3(256), vlds, s, w.din,
+                             w.dg, w.v.in + (size_t)vc * rows * 2 * D, beta, plan->T, plan->X, rows, dx);
         L2HMC_CHECK_LAUNCH("vnet_in_bwd");
         if (half == 1) {
           for (int sub = 1; sub >= 0; --sub) {
             const float* kf = sub == 0 ? m_f : mi_f;
             const float* kb = sub == 0 ? mi_b : m_b;
             if (int e = upd(&plan->xnet, w.x, 2 * step + sub, 2, kf, kb)) return e;
-            hipLaunchKernelGGL(xnet_in_bwd_kernel, dim3(rgrid), dim3(256), 0, s, w.din, kf, kb, dir, rows, D, dx, dv);
+            if (ncp)
+              hipLaunchKernelGGL(xnet_in_bwd_ncp_kernel, dim3(rgrid), dim3(256), 0, s, w.din,
+                                 w.x.in + (size_t)(2 * step + sub) * rows * inw, rows, D, dx, dv);
+            else
+              hipLaunchKernelGGL(xnet_in_bwd_kernel, dim3(rgrid), dim3(256), 0, s, w.din, kf, kb, dir, rows, D, dx, dv);
             L2HMC_CHECK_LAUNCH("xnet_in_bwd");
           }
         }

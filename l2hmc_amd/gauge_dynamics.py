@@ -57,11 +57,20 @@ class GaugeDynamics:
         # per trajectory or MCMC step where the plan has it (x_dim = 128 with a power-of-two space extent: 8x8, 4x16,
         # ...); any other lattice carries the flag and runs layer by layer.  Sampling only: training is unchanged.
         self.whole_step = False
+        # True (with periodic=True): the tiled training entries take the torus-exact plan (L2HMC_PLAN_PERIODIC_TRAIN) --
+        # GaugeTrainer and torch.autograd then run on l2hmc_gauge_train_* where every network width is a multiple of 32
+        # (T * X a multiple of 16); any other lattice carries the flag and trains on the layered walk.  Training only:
+        # every sampling entry ignores it, and it composes with `whole_step`.
+        self.tiled_train = False
         for key, val in kwargs.items():
             if key != 'eps':             # :73-75
                 setattr(self, key, val)
         self.periodic = bool(self.periodic)
         self.whole_step = bool(self.whole_step)
+        self.tiled_train = bool(self.tiled_train)
+        if self.tiled_train and not self.periodic and not self.hmc:
+            raise ValueError("tiled_train=True opens the tiled training entries to the torus-exact mode and needs "
+                             "periodic=True (the reference mode trains on them already)")
         if self.whole_step and not self.periodic and not self.hmc:
             raise ValueError("whole_step=True selects the whole-step kernel of the torus-exact mode and needs "
                              "periodic=True (the reference mode's one-launch step is `fused`, on by default)")
@@ -173,7 +182,8 @@ class GaugeDynamics:
                            | (_lib.PLAN_FULL_L1 if self.full_l1 else 0)
                            | (_lib.PLAN_SINGLE_KICKS if self.single_kicks else 0)
                            | (_lib.PLAN_PERIODIC if self.periodic and not self.hmc else 0)
-                           | (_lib.PLAN_PERIODIC_STEP if self.whole_step and self.periodic and not self.hmc else 0),
+                           | (_lib.PLAN_PERIODIC_STEP if self.whole_step and self.periodic and not self.hmc else 0)
+                           | (_lib.PLAN_PERIODIC_TRAIN if self.tiled_train and self.periodic and not self.hmc else 0),
                            masks=_lib.dev_ptr(self.mask, name="mask"))
         if not self.hmc:
             p.xnet = self.position_fn.pack()

@@ -16,7 +16,8 @@ direction's outputs by exactly 0, so it contributes exactly 0 to every gradient.
 
 The tiled training entries (l2hmc_gauge_train_*) need every network width to be a multiple of 32; GenericNet
 networks of other widths (lattices whose T * X is not a multiple of 16: 6x6, 3x5, 4x6, ...) are trained through the
-layered-training entries instead (the forward and backward stages of l2hmc_amd/layered_train.py).  Both are the
+layered-training entries instead (the forward and backward stages of l2hmc_amd/layered_train.py), and so is a torus-exact
+dynamics (`periodic=True`) unless `tiled_train=True` opens the tiled entries to it.  Both are the
 forward and the reverse of ONE step body (`calc_loss_and_grads`: stack, forward, loss reverse, reverse, exchange), so
 they share the draws, the flat buffer, the data-parallel exchange and the optimiser (l2hmc_amd/_flat_trainer.py)."""
 import ctypes as C
@@ -253,7 +254,21 @@ class GaugeTrainer(FlatTrainer):
         return loss, x_out, px, x_dq
 
     def _use_layered(self):
-        if getattr(self.dynamics, "periodic", False):      # the tiled entries have no torus-exact form
+        if getattr(self.dynamics, "periodic", False):
+            # tiled_train=True (L2HMC_PLAN_PERIODIC_TRAIN) opens the tiled entries to the mode where the widths tile
+            if getattr(self.dynamics, "tiled_train", False):
+                if self.layered:                           # the walk, as the cross-check
+                    return True
+                packs = [net.pack() for net in self._nets]
+                widths = [(st.D, st.H, st.Ka, st.Kb) for st in packs]
+                if all(w % 32 == 0 for ws in widths for w in ws):
+                    return False
+                if self.layered is not None:               # layered = False where the widths do not tile
+                    raise NotImplementedError(f"GaugeTrainer.layered = False on a periodic=True, tiled_train=True "
+                                              f"dynamics whose network widths (D, H, Ka, Kb) = {widths} are not all "
+                                              "multiples of 32: the tiled training entries refuse them; the layered "
+                                              "walk trains them")
+                return True
             if self.layered is not None and not self.layered:
                 raise NotImplementedError("GaugeTrainer.layered = False on a periodic=True dynamics: the tiled "
                                           "training entries refuse L2HMC_PLAN_PERIODIC plans; the layered walk trains them")

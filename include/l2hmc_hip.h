@@ -254,6 +254,23 @@ int l2hmc_mix_accept(const float* x, const float* xf, const float* vf, const flo
                                       * l2hmc_lf_update_x_ncp's.  Every sampling entry ignores the flag (same bits, same
                                       * l2hmc_gauge_ws_bytes); it composes with L2HMC_PLAN_PERIODIC_STEP.  Workspace: see
                                       * l2hmc_gauge_train_ws_bytes */
+#define L2HMC_PLAN_PERIODIC_TAPE 2048 /* with L2HMC_PLAN_PERIODIC and L2HMC_PLAN_PERIODIC_TRAIN only (without both an hmc = 0
+                                      * plan is refused; ignored with hmc = 1; L2HMC_PLAN_LAYERED wins over it): where the
+                                      * plan has the kernel -- GenericNet, D = 128 with X a power of two (8x8, 4x16, ...),
+                                      * H = 512, both nets' .packed set; L2HMC_PLAN_PERIODIC_STEP is not needed and composes
+                                      * -- l2hmc_gauge_train_forward and l2hmc_gauge_train_forward_ladder run the plan in ONE
+                                      * launch of the mode's whole-trajectory kernel (l2hmc_gauge_plan_train_fused() == 1),
+                                      * which writes the tape the layer-by-layer forward writes, in the same layout: `in`
+                                      * [3D], `st`, h1, h2 and the S / T / Q planes, next to x_out, v_out, sumlogdet and
+                                      * p_accept.  The relu `gate` words of the workspace are NOT written: their only reader
+                                      * is the reference mode's fused reverse kernel, and the reverse pass of a torus-exact
+                                      * plan stays layer by layer on the tiled kernels, gating on h1 > 0 / h2 > 0.  The
+                                      * launch has the bits of the untaped kernel (l2hmc_gauge_trajectory on a
+                                      * L2HMC_PLAN_PERIODIC_STEP plan) on the same rows; against the layer-by-layer taped
+                                      * forward it differs in rounding (fast exp, another k order).  Any other plan carries
+                                      * the flag and runs as without it.  Every sampling entry ignores the flag (same bits,
+                                      * same l2hmc_gauge_ws_bytes), and l2hmc_gauge_train_ws_bytes is the same with and
+                                      * without it */
 typedef struct l2hmc_gauge_plan {
   int32_t T, X;            /* lattice extents; D = 2*T*X */
   int32_t num_steps;       /* N_LF */
@@ -576,6 +593,11 @@ typedef struct l2hmc_conv3d_grads {
  * (both networks' input tapes, and the input cotangent rounded to the 256-byte grid every section starts on).  No other
  * plan's size depends on the flag. */
 size_t l2hmc_gauge_train_ws_bytes(const l2hmc_gauge_plan* plan, int64_t rows);
+/* How l2hmc_gauge_train_forward[_ladder] runs a plan (host logic only, no device call, no reference counterpart):
+ * 1 = as ONE launch of a taped whole-trajectory kernel -- the reference-mode plans with such a kernel (GenericNet on
+ * D = 128, ConvNet3D on 8x8) and the torus-exact plans L2HMC_PLAN_PERIODIC_TAPE describes; 0 = layer by layer (also with
+ * L2HMC_PLAN_LAYERED); negative = a plan the training entries refuse (l2hmc_last_error says why). */
+int l2hmc_gauge_plan_train_fused(const l2hmc_gauge_plan* plan);
 /* Same outputs as l2hmc_gauge_trajectory (dir: per-row 0 forward / 1 backward, NULL = all forward);
  * `ws` must stay untouched until the matching l2hmc_gauge_train_backward has run. */
 int l2hmc_gauge_train_forward(const l2hmc_gauge_plan* plan, float beta, const float* x0, const float* v0,

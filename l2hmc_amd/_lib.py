@@ -23,6 +23,7 @@ PLAN_SINGLE_KICKS = 128
 PLAN_PERIODIC = 256
 PLAN_PERIODIC_STEP = 512     # with PLAN_PERIODIC only: the torus-exact mode's whole-step kernel where the plan has it
 PLAN_PERIODIC_TRAIN = 1024   # with PLAN_PERIODIC only: the tiled training entries take the plan (widths multiples of 32)
+PLAN_PERIODIC_TAPE = 2048    # with both of them only: the training forward as one taped whole-trajectory launch where the plan has it
 GRAD_BUCKET_REST = 6
 BUCKET_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32)
 
@@ -101,6 +102,7 @@ _PROTOS = {
     "l2hmc_mix_accept": (C.c_int, [_P] * 9 + [_I32, _I64, _I32, _P, _P, _P, _P, _P]),
     "l2hmc_gauge_ws_bytes": (_SZ, [C.POINTER(GaugePlan), _I64]),
     "l2hmc_gauge_plan_fused": (C.c_int, [C.POINTER(GaugePlan)]),
+    "l2hmc_gauge_plan_train_fused": (C.c_int, [C.POINTER(GaugePlan)]),
     "l2hmc_gauge_step_plan": (C.c_int, [_I64, _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "l2hmc_gauge_pack_heads_bytes": (_SZ, [C.POINTER(GaugePlan)]),
     "l2hmc_gauge_pack_heads": (C.c_int, [C.POINTER(GaugePlan), _P, _P]),

@@ -14,7 +14,8 @@ stride 1): chain i is differentiated at ladder[i], with the bits of the scalar c
 are not differentiated.
 
 A torus-exact dynamics (`periodic=True`) is differentiated only with `tiled_train=True` (L2HMC_PLAN_PERIODIC_TRAIN), where
-the same entries take its plan; without the flag, or at widths that are no multiples of 32, it is refused.
+the same entries take its plan; without the flag, or at widths that are no multiples of 32, it is refused.  With
+`fused_forward=True` (L2HMC_PLAN_PERIODIC_TAPE) the forward of step 1 is one taped launch where the plan has the kernel.
 
 Every call owns its tape (a train workspace), the plan and the packed weight buffers it ran with, so several
 transitions may be differentiated by one backward (the reference loss runs two: x and z).  The tape is freed

@@ -80,6 +80,8 @@ int launch_fused32(const FusedArgs& a, hipStream_t stream);
 // recompute: form every first-layer product anew (L2HMC_PLAN_RECOMPUTE)
 int fused_ncp_net_supported(const l2hmc_dense_net* n);
 int fused_ncp_plan(const l2hmc_gauge_plan* p);
+// FusedArgs::tx / tv set: its taped instances (trajectory mode, a beta per row with step_beta_mod), the training forward
+// of the plans fused_ncp_tape_plan (stq_dense.h) accepts
 int launch_fused_ncp(const FusedArgs& a, int recompute, hipStream_t stream);
 
 }  // namespace l2hmc

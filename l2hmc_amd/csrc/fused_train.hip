@@ -747,11 +747,13 @@ size_t fused_bwd_pack_floats(const l2hmc_dense_net* n) {
 // latency, and this kernel runs one wave per SIMD (measured in-kernel: 12.9 ms against 4.4 ms for the
 // standalone conv3d_front_bwd_kernel over the same 40 calls), so conv plans keep the layered reverse pass.
 int fused_train_forward_supported(const l2hmc_gauge_plan* p) {
-  // (a torus-exact plan's whole-step kernel has no tape: check_train_plan refuses such plans, and nothing here sizes one)
-  return !(p->flags & (L2HMC_PLAN_LAYERED | L2HMC_PLAN_PERIODIC)) && fused_plan_supported(p);
+  // a torus-exact plan's whole-step kernel tapes where L2HMC_PLAN_PERIODIC_TAPE asks for it (fused_traj_ncp.hip)
+  if (p->flags & L2HMC_PLAN_PERIODIC) return fused_ncp_tape_plan(p);
+  return !(p->flags & L2HMC_PLAN_LAYERED) && fused_plan_supported(p);
 }
 int fused_train_supported(const l2hmc_gauge_plan* p) {
-  return !(p->flags & L2HMC_PLAN_CONV3D) && fused_train_forward_supported(p);
+  // (never a torus-exact plan: its tape is 3D wide and carries no gate words, and the kernel below reads neither)
+  return !(p->flags & (L2HMC_PLAN_CONV3D | L2HMC_PLAN_PERIODIC)) && fused_train_forward_supported(p);
 }
 
 int launch_fused_train_backward(const l2hmc_gauge_plan* p, float beta, const int* dir, int64_t rows, float* dx,

@@ -1234,10 +1234,18 @@ int launch_fused_trajectory(const l2hmc_gauge_plan* p, float beta, int step_begi
                             float* v_out, float* logdet, int logdet_accumulate, float* p_accept,
                             hipStream_t stream, int64_t x_mod, int64_t dir_split, const FusedTape* tape_x,
                             const FusedTape* tape_v, const float* betas, int64_t beta_mod, int64_t beta_stride) {
-  if (fused_ncp_plan(p)) {
+  // (a taped launch: the training forward of a plan with L2HMC_PLAN_PERIODIC_TAPE, whether or not it samples in one launch)
+  const bool ncp_tape = tape_x && tape_v && fused_ncp_tape_plan(p);
+  if (fused_ncp_plan(p) || ncp_tape) {
     // torus-exact plans: their own kernel, one form for every batch (fused_traj_ncp.hip), ahead of any form selection
-    L2HMC_REQUIRE(!tape_x && !tape_v && !betas, "fused trajectory: periodic plans have no taped or per-row-beta form");
+    L2HMC_REQUIRE(ncp_tape || (!tape_x && !tape_v && !betas),
+                  "fused trajectory: a periodic plan has a taped or per-row-beta form with L2HMC_PLAN_PERIODIC_TAPE only");
     FusedArgs a{};
+    if (ncp_tape) {
+      a.tx = *tape_x;
+      a.tv = *tape_v;
+      a.step_betas = betas; a.step_beta_mod = beta_mod; a.step_beta_stride = beta_stride;
+    }
     a.T = p->T; a.X = p->X; a.num_steps = p->num_steps; a.step_begin = step_begin; a.step_end = step_end;
     a.eps = p->eps; a.beta = beta; a.masks = p->masks; a.xnet = p->xnet; a.vnet = p->vnet;
     a.x0 = x0; a.v0 = v0; a.dir = dir; a.rows = rows; a.x_out = x_out; a.v_out = v_out;

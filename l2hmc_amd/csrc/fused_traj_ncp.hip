@@ -15,8 +15,9 @@
 //     sincosf, as l2hmc_u1_angle_features.
 // One form only: 16 rows per workgroup (8 chains x both directions, or 16 chains with L2HMC_PLAN_SELECTED_ONLY),
 // every batch as ceil(rows / 16) workgroups; no split form, no active-column heads, no kept-column first layer, no
-// paired half-kicks, no tape, no sub-tile or 32-row sibling.  The chain-local and step stages are fused_step.h's, the
-// streaming products fused_common.h's, the sub-update arithmetic lf_update.h's.
+// paired half-kicks, no sub-tile or 32-row sibling; the training tape in instances of their own (TAPE, below: the
+// forward of l2hmc_gauge_train_forward[_ladder] on a plan with L2HMC_PLAN_PERIODIC_TAPE).  The chain-local and step
+// stages are fused_step.h's, the streaming products fused_common.h's, the sub-update arithmetic lf_update.h's.
 //
 // Waves: 8 on the 4-wave image (two per SIMD, two per image section: RW = 2), the geometry of the GenericNet
 // instances of gauge_traj_fused_kernel, whose measurements (fused_traj.hip, FusedCfg) chose it: one wave's epilogues
@@ -52,9 +53,21 @@ struct NcpCfg {
   static_assert(LDS_FLOATS * sizeof(float) <= 160 * 1024, "one workgroup must fit the LDS of a CU");
 };
 
-template <bool LADDER>
+// TAPE: the training instances (L2HMC_PLAN_PERIODIC_TAPE; trajectory mode only), which also write the per-call tape of
+// train.hip's taped_call for a torus-exact plan -- in [3 D], st, h1, h2 and the S / T / Q planes, not the gate words
+// (their only reader is the reference mode's fused reverse kernel).  Taping only adds stores: the bits are the untaped
+// instance's.  TAPE && LADDER: the taped forward of a training step on a ladder (a beta per row; fused_step.h).
+// The taped instances keep the first-layer products too.  With keep_v / keep_x alive across the tape stores they sit at
+// 256 VGPRs with 76 - 80 B of scratch, and three (LADDER: four) spilled loop-invariant values are reloaded at the head
+// of every leapfrog step, none inside the four-call loop; without the kept products (L2HMC_NCP_TAPE_KEPT = 0: 234 - 235
+// VGPRs, no scratch at all, the same bits) the launch measured 8 % slower (profiles/periodic_train_forward.txt (c)).
+#ifndef L2HMC_NCP_TAPE_KEPT
+#define L2HMC_NCP_TAPE_KEPT 1
+#endif
+template <bool LADDER, bool TAPE = false>
 __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedArgs p, int recompute) {
   using Cfg = NcpCfg;
+  constexpr bool KEPT = !TAPE || L2HMC_NCP_TAPE_KEPT;
   constexpr int D = Cfg::D, H = Cfg::H, kThreads = Cfg::THREADS, kTPC = Cfg::TPC, kWaves = Cfg::WAVES;
   constexpr int SX = Cfg::SX, SH = Cfg::SH, SF = Cfg::SF, SP = Cfg::SP, NT1 = Cfg::NT1, NTI1 = Cfg::NTI1;
   constexpr int NTIH = Cfg::NTIH, RW = Cfg::RW, KCD = Cfg::KCD;
@@ -80,7 +93,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
 
   // ---- stage chain state, constants and the features of x0 (fused_step.h) ------
   const StepWg wg = step_workgroup<kFM>(p, stp, false);
-  stage_chains<kFM, kThreads, D, SX, LADDER, false>(p, wg, xs, vs, sdir);
+  stage_chains<kFM, kThreads, D, SX, LADDER, TAPE>(p, wg, xs, vs, sdir);
   load_consts<kThreads, D, H>(p.xnet, cx, tid);
   load_consts<kThreads, D, H>(p.vnet, cv, tid);
   if (tid < kWaves * kFM) ldw[tid] = 0.f;
@@ -109,6 +122,39 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
                         const float tsr, int callidx) {
     const float* pk = net.packed;
     const bool zig = (callidx & 1) != 0;                      // layers 2 and 3 alternate their direction (fused_common.h)
+    // training tape: this call's input rows as the first layer reads them and the state its sub-update consumes.  The
+    // inputs are complete behind the barrier that ended the previous stage, also where no product is formed from them
+    // (l1 == 2), and VNet's features leave here UNMASKED: this call's own epilogue puts the next keep on fs two
+    // barriers further on.
+    [[maybe_unused]] const FusedTape& tp = is_vnet ? p.tv : p.tx;
+    [[maybe_unused]] const size_t tcr0 = (size_t)callidx * (size_t)p.rows + (size_t)wg.row0;   // first taped row of this workgroup
+    if constexpr (TAPE) {
+      const float* stsrc = is_vnet ? vs : xs;
+      for (int i = tid; i < kFM * (D / 4); i += kThreads) {
+        const int rr = i / (D / 4), c4 = (i - rr * (D / 4)) * 4;
+        if (rr < wg.nrow) {
+          float* dst = tp.in + (tcr0 + rr) * (3 * D);
+          const f32x4 fc = *reinterpret_cast<const f32x4*>(fs + rr * SF + c4);
+          const f32x4 fn = *reinterpret_cast<const f32x4*>(fs + rr * SF + D + c4);
+          if (is_vnet) {          // [cos x | sin x | beta force]
+            tape_store(dst + c4, fc);
+            tape_store(dst + D + c4, fn);
+            tape_store(dst + 2 * D + c4, *reinterpret_cast<const f32x4*>(gs + rr * SX + c4));
+          } else {                // [v | keep cos x | keep sin x]
+            tape_store(dst + c4, *reinterpret_cast<const f32x4*>(vs + rr * SX + c4));
+            tape_store(dst + D + c4, fc);
+            tape_store(dst + 2 * D + c4, fn);
+          }
+          tape_store(tp.st + (tcr0 + rr) * D + c4, *reinterpret_cast<const f32x4*>(stsrc + rr * SX + c4));
+        }
+      }
+    }
+    [[maybe_unused]] auto tape_rows = [&](float* dst, const float* src) {     // [16][H] LDS rows -> tape
+      for (int i = tid; i < kFM * (H / 4); i += kThreads) {
+        const int rr = i / (H / 4), c4 = (i - rr * (H / 4)) * 4;
+        if (rr < wg.nrow) tape_store(dst + (tcr0 + rr) * H + c4, *reinterpret_cast<const f32x4*>(src + rr * SH + c4));
+      }
+    };
     const int wv = __builtin_amdgcn_readfirstlane(wave);      // wave-uniform: the weight loads' base stays in SGPRs
     const int wimg = wv / RW, wsub = wv - wimg * RW;          // image section, and this wave's share of it
     const float* wp1 = pk + (size_t)wimg * Cfg::KC1 * NTI1 * 256;
@@ -176,6 +222,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
       }
     }
     __syncthreads();
+    if constexpr (TAPE) tape_rows(tp.h1, h1);
     // ----- layer 2
     {
       f32x4 acc[NT1];
@@ -196,6 +243,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
       }
     }
     __syncthreads();
+    if constexpr (TAPE) tape_rows(tp.h2, h2);
     // ----- heads + update: this wave's 16 columns [S | T | Q] of row r
     {
       f32x4 acc[3];
@@ -224,6 +272,15 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
         float s_, t_, q_;
         heads_stq(acc[0][e], acc[1][e], acc[2][e], b_s[e], b_t[e], b_q[e], e_s[e], e_q[e], net.q_tanh, s_, t_, q_);
         S[e] = s_; Tt[e] = t_; Q[e] = q_;
+      }
+      if constexpr (TAPE) {
+        if (r < wg.nrow) {
+          const size_t plane = (size_t)p.rows * D;
+          float* o = tp.stq + (size_t)callidx * 3 * plane + ((size_t)wg.row0 + r) * D + c0;
+          tape_store(o, S);
+          tape_store(o + plane, Tt);
+          tape_store(o + 2 * plane, Q);
+        }
       }
       if (is_vnet) {
         const f32x4 g = *reinterpret_cast<const f32x4*>(gs + idx);
@@ -306,7 +363,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
       }
       // call 0: momentum half-kick (+ masked features)         call 1: position sub-update 1 (+ complement mask)
       // call 2: position sub-update 2 (+ unmasked features)    call 3: second momentum half-kick (product kept)
-      const int l1 = recompute ? 0 : call == 0 ? (keep_v_valid ? 2 : 0) : call == 1 ? 3 : call == 2 ? 4 : 1;
+      const int l1 = (!KEPT || recompute) ? 0 : call == 0 ? (keep_v_valid ? 2 : 0) : call == 1 ? 3 : call == 2 ? 4 : 1;
       net_update(is_v ? p.vnet : p.xnet, is_v ? cv : cx, is_v, /*sub=*/call >> 1, l1, tcr, tsr, 2 * step + (call >> 1));
     }
     keep_v_valid = !recompute;
@@ -316,7 +373,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
   float act1[1], kin1[1];
   force_pass<kFM, kTPC, 1, D, SX, SP, LADDER>(cl, xs, sp, gs, act1);
   kinetic_pass<kFM, kTPC, 1, D, SX>(cl, vs, kin1);
-  if (wg.stepm) {
+  if (!TAPE && wg.stepm) {              // (the taped instances are trajectory mode only)
     float* spx = wg.spx;
     step_accept_probs<kFM, 1, kWaves, LADDER>(cl, ldw, act0, act1, kin0, kin1, spx);
     __syncthreads();
@@ -330,7 +387,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
     step_write_next<kThreads, D, SX>(p, wg, gout);
     return;
   }
-  traj_logdet_accept<kFM, 1, kWaves, false>(p, wg, cl, ldw, act0, act1, kin0, kin1);
+  traj_logdet_accept<kFM, 1, kWaves, TAPE && LADDER>(p, wg, cl, ldw, act0, act1, kin0, kin1);
   traj_write_back<kFM, kThreads, D, SX>(p, wg, xs, vs);
 }
 
@@ -342,16 +399,61 @@ static int ncp_xnet(const l2hmc_dense_net* n) { return n->D == 128 && n->H == 51
 static int ncp_vnet(const l2hmc_dense_net* n) { return n->D == 128 && n->H == 512 && n->Ka == 256 && n->Kb == 128; }
 int fused_ncp_net_supported(const l2hmc_dense_net* n) { return ncp_xnet(n) || ncp_vnet(n); }
 
-int fused_ncp_plan(const l2hmc_gauge_plan* p) {
-  const int both = L2HMC_PLAN_PERIODIC | L2HMC_PLAN_PERIODIC_STEP;
-  return !p->hmc && (p->flags & both) == both && !(p->flags & L2HMC_PLAN_CONV3D) && 2 * p->T * p->X == 128 &&
-         (p->X & (p->X - 1)) == 0 && ncp_xnet(&p->xnet) && ncp_vnet(&p->vnet) && p->xnet.packed && p->vnet.packed;
+// the shapes the kernel serves, whatever asks for it
+static int ncp_shape(const l2hmc_gauge_plan* p) {
+  return !p->hmc && !(p->flags & L2HMC_PLAN_CONV3D) && 2 * p->T * p->X == 128 && (p->X & (p->X - 1)) == 0 &&
+         ncp_xnet(&p->xnet) && ncp_vnet(&p->vnet) && p->xnet.packed && p->vnet.packed;
 }
 
-// a: the descriptor of launch_fused_trajectory / launch_fused_step (fused_traj.hip), rows a multiple of 16 in step mode
+int fused_ncp_plan(const l2hmc_gauge_plan* p) {
+  const int both = L2HMC_PLAN_PERIODIC | L2HMC_PLAN_PERIODIC_STEP;
+  return (p->flags & both) == both && ncp_shape(p);
+}
+
+// the taped instances: the training forward of a plan with L2HMC_PLAN_PERIODIC_TAPE (no L2HMC_PLAN_PERIODIC_STEP needed;
+// L2HMC_PLAN_LAYERED wins)
+int fused_ncp_tape_plan(const l2hmc_gauge_plan* p) {
+  const int all = L2HMC_PLAN_PERIODIC | L2HMC_PLAN_PERIODIC_TRAIN | L2HMC_PLAN_PERIODIC_TAPE;
+  return (p->flags & all) == all && !(p->flags & L2HMC_PLAN_LAYERED) && ncp_shape(p);
+}
+
+// a: the descriptor of launch_fused_trajectory / launch_fused_step (fused_traj.hip), rows a multiple of 16 in step mode.
+// a.tx.in set: the taped instances (every tape array of both networks but `gate`, the whole trajectory, trajectory mode).
 int launch_fused_ncp(const FusedArgs& a, int recompute, hipStream_t stream) {
   static DeviceOnce once;
   const size_t lds = sizeof(float) * NcpCfg::LDS_FLOATS;
+  const bool tape = a.tx.in != nullptr || a.tv.in != nullptr;
+  if (tape) {
+    static DeviceOnce tape_once;
+    if (tape_once.pending()) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_ncp_kernel<false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_ncp_kernel<true, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        set_error("fused periodic step: cannot reserve %zu B of LDS", lds);
+        return L2HMC_ERR_HIP;
+      }
+      tape_once.done();
+    }
+    L2HMC_REQUIRE(a.rows > 0 && a.xnet.packed && a.vnet.packed && a.x0 && a.v0 && a.x_out && a.v_out,
+                  "fused periodic step: bad arguments");
+    L2HMC_REQUIRE(a.step_B == 0 && a.step_begin == 0 && a.step_end == a.num_steps,
+                  "fused periodic step: taping needs trajectory mode and the whole trajectory");
+    L2HMC_REQUIRE(a.tx.in && a.tx.h1 && a.tx.h2 && a.tx.stq && a.tx.st && a.tv.in && a.tv.h1 && a.tv.h2 && a.tv.stq &&
+                      a.tv.st,
+                  "fused periodic step: NULL tape pointer");
+    L2HMC_REQUIRE(!a.step_betas || (a.step_beta_mod > 0 && (a.step_beta_stride == 0 || a.step_beta_stride == 1)),
+                  "fused periodic step: a beta per row needs a modulus > 0 and an element stride of 0 or 1");
+    const dim3 tgrid((unsigned)ceil_div(a.rows, (int64_t)kFM));
+    prof_before(kProfFused, stream);
+    if (a.step_betas)
+      hipLaunchKernelGGL((gauge_traj_ncp_kernel<true, true>), tgrid, dim3(NcpCfg::THREADS), lds, stream, a, recompute);
+    else
+      hipLaunchKernelGGL((gauge_traj_ncp_kernel<false, true>), tgrid, dim3(NcpCfg::THREADS), lds, stream, a, recompute);
+    prof_after(kProfFused, stream);
+    L2HMC_CHECK_LAUNCH("gauge_traj_ncp_tape");
+    return L2HMC_OK;
+  }
   if (once.pending()) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gauge_traj_ncp_kernel<false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||

@@ -287,6 +287,10 @@ static int check_plan(const l2hmc_gauge_plan* p) {
   L2HMC_REQUIRE(p->masks != nullptr, "plan: masks is NULL");
   const int D = 2 * p->T * p->X;
   if (!p->hmc) {
+    L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_TAPE) ||
+                      ((p->flags & L2HMC_PLAN_PERIODIC) && (p->flags & L2HMC_PLAN_PERIODIC_TRAIN)),
+                  "plan: L2HMC_PLAN_PERIODIC_TAPE selects the taped whole-trajectory kernel of a torus-exact plan and "
+                  "needs L2HMC_PLAN_PERIODIC and L2HMC_PLAN_PERIODIC_TRAIN with it");
     L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_STEP) || (p->flags & L2HMC_PLAN_PERIODIC),
                   "plan: L2HMC_PLAN_PERIODIC_STEP selects the whole-step kernel of a torus-exact plan and needs "
                   "L2HMC_PLAN_PERIODIC with it");

@@ -198,6 +198,9 @@ size_t fused_step_hand_bytes(int64_t B, int D);
 size_t fused_bwd_pack_floats(const l2hmc_dense_net* n);
 int fused_train_supported(const l2hmc_gauge_plan* p);
 int fused_train_forward_supported(const l2hmc_gauge_plan* p);
+// the torus-exact plans among them (fused_traj_ncp.hip: L2HMC_PLAN_PERIODIC | _TRAIN | _TAPE on the kernel's shapes); for
+// these the forward is taped in one launch and the reverse pass stays layer by layer (fused_train_supported is 0)
+int fused_ncp_tape_plan(const l2hmc_gauge_plan* p);
 int launch_fused_train_backward(const l2hmc_gauge_plan* p, float beta, const int* dir, int64_t rows, float* dx,
                                 float* dv, const float* dld, const FusedTape& tx, const FusedTape& tv,
                                 float* const deltas_x[3], float* const deltas_v[3], float* pack_x, float* pack_v,

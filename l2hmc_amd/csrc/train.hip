@@ -1129,6 +1129,9 @@ static int check_train_plan(const l2hmc_gauge_plan* p) {
   L2HMC_REQUIRE(p != nullptr, "train: NULL plan");
   L2HMC_REQUIRE(p->T > 0 && p->X > 0 && p->num_steps > 0 && p->masks != nullptr, "train: bad plan");
   L2HMC_REQUIRE(!p->hmc, "train: hmc plans have no trainable networks");
+  L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_TAPE) || plan_ncp_train(p),
+                "train: L2HMC_PLAN_PERIODIC_TAPE selects the taped whole-trajectory kernel of a torus-exact plan and "
+                "needs L2HMC_PLAN_PERIODIC and L2HMC_PLAN_PERIODIC_TRAIN with it");
   L2HMC_REQUIRE(!(p->flags & L2HMC_PLAN_PERIODIC_TRAIN) || (p->flags & L2HMC_PLAN_PERIODIC),
                 "train: L2HMC_PLAN_PERIODIC_TRAIN opens the tiled training entries to a torus-exact plan and needs "
                 "L2HMC_PLAN_PERIODIC with it");
@@ -1369,6 +1372,12 @@ using namespace l2hmc;
 extern "C" size_t l2hmc_gauge_train_ws_bytes(const l2hmc_gauge_plan* plan, int64_t rows) {
   if (!plan || rows <= 0 || plan->hmc) return 0;
   return carve_train_ws(plan, rows, nullptr).bytes;
+}
+
+// host logic only, no device call: the branch train_forward_impl takes
+extern "C" int l2hmc_gauge_plan_train_fused(const l2hmc_gauge_plan* plan) {
+  if (int e = check_train_plan(plan)) return -e;
+  return fused_train_forward_supported(plan) ? 1 : 0;
 }
 
 // The refusals the three _ladder entries add to those of their scalar forms (`rows`: the rows the ladder is laid on,

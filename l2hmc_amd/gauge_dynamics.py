@@ -62,12 +62,24 @@ class GaugeDynamics:
         # (T * X a multiple of 16); any other lattice carries the flag and trains on the layered walk.  Training only:
         # every sampling entry ignores it, and it composes with `whole_step`.
         self.tiled_train = False
+        # True (with periodic=True and tiled_train=True): the forward half of a training step is ONE launch of the
+        # mode's whole-trajectory kernel, which writes the tape the tiled reverse pass reads (L2HMC_PLAN_PERIODIC_TAPE)
+        # -- where the plan has the kernel (x_dim = 128 with a power-of-two space extent, H = 512); any other lattice
+        # carries the flag and trains as without it.  Same arithmetic as `whole_step`'s kernel, so it differs from the
+        # layer-by-layer forward in rounding.  Training only; it does not need `whole_step` and composes with it.
+        self.fused_forward = False
         for key, val in kwargs.items():
             if key != 'eps':             # :73-75
                 setattr(self, key, val)
         self.periodic = bool(self.periodic)
         self.whole_step = bool(self.whole_step)
         self.tiled_train = bool(self.tiled_train)
+        self.fused_forward = bool(self.fused_forward)
+        if self.fused_forward and not self.hmc and not (self.periodic and self.tiled_train):
+            missing = [f"{k}=True" for k, on in (("periodic", self.periodic), ("tiled_train", self.tiled_train)) if not on]
+            raise ValueError("fused_forward=True selects the taped whole-trajectory kernel of the torus-exact mode's "
+                             "tiled training and needs " + " and ".join(missing) + " with it (the reference mode's "
+                             "training forward is one launch already)")
         if self.tiled_train and not self.periodic and not self.hmc:
             raise ValueError("tiled_train=True opens the tiled training entries to the torus-exact mode and needs "
                              "periodic=True (the reference mode trains on them already)")
@@ -183,7 +195,9 @@ class GaugeDynamics:
                            | (_lib.PLAN_SINGLE_KICKS if self.single_kicks else 0)
                            | (_lib.PLAN_PERIODIC if self.periodic and not self.hmc else 0)
                            | (_lib.PLAN_PERIODIC_STEP if self.whole_step and self.periodic and not self.hmc else 0)
-                           | (_lib.PLAN_PERIODIC_TRAIN if self.tiled_train and self.periodic and not self.hmc else 0),
+                           | (_lib.PLAN_PERIODIC_TRAIN if self.tiled_train and self.periodic and not self.hmc else 0)
+                           | (_lib.PLAN_PERIODIC_TAPE if self.fused_forward and self.tiled_train and self.periodic
+                              and not self.hmc else 0),
                            masks=_lib.dev_ptr(self.mask, name="mask"))
         if not self.hmc:
             p.xnet = self.position_fn.pack()

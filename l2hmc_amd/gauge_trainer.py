@@ -17,7 +17,8 @@ direction's outputs by exactly 0, so it contributes exactly 0 to every gradient.
 The tiled training entries (l2hmc_gauge_train_*) need every network width to be a multiple of 32; GenericNet
 networks of other widths (lattices whose T * X is not a multiple of 16: 6x6, 3x5, 4x6, ...) are trained through the
 layered-training entries instead (the forward and backward stages of l2hmc_amd/layered_train.py), and so is a torus-exact
-dynamics (`periodic=True`) unless `tiled_train=True` opens the tiled entries to it.  Both are the
+dynamics (`periodic=True`) unless `tiled_train=True` opens the tiled entries to it (`fused_forward=True` then makes
+their forward one taped launch where the mode has its whole-trajectory kernel; nothing here changes for it).  Both are the
 forward and the reverse of ONE step body (`calc_loss_and_grads`: stack, forward, loss reverse, reverse, exchange), so
 they share the draws, the flat buffer, the data-parallel exchange and the optimiser (l2hmc_amd/_flat_trainer.py)."""
 import ctypes as C

@@ -60,6 +60,11 @@ class DeviceOnce {
   }
 };
 
+// ---- relu that hands a NaN on, as the oracle's np.maximum(h, 0) and the reference's tf.nn.relu do.  fmaxf(h, 0.f) is
+// IEEE maxNum and returns 0 for a NaN, which lets a row with one non-finite input come back partly finite
+// (tests/test_gpu_periodic_scale.py, e.).  Finite h: the bits of fmaxf (-0 gives +0).  One compare and one select.
+__device__ __forceinline__ float relu_nan(float h) { return h <= 0.f ? 0.f : h; }
+
 // ---- XCD-aware tile id: blocks b, b+8, ... share an XCD, give each XCD a
 // contiguous run of logical tiles (bijective for any grid size).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

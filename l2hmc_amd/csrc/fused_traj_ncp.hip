@@ -217,7 +217,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
         const f32x4 w1 = *reinterpret_cast<const f32x4*>(cn + 2 * H + c0);
         f32x4 hv;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[t][e] + b[e] + (tcr * w0[e] + tsr * w1[e]), 0.f);
+        for (int e = 0; e < 4; ++e) hv[e] = relu_nan(acc[t][e] + b[e] + (tcr * w0[e] + tsr * w1[e]));
         *reinterpret_cast<f32x4*>(h1 + r * SH + c0) = hv;
       }
     }
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(NcpCfg::THREADS) void gauge_traj_ncp_kernel(FusedAr
         const f32x4 b = *reinterpret_cast<const f32x4*>(cn + 3 * H + c0);
         f32x4 hv;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[t][e] + b[e], 0.f);
+        for (int e = 0; e < 4; ++e) hv[e] = relu_nan(acc[t][e] + b[e]);
         *reinterpret_cast<f32x4*>(h2 + r * SH + c0) = hv;
       }
     }

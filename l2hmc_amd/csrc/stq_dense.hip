@@ -378,7 +378,7 @@ __global__ __launch_bounds__(kGemmThreads) __attribute__((amdgpu_waves_per_eu(2)
             h = acc[i][j][e] + bj;
           }
           if (KIND == 3) h = p.gate[row * p.ldg + col] > 0.f ? h : 0.f;
-          h = KIND <= 2 ? fmaxf(h, 0.f) : h;
+          h = KIND <= 2 ? relu_nan(h) : h;
           if (staged) lds[lrow * LDC + wn * WN + j * 32 + r] = h;
           else p.out[row * p.ldo + col] = h;
         }
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256) void l1_finish_kernel(L1FinishArgs p) {
     }
     f32x4 h;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = fmaxf(l1_preact(a[j], b[j], tc, ts, w0[j], w1[j]), 0.f);
+    for (int j = 0; j < 4; ++j) h[j] = relu_nan(l1_preact(a[j], b[j], tc, ts, w0[j], w1[j]));
     *reinterpret_cast<f32x4*>(p.out + row * p.N + c) = h;
   }
 }

@@ -62,8 +62,11 @@ class DeviceOnce {
 
 // ---- relu that hands a NaN on, as the oracle's np.maximum(h, 0) and the reference's tf.nn.relu do.  fmaxf(h, 0.f) is
 // IEEE maxNum and returns 0 for a NaN, which lets a row with one non-finite input come back partly finite
-// (tests/test_gpu_periodic_scale.py, e.).  Finite h: the bits of fmaxf (-0 gives +0).  One compare and one select.
-__device__ __forceinline__ float relu_nan(float h) { return h <= 0.f ? 0.f : h; }
+// (tests/test_gpu_periodic_scale.py, e.; tests/test_gpu_nonfinite.py).  Finite h: the bits of fmaxf (-0 gives +0).
+// IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950.  max_nan is the max-pool of the ConvNet3D front-ends, which
+// np.maximum likewise makes NaN where any entry of the window is.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float relu_nan(float h) { return max_nan(h, 0.f); }
 
 // ---- XCD-aware tile id: blocks b, b+8, ... share an XCD, give each XCD a
 // contiguous run of logical tiles (bijective for any grid size).

@@ -213,11 +213,11 @@ __global__ __launch_bounds__(kConvThreads) __attribute__((amdgpu_waves_per_eu(4,
                 v1 += x1 * k0[ti * 3 + tj];
               }
             }
-            m[0] = fmaxf(m[0], fmaxf(v0[0], v1[0]));
-            m[1] = fmaxf(m[1], fmaxf(v0[1], v1[1]));
+            m[0] = max_nan(m[0], max_nan(v0[0], v1[0]));
+            m[1] = max_nan(m[1], max_nan(v0[1], v1[1]));
           }
         }
-        *reinterpret_cast<f32x2*>(p1 + ((c * T2P + I) * X2P + J) * FS + 2 * fp) = f32x2{fmaxf(m[0], 0.f), fmaxf(m[1], 0.f)};
+        *reinterpret_cast<f32x2*>(p1 + ((c * T2P + I) * X2P + J) * FS + 2 * fp) = f32x2{relu_nan(m[0]), relu_nan(m[1])};
         __builtin_amdgcn_sched_barrier(0);       // (one item's patch registers at a time)
       }
     };
@@ -249,9 +249,9 @@ __global__ __launch_bounds__(kConvThreads) __attribute__((amdgpu_waves_per_eu(4,
         f32x4 m = acc[gt];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          m[e] = fmaxf(m[e], __shfl_xor(m[e], 1, 64));
-          m[e] = fmaxf(m[e], __shfl_xor(m[e], X2 >= 16 ? 0 : X2, 64));
-          m[e] = fmaxf(m[e], 0.f);
+          m[e] = max_nan(m[e], __shfl_xor(m[e], 1, 64));
+          m[e] = max_nan(m[e], __shfl_xor(m[e], X2 >= 16 ? 0 : X2, 64));
+          m[e] = relu_nan(m[e]);
         }
         if ((J & 1) == 0 && (I & 1) == 0 && c < nrow) {
           float* o = out + (row0 + c) * p.ldo + ((I >> 1) * X4 + (J >> 1)) * F2 + 16 * gt + 4 * q;
@@ -362,10 +362,10 @@ __global__ __launch_bounds__(kConvThreads) __attribute__((amdgpu_waves_per_eu(4,
             v1 += x1 * k0;                 // output depth 1 sees (mu=1, pad)
           }
         }
-        m = fmaxf(m, fmaxf(v0, v1));
+        m = max_nan(m, max_nan(v0, v1));
       }
     }
-    p1[((c * T2P + I) * X2P + J) * F + f] = fmaxf(m, 0.f);
+    p1[((c * T2P + I) * X2P + J) * F + f] = relu_nan(m);
   }
   __syncthreads();
 
@@ -402,8 +402,8 @@ __global__ __launch_bounds__(kConvThreads) __attribute__((amdgpu_waves_per_eu(4,
               for (int bb = 0; bb < 2; ++bb) acc[a][bb] += w[a + di][bb + dj][cc] * kw;
           }
     }
-    const float m = fmaxf(fmaxf(acc[0][0], acc[0][1]), fmaxf(acc[1][0], acc[1][1]));
-    out[(row0 + c) * p.ldo + (I2 * X4 + J2) * F2 + g] = fmaxf(m, 0.f);
+    const float m = max_nan(max_nan(acc[0][0], acc[0][1]), max_nan(acc[1][0], acc[1][1]));
+    out[(row0 + c) * p.ldo + (I2 * X4 + J2) * F2 + g] = relu_nan(m);
   }
 }
 

@@ -381,11 +381,11 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
                 v1 += x1 * k0[di * 3 + dj];
               }
             }
-            m[0] = fmaxf(m[0], fmaxf(v0[0], v1[0]));
-            m[1] = fmaxf(m[1], fmaxf(v0[1], v1[1]));
+            m[0] = max_nan(m[0], max_nan(v0[0], v1[0]));
+            m[1] = max_nan(m[1], max_nan(v0[1], v1[1]));
           }
         }
-        *reinterpret_cast<f32x2*>(cp1 + c * Cfg::CP1 + (I * L2P + J) * F + 2 * fp) = f32x2{fmaxf(m[0], 0.f), fmaxf(m[1], 0.f)};
+        *reinterpret_cast<f32x2*>(cp1 + c * Cfg::CP1 + (I * L2P + J) * F + 2 * fp) = f32x2{relu_nan(m[0]), relu_nan(m[1])};
       }
     }
     __syncthreads();
@@ -427,9 +427,9 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
                   }
               }
         }
-        const float m0 = fmaxf(fmaxf(acc[0][0][0], acc[0][1][0]), fmaxf(acc[1][0][0], acc[1][1][0]));
-        const float m1 = fmaxf(fmaxf(acc[0][0][1], acc[0][1][1]), fmaxf(acc[1][0][1], acc[1][1][1]));
-        *reinterpret_cast<f32x2*>(dst + c * SA + (I2 * L4 + J2) * F2 + 2 * gp) = f32x2{fmaxf(m0, 0.f), fmaxf(m1, 0.f)};
+        const float m0 = max_nan(max_nan(acc[0][0][0], acc[0][1][0]), max_nan(acc[1][0][0], acc[1][1][0]));
+        const float m1 = max_nan(max_nan(acc[0][0][1], acc[0][1][1]), max_nan(acc[1][0][1], acc[1][1][1]));
+        *reinterpret_cast<f32x2*>(dst + c * SA + (I2 * L4 + J2) * F2 + 2 * gp) = f32x2{relu_nan(m0), relu_nan(m1)};
       }
     }
     __syncthreads();
@@ -626,10 +626,10 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
             const f32x4 w1 = *reinterpret_cast<const f32x4*>(cn + 2 * H + c0);
             f32x4 hv;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[t][e] + b[e] + (tcr * w0[e] + tsr * w1[e]), 0.f);
+            for (int e = 0; e < 4; ++e) hv[e] = relu_nan(acc[t][e] + b[e] + (tcr * w0[e] + tsr * w1[e]));
             *reinterpret_cast<f32x4*>(h1 + r * SH + c0) = hv;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[t][e] + b[e] + (tcr2 * w0[e] + tsr2 * w1[e]), 0.f);
+            for (int e = 0; e < 4; ++e) hv[e] = relu_nan(acc[t][e] + b[e] + (tcr2 * w0[e] + tsr2 * w1[e]));
             *reinterpret_cast<f32x4*>(h2 + r * SH + c0) = hv;
           }
           L2HMC_CYCLES_ADD(ft, 3, t0);
@@ -665,7 +665,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
               const f32x4 b = *reinterpret_cast<const f32x4*>(cn + 3 * H + c0);
               f32x4 hv;
 #pragma unroll
-              for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc2[t][e] + b[e], 0.f);
+              for (int e = 0; e < 4; ++e) hv[e] = relu_nan(acc2[t][e] + b[e]);
               *reinterpret_cast<f32x4*>(hs + r * SH + c0) = hv;
             }
             L2HMC_CYCLES_ADD(ft, 4, t0);
@@ -782,7 +782,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         f32x4 hv;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          hv[e] = fmaxf(acc[t][e] + b[e] + (tcr * w0[e] + tsr * w1[e]), 0.f);
+          hv[e] = relu_nan(acc[t][e] + b[e] + (tcr * w0[e] + tsr * w1[e]));
           if constexpr (TAPE) gmask |= (hv[e] > 0.f ? 1u : 0u) << (t * 4 + e);
         }
         *reinterpret_cast<f32x4*>(h1 + r * SH + c0) = hv;
@@ -825,7 +825,7 @@ __global__ __launch_bounds__((FusedCfg<D, H, KA, CONV>::THREADS)) void gauge_tra
         f32x4 hv;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          hv[e] = fmaxf(acc[t][e] + b[e], 0.f);
+          hv[e] = relu_nan(acc[t][e] + b[e]);
           if constexpr (TAPE) gmask |= (hv[e] > 0.f ? 1u : 0u) << (t * 4 + e);
         }
         *reinterpret_cast<f32x4*>(h2 + r * SH + c0) = hv;

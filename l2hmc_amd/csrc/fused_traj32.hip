@@ -229,7 +229,7 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
         for (int g = 0; g < kG32; ++g) {
           f32x4 hv;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[g][t][e] + b[e] + (tcr[g] * w0[e] + tsr[g] * w1[e]), 0.f);
+          for (int e = 0; e < 4; ++e) hv[e] = relu_nan(acc[g][t][e] + b[e] + (tcr[g] * w0[e] + tsr[g] * w1[e]));
           *reinterpret_cast<f32x4*>(hh + (16 * g + r) * SH + c0) = hv;
         }
       }
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(kT32) void gauge_traj_fused32_kernel(FusedArgs p) {
         for (int g = 0; g < kG32; ++g) {
           f32x4 hv;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) hv[e] = fmaxf(acc[g][t][e] + b[e], 0.f);
+          for (int e = 0; e < 4; ++e) hv[e] = relu_nan(acc[g][t][e] + b[e]);
           *reinterpret_cast<f32x4*>(hh + (16 * g + r) * SH + c0) = hv;
         }
       }

@@ -241,7 +241,7 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
         for (int g = 0; g < RG; ++g)
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            h1[(4 * g + i) * SH + c] = fmaxf(acc[g][cb][i] + b + (tcr[g][i] * w0 + tsr[g][i] * w1), 0.f);
+            h1[(4 * g + i) * SH + c] = relu_nan(acc[g][cb][i] + b + (tcr[g][i] * w0 + tsr[g][i] * w1));
       }
     }
     __syncthreads();
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(kThreads4) void gauge_traj_fused4_kernel(FusedArgs 
 #pragma unroll
         for (int g = 0; g < RG; ++g)
 #pragma unroll
-          for (int i = 0; i < 4; ++i) h2[(4 * g + i) * SH + c] = fmaxf(acc[g][cb][i] + b, 0.f);
+          for (int i = 0; i < 4; ++i) h2[(4 * g + i) * SH + c] = relu_nan(acc[g][cb][i] + b);
       }
     }
     __syncthreads();

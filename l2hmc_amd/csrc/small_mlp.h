@@ -83,7 +83,7 @@ __device__ void net_eval(const float* L, int dim, int q_tanh, const float* a, co
   __syncthreads();                          // previous readers of hrow are done
 #pragma unroll
   for (int j = 0; j < UPL; ++j) {
-    h1[j] = fmaxf(h1[j], 0.f);
+    h1[j] = relu_nan(h1[j]);
     hrow[n0 + j] = h1[j];
   }
   __syncthreads();
@@ -105,7 +105,7 @@ __device__ void net_eval(const float* L, int dim, int q_tanh, const float* a, co
     }
   }
 #pragma unroll
-  for (int j = 0; j < UPL; ++j) h2[j] = fmaxf(h2[j], 0.f);
+  for (int j = 0; j < UPL; ++j) h2[j] = relu_nan(h2[j]);
   // heads: k-split over the lanes, 16-lane butterfly
 #pragma unroll
   for (int d = 0; d < kMaxDim; ++d) {

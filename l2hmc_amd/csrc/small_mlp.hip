@@ -271,7 +271,7 @@ __device__ __forceinline__ void net_eval_twin(const NetRegsTwin<HP, MD, KS_, KSH
   }
   float h1[K2];
 #pragma unroll
-  for (int s = 0; s < K2; ++s) h1[s] = fmaxf(acc[s >> 2][s & 3], 0.f);
+  for (int s = 0; s < K2; ++s) h1[s] = relu_nan(acc[s >> 2][s & 3]);
   // ---- layer 2, own two tiles
   f32x4s a2[2] = {f32x4s{0.f, 0.f, 0.f, 0.f}, f32x4s{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
@@ -281,7 +281,7 @@ __device__ __forceinline__ void net_eval_twin(const NetRegsTwin<HP, MD, KS_, KSH
       a2[tl] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.w2[tl * K2 + s], h1[s], a2[tl], 0, 0, 0);
   float h2[KO];
 #pragma unroll
-  for (int j = 0; j < KO; ++j) h2[j] = fmaxf(a2[j >> 2][j & 3] + W.bh[j], 0.f);
+  for (int j = 0; j < KO; ++j) h2[j] = relu_nan(a2[j >> 2][j & 3] + W.bh[j]);
   // ---- heads: partial sums over the own k-steps, exchanged through LDS, added part 0 first in BOTH waves
   f32x4s* mine = xch + (parity * 2 + part) * NTH * 64 + lane;
   const f32x4s* other = xch + (parity * 2 + (part ^ 1)) * NTH * 64 + lane;
@@ -386,7 +386,7 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
         acc[to] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.w1[to * KS1 + s], mine, acc[to], 0, 0, 0);
     }
 #pragma unroll
-    for (int s = 0; s < K2; ++s) h1[s] = fmaxf(acc[s >> 2][s & 3], 0.f);
+    for (int s = 0; s < K2; ++s) h1[s] = relu_nan(acc[s >> 2][s & 3]);
   } else {
     float in[K1];
 #pragma unroll
@@ -403,7 +403,7 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
 #pragma unroll
         for (int j = 0; j < 4; ++j) pre = __builtin_fmaf(w[j], in[k4 + j], pre);
       }
-      h1[s] = fmaxf(pre, 0.f);
+      h1[s] = relu_nan(pre);
     }
   }
   L2HMC_CYCLES_ADD(st, 0, t0);
@@ -422,7 +422,7 @@ __device__ __forceinline__ void net_eval_mfma(const float* L, const NetRegs<HP, 
     float bias;
     if constexpr (L1M) bias = W.bh[s];
     else bias = L[V::bh + 16 * (s >> 2) + 4 * q + (s & 3)];
-    h2[s] = fmaxf(acc[s >> 2][s & 3] + bias, 0.f);
+    h2[s] = relu_nan(acc[s >> 2][s & 3] + bias);
   }
   L2HMC_CYCLES_ADD(st, 1, t0);
   t0 = L2HMC_CYCLES_NOW();
